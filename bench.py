@@ -13,10 +13,14 @@ surface implode (a ~ 3000 in the outer cell layer) and collisions, cell overflow
 full segments remove half the particles within a few steps.  So each timed step is
 one pass over the SAME batch: the N = 2^20 cloud is restored from a device-side
 snapshot (an HBM-to-HBM copy, inside the timed region) and advanced by one step --
-exactly the work the CPU baseline samples.  The line's `evolve` key reports a
+exactly the work the CPU baseline samples.  With --full the line's `evolve` key reports a
 free-running stretch beside it (--evolve makes that the timed loop).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line; --full adds what the
+headline does not need (the sustained region, the side runs, the CPU oracle's figures).
+--dump-outputs DIR (one GPU) writes the state the last timed step left as .npy files.
 
 N > 1 starts one process per GPU (python -m torch.distributed.run; or is started that way by
 the caller) and runs the SLAB-PARTITIONED path: every rank holds only the segments of its
@@ -84,9 +88,9 @@ def parse_args():
     ap.add_argument("--backend", default="ring", help="--gpus > 1: ring = one C++ rank per GPU (host/ps_ring_rccl: RCCL on a second HIP stream, "
                     "stage sequences as hipGraphs; the default); nccl = the same step from Python over torch.distributed (RCCL); gloo: "
                     "messages staged through host memory, for rehearsals on one GPU")
-    ap.add_argument("--host", default="ring", choices=("ring", "python"), help="who drives the timed loop: ring = the C++ host (host/ps_ring_rccl on include/psamd.h), "
-                    "for EVERY --gpus N including 1 -- one host for the whole scaling curve (the default); python = this process through ctypes "
-                    "(one GPU; what the side runs beside the headline use)")
+    ap.add_argument("--host", default="python", choices=("ring", "python"), help="who drives the one-GPU timed loop: python = this process "
+                    "through ctypes on libpsamd.so (the default; what the side runs and --dump-outputs read the state of); ring = the C++ host "
+                    "(host/ps_ring_rccl on include/psamd.h), the program --gpus N > 1 starts per GPU (the two agree within 0.3 %%: DESIGN.md)")
     ap.add_argument("--graphs", action="store_true", help="one GPU / --sim-world / torch ranks: stage sequences as hipGraphs (psamd_set_graphs)")
     ap.add_argument("--wait-policy", type=int, default=-1, help="how the host waits for a step's scalars: 0 spin, 1 short spin then naps (default: the library's)")
     ap.add_argument("--ring-graphs", type=int, default=0, help="C++ ranks: stage sequences as hipGraphs (default 0, plain launches: a graph launch costs "
@@ -95,9 +99,22 @@ def parse_args():
                     "streams costs ~15 us each way on the GPU's timeline, measured); 1 = the status gather, and with --overlap-interior the halo, on a second HIP stream; "
                     "2 = every transfer on the second stream (round 4's form)")
     ap.add_argument("--ring-timeout", type=float, default=0.0, help="seconds a C++ rank may take before it is ended and the ranks fall back (0: from --steps)")
-    ap.add_argument("--sustained-steps", type=int, default=200, help="one GPU: when --steps is shorter than this, a second timed region of this "
+    ap.add_argument("--sustained-steps", type=int, default=200, help="one GPU, with --full: when --steps is shorter than this, a second timed region of this "
                     "many steps is reported beside the line's figure (which clock a figure was taken at is part of the figure); 0: none")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the sustained region, the side runs "
+                    "and the CPU oracle's figures (without it a run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="one GPU: after the timed steps, write the state the last one left -- the "
+                    "reference-layout buffers a caller of the step receives -- as float32 / float64 .npy files in DIR (see write_outputs)")
+    args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.sim_world or args.launch_check):
+        ap.error("--dump-outputs: one GPU only (not with --gpus > 1, --sim-world or --launch-check)")
+    if args.dump_outputs and args.host == "ring":
+        ap.error("--dump-outputs reads the timed context's state in this process: not with --host ring")
+    if not args.full:
+        # a plain run does only what the headline needs
+        args.no_cpu = args.no_side_runs = True
+        args.sustained_steps = 0
+    return args
 
 
 def launch_ranks(args):
@@ -152,6 +169,30 @@ def make_inputs(sysobj, n, seed):
     age = rng.uniform(life / 7.0, life / 2.0, n).astype(np.float32)   # [MIN_ADULT_AGE, MAX_ADULT_AGE)
     fert = np.full(n, 1e6, np.float32)
     return xyz, age, fert
+
+
+DUMP_SLOTS = 1 << 18         # particle slots --dump-outputs writes: a fixed, seeded sample when the container holds more
+
+
+def write_outputs(out_dir, p, qi, q):
+    """The state the last timed step left, as the caller of the step receives it (particles in the reference's 72-byte
+    records, QUEUE_INFO, the queue array), written to out_dir as .npy files: for a fixed sample of particle slots (the
+    same slots in every run at the same size: seeded) their twelve float fields as float32 and their seven integer fields
+    and queue entries as float64 (exact), the sampled slot numbers, and every QUEUE_INFO record as float64."""
+    import particlesystem_amd as ps
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(p)
+    slots = np.arange(n) if n <= DUMP_SLOTS else np.sort(np.random.default_rng(20260).choice(n, DUMP_SLOTS, replace=False))
+    s = p[slots]
+    fl = [f for f in ps.P_DTYPE.names if ps.P_DTYPE.fields[f][0] == np.float32]
+    it = [f for f in ps.P_DTYPE.names if f not in fl]
+    arrays = {"particle_slots": slots.astype(np.float64),
+              "particles_float": np.stack([s[f] for f in fl], axis=1).astype(np.float32),
+              "particles_int": np.stack([s[f].astype(np.float64) for f in it], axis=1),
+              "queue": q[slots].astype(np.float64),
+              "queue_info": np.stack([qi[f].astype(np.float64) for f in qi.dtype.names], axis=1)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def measured_traffic(kernel_prefix, args, world):
@@ -833,7 +874,7 @@ def main():
                                 json.dump({"one": out["cpu_baseline"], "many": out["cpu_baseline_many_threads"]}, f)
                         except OSError:
                             pass
-                elif not args.all_pairs:
+                elif not args.all_pairs and not args.no_cpu:
                     out["cpu_baseline"], out["cpu_baseline_many_threads"] = cpu_baseline_cached(args, cfg_over, world)
                 print(json.dumps(out))
             return
@@ -998,6 +1039,8 @@ def main():
     g.set_timing(False)
     ctr = g.counters
     own_updates = float(ctr["particles_processed"] - processed0)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, g.download_particles(), *g.download_queues())
     sustained = None
     if world == 1 and not args.evolve and 0 < args.steps < args.sustained_steps:
         # A timed region of tens of milliseconds (the driver's --steps 20) says little about the clock a long run holds:

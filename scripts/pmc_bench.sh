@@ -7,5 +7,5 @@ ctrs=$1; shift
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/pmc_$tag
 mkdir -p "$out"
-rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d "$out" -o pmc -- python3 bench.py --no-cpu "$@" > "$out/stdout.json" 2> "$out/stderr.log"
+rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d "$out" -o pmc -- python3 bench.py --full --no-cpu "$@" > "$out/stdout.json" 2> "$out/stderr.log"
 ls "$out"

@@ -6,8 +6,8 @@ mkdir -p $out
 export TMPDIR=/tmp
 say() { echo "[$(date +%H:%M:%S)] $*" | tee -a $out/progress.log; }
 say "default bench line, and the driver's form of it (--steps 20)"
-python bench.py > $out/bench_line.json 2> $out/bench_line.err
-python bench.py --steps 20 --no-cpu --no-side-runs > $out/bench_steps20.json 2>> $out/bench_line.err
+python bench.py --full > $out/bench_line.json 2> $out/bench_line.err
+python bench.py --full --steps 20 --no-cpu --no-side-runs > $out/bench_steps20.json 2>> $out/bench_line.err
 say "kernel stats (exact)"
 bash scripts/profile_bench.sh r4art_exact --steps 20 --warmup 3 --settle-seconds 0 --no-side-runs > $out/prof_exact.log 2>&1
 say "kernel stats (tolerance mode)"
@@ -21,20 +21,20 @@ bash scripts/pmc_bench.sh r4art_wc "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
 say "PMC SQ (tolerance mode)"
 bash scripts/pmc_bench.sh r4art_fast_sq "SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SMEM GRBM_GUI_ACTIVE" --fast-math --steps 3 --warmup 2 --settle-seconds 0 --no-side-runs > $out/pmc_fast_sq.log 2>&1
 say "all-pairs (configs[1])"
-python bench.py --all-pairs --steps 10 --warmup 3 > $out/allpairs_line.json 2> $out/allpairs_line.err
+python bench.py --full --all-pairs --steps 10 --warmup 3 > $out/allpairs_line.json 2> $out/allpairs_line.err
 say "kernel stats (all-pairs)"
 bash scripts/profile_bench.sh r4art_allpairs --all-pairs --steps 5 --warmup 2 --settle-seconds 0 --no-side-runs > $out/prof_allpairs.log 2>&1
 say "projections, N = 2^20"
-python bench.py --no-cpu --no-side-runs --steps 30 --warmup 5 > $out/one_n20_s30.json 2> /dev/null
+python bench.py --full --no-cpu --no-side-runs --steps 30 --warmup 5 > $out/one_n20_s30.json 2> /dev/null
 for w in 2 4 8; do python bench.py --sim-world $w --steps 30 --warmup 5 > $out/sim${w}_n20.json 2> $out/sim${w}_n20.err; done
 say "projections, N = 2^22 in 24^3 cells"
-python bench.py --no-cpu --no-side-runs --steps 30 --warmup 5 --n 4194304 --chunk-factor 6 > $out/one_n22_grid24_s30.json 2> /dev/null
+python bench.py --full --no-cpu --no-side-runs --steps 30 --warmup 5 --n 4194304 --chunk-factor 6 > $out/one_n22_grid24_s30.json 2> /dev/null
 python bench.py --sim-world 8 --steps 30 --warmup 5 --n 4194304 --chunk-factor 6 > $out/sim8_n22_grid24.json 2> $out/sim8_n22.err
 say "projections, N = 2^24 in 40^3 cells (BASELINE configs[4])"
-python bench.py --no-cpu --no-side-runs --steps 8 --warmup 2 --n 16777216 --chunk-factor 10 > $out/one_n24_grid40.json 2> $out/one_n24.err
+python bench.py --full --no-cpu --no-side-runs --steps 8 --warmup 2 --n 16777216 --chunk-factor 10 > $out/one_n24_grid40.json 2> $out/one_n24.err
 python bench.py --sim-world 8 --steps 8 --warmup 2 --n 16777216 --chunk-factor 10 > $out/sim8_n24_grid40.json 2> $out/sim8_n24.err
 say "all-pairs across eight ranks (BASELINE configs[3]'s exchange), N = 2^20"
-python bench.py --all-pairs --n 1048576 --no-cpu --no-side-runs --steps 3 --warmup 1 > $out/ap_n20_one.json 2> /dev/null
+python bench.py --full --all-pairs --n 1048576 --no-cpu --no-side-runs --steps 3 --warmup 1 > $out/ap_n20_one.json 2> /dev/null
 python bench.py --sim-world 8 --all-pairs --n 1048576 --steps 3 --warmup 1 > $out/ap_n20_sim8.json 2> $out/ap_n20_sim8.err
 say "the C++ host: eight slabs in one process, every message through RCCL (loopback)"
 for v in "0 1" "1 1" "0 0"; do set -- $v

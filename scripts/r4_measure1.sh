@@ -3,7 +3,7 @@
 set -o pipefail
 O=gpurun_out
 python -m pytest tests/test_gpu_bench_multi.py -m gpu -x -q > $O/r4_t4.log 2>&1; tail -3 $O/r4_t4.log
-python bench.py --steps 20 > $O/r4_bench_steps20.json 2> $O/r4_bench_steps20.err; tail -c 600 $O/r4_bench_steps20.json; echo
+python bench.py --full --steps 20 > $O/r4_bench_steps20.json 2> $O/r4_bench_steps20.err; tail -c 600 $O/r4_bench_steps20.json; echo
 python bench.py --no-side-runs --no-cpu > $O/r4_bench_plain.json 2>> $O/r4_bench_steps20.err
 python bench.py --no-side-runs --no-cpu --graphs > $O/r4_bench_graphs.json 2>> $O/r4_bench_steps20.err
 for g in 1 0; do for s in 1 0; do

@@ -15,6 +15,7 @@ stored):
   ref_pairs.npz       bodyBodyInteraction / bodyBodyCollision known answers
   ref_accumulate.npz  serial fp32 accumulation over long neighbour lists (order matters)
   ref_queue.npz       a q_insert / q_remove script with every return value
+  ref_vs_oracle.npz   (--vs-oracle, alone) the answers to tests/test_oracle_vs_ref.py's seeded inputs
   g2_cloud_n4096_seed12345.f32  (made by gen_cloud.cpp)
 """
 import ctypes as C
@@ -218,5 +219,14 @@ def main():
     print("golden vectors written to", HERE)
 
 
+def vs_oracle():
+    """ref_vs_oracle.npz: what the reference returns for the seeded inputs of tests/test_oracle_vs_ref.py (which builds
+    them; field-wise, but the state helpers' records as the bytes they come back as, pad bytes included)"""
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    import test_oracle_vs_ref as T
+    np.savez_compressed(os.path.join(HERE, "ref_vs_oracle.npz"), **T.reference_answers())
+    print("reference answers written to", os.path.join(HERE, "ref_vs_oracle.npz"))
+
+
 if __name__ == "__main__":
-    main()
+    vs_oracle() if "--vs-oracle" in sys.argv else main()

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -104,12 +105,12 @@ def _bench(args, env_extra=None, timeout=560):
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_one_gpu_through_the_cpp_host_agrees_with_the_python_host():
-    """The whole scaling curve is driven by ONE host: `bench.py --gpus 1` goes through host/ps_ring_rccl --world 1 by
-    default.  Its figure must be the Python host's (psamd_step through ctypes) within 2 % -- same kernels, and neither
+    """The whole scaling curve can be driven by ONE host: `bench.py --gpus 1 --host ring` goes through host/ps_ring_rccl
+    --world 1.  Its figure must be the Python host's (psamd_step through ctypes) within 2 % -- same kernels, and neither
     host is on the step's critical path; measured 0.6-0.9 % apart on one box, profiles/r5_ab_host.txt, of which 0.35 %
     are the C++ host's own stage events on every eighth step -- and its record must be the full one-GPU line."""
     common = ["--gpus", "1", "--steps", "150", "--warmup", "5", "--no-side-runs", "--no-cpu"]
-    ring, _ = _bench(common)                                   # (--host ring is the default)
+    ring, _ = _bench(common + ["--host", "ring"])
     py, _ = _bench(common + ["--host", "python"])
     assert "C++ ranks" in ring["config"]["host"] and "ring_failed" not in ring and "Python" in py["config"]["host"]
     assert ring["n_gpus"] == py["n_gpus"] == 1 and ring["steps"] == py["steps"] == 150
@@ -126,14 +127,53 @@ def test_one_gpu_through_the_cpp_host_agrees_with_the_python_host():
 @pytest.mark.gpu
 @pytest.mark.timeout(600)
 def test_the_drivers_form_of_the_bench_runs_through_the_cpp_host():
-    """`bench.py --steps 20 --warmup 5` -- what the driver runs at round end -- must be served by the C++ host and not by
+    """`bench.py --steps 20 --warmup 5 --host ring` -- the driver's form on the C++ host -- must be served by it and not by
     the fallback: a timed region whose length is no multiple of the timing period leaves stage events unrecorded, and
     asking those for their time once left a HIP error behind that failed the next launch (the ranks fell back, quietly)."""
     for steps in ("20", "50"):
-        d, _ = _bench(["--gpus", "1", "--steps", steps, "--warmup", "5", "--no-side-runs", "--no-cpu"])
+        d, _ = _bench(["--gpus", "1", "--steps", steps, "--warmup", "5", "--no-side-runs", "--no-cpu", "--full", "--host", "ring"])
         assert "C++ ranks" in d["config"]["host"] and "FALLBACK" not in d["config"]["host"] and "ring_failed" not in d, d["config"]["host"]
         assert d["steps"] == int(steps) and d["rccl_ranks"] == 1
         assert d["sustained"] and abs(d["sustained"]["ms_per_step"] / d["ms_per_step"] - 1.0) < 0.05
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(600)
+def test_plain_run_is_lean_and_dumps_what_the_last_step_left(tmp_path):
+    """A plain run times --steps steps in this process through libpsamd.so and nothing beside them (no sustained region,
+    side runs or CPU figures: --full's); --dump-outputs writes the state the last timed step left, float32 / float64 only,
+    and a second run with the same arguments writes the same bytes -- which are those of one step of the same cloud in
+    a context of its own (every timed step replays one step from the restored snapshot)."""
+    import particlesystem_amd as ps
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 131072
+    common = ["--gpus", "1", "--n", str(n), "--steps", "7", "--warmup", "2", "--settle-seconds", "0.05"]
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        d, _ = _bench(common + ["--dump-outputs", str(out)])
+        assert d["steps"] == 7 and d["ms_per_step"] > 0 and d["config"]["updates_in_timed_region"] == 7 * n
+        assert "this Python process" in d["config"]["host"] and "FALLBACK" not in d["config"]["host"]
+        assert d["sustained"] is None and d["cpu_baseline"] is None and "lifecycle_off" not in d and "cpu_baseline_many_threads" not in d
+        assert sorted(os.listdir(out)) == ["particle_slots.npy", "particles_float.npy", "particles_int.npy", "queue.npy", "queue_info.npy"]
+        a = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+        assert a["particles_float"].shape == (len(a["particle_slots"]), 12) and a["particles_int"].shape == (len(a["particle_slots"]), 7)
+        dumps.append(a)
+    assert all(dumps[0][k].tobytes() == dumps[1][k].tobytes() for k in dumps[0])
+    # the same step on a fresh context, written the same way
+    g = ps.ParticleSystem(ps.default_config(device=0, chunk_factor=4, chunk_dim=4, max_particles_num=1 << 20))
+    g.set_tdata_mirror(False)
+    xyz, age, fert = bench.make_inputs(g, n, 2026)
+    g.fill_particles(xyz, age=age, fert_age=fert)
+    g.snapshot_save()
+    g.snapshot_restore()
+    g.step(1)
+    bench.write_outputs(str(tmp_path / "one"), g.download_particles(), *g.download_queues())
+    g.close()
+    for k in dumps[0]:
+        assert np.load(tmp_path / "one" / (k + ".npy")).tobytes() == dumps[0][k].tobytes(), k
 
 
 @pytest.mark.gpu

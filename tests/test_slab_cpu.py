@@ -279,3 +279,19 @@ def test_bench_launcher_ends_the_job_when_a_rank_dies():
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=100)
     assert p.returncode == 3, (p.returncode, p.stderr[-1000:])
     assert not [l for l in p.stdout.splitlines() if l.startswith("{")]
+
+
+@pytest.mark.timeout(120)
+def test_bench_refuses_to_dump_outputs_it_cannot_read(tmp_path):
+    """--dump-outputs writes the state of the whole system, which only a one-GPU run holds in one place: with --gpus 2
+    bench.py says so and exits before it starts anything; likewise with --host ring."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs", str(tmp_path / "out")],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=100)
+    assert p.returncode == 2 and "--dump-outputs: one GPU only" in p.stderr, (p.returncode, p.stderr[-1000:])
+    assert not p.stdout and not (tmp_path / "out").exists()
+    # ... nor where the timed loop runs in another program, whose state this process cannot read
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--host", "ring", "--dump-outputs", str(tmp_path / "out")],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=100)
+    assert p.returncode == 2 and "not with --host ring" in p.stderr, (p.returncode, p.stderr[-1000:])
+    assert not p.stdout and not (tmp_path / "out").exists()

@@ -10,9 +10,12 @@
 // then the fill stage (task 5) places the particles in order.
 //
 // usage: ps_driver [--n N | --cloud file.f32] [--iters K] [--dt DT] [--seed S]
-//                  [--fetch-back] [--age A] [--describe]
+//                  [--fetch-back] [--age A] [--describe] [--frames DIR [--frame-every K]]
 //   --cloud    raw little-endian float32 x,y,z triples (tests/golden/g2_cloud_*.f32)
 //   --describe host-only: print the sizes DoInit derives and exit (no GPU needed)
+//   --frames   after every K-th iteration (default 1) write DIR/frame_<iteration>.bin: the live particles as
+//              psamd_download_live hands them out -- int64 count, then count float4 (x, y, z, w), then count int32
+//              global slot ids, in slot order.  How a front end takes frames out of the library.
 // Last line of output: "state-hash <16 hex digits> live <n>", a digest of the P_DATA_TYPE
 // records of every slot (pad bytes excluded), for comparison with the oracle.
 #include <algorithm>
@@ -65,6 +68,25 @@ uint64_t state_digest(const std::vector<Particle72> &p)
     return h;
 }
 
+// One frame: the live particles' positions and ids (psamd_download_live copies only those across PCIe).
+int write_frame(psamd_ctx *ctx, const std::string &dir, int iter, int64_t slots, std::vector<float> &pos, std::vector<int32_t> &id)
+{
+    pos.resize((size_t)slots * 4);
+    id.resize((size_t)slots);
+    int64_t count = 0;
+    const int rc = psamd_download_live(ctx, PSAMD_EXPORT_POS | PSAMD_EXPORT_ID, pos.data(), nullptr, nullptr, id.data(), nullptr,
+                                       slots, &count);
+    if (rc != PSAMD_OK) return rc;
+    const std::string path = dir + "/frame_" + std::to_string(iter) + ".bin";
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return PSAMD_ERR_INVALID_ARG; }
+    const size_t n = (size_t)std::min(count, slots);
+    const bool ok = std::fwrite(&count, sizeof count, 1, f) == 1 && std::fwrite(pos.data(), 4 * sizeof(float), n, f) == n &&
+                    std::fwrite(id.data(), sizeof(int32_t), n, f) == n;
+    if (std::fclose(f) != 0 || !ok) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return PSAMD_ERR_INVALID_ARG; }
+    return PSAMD_OK;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -75,7 +97,8 @@ int main(int argc, char **argv)
     uint32_t seed = 12345;
     bool fetch_back = false, describe = false;
     float age0 = -1.0f;
-    std::string cloud;
+    std::string cloud, frames;
+    int frame_every = 1;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
@@ -87,6 +110,8 @@ int main(int argc, char **argv)
         else if (a == "--age") age0 = (float)std::atof(next());
         else if (a == "--fetch-back") fetch_back = true;
         else if (a == "--describe") describe = true;
+        else if (a == "--frames") frames = next();
+        else if (a == "--frame-every") frame_every = std::max(1, std::atoi(next()));
         else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
 
@@ -142,6 +167,8 @@ int main(int argc, char **argv)
         hostCellgrid.resize((size_t)sz.n_cellgrid);
     }
     int32_t hostGridMax[2] = {0, 0};
+    std::vector<float> framePos;       // --frames
+    std::vector<int32_t> frameId;
 
     const double lStartTime = now_secs();
     for (int niter = 0; niter < iters; niter++) {
@@ -175,6 +202,8 @@ int main(int argc, char **argv)
         const double time3 = now_secs();
         std::printf(">>>>>>>>>>> Execution time of iteration (sec): \n%f\n%f\n%f\n%f\n\n\n\n", time3 - time0, time1 - time0,
                     time2 - time1, time3 - time2);
+        if (!frames.empty() && (niter + 1) % frame_every == 0)
+            CHECK(write_frame(ctx, frames, niter + 1, sz.container_size, framePos, frameId));
     }
     const double lEndTime = now_secs();
     std::printf("total %f s for %d iterations\n", lEndTime - lStartTime, iters);

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PSAMD_ABI_VERSION 6
+#define PSAMD_ABI_VERSION 7
 
 #define PSAMD_MAX_RANKS 64
 
@@ -144,6 +144,43 @@ typedef struct psamd_device_view {
     int64_t  sorted_cap;  /* plane stride of snap_soa, in floats                */
     void    *stream;      /* hipStream_t the stages are enqueued on            */
 } psamd_device_view;
+
+/* Fields of psamd_export_live / psamd_download_live (the bits of `fields`) */
+#define PSAMD_EXPORT_POS  0x1u   /* float4 x,y,z,w                 */
+#define PSAMD_EXPORT_VEL  0x2u   /* float4 vx,vy,vz,age            */
+#define PSAMD_EXPORT_ACC  0x4u   /* float4 ax,ay,az,fertility_age  */
+#define PSAMD_EXPORT_ID   0x8u   /* int32 global slot id (P_DATA_TYPE.id) */
+#define PSAMD_EXPORT_CELL 0x10u  /* int32 cell                     */
+#define PSAMD_EXPORT_ALL  0x1fu
+
+/* Statistics of the live particles.  Every term is formed in fp64 from the fp32 fields; a particle whose position or
+ * velocity (x, y, z, vx, vy, vz) is not a finite number counts in `live` and `nonfinite` and nowhere else.  The sums
+ * run in a fixed order (a fixed tree inside each tile of 4096 owned slots, then the tiles in index order), so they are
+ * the same bits from run to run, with graphs on or off, for a given context geometry.  No live particle: the sums
+ * are 0, lo / age_min are +inf and hi / age_max are -inf. */
+typedef struct psamd_live_stats {
+    int64_t live;
+    int64_t nonfinite;
+    double  mass;            /* sum w                                   */
+    double  momentum[3];     /* sum w*v                                 */
+    double  kinetic;         /* sum 0.5*w*|v|^2                         */
+    double  mass_moment[3];  /* sum w*x: the centre of mass is mass_moment / mass */
+    double  lo[3], hi[3];    /* bounding box of the positions           */
+    double  age_min, age_max, age_sum;
+} psamd_live_stats;
+
+/* What psamd_export_live writes and where (device pointers).  A field whose bit is set needs its pointer (float4
+ * arrays 16-byte aligned, int32 arrays 4-byte aligned, `capacity` entries each); the pointer of a field that is not
+ * asked for is ignored.  count_dev / stats_dev: optional; NULL = not wanted. */
+typedef struct psamd_export {
+    uint32_t fields;          /* PSAMD_EXPORT_* bits                    */
+    int32_t  reserved;        /* 0                                      */
+    void    *pos4, *vel4, *acc4;
+    void    *id, *cell;
+    int64_t  capacity;        /* entries the arrays hold                */
+    int64_t *count_dev;       /* int64: the number of live particles    */
+    psamd_live_stats *stats_dev;
+} psamd_export;
 
 typedef struct psamd_ctx psamd_ctx;
 
@@ -364,6 +401,35 @@ int psamd_get_graph_stats(psamd_ctx *ctx, int64_t *launches, int64_t *captures);
  * 5-us naps (default of a slab: a node's eight ranks do not pin eight cores).  While it naps the library lowers the
  * calling thread's timer slack (prctl PR_SET_TIMERSLACK) to 1 us and restores the old value before the call returns. */
 int psamd_set_wait_policy(psamd_ctx *ctx, int policy);
+
+/* ---- getting frames out ---------------------------------------------------- */
+/* The live particles (0 <= cell < num_cells, what psamd_live_count counts; the mid-step encodings cell <= -2 are not
+ * live) as compact arrays in ascending global slot id, one array per field, with their count and statistics: a frame
+ * for a renderer, an analysis or a checkpoint, without the whole container (psamd_download_particles packs every slot,
+ * free ones included, into 72-byte records).  The first min(count, capacity) live particles are written; the count
+ * is always the full one.  Entry k equals, field for field and bit for bit, the k-th record of
+ * psamd_download_particles filtered by the same predicate at the same point of the stream.
+ *
+ * psamd_export_live: enqueued on the context's stream (psamd_get_stream) and nothing else -- it allocates nothing,
+ * waits for nothing and reads nothing back, so it may be captured into a graph.  It sees the state that the work
+ * enqueued before it leaves behind: after psamd_step(ctx, n) it sees step n, also with run-ahead 1 and graphs on.
+ * The arrays, *count_dev and *stats_dev are written by the time the stream reaches the end of the export.  The
+ * launches cover every owned slot; the cost is about two passes over the live particles' fields plus the cell array.
+ * PSAMD_ERR_INVALID_ARG: a NULL context or spec, unknown field bits, reserved != 0, capacity < 0, or a field asked for
+ * with a NULL or misaligned pointer.  PSAMD_ERR_STATE: the context is wedged.
+ *
+ * A slab (world > 1) exports its own slots, with their global ids; the union of the ranks' exports sorted by id is
+ * the export of one context that holds the whole system, and psamd_live_stats of the ranks combine by adding the
+ * counts and sums and taking the minima and maxima (sums then agree to rounding, not to the bit).
+ *
+ * psamd_download_live: the same into host arrays (`capacity` entries each, a NULL pointer where the field is not
+ * asked for); only the min(count, capacity) entries cross PCIe.  *count (required) = the full count.  Waits for the
+ * context's stream.
+ * psamd_live_stats_get: the statistics alone, into host memory; waits for the context's stream. */
+int psamd_export_live(psamd_ctx *ctx, const psamd_export *spec);
+int psamd_download_live(psamd_ctx *ctx, uint32_t fields, void *pos4, void *vel4, void *acc4, int32_t *id,
+                        int32_t *cell, int64_t capacity, int64_t *count);
+int psamd_live_stats_get(psamd_ctx *ctx, psamd_live_stats *out);
 
 /* ---- introspection -------------------------------------------------------- */
 int psamd_get_counters(psamd_ctx *ctx, psamd_counters *out);

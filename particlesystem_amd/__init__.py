@@ -20,7 +20,7 @@ from . import build as _build
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PSAMD_LIB") or os.path.join(HERE, "libpsamd.so")   # PSAMD_LIB: another build, for A/B measurements
 
-ABI_VERSION = 6         # the struct layouts below are include/psamd.h's at this PSAMD_ABI_VERSION
+ABI_VERSION = 7         # the struct layouts below are include/psamd.h's at this PSAMD_ABI_VERSION
 MAX_RANKS = 64
 FLAG_EXPLOSIONS = 0x1
 FLAG_FAST_MATH = 0x2
@@ -100,6 +100,53 @@ class SlabBuffers(C.Structure):
                 ("far_out", C.c_void_p), ("far_in", C.c_void_p), ("far_bytes", C.c_int64), ("xfer_bytes_max", C.c_int64)]
 
 
+# psamd_export_live / psamd_download_live: the fields (bits of `fields`)
+EXPORT_POS, EXPORT_VEL, EXPORT_ACC, EXPORT_ID, EXPORT_CELL = 0x1, 0x2, 0x4, 0x8, 0x10
+EXPORT_ALL = 0x1F
+_EXPORT_FIELDS = (("pos4", EXPORT_POS, 4, np.float32), ("vel4", EXPORT_VEL, 4, np.float32), ("acc4", EXPORT_ACC, 4, np.float32),
+                  ("id", EXPORT_ID, 1, np.int32), ("cell", EXPORT_CELL, 1, np.int32))
+
+
+class LiveStats(C.Structure):
+    """psamd_live_stats: count and fp64 statistics of the live particles."""
+    _fields_ = [("live", C.c_int64), ("nonfinite", C.c_int64), ("mass", C.c_double), ("momentum", C.c_double * 3),
+                ("kinetic", C.c_double), ("mass_moment", C.c_double * 3), ("lo", C.c_double * 3), ("hi", C.c_double * 3),
+                ("age_min", C.c_double), ("age_max", C.c_double), ("age_sum", C.c_double)]
+
+    def to_dict(self):
+        out = {}
+        for n, t in self._fields_:
+            v = getattr(self, n)
+            out[n] = np.array(v[:], np.float64) if hasattr(t, "_length_") else v
+        return out
+
+
+class Export(C.Structure):
+    """psamd_export: what psamd_export_live writes and where (device pointers)."""
+    _fields_ = [("fields", C.c_uint32), ("reserved", C.c_int32),
+                ("pos4", C.c_void_p), ("vel4", C.c_void_p), ("acc4", C.c_void_p), ("id", C.c_void_p), ("cell", C.c_void_p),
+                ("capacity", C.c_int64), ("count_dev", C.c_void_p), ("stats_dev", C.c_void_p)]
+
+
+def merge_live_stats(stats):
+    """The statistics of a system from its ranks' (dicts of live_stats() / export_live()["stats"]): counts and sums
+    add, in rank order; the box and the ages take the minima and maxima."""
+    stats = list(stats)
+    out = {}
+    for n, _ in LiveStats._fields_:
+        vals = [np.asarray(s[n], np.float64) for s in stats]
+        if n in ("lo", "age_min"):
+            v = np.minimum.reduce(vals)
+        elif n in ("hi", "age_max"):
+            v = np.maximum.reduce(vals)
+        else:
+            v = vals[0]
+            for x in vals[1:]:
+                v = v + x
+        out[n] = int(v) if n in ("live", "nonfinite") else (v if v.ndim else float(v))
+    return out
+
+
 # psamd_slab_msg_download / _upload `which`
 MSG_HALO_OUT, MSG_HALO_IN, MSG_FORCE_OUT, MSG_FORCE_IN, MSG_XFER_OUT, MSG_XFER_IN, MSG_STATUS_OUT, MSG_STATUS_IN = 0, 2, 4, 5, 6, 8, 10, 11
 MSG_ALLG_OUT, MSG_ALLG_IN = 12, 13
@@ -176,6 +223,9 @@ ABI = [
     ("psamd_get_timing_stats", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64)]),
     ("psamd_set_run_ahead", C.c_int, [_vp, C.c_int]),
     ("psamd_set_tdata_mirror", C.c_int, [_vp, C.c_int]),
+    ("psamd_export_live", C.c_int, [_vp, C.POINTER(Export)]),
+    ("psamd_download_live", C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
+    ("psamd_live_stats_get", C.c_int, [_vp, C.POINTER(LiveStats)]),
 ]
 
 _lib = None
@@ -465,6 +515,67 @@ class ParticleSystem:
         n = C.c_int64()
         self._ck(self.lib.psamd_live_count(self.h, C.byref(n)))
         return n.value
+
+    # ---- getting frames out (include/psamd.h) --------------------------------
+    def stream(self):
+        """the hipStream_t the context enqueues on, as an integer"""
+        p = C.c_void_p()
+        self._ck(self.lib.psamd_get_stream(self.h, C.byref(p)))
+        return p.value or 0
+
+    def owned_slots(self):
+        """slots this context holds (the whole container on one context): the most live particles it can have"""
+        return int(self.device_view().container_size)
+
+    def export_live(self, fields, capacity=None):
+        """psamd_export_live into fresh torch device tensors: {"count": n, "stats": dict, field: tensor sliced to
+        min(n, capacity)} for the fields asked for ("pos4", "vel4", "acc4": float32 [k, 4]; "id", "cell": int32 [k]).
+        Waits for the context's stream before it returns.  torch must have been imported before the library was loaded
+        (tests/conftest.py does) so that both use one HIP runtime."""
+        import torch
+        capacity = self.owned_slots() if capacity is None else int(capacity)
+        dev = torch.device("cuda", int(self.cfg.device))
+        spec = Export(fields=int(fields), capacity=capacity)
+        out = {}
+        for name, bit, width, dt in _EXPORT_FIELDS:
+            if fields & bit:
+                t = torch.empty((max(capacity, 1), width) if width > 1 else (max(capacity, 1),),
+                                dtype=torch.float32 if dt is np.float32 else torch.int32, device=dev)
+                out[name] = t
+                setattr(spec, name, t.data_ptr())
+        count = torch.zeros(1, dtype=torch.int64, device=dev)
+        stats = torch.zeros(C.sizeof(LiveStats), dtype=torch.uint8, device=dev)
+        spec.count_dev, spec.stats_dev = count.data_ptr(), stats.data_ptr()
+        st = torch.cuda.ExternalStream(self.stream(), device=dev)
+        st.wait_stream(torch.cuda.current_stream(dev))        # (the tensors are torch's: the export follows their allocation)
+        self._ck(self.lib.psamd_export_live(self.h, C.byref(spec)))
+        st.synchronize()
+        n = int(count.item())
+        res = {name: t[:min(n, capacity)] for name, t in out.items()}
+        res["count"] = n
+        res["stats"] = LiveStats.from_buffer_copy(stats.cpu().numpy().tobytes()).to_dict()
+        return res
+
+    def download_live(self, fields, capacity=None):
+        """psamd_download_live: {"count": n, field: numpy array of min(n, capacity) entries} (fields as export_live)"""
+        capacity = self.owned_slots() if capacity is None else int(capacity)
+        arrs = {}
+        ptrs = []
+        for name, bit, width, dt in _EXPORT_FIELDS:
+            if fields & bit:
+                arrs[name] = np.zeros((capacity, width) if width > 1 else capacity, dt)
+            ptrs.append(_ptr(arrs.get(name)))
+        n = C.c_int64()
+        self._ck(self.lib.psamd_download_live(self.h, int(fields), *ptrs, capacity, C.byref(n)))
+        res = {name: a[:min(n.value, capacity)] for name, a in arrs.items()}
+        res["count"] = n.value
+        return res
+
+    def live_stats(self):
+        """psamd_live_stats_get as a dict (momentum, mass_moment, lo, hi: float64 arrays of 3)"""
+        s = LiveStats()
+        self._ck(self.lib.psamd_live_stats_get(self.h, C.byref(s)))
+        return s.to_dict()
 
     def device_view(self):
         v = DeviceView()

@@ -597,6 +597,9 @@ int psamd_create(const psamd_config *cfg, psamd_ctx **out)
     PS_HIP(c, dev_alloc(c, &d.moves, (size_t)d.moves_cap));
     PS_HIP(c, dev_alloc(c, &d.stage, 3 * (size_t)d.moves_cap));
     PS_HIP(c, dev_alloc(c, &d.ctr, (size_t)COUNTER_COPIES));
+    PS_HIP(c, dev_alloc(c, &d.exp_count, (size_t)export_tiles(P.slots_total)));     // psamd_export_live's scratch
+    PS_HIP(c, dev_alloc(c, &d.exp_tiles, (size_t)export_tiles(P.slots_total)));
+    PS_HIP(c, dev_alloc(c, &d.exp_out, 1));
     PS_HIP(c, dev_alloc(c, &d.trace, 3 * (LC * P.slices + 4)));
     PS_HIP(c, hipMemsetAsync(d.trace, 0, 3 * (LC * P.slices + 4) * sizeof(unsigned long long), c->stream));
 
@@ -1743,6 +1746,83 @@ int psamd_device_view_get(psamd_ctx *c, psamd_device_view *o)
     o->container_size = c->P.slots_total; o->num_cells = c->P.n_own_cells;
     o->live = c->live_at_build;
     o->stream = (void *)c->stream;
+    return PSAMD_OK;
+}
+
+// ---- getting frames out (export.hip) ----
+static const uint32_t export_bits[5] = {PSAMD_EXPORT_POS, PSAMD_EXPORT_VEL, PSAMD_EXPORT_ACC, PSAMD_EXPORT_ID, PSAMD_EXPORT_CELL};
+static const size_t export_size[5] = {sizeof(float4), sizeof(float4), sizeof(float4), sizeof(int32_t), sizeof(int32_t)};
+
+// device: the kernel stores to the arrays (float4 and int32 stores want their natural alignment); host arrays are copied into
+static int export_args(psamd_ctx *c, uint32_t fields, void *const ptr[5], int64_t capacity, bool device)
+{
+    if (fields & ~PSAMD_EXPORT_ALL) return fail(c, PSAMD_ERR_INVALID_ARG, "export: unknown field bits");
+    if (capacity < 0) return fail(c, PSAMD_ERR_INVALID_ARG, "export: capacity < 0");
+    for (int k = 0; k < 5; k++)
+        if ((fields & export_bits[k]) && (!ptr[k] || (device && (uintptr_t)ptr[k] % export_size[k] != 0)))
+            return fail(c, PSAMD_ERR_INVALID_ARG, "export: a field asked for has a null or misaligned pointer");
+    return PSAMD_OK;
+}
+
+static ExportFields export_fields(uint32_t fields, void *const ptr[5])
+{
+    void *p[5];
+    for (int k = 0; k < 5; k++) p[k] = (fields & export_bits[k]) ? ptr[k] : nullptr;
+    return ExportFields{(float4 *)p[0], (float4 *)p[1], (float4 *)p[2], (int *)p[3], (int *)p[4]};
+}
+
+int psamd_export_live(psamd_ctx *c, const psamd_export *spec)
+{
+    if (!c || !spec) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    void *const ptr[5] = {spec->pos4, spec->vel4, spec->acc4, spec->id, spec->cell};
+    if (spec->reserved != 0) return fail(c, PSAMD_ERR_INVALID_ARG, "export: reserved must be 0");
+    const int rc = export_args(c, spec->fields, ptr, spec->capacity, true);
+    if (rc != PSAMD_OK) return rc;
+    PS_HIP(c, launch_export_live(c->stream, c->P, c->d, export_fields(spec->fields, ptr), spec->capacity,
+                                 spec->count_dev ? spec->count_dev : &c->d.exp_out->count,
+                                 spec->stats_dev ? spec->stats_dev : &c->d.exp_out->stats));
+    return PSAMD_OK;
+}
+
+int psamd_download_live(psamd_ctx *c, uint32_t fields, void *pos4, void *vel4, void *acc4, int32_t *id, int32_t *cell,
+                        int64_t capacity, int64_t *count)
+{
+    if (!c || !count) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    void *const host[5] = {pos4, vel4, acc4, id, cell};
+    int rc = export_args(c, fields, host, capacity, false);
+    if (rc != PSAMD_OK) return rc;
+    // the chosen fields of at most min(capacity, owned slots) particles, one after the other in the staging buffer
+    const int64_t n = std::min<int64_t>(capacity, c->P.slots_total);
+    size_t off[5] = {0, 0, 0, 0, 0}, bytes = 0;
+    for (int k = 0; k < 5; k++)
+        if (fields & export_bits[k]) { off[k] = bytes; bytes += ((size_t)n * export_size[k] + 255) / 256 * 256; }
+    rc = ensure_staging(c, std::max<size_t>(bytes, 256));
+    if (rc != PSAMD_OK) return rc;
+    void *dev[5];
+    for (int k = 0; k < 5; k++) dev[k] = (char *)c->staging + off[k];
+    PS_HIP(c, launch_export_live(c->stream, c->P, c->d, export_fields(fields, dev), n, &c->d.exp_out->count, &c->d.exp_out->stats));
+    int64_t total = 0;
+    PS_HIP(c, hipMemcpyAsync(&total, &c->d.exp_out->count, sizeof total, hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t got = (size_t)std::min<int64_t>(total, n);
+    if (got > 0)
+        for (int k = 0; k < 5; k++)
+            if (fields & export_bits[k]) PS_HIP(c, hipMemcpyAsync(host[k], dev[k], got * export_size[k], hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    *count = total;
+    return PSAMD_OK;
+}
+
+int psamd_live_stats_get(psamd_ctx *c, psamd_live_stats *out)
+{
+    if (!c || !out) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    PS_HIP(c, launch_export_live(c->stream, c->P, c->d, ExportFields{nullptr, nullptr, nullptr, nullptr, nullptr}, 0,
+                                 &c->d.exp_out->count, &c->d.exp_out->stats));
+    PS_HIP(c, hipMemcpyAsync(out, &c->d.exp_out->stats, sizeof *out, hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
     return PSAMD_OK;
 }
 

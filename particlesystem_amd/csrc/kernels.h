@@ -3,10 +3,33 @@
 
 #include <hip/hip_runtime.h>
 
+#include "../../include/psamd.h"
 #include "device_types.h"
 #include "geometry.hpp"
 
 namespace psamd {
+
+// psamd_export_live (export.hip): the owned slots in tiles of EXPORT_TILE; pass A leaves per tile its live count
+// (DeviceState::exp_count) and these partials of the statistics (fp64 sums: mass, momentum x y z, kinetic energy,
+// mass moment x y z, age; fp32 extrema: x, y, z, age)
+constexpr int EXPORT_TILE = 4096;
+constexpr int EXPORT_SUMS = 9;
+struct __align__(16) ExportTile {
+    double sum[EXPORT_SUMS];
+    float lo[4], hi[4];
+    int nonfinite, pad;
+};
+inline int export_tiles(int slots_total) { return (slots_total + EXPORT_TILE - 1) / EXPORT_TILE; }
+// where the chosen fields go (null: not wanted)
+struct ExportFields {
+    float4 *pos4, *vel4, *acc4;
+    int *id, *cell;
+};
+// the count and statistics of psamd_download_live / psamd_live_stats_get (a caller of psamd_export_live may give its own)
+struct ExportOut {
+    int64_t count;
+    psamd_live_stats stats;
+};
 
 // Container layout by segment type (slots and QUEUE_INFO records), device copy.
 struct SegLayout {
@@ -85,6 +108,10 @@ struct DeviceState {
     int *dense_gi = nullptr;      // all-pairs: [container] sorted index of the r-th particle that needs a force (cell order)
     int *dense_cell = nullptr;    // all-pairs: [container] its cell
     DevCounters *ctr = nullptr;
+    // psamd_export_live: per tile of EXPORT_TILE owned slots, the live count and the statistics' partials; the context's own result record
+    int *exp_count = nullptr;
+    ExportTile *exp_tiles = nullptr;
+    ExportOut *exp_out = nullptr;
     unsigned long long *trace = nullptr;  // 3 words per pair-kernel wave slot (diagnostic builds only)
 };
 
@@ -137,5 +164,10 @@ hipError_t launch_chunk_census(hipStream_t st, const DevParams &P, const DeviceS
 // status records of all ranks (error bits, cell-overflow kills, the transfer messages' next capacity) + the force records of the lent-out layers (force_msg, may be null)
 hipError_t launch_status_merge(hipStream_t st, const DevParams &P, const DeviceState &d, const int *status_all,
                                int force_j0, const int *force_msg, const int *pack_off);
+
+// psamd_export_live: pass A over every owned slot, then pass B (the chosen fields of the first `capacity` live particles in
+// slot order; workgroup 0 writes the count and the statistics)
+hipError_t launch_export_live(hipStream_t st, const DevParams &P, const DeviceState &d, const ExportFields &out,
+                              int64_t capacity, int64_t *count_out, psamd_live_stats *stats_out);
 
 }  // namespace psamd

@@ -110,8 +110,8 @@ struct Ring {
     bool loopback = false, overlap_interior = false;
     int side = 0;                       // 0: every RCCL call on the compute stream (default); 1: what has compute to travel beside goes on the transfer stream; 2: everything does (round 4)
     ncclComm_t comm = nullptr;
-    bool compute_owned = true;          // (false: the compute stream is the first context's own)
-    hipStream_t compute = nullptr, transfer = nullptr;      // (transfer == compute without --no-side-stream's opposite)
+    hipStream_t compute = nullptr;      // the first context's own stream
+    hipStream_t transfer = nullptr;     // a stream of this program's (--side-stream 1 or 2), else the compute stream
     hipEvent_t ev_built = nullptr, ev_halo = nullptr, ev_paired = nullptr, ev_force = nullptr, ev_applied = nullptr, ev_xfer = nullptr;
     std::vector<Slab> local;            // the slabs this process holds (one per process in a real run; all of them in loopback mode, where every peer is comm rank 0)
     int64_t moved = 0;
@@ -447,9 +447,7 @@ int main(int argc, char **argv)
     R.world = world; R.loopback = loopback; R.side = side_stream; R.overlap_interior = overlap_interior;
     if (!no_gpu) {
         HIP_OK(hipSetDevice(device));
-        HIP_OK(hipStreamCreateWithFlags(&R.compute, hipStreamNonBlocking));
         if (side_stream) HIP_OK(hipStreamCreateWithFlags(&R.transfer, hipStreamNonBlocking));
-        else R.transfer = R.compute;
         for (hipEvent_t *e : {&R.ev_built, &R.ev_halo, &R.ev_paired, &R.ev_force, &R.ev_applied, &R.ev_xfer}) HIP_OK(hipEventCreateWithFlags(e, hipEventDisableTiming));
     }
 
@@ -507,8 +505,7 @@ int main(int argc, char **argv)
         }
         return 0;
     }
-    const bool no_comm = comm_world == 1 && !loopback && std::getenv("PSAMD_RING_NO_RCCL") != nullptr;      // (A/B: a world of one without a communicator)
-    if (!no_comm) NCCL_OK(ncclCommInitRank(&R.comm, comm_world, id, comm_rank));
+    NCCL_OK(ncclCommInitRank(&R.comm, comm_world, id, comm_rank));
     g_comm = R.comm;
     if (comm_rank == 0 && !id_file.empty()) std::remove(id_file.c_str());      // every rank has joined: the file has served
 
@@ -544,20 +541,14 @@ int main(int argc, char **argv)
         PS_OK(ctx, psamd_fill_particles(ctx, n, xyz.data(), nullptr, nullptr, age.data(), fert.data(), nullptr, nullptr));
         if (R.local.empty()) {
             // Which stream the stage kernels (and, by default, the RCCL calls) run on: the first context's OWN stream.  Measured
-            // (profiles/r5_ab_host.txt): with a stream this program created itself -- before the contexts (PSAMD_RING_STREAM=0,
-            // what it did until late in round 5) or after the first one (2) -- a one-rank step takes 0.8-1.2 % longer, all of it
-            // inside the force pass's own time; on the context's own stream the C++ host is as fast as the Python host.  Eight
-            // slabs in one process: no difference.  The cause is not known (same flags, same kernels, same arguments).
-            const char *e = std::getenv("PSAMD_RING_STREAM");
-            const int mode = e ? std::atoi(e) : 1;
-            if (mode >= 1 && mode <= 4) {
-                const bool shared = R.transfer == R.compute;
-                (void)hipStreamDestroy(R.compute);
-                if (mode == 1) { void *st = nullptr; PS_OK(ctx, psamd_get_stream(ctx, &st)); R.compute = (hipStream_t)st; R.compute_owned = false; }
-                else if (mode == 2) HIP_OK(hipStreamCreateWithFlags(&R.compute, hipStreamNonBlocking));
-                else { int lo = 0, hi = 0; HIP_OK(hipDeviceGetStreamPriorityRange(&lo, &hi)); HIP_OK(hipStreamCreateWithPriority(&R.compute, hipStreamNonBlocking, mode == 3 ? hi : lo)); }      // (3: highest priority, 4: lowest)
-                if (shared) R.transfer = R.compute;
-            }
+            // (profiles/r5_ab_host.txt): with a stream this program created itself -- before the contexts or after the first
+            // one -- a one-rank step takes 0.8-1.2 % longer, all of it inside the force pass's own time; on the context's own
+            // stream the C++ host is as fast as the Python host.  Eight slabs in one process: no difference.  The cause is not
+            // known (same flags, same kernels, same arguments).
+            void *st = nullptr;
+            PS_OK(ctx, psamd_get_stream(ctx, &st));
+            R.compute = (hipStream_t)st;
+            if (!side_stream) R.transfer = R.compute;
         }
         PS_OK(ctx, psamd_set_stream(ctx, (void *)R.compute));
         PS_OK(ctx, psamd_set_graphs(ctx, graphs ? 1 : 0));
@@ -843,6 +834,5 @@ int main(int argc, char **argv)
     g_comm = nullptr;
     if (R.comm) ncclCommDestroy(R.comm);
     if (R.transfer != R.compute) (void)hipStreamDestroy(R.transfer);
-    if (R.compute_owned) (void)hipStreamDestroy(R.compute);
     return rc;
 }

@@ -18,11 +18,9 @@ struct ApplyEmit {
     unsigned bits;          // 1 killed, 2 born, 4 relocate, 8 remote, 16 up
 };
 
-// ITEMS slots per thread (item `it` of workgroup b is slot (b * ITEMS + it) * 1024 + tid: coalesced).
-// Measured on the full N = 2^20 container: 1 / 2 / 4 slots per thread 44 / 55 / 50 us, and 256-thread
-// workgroups 71 us -- neither the per-workgroup list reservation (one same-address atomic each) nor
-// the workgroup count is what bounds it; one slot per thread in 1024-thread workgroups stays.
-template <int ITEMS>
+// One slot per thread (slot b * 1024 + tid of workgroup b: coalesced).  Measured on the full N = 2^20
+// container: 1 / 2 / 4 slots per thread 44 / 55 / 50 us, and 256-thread workgroups 71 us -- neither the
+// per-workgroup list reservation (one same-address atomic each) nor the workgroup count is what bounds it.
 __global__ __launch_bounds__(1024) void k_apply(DevParams P, SegLayout S, const StepState *__restrict__ stp,
                                                 const uint8_t *__restrict__ flag_slot,
                                                 float4 *pos4, float4 *vel4, float4 *acc4,
@@ -34,6 +32,9 @@ __global__ __launch_bounds__(1024) void k_apply(DevParams P, SegLayout S, const 
                                                 const int *__restrict__ chunk_count, const uint8_t *__restrict__ chunk_skip,
                                                 FrameScalars *fs, DevCounters *ctr)
 {
+    // (The slot's phases are written as loops over ITEMS = 1 slots: the same code without the loops is compiled to
+    // another schedule -- 42 VGPRs instead of 52 -- and the kernel took 1 us longer, 41.1 against 40.0 us at N = 2^20.)
+    constexpr int ITEMS = 1;
     __shared__ int s_ops, s_moves, s_base_ops, s_base_moves;
     __shared__ unsigned int s_cnt[4];
     if (threadIdx.x == 0) { s_ops = 0; s_moves = 0; s_cnt[0] = s_cnt[1] = s_cnt[2] = s_cnt[3] = 0; }
@@ -290,14 +291,10 @@ __global__ __launch_bounds__(1024) void k_apply(DevParams P, SegLayout S, const 
 hipError_t launch_apply(hipStream_t st, const DevParams &P, const SegLayout &S, const DeviceState &d)
 {
     if (P.slots_total <= 0) return hipSuccess;
-    // slots per thread: one (PSAMD_APPLY_ITEMS: the measurement quoted at the kernel)
-#define PS_APPLY(I) k_apply<I><<<(P.slots_total + I * 1024 - 1) / (I * 1024), 1024, 0, st>>>(P, S, d.st, d.flag_slot, d.pos4, \
-        d.vel4, d.acc4, d.cell, d.pflags, d.celltab, d.op_keys, d.op_args, d.ops_cap, \
-        d.moves, d.moves_cap, Outboxes{{d.xfer_out[0], d.xfer_out[1], d.xfer_out[2], d.xfer_out[3], d.xfer_out[4]}}, d.chunk_count, d.chunk_skip, d.fs, d.ctr)
-    static const int items_env = std::getenv("PSAMD_APPLY_ITEMS") ? std::atoi(std::getenv("PSAMD_APPLY_ITEMS")) : 0;
-    const int items = items_env ? items_env : 1;
-    if (items >= 4) PS_APPLY(4); else if (items >= 2) PS_APPLY(2); else PS_APPLY(1);
-#undef PS_APPLY
+    k_apply<<<(P.slots_total + 1023) / 1024, 1024, 0, st>>>(P, S, d.st, d.flag_slot, d.pos4, d.vel4, d.acc4, d.cell, d.pflags, d.celltab,
+                                                        d.op_keys, d.op_args, d.ops_cap, d.moves, d.moves_cap,
+                                                        Outboxes{{d.xfer_out[0], d.xfer_out[1], d.xfer_out[2], d.xfer_out[3], d.xfer_out[4]}},
+                                                        d.chunk_count, d.chunk_skip, d.fs, d.ctr);
     PS_LAUNCH_CHECK();
     return hipSuccess;
 }

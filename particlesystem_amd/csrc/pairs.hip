@@ -285,12 +285,7 @@ __device__ __forceinline__ void pairs_finish_fast(const PairRows<NQ> &r, const v
     }
 }
 
-#if defined(PSAMD_TWO_TRANSCENDENTALS)      // (A/B builds)
-constexpr bool ONE_T_DEFAULT = false;
-#else
-constexpr bool ONE_T_DEFAULT = true;
-#endif
-template <int NQ, bool ONE_T = ONE_T_DEFAULT>
+template <int NQ, bool ONE_T = true>
 __device__ __forceinline__ void pairsN_exact_lean(const DevParams &P, const PairCtx &c, const v2f (&qx)[NQ / 2],
                                                   const v2f (&qy)[NQ / 2], const v2f (&qz)[NQ / 2],
                                                   const v2f (&qw)[NQ / 2], int gj0,
@@ -662,11 +657,10 @@ __global__ __launch_bounds__(256, CAP <= 1024 ? 6 : 3) void k_collide_cell(DevPa
 // writes a share.  (These were three launches, k_build_active / k_active_tasks / k_split_tasks, 60 us
 // of mostly one-workgroup latency on the step's critical path; the prefixes are cheap enough to
 // be recomputed eight times.)
-// merge: 0 every slice is an ordinary task; 1 the packs are the merged tasks of k_pairs_merged (run
-// beside the balanced pass); 2 the packs are tasks of the balanced pass itself (tile walk): pack m is
-// task n_tasks2 + m, with one virtual "cell" ncomp + m in the prefix arrays.
-constexpr int PLAN_LDS = 6144;        // prefix entries (computed cells + virtual pack cells + 1) kept in LDS
-__global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, int merge, const int *__restrict__ cell_start_g,
+// merge: false every slice is an ordinary task; true the packs are walked by the first workgroups of the
+// balanced pass (merged_pack_task), beside its ordinary tasks.
+constexpr int PLAN_LDS = 6144;        // prefix entries (computed cells + 1) kept in LDS
+__global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, bool merge, const int *__restrict__ cell_start_g,
                                                      const int *__restrict__ active_count, const int *__restrict__ task_cost,
                                                      int *__restrict__ task_list2, int *__restrict__ ctask_start_g,
                                                      long long *__restrict__ cost_start_g, int4 *__restrict__ merged_tasks,
@@ -682,13 +676,12 @@ __global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, int me
     __shared__ long long s_cost[PLAN_LDS + 1];
     __shared__ int s_task[PLAN_LDS + 1];
     __shared__ int s_ac[PLAN_LDS];                     // active_count | task_cost << 13 of the j-th computed cell
-    __shared__ long long wave_tot[16], wave_cost[16], wave_pcost[16];
+    __shared__ long long wave_tot[16], wave_cost[16];
     __shared__ long long s_run[2];
     __shared__ long long s_runcost[2];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, x = blockIdx.x;
     const int ncomp = comp_count(P);
-    const bool ext = merge == 2;
-    const bool in_lds = (ext ? 2 * ncomp : ncomp) + 1 <= PLAN_LDS && P.max_per_cell < (1 << 13);
+    const bool in_lds = ncomp + 1 <= PLAN_LDS && P.max_per_cell < (1 << 13);
     long long *cost_start = in_lds ? s_cost : cost_start_g;
     int *ctask_start = in_lds ? s_task : ctask_start_g;
     if (in_lds) for (int j = tid; j < ncomp; j += 1024) { const int c = comp_cell(P, j), n = active_count[c]; s_ac[j] = n | ((n ? task_cost[c] : 0) << 13); }
@@ -705,16 +698,14 @@ __global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, int me
     // dependent LDS round trip, and this walk is done twice
     const int pper = max(6, (ncomp + 1023) / 1024);
     const int p0 = min(ncomp, tid * pper), p1 = min(ncomp, p0 + pper);
-    // out / cost_out (may be null): the packs and, per pack, what its wave walks (its longest stencil)
-    auto pack = [&](int4 *out, long long *cost_out, long long cost_base, long long *cost_sum) -> int {
-        int npack = 0, used = 0, ng = 0, pc = 0;
-        long long acc = 0;
+    // out (may be null): the packs
+    auto pack = [&](int4 *out) -> int {
+        int npack = 0, used = 0, ng = 0;
         int4 cur = make_int4(-1, -1, -1, -1);
         auto flush = [&]() {
             if (out) out[npack] = cur;
-            if (cost_out) cost_out[npack] = cost_base + acc;
-            acc += pc; npack++;
-            cur = make_int4(-1, -1, -1, -1); used = 0; ng = 0; pc = 0;
+            npack++;
+            cur = make_int4(-1, -1, -1, -1); used = 0; ng = 0;
         };
         for (int j = p0; j < p1; j++) {
             const int r = act_of(j) & 63;
@@ -722,30 +713,29 @@ __global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, int me
             const int c = comp_cell(P, j);
             if (ng == 4 || used + r > 64) flush();
             if (ng == 0) cur.x = c; else if (ng == 1) cur.y = c; else if (ng == 2) cur.z = c; else cur.w = c;
-            ng++; used += r; pc = max(pc, cost_of(j));
+            ng++; used += r;
         }
         if (ng) flush();
-        if (cost_sum) *cost_sum = acc;
         return npack;
     };
-    long long mine = 0, mycost = 0, mypcost = 0;   // tasks (low word) and packs (high word); bodies the tasks walk; ... the packs walk
+    long long mine = 0, mycost = 0;   // tasks (low word) and packs (high word); bodies the tasks walk
     for (int j = c0; j < c1; j++) {
         const int n = act_of(j), nt = merge ? (n >> 6) : ((n + 63) >> 6);
         mine += nt;
         mycost += (long long)nt * cost_of(j);
     }
-    if (merge) mine |= (long long)pack(nullptr, nullptr, 0, &mypcost) << 32;
-    long long incl = mine, cincl = mycost, pincl = mypcost;
+    if (merge) mine |= (long long)pack(nullptr) << 32;
+    long long incl = mine, cincl = mycost;
     for (int d = 1; d < 64; d <<= 1) {
-        const long long o = __shfl_up(incl, d), oc = __shfl_up(cincl, d), op = __shfl_up(pincl, d);
-        if (lane >= d) { incl += o; cincl += oc; pincl += op; }
+        const long long o = __shfl_up(incl, d), oc = __shfl_up(cincl, d);
+        if (lane >= d) { incl += o; cincl += oc; }
     }
-    if (lane == 63) { wave_tot[wv] = incl; wave_cost[wv] = cincl; wave_pcost[wv] = pincl; }
+    if (lane == 63) { wave_tot[wv] = incl; wave_cost[wv] = cincl; }
     __syncthreads();
-    long long run2 = incl - mine, total2 = 0, crun = cincl - mycost, ctotal = 0, prun = pincl - mypcost, ptotal = 0;
+    long long run2 = incl - mine, total2 = 0, crun = cincl - mycost, ctotal = 0;
     for (int k = 0; k < 16; k++) {
-        if (k < wv) { run2 += wave_tot[k]; crun += wave_cost[k]; prun += wave_pcost[k]; }
-        total2 += wave_tot[k]; ctotal += wave_cost[k]; ptotal += wave_pcost[k];
+        if (k < wv) { run2 += wave_tot[k]; crun += wave_cost[k]; }
+        total2 += wave_tot[k]; ctotal += wave_cost[k];
     }
     int run = (int)(run2 & 0xffffffffll);
     const int total = (int)(total2 & 0xffffffffll), npacks = (int)(total2 >> 32);
@@ -758,16 +748,12 @@ __global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, int me
         run += n;
         crun += (long long)n * cost_of(j);
     }
-    if (merge) {
-        const int m0 = (int)(run2 >> 32);
-        const int np = pack(x == 0 ? merged_tasks + m0 : nullptr, ext ? cost_start + ncomp + m0 : nullptr, ctotal + prun, nullptr);
-        if (ext) for (int m = 0; m < np; m++) ctask_start[ncomp + m0 + m] = total + m0 + m;
-    }
-    const int ncells = ncomp, nent = ncomp + (ext ? npacks : 0), ntask = total + (ext ? npacks : 0);
-    const long long T = ctotal + (ext ? ptotal : 0);
+    if (merge && x == 0) pack(merged_tasks + (int)(run2 >> 32));
+    const int ntask = total;
+    const long long T = ctotal;
     if (tid == 0) {
-        ctask_start[nent] = ntask;
-        cost_start[nent] = T;
+        ctask_start[ncomp] = ntask;
+        cost_start[ncomp] = T;
         if (x == 0) { fs->n_tasks2 = total; fs->n_merged = npacks; fs->cost_total = T; }
     }
     if (!in_lds) __threadfence();                    // (every workgroup wrote the same values; this one reads its own)
@@ -779,19 +765,12 @@ __global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, int me
     // A position in the pass's work is (task, cost already walked inside the task): which stencil step
     // that is depends on the populations of the task's stencil, which the wave that starts (or stops)
     // there looks up anyway -- k_pairs_balanced turns the residual into a step.  (Walking the 27 counts
-    // here, per wave slot, was most of this kernel's 40 us.)  For a merged pack the residual IS the
-    // step (its steps are taken as equally long), marked by bit 30.  whole = round up to the next task start.
+    // here, per wave slot, was most of this kernel's 40 us.)  whole = round up to the next task start.
     auto pos_at = [&](long long v, bool whole) -> long long {
         if (v >= T) return (long long)ntask << 32;
-        int a = 0, b = nent - 1;                          // last entry whose tasks start at or before v
+        int a = 0, b = ncomp - 1;                         // last cell whose tasks start at or before v
         while (a < b) { const int m = (a + b + 1) >> 1; if (cost_start[m] <= v) a = m; else b = m - 1; }
         const int nt = ctask_start[a + 1] - ctask_start[a];
-        if (a >= ncells) {                                // a merged pack: one task
-            const long long S = cost_start[a + 1] - cost_start[a], off = v - cost_start[a];
-            const int k = S > 0 ? (int)min((long long)(STENCIL - 1), off * STENCIL / S) : 0;
-            if (whole) return (long long)(ctask_start[a] + (off > 0 ? 1 : 0)) << 32;
-            return ((long long)ctask_start[a] << 32) | (long long)(k | (1 << 30));
-        }
         const int S = cost_of(a);
         if (nt == 0 || S <= 0) return (long long)ctask_start[a + 1] << 32;     // (v < T: cannot be the last cell)
         const long long off = v - cost_start[a];
@@ -803,9 +782,8 @@ __global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, int me
     };
     auto cost_of_task_start = [&](int t) -> long long {
         if (t >= ntask) return T;
-        int a = 0, b = nent - 1;
+        int a = 0, b = ncomp - 1;
         while (a < b) { const int mm = (a + b + 1) >> 1; if (ctask_start[mm] <= t) a = mm; else b = mm - 1; }
-        if (a >= ncells) return cost_start[a];             // a merged pack is one task
         return cost_start[a] + (long long)(t - ctask_start[a]) * cost_of(a);
     };
     const int m = nw >> 3;                                // wave slots per XCD run (nw is a multiple of 32)
@@ -842,8 +820,7 @@ __device__ __forceinline__ int resolve_unit(const DevParams &P, long long pos, c
     const int lane = (int)(threadIdx.x & 63);
     const int t = __builtin_amdgcn_readfirstlane((int)(pos >> 32)), r = __builtin_amdgcn_readfirstlane((int)(pos & 0xffffffffll));
     int k = 0;
-    if (r & (1 << 30)) k = r & 63;                           // a merged pack: the residual is the step
-    else if (r > 0) {
+    if (r > 0) {
         const int c = __builtin_amdgcn_readfirstlane(task_list[t]) / P.slices;
         int i1, i2, i3, cnt = 0;
         cell_coords(P, c, i1, i2, i3);
@@ -880,9 +857,7 @@ __device__ __forceinline__ int resolve_unit(const DevParams &P, long long pos, c
 // tiles through 1 KiB of LDS per wave.  No s_barrier: a wave only ever touches its own
 // tile, and a wave's LDS operations complete in issue order, so a compiler-level fence
 // is all the ordering needed.
-#ifndef PSAMD_BALANCED_WAVES
-#define PSAMD_BALANCED_WAVES 7      // resident waves per SIMD the scalar-walk force pass is built for (70 VGPRs; measured, exact / tolerance arithmetic: 6 waves 2.15 / 1.25 ms, 7 waves 2.11 / 1.22 ms)
-#endif
+constexpr int BALANCED_WAVES = 7;      // resident waves per SIMD the scalar-walk force pass is built for (70 VGPRs; measured, exact / tolerance arithmetic: 6 waves 2.15 / 1.25 ms, 7 waves 2.11 / 1.22 ms)
 
 #ifdef PSAMD_WAVE_TRACE   // diagnostic build only: when and where did this wave run
 #define PS_TRACE_BEGIN() const unsigned long long trace_t0 = __builtin_amdgcn_s_memrealtime()
@@ -894,9 +869,6 @@ __device__ __forceinline__ int resolve_unit(const DevParams &P, long long pos, c
 #else
 #define PS_TRACE_BEGIN() do {} while (0)
 #define PS_TRACE_END() do {} while (0)
-#endif
-#ifndef TILE_PIPELINED
-#define TILE_PIPELINED 1            // the tile walk reads a group of bodies from LDS while it works through the one before (A/B builds: 0)
 #endif
 
 // One task: 64 consecutive particles of one cell against the cell's stencil.
@@ -1207,10 +1179,7 @@ __global__ __launch_bounds__(256) void k_pairs(DevParams P, const int *__restric
 // all -- is walked in one go, with one ragged tail per chunk instead of one per cell.  The association depends on
 // nothing but the global cell order: the same bits on one GPU and on any number of ranks, where far_buf is the
 // all-gathered snapshot of all ranks with its index by global cell (k_allg_index) instead of the own snapshot.
-#ifndef PSAMD_ALLP_CHUNK
-#define PSAMD_ALLP_CHUNK 4
-#endif
-constexpr int ALLP_CHUNK = PSAMD_ALLP_CHUNK;          // (divides 64)
+constexpr int ALLP_CHUNK = 4;          // (divides 64)
 
 // act_start[j]: how many particles need a force in the pass's cells before its j-th; [comp_count]: in all.  One workgroup.
 __global__ __launch_bounds__(1024) void k_allp_prefix(DevParams P, const int *__restrict__ active_count, int *__restrict__ act_start)
@@ -1268,7 +1237,7 @@ __device__ __forceinline__ void walk_far(const DevParams &P, const PairCtx &ctx,
 }
 
 template <int MODE, int NQ>
-__global__ __launch_bounds__(256, PSAMD_BALANCED_WAVES) void k_allp_far(DevParams P, const SnapSoa snap4, const int *__restrict__ act_start,
+__global__ __launch_bounds__(256, BALANCED_WAVES) void k_allp_far(DevParams P, const SnapSoa snap4, const int *__restrict__ act_start,
                                                                         const int *__restrict__ dense_gi, const int *__restrict__ dense_cell,
                                                                         const FarCells far, const float *__restrict__ far_buf,
                                                                         const int *__restrict__ far_start, const int *__restrict__ far_n)
@@ -1368,8 +1337,8 @@ constexpr int MERGE_TILE = 4 * 64 + 4;          // floats per lane group: x[64] 
 
 // The same walk for a wave that has its SIMD (almost) to itself -- a slab of a multi-GPU run has
 // about 1.5 force tasks per SIMD.  There the scalar-load walk of pairs_task is latency-bound (one
-// wave cannot cover its own s_load round trips: 1.6x slower per task, PSAMD_WAVES sweep in
-// DESIGN.md), so the bodies come as 64-body tiles instead: one vector load per lane, issued a
+// wave cannot cover its own s_load round trips: 1.6x slower per task, the sweep of the wave
+// count in DESIGN.md), so the bodies come as 64-body tiles instead: one vector load per lane, issued a
 // whole tile ahead (vector loads retire in order, so they pipeline), through LDS (SoA, no
 // barrier: a wave reads only its own tiles and its LDS operations complete in order), read back
 // as broadcast 16-byte rows.  Same arithmetic, same order: short last tiles are padded with
@@ -1499,164 +1468,19 @@ __device__ __forceinline__ void pairs_task_tile(const DevParams &P, const int *_
             else
                 dmin = fminf(dmin, pairsN_fast<NQ>(ctx, g.qx, g.qy, g.qz, g.qw, eps2f, ax, ay, az));
         };
-        if (TILE_PIPELINED) {
-            Group a, b;
-            read_group(0, a);
-            for (int jj = 0; jj < n; jj += 2 * NQ) {
-                if (jj + NQ < n) read_group(jj + NQ, b);
-                work_group(a);
-                if (jj + NQ < n) {
-                    if (jj + 2 * NQ < n) read_group(jj + 2 * NQ, a);
-                    work_group(b);
-                }
-            }
-        } else {
-            for (int jj = 0; jj < n; jj += NQ) {
-                Group g;
-                read_group(jj, g);
-                work_group(g);
+        Group a, b;
+        read_group(0, a);
+        for (int jj = 0; jj < n; jj += 2 * NQ) {
+            if (jj + NQ < n) read_group(jj + NQ, b);
+            work_group(a);
+            if (jj + NQ < n) {
+                if (jj + 2 * NQ < n) read_group(jj + 2 * NQ, a);
+                work_group(b);
             }
         }
     }
     if (k1 < STENCIL) { handoff_publish(force4 + gi, ax, ay, az, flag, valid, ready, k1); return; }
     if (valid) force4.put(P, gc, gi, make_float4(ax, ay, az, __int_as_float(flag)));
-}
-
-// The force pass, balanced: `nw` waves (all resident), wave slot s walks the (task, stencil step)
-// units from wave_pos[s] up to wave_pos[s + 1] -- the same number of bodies for every wave
-// (k_split_tasks).  Most of a wave's share is whole tasks; the task its share ends in is started
-// FIRST (steps 0 .. k-1, sums published), then the whole tasks, and LAST the task its share
-// begins in is finished from the sums the previous wave slot published at the very start of its
-// own work -- so nobody waits in practice, and a particle's sum is still one serial chain of
-// fp32 additions in the reference's order.  A share that lies inside one task (few tasks, many
-// waves) is one middle piece: consume, walk, publish.
-// Wave slots are dealt XCD by XCD like the tasks of k_pairs; k_split_tasks starts every XCD's
-// run at a whole task, so the wave that continues a task runs in a workgroup that was
-// dispatched no later (block b - 8) or is the same workgroup.
-// WALK 0: scalar-load walk, ordinary tasks only (packs, if any, run in k_pairs_merged beside it);
-//      1: tile walk for everything, packs of partial slices included (few waves per SIMD);
-//      2: scalar-load walk for the ordinary tasks, tile walk for the packs, all in one balanced list.
-template <int MODE, int NQ>
-__device__ __forceinline__ void merged_pack_task(const DevParams &P, const int *__restrict__ cell_start,
-                                                 const SnapSoa snap4,
-                                                 const int *__restrict__ active_list,
-                                                 const int *__restrict__ active_count,
-                                                 const int4 *__restrict__ merged_tasks,
-                                                 const ForceBuf force4, int slot, float *tile, WavePace *pace = nullptr);
-
-// nmb (WALK 0, a multiple of 8 so that the XCD dealing is undisturbed): the first nmb workgroups of the
-// launch serve the merged packs of partly filled slices instead (merged_pack_task) -- dispatched first,
-// their waves are the oldest on their SIMDs and are served first, which is what lets these long,
-// stall-prone waves finish well inside the pass.  (As a kernel of their own on a second stream they
-// needed a head start to get that: forked at the same moment as the balanced pass they ended with it,
-// and the stage took 0.1 ms longer.)
-template <int MODE, int NQ, int WALK>
-__global__ __launch_bounds__(256, WALK == 0 ? PSAMD_BALANCED_WAVES : WALK == 1 ? 2 : 4) void k_pairs_balanced(DevParams P, const int *__restrict__ cell_start,
-                                                        const SnapSoa snap4,
-                                                        const float *__restrict__ snap_soa,
-                                                        const float *__restrict__ snap_age,
-                                                        const int *__restrict__ sorted_id,
-                                                        const int *__restrict__ task_list,
-                                                        const ForceBuf force4,
-                                                        FrameScalars *fs, unsigned long long *trace,
-                                                        const int *__restrict__ active_list, const int *__restrict__ active_count,
-                                                        const long long *__restrict__ wave_pos, int *__restrict__ task_ready,
-                                                        const int4 *__restrict__ merged_tasks, int nmb, StepState *st, int pass, int paced)
-{
-    __shared__ __attribute__((aligned(16))) float tiles[4][4 * MERGE_TILE];   // up to four 1-KiB tiles per wave
-    const int wave = threadIdx.x >> 6;
-#ifdef PSAMD_END_TRACE    // (diagnostic build: when every wave ended, and nothing else -- one store at its end: scripts/r5_end_trace.sh)
-    struct EndNote {
-        unsigned long long *trace;
-        __device__ ~EndNote() { if ((threadIdx.x & 63) == 0) trace[blockIdx.x * 4 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime(); }
-    } end_note{trace};
-#endif
-#ifdef PSAMD_WAVE_TRACE   // (diagnostic build: the wave's whole life, first instruction to last piece -- overwrites what its pieces noted)
-    const unsigned long long wave_t0 = __builtin_amdgcn_s_memrealtime();
-    struct WholeWave {
-        unsigned long long *trace; unsigned long long t0;
-        __device__ ~WholeWave() { if ((threadIdx.x & 63) == 0) { unsigned long long *t_ = trace + (size_t)3 * (blockIdx.x * 4 + (threadIdx.x >> 6)); t_[0] = t0; t_[1] = __builtin_amdgcn_s_memrealtime(); } }
-    } whole_wave{trace, wave_t0};
-#endif
-    if (WALK == 0 && (int)blockIdx.x < nmb) {
-        // The packs of partly filled slices, dealt round-robin to the 4 * nmb pack waves: a pack wave takes every
-        // (4 * nmb)-th pack, one after the other, and paces itself over all of them -- so the launch holds the number of
-        // pack workgroups that the packs' share of the WORK asks for, whatever their number (N = 2^22 in 24^3 cells has
-        // 6 900 packs: one workgroup per four of them would be the whole GPU).
-        const int first = blockIdx.x * 4 + wave, stride = nmb * 4, npack = fs->n_merged;
-        if (first < npack) {
-            WavePace pace;                       // a pack is 27 steps of (up to) four cells' stencils
-            if (paced) {
-                const int ticks = st->pairs_ticks[pass];
-                pace.t0 = st->pairs_t0[pass];
-                pace.per_tick = ticks > 0 ? 1.0f / (float)ticks : 0.f;
-                pace.per_unit = 1.0f / (float)(STENCIL * ((npack - first + stride - 1) / stride));
-                pace.band = paced;
-            }
-            for (int pack = first; pack < npack; pack += stride)     // (4 bodies per group: the 8-wide form costs this kernel its sixth wave per SIMD)
-                merged_pack_task<MODE, (NQ > 4 ? 4 : NQ)>(P, cell_start, snap4, active_list, active_count, merged_tasks, force4, pack, tiles[wave], &pace);
-        }
-        return;
-    }
-    const int slot = xcd_contiguous((int)blockIdx.x - nmb, (int)gridDim.x - nmb) * 4 + wave;
-    const long long pos_b = wave_pos[slot], pos_e = wave_pos[slot + 1];
-    if (pos_e <= pos_b) return;                              // (positions order like units: task-major, cost inside the task)
-    const int ub = resolve_unit(P, pos_b, cell_start, task_list), ue = resolve_unit(P, pos_e, cell_start, task_list);
-    if (ue <= ub) return;
-    WavePace pace;
-    if (WALK == 0 && paced) {
-        const int ticks = st->pairs_ticks[pass];
-        pace.t0 = st->pairs_t0[pass];
-        pace.per_tick = ticks > 0 ? 1.0f / (float)ticks : 0.f;
-        pace.per_unit = 1.0f / (float)(ue - ub);
-        pace.band = paced;
-    }
-    struct PassEnd {        // the pass's end, for the next one's clock: the latest wave's last instruction
-        StepState *st; int pass; bool on;
-        __device__ ~PassEnd() { if (on && (threadIdx.x & 63) == 0) atomicMax(&st->pairs_end[pass], (unsigned long long)__builtin_amdgcn_s_memrealtime()); }
-    } pass_end{st, pass, WALK == 0 && paced != 0};
-    const int tb = ub / STENCIL, lb = ub - tb * STENCIL;            // first unit: task tb, step lb
-    const int tl = (ue - 1) / STENCIL, le = ue - tl * STENCIL;      // last task tl, its steps [.., le)
-    // one call site, so one copy of the walk: the pieces in the order they are done
-    const bool single = tb == tl;
-    const int has_head = (!single && le < STENCIL) ? 1 : 0, has_tail = (!single && lb > 0) ? 1 : 0;
-    const int first_whole = tb + has_tail, last_whole = tl + (has_head ? 0 : 1);      // tasks walked whole: [first, last)
-    const int nwhole = single ? 0 : last_whole - first_whole;
-    const int pieces = single ? 1 : has_head + nwhole + has_tail;
-    for (int i = 0; i < pieces; i++) {
-        int t, k0 = 0, k1 = STENCIL;
-        if (single) { t = tb; k0 = lb; k1 = le; }
-        else if (has_head && i == 0) { t = tl; k1 = le; }                 // the head of the last task first: publish early
-        else if (i - has_head < nwhole) t = first_whole + (i - has_head);
-        else { t = tb; k0 = lb; }                                         // the tail of the first task last: its head was published long ago
-        const int nord = fs->n_tasks2;
-        if (WALK == 1 || (WALK == 2 && t >= nord)) {
-            // task t: an ordinary (cell, slice) task, or -- past them -- merged pack t - n_tasks2
-            TileGroups G;
-            if (t < nord) {
-                const int task = task_list[t], c = task / P.slices, slice = task - c * P.slices;
-                G.ng = 1; G.cell[0] = c; G.first[0] = slice * 64; G.count[0] = min(64, active_count[c] - slice * 64);
-                G.cell[1] = G.cell[2] = G.cell[3] = c; G.first[1] = G.first[2] = G.first[3] = 0; G.count[1] = G.count[2] = G.count[3] = 0;
-            } else {
-                const int4 pk = merged_tasks[t - nord];
-                const int cells[4] = {pk.x, pk.y, pk.z, pk.w};
-                G.ng = 0;
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const bool on = cells[q] >= 0;
-                    G.cell[q] = on ? cells[q] : pk.x;
-                    G.first[q] = on ? (active_count[cells[q]] & ~63) : 0;
-                    G.count[q] = on ? (active_count[cells[q]] & 63) : 0;
-                    if (on) G.ng = q + 1;
-                }
-            }
-            if (t < nord) pairs_task_tile<MODE, NQ, 1, WALK != 1>(P, cell_start, snap4, force4, G, tiles[wave], active_list, k0, k1, task_ready + t, fs);
-            else pairs_task_tile<MODE, NQ, 4, WALK != 1>(P, cell_start, snap4, force4, G, tiles[wave], active_list, k0, k1, task_ready + t, fs);
-        } else
-            pairs_task<MODE, NQ, true>(P, cell_start, snap4, snap_soa, snap_age, sorted_id, force4, task_list[t], nullptr, trace,
-                                       active_list, active_count, k0, k1, task_ready + t, fs,
-                                       WALK == 0 ? &pace : nullptr);          // (per_tick == 0: no pacing)
-    }
 }
 
 // Merged task of the two-pass force pass: the partly filled last slices of up to four cells
@@ -1666,16 +1490,15 @@ __global__ __launch_bounds__(256, WALK == 0 ? PSAMD_BALANCED_WAVES : WALK == 1 ?
 // different banks -- scripts/microbench/lds_groups.hip) and a lane reads its group's tile.
 // All groups walk stencil step k together, tile by tile, for as many rows as the longest of
 // their lists; shorter lists are padded with massless bodies far outside the box: such a
-// row adds r * 0 = +-0 to a sum that started at +0 (bit-identical, as for kids).  Launched
-// on its own (different register budget from k_pairs).
-
+// row adds r * 0 = +-0 to a sum that started at +0 (bit-identical, as for kids).  Walked by the
+// first workgroups of the balanced pass (WALK 0), beside its ordinary tasks.
 template <int MODE, int NQ>
 __device__ __forceinline__ void merged_pack_task(const DevParams &P, const int *__restrict__ cell_start,
                                                  const SnapSoa snap4,
                                                  const int *__restrict__ active_list,
                                                  const int *__restrict__ active_count,
                                                  const int4 *__restrict__ merged_tasks,
-                                                 const ForceBuf force4, int slot, float *tile, WavePace *pace)
+                                                 const ForceBuf force4, int slot, float *tile, WavePace &pace)
 {
     const int lane = threadIdx.x & 63;
     // (Raising these waves' issue priority -- they run one per SIMD among six of the balanced
@@ -1762,24 +1585,129 @@ __device__ __forceinline__ void merged_pack_task(const DevParams &P, const int *
                     dmin = fminf(dmin, pairsN_fast<NQ>(ctx, qx, qy, qz, qw, eps2f, ax, ay, az));
             }
         }
-        if (pace) pace->step();
+        pace.step();
     }
     if (valid) force4.put(P, c, gi, make_float4(ax, ay, az, 0.f));
 }
 
-template <int MODE, int NQ>
-__global__ __launch_bounds__(256, 6) void k_pairs_merged(DevParams P, const int *__restrict__ cell_start,
-                                                      const SnapSoa snap4,
-                                                      const int *__restrict__ active_list,
-                                                      const int *__restrict__ active_count,
-                                                      const int4 *__restrict__ merged_tasks,
-                                                      const ForceBuf force4, const FrameScalars *__restrict__ fs)
+// The force pass, balanced: `nw` waves (all resident), wave slot s walks the (task, stencil step)
+// units from wave_pos[s] up to wave_pos[s + 1] -- the same number of bodies for every wave
+// (k_split_tasks).  Most of a wave's share is whole tasks; the task its share ends in is started
+// FIRST (steps 0 .. k-1, sums published), then the whole tasks, and LAST the task its share
+// begins in is finished from the sums the previous wave slot published at the very start of its
+// own work -- so nobody waits in practice, and a particle's sum is still one serial chain of
+// fp32 additions in the reference's order.  A share that lies inside one task (few tasks, many
+// waves) is one middle piece: consume, walk, publish.
+// Wave slots are dealt XCD by XCD like the tasks of k_pairs; k_split_tasks starts every XCD's
+// run at a whole task, so the wave that continues a task runs in a workgroup that was
+// dispatched no later (block b - 8) or is the same workgroup.
+// WALK 0: scalar-load walk (pairs_task) for the ordinary tasks, and the packs of partial slices in
+//         workgroups of their own at the head of the launch;
+//      1: tile walk (pairs_task_tile) for the ordinary tasks, no packs (few waves per SIMD).
+// nmb (WALK 0, a multiple of 8 so that the XCD dealing is undisturbed): the first nmb workgroups of the
+// launch serve the merged packs of partly filled slices instead (merged_pack_task) -- dispatched first,
+// their waves are the oldest on their SIMDs and are served first, which is what lets these long,
+// stall-prone waves finish well inside the pass.  (As a kernel of their own on a second stream they
+// needed a head start to get that: forked at the same moment as the balanced pass they ended with it,
+// and the stage took 0.1 ms longer.)
+template <int MODE, int NQ, int WALK>
+__global__ __launch_bounds__(256, WALK == 0 ? BALANCED_WAVES : 2) void k_pairs_balanced(DevParams P, const int *__restrict__ cell_start,
+                                                        const SnapSoa snap4,
+                                                        const float *__restrict__ snap_soa,
+                                                        const float *__restrict__ snap_age,
+                                                        const int *__restrict__ sorted_id,
+                                                        const int *__restrict__ task_list,
+                                                        const ForceBuf force4,
+                                                        FrameScalars *fs, unsigned long long *trace,
+                                                        const int *__restrict__ active_list, const int *__restrict__ active_count,
+                                                        const long long *__restrict__ wave_pos, int *__restrict__ task_ready,
+                                                        const int4 *__restrict__ merged_tasks, int nmb, StepState *st, int pass)
 {
-    __shared__ __attribute__((aligned(16))) float tiles[4][4 * MERGE_TILE];
+    __shared__ __attribute__((aligned(16))) float tiles[4][4 * MERGE_TILE];   // up to four 1-KiB tiles per wave (a pack's four groups)
     const int wave = threadIdx.x >> 6;
-    const int slot = blockIdx.x * 4 + wave;
-    if (slot >= fs->n_merged) return;
-    merged_pack_task<MODE, NQ>(P, cell_start, snap4, active_list, active_count, merged_tasks, force4, slot, tiles[wave]);
+#ifdef PSAMD_WAVE_TRACE   // (diagnostic build: the wave's whole life, first instruction to last piece -- overwrites what its pieces noted)
+    const unsigned long long wave_t0 = __builtin_amdgcn_s_memrealtime();
+    struct WholeWave {
+        unsigned long long *trace; unsigned long long t0;
+        __device__ ~WholeWave() { if ((threadIdx.x & 63) == 0) { unsigned long long *t_ = trace + (size_t)3 * (blockIdx.x * 4 + (threadIdx.x >> 6)); t_[0] = t0; t_[1] = __builtin_amdgcn_s_memrealtime(); } }
+    } whole_wave{trace, wave_t0};
+#endif
+    if (WALK == 0 && (int)blockIdx.x < nmb) {
+        // The packs of partly filled slices, dealt round-robin to the 4 * nmb pack waves: a pack wave takes every
+        // (4 * nmb)-th pack, one after the other, and paces itself over all of them -- so the launch holds the number of
+        // pack workgroups that the packs' share of the WORK asks for, whatever their number (N = 2^22 in 24^3 cells has
+        // 6 900 packs: one workgroup per four of them would be the whole GPU).
+        const int first = blockIdx.x * 4 + wave, stride = nmb * 4, npack = fs->n_merged;
+        if (first < npack) {
+            WavePace pace;                       // a pack is 27 steps of (up to) four cells' stencils
+            const int ticks = st->pairs_ticks[pass];
+            pace.t0 = st->pairs_t0[pass];
+            pace.per_tick = ticks > 0 ? 1.0f / (float)ticks : 0.f;
+            pace.per_unit = 1.0f / (float)(STENCIL * ((npack - first + stride - 1) / stride));
+            for (int pack = first; pack < npack; pack += stride)     // (4 bodies per group: the 8-wide form costs this kernel its sixth wave per SIMD)
+                merged_pack_task<MODE, 4>(P, cell_start, snap4, active_list, active_count, merged_tasks, force4, pack, tiles[wave], pace);
+        }
+        return;
+    }
+    const int slot = xcd_contiguous((int)blockIdx.x - nmb, (int)gridDim.x - nmb) * 4 + wave;
+    const long long pos_b = wave_pos[slot], pos_e = wave_pos[slot + 1];
+    if (pos_e <= pos_b) return;                              // (positions order like units: task-major, cost inside the task)
+    const int ub = resolve_unit(P, pos_b, cell_start, task_list), ue = resolve_unit(P, pos_e, cell_start, task_list);
+    if (ue <= ub) return;
+    WavePace pace;
+    if (WALK == 0) {
+        const int ticks = st->pairs_ticks[pass];
+        pace.t0 = st->pairs_t0[pass];
+        pace.per_tick = ticks > 0 ? 1.0f / (float)ticks : 0.f;
+        pace.per_unit = 1.0f / (float)(ue - ub);
+    }
+    struct PassEnd {        // the pass's end, for the next one's clock: the latest wave's last instruction
+        StepState *st; int pass; bool on;
+        __device__ ~PassEnd() { if (on && (threadIdx.x & 63) == 0) atomicMax(&st->pairs_end[pass], (unsigned long long)__builtin_amdgcn_s_memrealtime()); }
+    } pass_end{st, pass, WALK == 0};
+    const int tb = ub / STENCIL, lb = ub - tb * STENCIL;            // first unit: task tb, step lb
+    const int tl = (ue - 1) / STENCIL, le = ue - tl * STENCIL;      // last task tl, its steps [.., le)
+    // one call site, so one copy of the walk: the pieces in the order they are done
+    const bool single = tb == tl;
+    const int has_head = (!single && le < STENCIL) ? 1 : 0, has_tail = (!single && lb > 0) ? 1 : 0;
+    const int first_whole = tb + has_tail, last_whole = tl + (has_head ? 0 : 1);      // tasks walked whole: [first, last)
+    const int nwhole = single ? 0 : last_whole - first_whole;
+    const int pieces = single ? 1 : has_head + nwhole + has_tail;
+    for (int i = 0; i < pieces; i++) {
+        int t, k0 = 0, k1 = STENCIL;
+        if (single) { t = tb; k0 = lb; k1 = le; }
+        else if (has_head && i == 0) { t = tl; k1 = le; }                 // the head of the last task first: publish early
+        else if (i - has_head < nwhole) t = first_whole + (i - has_head);
+        else { t = tb; k0 = lb; }                                         // the tail of the first task last: its head was published long ago
+        const int nord = fs->n_tasks2;
+        if (WALK == 1) {
+            // task t: an ordinary (cell, slice) task, or -- past them -- merged pack t - n_tasks2.  (The plan lists no
+            // packs for a tile-walk pass, so the second form is never taken.  Without it the compiler allocates the walk
+            // differently -- 238 VGPRs instead of 256 -- and the pass took 1 % longer on an eighth of the N = 2^20 cloud.)
+            TileGroups G;
+            if (t < nord) {
+                const int task = task_list[t], c = task / P.slices, slice = task - c * P.slices;
+                G.ng = 1; G.cell[0] = c; G.first[0] = slice * 64; G.count[0] = min(64, active_count[c] - slice * 64);
+                G.cell[1] = G.cell[2] = G.cell[3] = c; G.first[1] = G.first[2] = G.first[3] = 0; G.count[1] = G.count[2] = G.count[3] = 0;
+            } else {
+                const int4 pk = merged_tasks[t - nord];
+                const int cells[4] = {pk.x, pk.y, pk.z, pk.w};
+                G.ng = 0;
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const bool on = cells[q] >= 0;
+                    G.cell[q] = on ? cells[q] : pk.x;
+                    G.first[q] = on ? (active_count[cells[q]] & ~63) : 0;
+                    G.count[q] = on ? (active_count[cells[q]] & 63) : 0;
+                    if (on) G.ng = q + 1;
+                }
+            }
+            if (t < nord) pairs_task_tile<MODE, NQ, 1, false>(P, cell_start, snap4, force4, G, tiles[wave], active_list, k0, k1, task_ready + t, fs);
+            else pairs_task_tile<MODE, NQ, 4, false>(P, cell_start, snap4, force4, G, tiles[wave], active_list, k0, k1, task_ready + t, fs);
+        } else
+            pairs_task<MODE, NQ, true>(P, cell_start, snap4, snap_soa, snap_age, sorted_id, force4, task_list[t], nullptr, trace,
+                                       active_list, active_count, k0, k1, task_ready + t, fs, &pace);      // (per_tick == 0: no pacing)
+    }
 }
 
 // ------------------------------------------------------------------ self test
@@ -1849,84 +1777,58 @@ hipError_t launch_selftest_math(hipStream_t st, uint32_t lo_bits, uint32_t hi_bi
 // How one pass of the pair stage is launched, from the hint of its task count: everything that shapes the
 // launches and is not read from device memory by the kernels themselves (what a captured graph is keyed by).
 struct PairShape {
-    bool two, merge, balanced, tile, packs_in_list;
+    bool two;                // two-pass stage: collision flags first, then the balanced force pass
+    bool tile;               // ... with the tile walk and no packs (WALK 1); else the scalar walk and the packs (WALK 0)
     int nw;                  // wave slots of the balanced force pass
     int nmb;                 // workgroups of the same launch, ahead of them, that serve the packs of partly filled slices (WALK 0)
 };
+
+constexpr double PACK_COST = 1.4;      // a pack's walk in ordinary tasks: four lane groups, each with its own LDS tile
 
 static PairShape pair_shape(const DevParams &P, bool lean, int64_t hint)
 {
     const int64_t tasks_hint = hint & 0xffffffffll, packs_hint = hint >> 32;      // (capi.hip, pairs_hint)
     PairShape s{};
     s.two = lean && P.two_pass;
-    // leftover slices of several cells in one wave (k_pairs_merged).  A merged wave is long and
-    // stalls on its tile loads; a small share (a slab with fewer than ~3 tasks per SIMD) has too
-    // little other work to cover that and it becomes the critical path (measured on 1/4 and 1/8
-    // shares of the N = 2^20 cloud).
-    static const bool merge_off = std::getenv("PSAMD_NO_MERGE") != nullptr;
-    static const bool balance_off = std::getenv("PSAMD_NO_BALANCE") != nullptr;
-    static const int waves_env = std::getenv("PSAMD_WAVES") ? std::atoi(std::getenv("PSAMD_WAVES")) : 0;
-    s.merge = s.two && !merge_off && (P.world == 1 || tasks_hint >= 3000);
-    s.balanced = s.two && !balance_off;
+    if (!s.two) return s;
     // Balanced pass: a fixed number of waves, all resident, each walking the same number of
     // bodies.  At least four per SIMD when there are that many tasks (fewer cannot cover their
     // scalar-load latency: 1024 / 2048 / 4096 / 6144 waves took 3.73 / 2.54 / 2.27 / 2.29 ms on
     // the N = 2^20 cloud), but not more waves than tasks (a task cut in three or more pieces is
     // a chain of waves that wait for each other).
-    if (s.balanced) {
-        static const int waves_per_simd = std::getenv("PSAMD_WAVES_PER_SIMD") ? std::atoi(std::getenv("PSAMD_WAVES_PER_SIMD")) : PSAMD_BALANCED_WAVES;      // (A/B runs)
-        s.nw = 1024 * (int)std::min<int64_t>(waves_per_simd, std::max<int64_t>(1, tasks_hint / 1024));
-        if (waves_env >= 32) s.nw = std::min(waves_env & ~31, MAX_PAIR_WAVES);
-    }
-    // few waves per SIMD (a slab of a multi-GPU run): the scalar-load walk cannot cover its own
-    // load latency, bodies come through LDS tiles fetched a tile ahead instead -- and the partly
-    // filled last slices are packed into tasks of the same pass
-    static const int tile_env = std::getenv("PSAMD_TILE") ? std::atoi(std::getenv("PSAMD_TILE")) : -1;
-    static const bool unified_packs = std::getenv("PSAMD_UNIFIED_PACKS") != nullptr;
-    static const bool tile_packs = std::getenv("PSAMD_TILE_PACKS") != nullptr;
-    s.tile = s.balanced && (tile_env >= 0 ? tile_env != 0 : s.nw <= 2048);
-    // The packs of partly filled last slices as tasks of the balanced pass itself (tile walk).
-    // Measured (pair stage, N = 2^20): one GPU, 8200 tasks: beside the pass in k_pairs_merged 2.31 ms,
-    // in the list 2.40 (one kernel holding both walks needs 99 VGPRs: 4 waves per SIMD, not 6);
-    // half the cloud (a slab of two): 1.67 vs 1.40 -- the separate kernel's 512 waves end long after
-    // a pass that has only 4 waves per SIMD; an eighth (tile walk): no packs 0.58, packs 0.60 -- a
-    // pack's four-group walk costs more than the two tasks it saves.  So (rounds 2-3): in the list for the slabs
-    // that use the scalar walk, beside the pass on one GPU, none with the tile walk.
-    // (Round 4: with persistent pack workgroups sized by the packs' share of the work and the waves paced, a slab of two
-    // is served better by the one-GPU form too -- pair stage 1.32 -> 1.12 ms -- so the packs are in the list only on request.)
-    s.packs_in_list = s.balanced && !merge_off && (s.tile ? tile_packs : (s.merge && unified_packs));
-    if (s.packs_in_list) { s.merge = false; s.nw = std::min(s.nw, 4096); }      // (98 VGPRs with the tile walk in: 4 resident waves per SIMD)
-    if (s.tile) s.merge = false;                  // no separate merged kernel beside a tile-walk pass
-    // The packs' workgroups are the first of the same launch and hold residency slots for about half of it: with
-    // a wave slot for every resident wave besides, the workgroups dispatched last could only start when a pack ended
-    // (wave trace, round 4: a quarter of the balanced waves started 0.6-0.9 ms into a 2.3-ms launch).  So the balanced
-    // part gets as many wave slots as the packs leave free: everything is resident from the start.
-    // How many pack workgroups: the packs' share of the pass's work (a pack costs about PACK_COST ordinary tasks: four lane
-    // groups with their own LDS tiles), in workgroups of the resident set; a pack wave takes several packs one after the
-    // other.  Without a hint (a context's first step) a quarter.
-    static const bool nw_minus_packs = !(std::getenv("PSAMD_NW_PACKS") && std::atoi(std::getenv("PSAMD_NW_PACKS")) == 0);
-    static const double pack_cost = std::getenv("PSAMD_PACK_COST") ? std::atof(std::getenv("PSAMD_PACK_COST")) : 1.4;
-    s.nmb = 0;
-    if (s.merge && !s.packs_in_list && s.balanced) {
-        const int resident = s.nw / 4;                     // workgroups the launch keeps resident
-        if (nw_minus_packs && waves_env < 32 && s.nw >= 4096) {
-            const double pw = pack_cost * (double)packs_hint, tw = (double)std::max<int64_t>(tasks_hint - packs_hint, 1);
-            const double share = packs_hint > 0 ? pw / (pw + tw) : 0.25;
-            int wgs = ((int)(resident * share + 0.5) + 7) & ~7;
-            wgs = std::max(8, std::min(wgs, resident / 2));
-            if (packs_hint > 0) wgs = std::min(wgs, (int)(((packs_hint + 3) / 4 + 7) & ~7));      // (a pack wave with no pack is a wasted slot)
-            s.nmb = wgs;
-            s.nw = (s.nw - 4 * wgs) & ~255;
-        } else
-            s.nmb = (int)std::min<int64_t>(((packs_hint > 0 ? (packs_hint + 3) / 4 : resident / 4) + 7) & ~7, resident);
-    }
+    s.nw = 1024 * (int)std::min<int64_t>(BALANCED_WAVES, std::max<int64_t>(1, tasks_hint / 1024));
+    // Few waves per SIMD (a slab of a multi-GPU run): the scalar-load walk cannot cover its own load latency,
+    // bodies come through LDS tiles fetched a tile ahead instead, and the partly filled last slices stay
+    // ordinary tasks.  A pack wave is long and stalls on its tile loads; a share this small has too little other
+    // work to cover that (an eighth of the N = 2^20 cloud, tile walk: no packs 0.58 ms, packs 0.60).
+    s.tile = s.nw <= 2048;
+    if (s.tile) return s;
+    // The packs of partly filled last slices: persistent workgroups at the head of the launch, sized by the packs'
+    // share of the work, their waves paced (a slab of two: pair stage 1.32 -> 1.12 ms against packs in the task list).
+    // They hold residency slots for about half of the launch: with a wave slot for every resident wave besides, the
+    // workgroups dispatched last could only start when a pack ended (wave trace, round 4: a quarter of the balanced
+    // waves started 0.6-0.9 ms into a 2.3-ms launch).  So the balanced part gets as many wave slots as the packs leave
+    // free: everything is resident from the start.  How many pack workgroups: the packs' share of the pass's work, in
+    // workgroups of the resident set; a pack wave takes several packs one after the other.  Without a hint (a
+    // context's first step) a quarter.
+    const int resident = s.nw / 4;                     // workgroups the launch keeps resident
+    if (s.nw >= 4096) {
+        const double pw = PACK_COST * (double)packs_hint, tw = (double)std::max<int64_t>(tasks_hint - packs_hint, 1);
+        const double share = packs_hint > 0 ? pw / (pw + tw) : 0.25;
+        int wgs = ((int)(resident * share + 0.5) + 7) & ~7;
+        wgs = std::max(8, std::min(wgs, resident / 2));
+        if (packs_hint > 0) wgs = std::min(wgs, (int)(((packs_hint + 3) / 4 + 7) & ~7));      // (a pack wave with no pack is a wasted slot)
+        s.nmb = wgs;
+        s.nw = (s.nw - 4 * wgs) & ~255;
+    } else
+        s.nmb = (int)std::min<int64_t>(((packs_hint > 0 ? (packs_hint + 3) / 4 : resident / 4) + 7) & ~7, resident);
     return s;
 }
 
 uint64_t launch_pairs_shape(const DevParams &P, int64_t tasks_hint)
 {
     const PairShape s = pair_shape(P, P.lean_math != 0, tasks_hint);
-    return (uint64_t)(s.nw / 32) | (s.merge ? 1ull << 10 : 0) | (s.tile ? 1ull << 11 : 0) | (s.packs_in_list ? 1ull << 12 : 0) | (s.balanced ? 1ull << 13 : 0) | ((uint64_t)(s.nmb / 8) << 14);
+    return (uint64_t)(s.nw / 32) | (s.tile ? 1ull << 10 : 0) | (s.two ? 1ull << 11 : 0) | ((uint64_t)(s.nmb / 8) << 12);
 }
 
 template <int MODE, int NQ>
@@ -1936,84 +1838,77 @@ static hipError_t launch_pairs_mode(hipStream_t st, const DevParams &P, const De
     if (ncomp <= 0) return hipSuccess;
     const ForceBuf fbuf = force_buf(d);
     const int tasks = ncomp * P.slices;
-    const PairShape shape = pair_shape(P, MODE != 0, tasks_hint);
-    const bool two = shape.two, merge = shape.merge, balanced = shape.balanced, tile = shape.tile, packs_in_list = shape.packs_in_list;
-    const int nw = shape.nw;
-    if (two) {
-        // collision flags and the per-cell lists of the particles that need a force, then the plan of the force pass
-        if (P.max_per_cell + HALO_CAP / 2 <= 1024)
-            k_collide_cell<1024><<<ncomp, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.snap_cid, d.halo_count, d.halo_f,
-                                                        d.halo_id, d.active_list, d.active_count, d.task_cost, fbuf);
-        else
-            k_collide_cell<2560><<<ncomp, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.snap_cid, d.halo_count, d.halo_f,
-                                                        d.halo_id, d.active_list, d.active_count, d.task_cost, fbuf);
-        k_plan_force<<<8, 1024, 0, st>>>(P, balanced ? nw : 0, packs_in_list ? 2 : merge ? 1 : 0, d.cell_start, d.active_count, d.task_cost,
-                                         d.task_list2, d.ctask_start, d.cost_start, d.merged_tasks, d.wave_pos, d.fs, d.trace, d.st, pass);
-    }
-    if (ev_force) (void)hipEventRecord(ev_force, st);      // timing: the force pass proper starts here
-    const int *task_list = two ? d.task_list2 : d.task_list;
-    const int *active_list = two ? d.active_list : nullptr, *active_count = two ? d.active_count : nullptr;
-    // the hand-off flags are indexed by task number, which starts at 0 in every pass of a frame:
-    // each pass has its own block of them (both zeroed with the frame)
-    int *task_ready = d.task_ready + (size_t)pass * P.n_local_cells * P.slices;
-    if (balanced) {
-        constexpr int M = MODE == 0 ? 1 : MODE;
-        static const int paced = std::getenv("PSAMD_PACE") ? std::atoi(std::getenv("PSAMD_PACE")) : 20;      // (A/B runs: 0 = no pacing of the waves; else WavePace::band)
-        // the packs of partly filled slices (merge): the first nmb workgroups of the same launch
-        const int nmb = merge ? std::max(8, shape.nmb) : 0;
-#define PS_BALANCED_Q(W, Q) k_pairs_balanced<M, Q, W><<<nmb + nw / 4, 256, 0, st>>>(P, d.cell_start, SnapSoa{d.snap_soa, (size_t)P.sorted_cap}, d.snap_soa, d.snap_age, d.sorted_id, task_list, \
-                                                                     fbuf, d.fs, d.trace, active_list, active_count, d.wave_pos, task_ready, d.merged_tasks, nmb, d.st, pass, paced)
-#define PS_BALANCED(W) PS_BALANCED_Q(W, NQ)
-        // The tile walk -- a wave with its SIMD (almost) to itself -- takes 16 bodies per group: every group costs such a
-        // wave two branches on a vector compare and the tail of three chains of dependent additions, all of it exposed;
-        // half as many groups: -5 % on the pair stage of an eighth of the N = 2^20 cloud, -6 % in the tolerance mode (profiles/r4_ab_tile_nq.txt).
-        // (The next group's distances between a group's scale factors and its additions, in one basic block: 9 % SLOWER.)
-        static const int tile_nq = std::getenv("PSAMD_TILE_NQ") ? std::atoi(std::getenv("PSAMD_TILE_NQ")) : 16;      // (A/B runs)
-        // (The same in the scalar walk where a SIMD holds four waves -- N = 2^22 on eight ranks -- gave 1 %: not kept.)
-        if (tile && NQ == 8 && tile_nq == 16) PS_BALANCED_Q(1, 16);
-        else if (tile) PS_BALANCED(1); else if (packs_in_list) PS_BALANCED(2); else PS_BALANCED(0);
+    if constexpr (MODE == 0) {
+        // softening lengths outside the lean range: the one-pass stage with the generic exact arithmetic, nothing else
+        // (a context with all-pairs forces is created only with lean arithmetic)
+        if (ev_force) (void)hipEventRecord(ev_force, st);      // timing: the force pass proper starts here
+        k_pairs<0, NQ><<<(tasks + 3) / 4, 256, 0, st>>>(P, d.cell_start, SnapSoa{d.snap_soa, (size_t)P.sorted_cap}, d.snap_soa, d.snap_age, d.sorted_id, d.task_list, fbuf,
+                                                      d.fs, d.trace, nullptr, nullptr);
+        return hipGetLastError();
+    } else {
+        const PairShape shape = pair_shape(P, true, tasks_hint);
+        const bool two = shape.two;
+        if (two) {
+            // collision flags and the per-cell lists of the particles that need a force, then the plan of the force pass
+            if (P.max_per_cell + HALO_CAP / 2 <= 1024)
+                k_collide_cell<1024><<<ncomp, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.snap_cid, d.halo_count, d.halo_f,
+                                                            d.halo_id, d.active_list, d.active_count, d.task_cost, fbuf);
+            else
+                k_collide_cell<2560><<<ncomp, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.snap_cid, d.halo_count, d.halo_f,
+                                                            d.halo_id, d.active_list, d.active_count, d.task_cost, fbuf);
+            k_plan_force<<<8, 1024, 0, st>>>(P, shape.nw, !shape.tile, d.cell_start, d.active_count, d.task_cost,
+                                             d.task_list2, d.ctask_start, d.cost_start, d.merged_tasks, d.wave_pos, d.fs, d.trace, d.st, pass);
+        }
+        if (ev_force) (void)hipEventRecord(ev_force, st);      // timing: the force pass proper starts here
+        if (two) {
+            // the hand-off flags are indexed by task number, which starts at 0 in every pass of a frame:
+            // each pass has its own block of them (both zeroed with the frame)
+            int *task_ready = d.task_ready + (size_t)pass * P.n_local_cells * P.slices;
+            // the packs of partly filled slices: the first nmb workgroups of the same launch (scalar walk only)
+            const int nmb = shape.nmb;
+#define PS_BALANCED(W, Q) k_pairs_balanced<MODE, Q, W><<<nmb + shape.nw / 4, 256, 0, st>>>(P, d.cell_start, SnapSoa{d.snap_soa, (size_t)P.sorted_cap}, d.snap_soa, \
+        d.snap_age, d.sorted_id, d.task_list2, fbuf, d.fs, d.trace, d.active_list, d.active_count, d.wave_pos, task_ready, d.merged_tasks, nmb, d.st, pass)
+            // The tile walk -- a wave with its SIMD (almost) to itself -- takes 16 bodies per group: every group costs such a
+            // wave two branches on a vector compare and the tail of three chains of dependent additions, all of it exposed;
+            // half as many groups: -5 % on the pair stage of an eighth of the N = 2^20 cloud, -6 % in the tolerance mode (profiles/r4_ab_tile_nq.txt).
+            // (The next group's distances between a group's scale factors and its additions, in one basic block: 9 % SLOWER.)
+            // (The same in the scalar walk where a SIMD holds four waves -- N = 2^22 on eight ranks -- gave 1 %: not kept.)
+            if (shape.tile) PS_BALANCED(1, 16); else PS_BALANCED(0, NQ);
 #undef PS_BALANCED
-#undef PS_BALANCED_Q
+        } else
+            k_pairs<MODE, NQ><<<(tasks + 3) / 4, 256, 0, st>>>(P, d.cell_start, SnapSoa{d.snap_soa, (size_t)P.sorted_cap}, d.snap_soa, d.snap_age, d.sorted_id, d.task_list, fbuf,
+                                                             d.fs, d.trace, nullptr, nullptr);
+        if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
+            // All-pairs forces: what ran above is the stencil's chain; now every other cell (k_allp_far) and the sum.
+            // (two == true here: all-pairs contexts are created only with the two-pass pair stage.)  Where the far cells are
+            // found: the own snapshot (one GPU: local cell == global cell, lengths from consecutive starts) or the
+            // all-gathered snapshot of all ranks with its index by global cell.
+            FarCells far;
+            const bool gathered = P.world > 1;
+            const float *far_buf = gathered ? reinterpret_cast<const float *>(d.allg_in) : d.snap_soa;
+            const int *far_start = gathered ? d.gstart : d.cell_start, *far_n = gathered ? d.gn : nullptr;
+            far.plane = gathered ? (unsigned long long)P.allg_cap : (unsigned long long)P.sorted_cap;
+            far.part_acc = d.part_acc; far.part_plane = (unsigned long long)d.part_tasks * 64;
+            // dense tasks: at most the particles alive (the host's bound; a slab also computes its neighbour's lent layers:
+            // every entry of the sorted order).  The kernels go by the device's own count.
+            const int64_t dense_bound = std::min<int64_t>(d.part_tasks, ((live_bound >= 0 && P.world == 1) ? live_bound : (int64_t)P.sorted_cap) / 64 + 2);
+            k_allp_prefix<<<1, 1024, 0, st>>>(P, d.active_count, d.act_start);
+            k_allp_dense<<<(ncomp + 3) / 4, 256, 0, st>>>(P, d.cell_start, d.active_list, d.active_count, d.act_start, d.dense_gi, d.dense_cell);
+            k_allp_far<MODE, NQ><<<(unsigned)((dense_bound * ALLP_PARTS + 3) / 4), 256, 0, st>>>(P, SnapSoa{d.snap_soa, (size_t)P.sorted_cap}, d.act_start, d.dense_gi, d.dense_cell,
+                                                                                              far, far_buf, far_start, far_n);
+            k_allpairs_combine<<<(unsigned)((dense_bound * 64 + 255) / 256), 256, 0, st>>>(P, d.act_start, d.dense_gi, d.dense_cell, far, fbuf);
+        }
+        return hipGetLastError();
     }
-    else {
-        k_pairs<MODE, NQ><<<(tasks + 3) / 4, 256, 0, st>>>(P, d.cell_start, SnapSoa{d.snap_soa, (size_t)P.sorted_cap}, d.snap_soa, d.snap_age, d.sorted_id, task_list, fbuf,
-                                                         d.fs, d.trace, active_list, active_count);
-        // (unbalanced pass, A/B runs only: the packs as a kernel of their own behind it)
-        if (merge) k_pairs_merged<MODE == 0 ? 1 : MODE, NQ><<<(ncomp + 3) / 4, 256, 0, st>>>(
-                P, d.cell_start, SnapSoa{d.snap_soa, (size_t)P.sorted_cap}, d.active_list, d.active_count, d.merged_tasks, fbuf, d.fs);
-    }
-    if (MODE != 0 && (P.flags & PSAMD_FLAG_ALL_PAIRS)) {
-        // All-pairs forces: what ran above is the stencil's chain; now every other cell (k_allp_far) and the sum.
-        // (two == true here: all-pairs contexts are created only with the two-pass pair stage.)  Where the far cells are
-        // found: the own snapshot (one GPU: local cell == global cell, lengths from consecutive starts) or the
-        // all-gathered snapshot of all ranks with its index by global cell.
-        FarCells far;
-        const bool gathered = P.world > 1;
-        const float *far_buf = gathered ? reinterpret_cast<const float *>(d.allg_in) : d.snap_soa;
-        const int *far_start = gathered ? d.gstart : d.cell_start, *far_n = gathered ? d.gn : nullptr;
-        far.plane = gathered ? (unsigned long long)P.allg_cap : (unsigned long long)P.sorted_cap;
-        far.part_acc = d.part_acc; far.part_plane = (unsigned long long)d.part_tasks * 64;
-        // dense tasks: at most the particles alive (the host's bound; a slab also computes its neighbour's lent layers:
-        // every entry of the sorted order).  The kernels go by the device's own count.
-        const int64_t dense_bound = std::min<int64_t>(d.part_tasks, ((live_bound >= 0 && P.world == 1) ? live_bound : (int64_t)P.sorted_cap) / 64 + 2);
-        k_allp_prefix<<<1, 1024, 0, st>>>(P, d.active_count, d.act_start);
-        k_allp_dense<<<(ncomp + 3) / 4, 256, 0, st>>>(P, d.cell_start, d.active_list, d.active_count, d.act_start, d.dense_gi, d.dense_cell);
-        k_allp_far<MODE == 0 ? 1 : MODE, NQ><<<(unsigned)((dense_bound * ALLP_PARTS + 3) / 4), 256, 0, st>>>(P, SnapSoa{d.snap_soa, (size_t)P.sorted_cap}, d.act_start, d.dense_gi, d.dense_cell,
-                                                                                                  far, far_buf, far_start, far_n);
-        k_allpairs_combine<<<(unsigned)((dense_bound * 64 + 255) / 256), 256, 0, st>>>(P, d.act_start, d.dense_gi, d.dense_cell, far, fbuf);
-    }
-    return hipGetLastError();
 }
 
 hipError_t launch_pairs(hipStream_t st, const DevParams &P, const DeviceState &d, hipEvent_t ev_force, int64_t tasks_hint, int pass, int64_t live_bound)
 {
+    if (!P.lean_math) return launch_pairs_mode<0, 4>(st, P, d, ev_force, tasks_hint, pass, live_bound);
     // fast math shares the lean modes' validity range (finite 1/sqrt(eps2^3))
-    static const int fast_nq = std::getenv("PSAMD_FAST_NQ") ? std::atoi(std::getenv("PSAMD_FAST_NQ")) : 8;      // (A/B runs)
-    if ((P.flags & PSAMD_FLAG_FAST_MATH) && P.lean_math)
-        return fast_nq == 4 ? launch_pairs_mode<2, 4>(st, P, d, ev_force, tasks_hint, pass, live_bound) : launch_pairs_mode<2, 8>(st, P, d, ev_force, tasks_hint, pass, live_bound);
+    if (P.flags & PSAMD_FLAG_FAST_MATH) return launch_pairs_mode<2, 8>(st, P, d, ev_force, tasks_hint, pass, live_bound);
     // 8 pairs per slow-branch test: measured 3 % (full GPU) to 5 % (a 1/8 share) faster than 4
-    if (P.lean_math) return launch_pairs_mode<1, 8>(st, P, d, ev_force, tasks_hint, pass, live_bound);
-    return launch_pairs_mode<0, 4>(st, P, d, ev_force, tasks_hint, pass, live_bound);
+    return launch_pairs_mode<1, 8>(st, P, d, ev_force, tasks_hint, pass, live_bound);
 }
 
 }  // namespace psamd

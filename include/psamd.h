@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PSAMD_ABI_VERSION 7
+#define PSAMD_ABI_VERSION 8
 
 #define PSAMD_MAX_RANKS 64
 
@@ -181,6 +181,29 @@ typedef struct psamd_export {
     int64_t *count_dev;       /* int64: the number of live particles    */
     psamd_live_stats *stats_dev;
 } psamd_export;
+
+/* What psamd_inject did (see "putting particles in" below). */
+typedef struct psamd_inject_result {
+    int64_t done;             /* entries processed: n, or the index of the entry that stopped the call       */
+    int64_t placed;           /* entries placed on THIS context (a slab places its own segments' entries)     */
+    int32_t status;           /* PSAMD_OK, PSAMD_ERR_OUTSIDE_BOX or PSAMD_ERR_QUEUE_EMPTY: why it stopped     */
+    int32_t reserved;
+} psamd_inject_result;
+
+/* What psamd_inject reads and where it writes (device pointers). */
+typedef struct psamd_inject_spec {
+    uint32_t flags;           /* 0 (reserved for later)                                                       */
+    int32_t  reserved;        /* 0                                                                            */
+    const void  *pos4;        /* float4[max_count] x, y, z, w -- required, 16-byte aligned                    */
+    const void  *vel4;        /* float4[max_count] vx, vy, vz, age -- NULL: zeros; 16-byte aligned            */
+    const float *fert_age;    /* float[max_count] -- NULL: 0                                                  */
+    int64_t  max_count;       /* entries the arrays hold; sizes the launches; 0 <= max_count < 2^31           */
+    const int64_t *count_dev; /* optional device int64: n = clamp(*count_dev, 0, max_count), read by the
+                                 kernels; NULL: n = max_count                                                 */
+    int32_t *ids_dev;         /* optional out, int32[max_count]: for every entry < n the slot id it was given,
+                                 -1 if it was not placed here                                                 */
+    psamd_inject_result *result_dev;   /* optional out (device); NULL: the context's own record only         */
+} psamd_inject_spec;
 
 typedef struct psamd_ctx psamd_ctx;
 
@@ -430,6 +453,38 @@ int psamd_export_live(psamd_ctx *ctx, const psamd_export *spec);
 int psamd_download_live(psamd_ctx *ctx, uint32_t fields, void *pos4, void *vel4, void *acc4, int32_t *id,
                         int32_t *cell, int64_t capacity, int64_t *count);
 int psamd_live_stats_get(psamd_ctx *ctx, psamd_live_stats *out);
+
+/* ---- putting particles in ------------------------------------------------- */
+/* psamd_inject: the device-side, stream-ordered psamd_fill_particles.  Entries [0, n) are placed with xyz = pos4.xyz,
+ * w = pos4.w, vxyz = vel4.xyz, age = vel4.w and fert_age, at the point of the stream where the call is made, and leave
+ * the same bytes fill leaves when called there with the same particles: the particle arrays, the queues and their
+ * QUEUE_INFO records, the ids, `done` (fill's *n_done), `placed` and the status.  Each entry takes the next free slot
+ * of its segment's queue, in entry order (q_remove), and the slot is written as create_particle_s writes it
+ * (acceleration 0, fertility age, not a parent).  A slab (world > 1) places only the entries whose segment record it
+ * owns; the others get id -1 and count in `done`, not in `placed` -- every rank is given all entries and keeps its own.
+ *
+ * The call stops at the first failure, as fill does: an entry outside the box (what Geometry::locate rejects: the
+ * fp64 floor((+-1.0 * c) / cell_size) + G / 2 range test, non-finite and huge coordinates included) stops it at its
+ * index with PSAMD_ERR_OUTSIDE_BOX; an owned entry whose segment's queue is empty at its turn stops it at its index with
+ * PSAMD_ERR_QUEUE_EMPTY; nothing at or after that index is placed.  Only the result record reports the stop: the call
+ * returns PSAMD_OK once the work is enqueued, and the context carries on.
+ *
+ * Everything is enqueued on the context's stream: nothing waits and nothing is read back.  Scratch for the entries is
+ * allocated when max_count exceeds what an earlier call allocated for (that growth may wait for the device); steady
+ * use neither allocates nor waits.  Like fill, the call ends a frame in progress: psamd_calc_forces refuses with
+ * PSAMD_ERR_STATE until psamd_build_grid runs again.  The host's bound of the live count (what sizes the all-pairs far
+ * pass) grows by max_count at the call, also across steps enqueued before it whose records the host has yet to read.
+ * Because of that bookkeeping the call is refused while the context's stream is being captured (PSAMD_ERR_STATE): a
+ * replayed graph would inject without it.
+ *
+ * PSAMD_ERR_INVALID_ARG: a NULL context or spec, flags or reserved not 0, max_count out of range, pos4 NULL or not
+ * 16-byte aligned, vel4 not 16-byte aligned, fert_age or ids_dev not 4-byte aligned, count_dev or result_dev not
+ * 8-byte aligned.  PSAMD_ERR_STATE: the context is wedged, or its stream is being captured.  max_count == 0 writes a
+ * zero result and launches nothing else.
+ *
+ * psamd_inject_result_get: the last inject's record, into host memory; waits for the context's stream. */
+int psamd_inject(psamd_ctx *ctx, const psamd_inject_spec *spec);
+int psamd_inject_result_get(psamd_ctx *ctx, psamd_inject_result *out);
 
 /* ---- introspection -------------------------------------------------------- */
 int psamd_get_counters(psamd_ctx *ctx, psamd_counters *out);

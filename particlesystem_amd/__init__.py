@@ -20,7 +20,7 @@ from . import build as _build
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PSAMD_LIB") or os.path.join(HERE, "libpsamd.so")   # PSAMD_LIB: another build, for A/B measurements
 
-ABI_VERSION = 7         # the struct layouts below are include/psamd.h's at this PSAMD_ABI_VERSION
+ABI_VERSION = 8         # the struct layouts below are include/psamd.h's at this PSAMD_ABI_VERSION
 MAX_RANKS = 64
 FLAG_EXPLOSIONS = 0x1
 FLAG_FAST_MATH = 0x2
@@ -128,6 +128,21 @@ class Export(C.Structure):
                 ("capacity", C.c_int64), ("count_dev", C.c_void_p), ("stats_dev", C.c_void_p)]
 
 
+class InjectResult(C.Structure):
+    """psamd_inject_result: what psamd_inject did (done, placed, status)."""
+    _fields_ = [("done", C.c_int64), ("placed", C.c_int64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+    def to_dict(self):
+        return {"done": int(self.done), "placed": int(self.placed), "status": int(self.status)}
+
+
+class Inject(C.Structure):
+    """psamd_inject_spec: what psamd_inject reads and where it writes (device pointers)."""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_int32), ("pos4", C.c_void_p), ("vel4", C.c_void_p),
+                ("fert_age", C.c_void_p), ("max_count", C.c_int64), ("count_dev", C.c_void_p), ("ids_dev", C.c_void_p),
+                ("result_dev", C.c_void_p)]
+
+
 def merge_live_stats(stats):
     """The statistics of a system from its ranks' (dicts of live_stats() / export_live()["stats"]): counts and sums
     add, in rank order; the box and the ages take the minima and maxima."""
@@ -226,6 +241,8 @@ ABI = [
     ("psamd_export_live", C.c_int, [_vp, C.POINTER(Export)]),
     ("psamd_download_live", C.c_int, [_vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
     ("psamd_live_stats_get", C.c_int, [_vp, C.POINTER(LiveStats)]),
+    ("psamd_inject", C.c_int, [_vp, C.POINTER(Inject)]),
+    ("psamd_inject_result_get", C.c_int, [_vp, C.POINTER(InjectResult)]),
 ]
 
 _lib = None
@@ -576,6 +593,43 @@ class ParticleSystem:
         s = LiveStats()
         self._ck(self.lib.psamd_live_stats_get(self.h, C.byref(s)))
         return s.to_dict()
+
+    # ---- putting particles in (include/psamd.h) --------------------------------
+    def inject(self, pos4, vel4=None, fert_age=None, count=None, ids=False):
+        """psamd_inject from torch device tensors: pos4 float32 [m, 4] (x, y, z, w), vel4 float32 [m, 4] (vx, vy, vz, age)
+        or None, fert_age float32 [m] or None; count: None (all m entries) or a 1-element int64 device tensor that work
+        on torch's current stream may write just before.  Returns {"done", "placed", "status"} and, with ids=True,
+        "ids": an int32 device tensor of m entries (-1 where nothing was placed here).  Waits for the context's stream."""
+        import torch
+        dev = pos4.device
+        m = int(pos4.shape[0])
+
+        def ptr(t, dtype, shape):
+            if t is None:
+                return None
+            assert t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(), "inject: bad tensor"
+            return t.data_ptr()
+        spec = Inject(max_count=m)
+        spec.pos4 = ptr(pos4, torch.float32, (m, 4))
+        spec.vel4 = ptr(vel4, torch.float32, (m, 4))
+        spec.fert_age = ptr(fert_age, torch.float32, (m,))
+        spec.count_dev = ptr(count, torch.int64, (1,))
+        out_ids = torch.full((max(m, 1),), -1, dtype=torch.int32, device=dev) if ids else None
+        spec.ids_dev = None if out_ids is None else out_ids.data_ptr()
+        st = torch.cuda.ExternalStream(self.stream(), device=dev)
+        st.wait_stream(torch.cuda.current_stream(dev))        # (the inputs are written on torch's stream)
+        self._ck(self.lib.psamd_inject(self.h, C.byref(spec)))
+        st.synchronize()
+        res = self.inject_result()
+        if ids:
+            res["ids"] = out_ids[:m]
+        return res
+
+    def inject_result(self):
+        """psamd_inject_result_get: the last inject's {"done", "placed", "status"}"""
+        r = InjectResult()
+        self._ck(self.lib.psamd_inject_result_get(self.h, C.byref(r)))
+        return r.to_dict()
 
     def device_view(self):
         v = DeviceView()

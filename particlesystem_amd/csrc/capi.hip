@@ -87,6 +87,11 @@ struct psamd_ctx {
     // upper bound of the live count at the next build_grid, kept on the host so that the
     // life-cycle kernels can be sized without a read-back (-1 = unknown)
     int64_t live_bound = 0, snapshot_live_bound = 0;
+    // psamd_inject: max_count of the injects enqueued after step k (key k = scalars_seq at the call), until the record
+    // of step k + 1 -- the first that counts them -- has been read
+    std::map<int, int64_t> inject_tally;
+    InjectScratch inj{};              // its scratch: ent / tcount / tile_out grow with max_count (inj_cap), the rest is fixed
+    int64_t inj_cap = 0;
     // timing
     int timing = 0;                    // 0 off, 1 pair pass / apply / life cycle, 2 every stage
     int timing_period = 1;             // events are recorded on every timing_period-th step since set_timing
@@ -602,6 +607,10 @@ int psamd_create(const psamd_config *cfg, psamd_ctx **out)
     PS_HIP(c, dev_alloc(c, &d.exp_count, (size_t)export_tiles(P.slots_total)));     // psamd_export_live's scratch
     PS_HIP(c, dev_alloc(c, &d.exp_tiles, (size_t)export_tiles(P.slots_total)));
     PS_HIP(c, dev_alloc(c, &d.exp_out, 1));
+    PS_HIP(c, dev_alloc(c, &c->inj.removed, (size_t)g.queue_infos));    // psamd_inject's fixed scratch and result record
+    PS_HIP(c, dev_alloc(c, &c->inj.hdr, 2));
+    PS_HIP(c, dev_alloc(c, &c->inj.own, 1));
+    PS_HIP(c, hipMemsetAsync(c->inj.own, 0, sizeof(psamd_inject_result), c->stream));
     PS_HIP(c, dev_alloc(c, &d.trace, 3 * (LC * P.slices + 4)));
     PS_HIP(c, hipMemsetAsync(d.trace, 0, 3 * (LC * P.slices + 4) * sizeof(unsigned long long), c->stream));
 
@@ -769,6 +778,7 @@ int psamd_destroy(psamd_ctx *c)
     for (auto &cache : c->gcache) for (auto &g : cache) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     for (void *p : c->allocs) (void)hipFree(p);
     if (c->staging) (void)hipFree(c->staging);
+    for (void *p : {(void *)c->inj.ent, (void *)c->inj.tcount, (void *)c->inj.tile_out}) if (p) (void)hipFree(p);
     if (c->h_fs) (void)hipHostFree(c->h_fs);
     if (c->ev_made) for (auto &set : c->ev) for (auto &e : set) (void)hipEventDestroy(e);
     if (c->d.ev_fork) (void)hipEventDestroy(c->d.ev_fork);
@@ -1364,6 +1374,12 @@ static int consume_scalars(psamd_ctx *c, int upto)
         c->tasks_last = two ? tasks_now * comp_count(c->P) / std::max(1, comp_count(c->P_rest)) : tasks_now;
         c->packs_last = two ? (int64_t)r.n_merged * comp_count(c->P) / std::max(1, comp_count(c->P_rest)) : r.n_merged;
         c->live_bound = std::min<int64_t>(c->P.slots_total, (int64_t)r.live + r.n_moves);   // births and arrivals <= moves
+        // ... and what was injected after this step was enqueued (the record's live count does not include it)
+        for (auto it = c->inject_tally.begin(); it != c->inject_tally.end();) {
+            if (it->first < s) { it = c->inject_tally.erase(it); continue; }
+            c->live_bound = std::min<int64_t>(c->P.slots_total, c->live_bound + it->second);
+            ++it;
+        }
         c->processed_total += r.live;
         c->max_bucket_seen = std::max<int64_t>(c->max_bucket_seen, r.max_bucket);
         if (c->P.world > 1 && r.xfer_cap_next > 0) c->cap_decisions[s] = r.xfer_cap_next;      // (every step's: an absolute number, the same on every rank)
@@ -1822,6 +1838,67 @@ int psamd_live_stats_get(psamd_ctx *c, psamd_live_stats *out)
     PS_HIP(c, launch_export_live(c->stream, c->P, c->d, ExportFields{nullptr, nullptr, nullptr, nullptr, nullptr}, 0,
                                  &c->d.exp_out->count, &c->d.exp_out->stats));
     PS_HIP(c, hipMemcpyAsync(out, &c->d.exp_out->stats, sizeof *out, hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    return PSAMD_OK;
+}
+
+// ---- putting particles in (inject.hip) ----
+static bool aligned(const void *p, size_t a) { return (uintptr_t)p % a == 0; }
+
+// the entries' scratch for max_count entries: grows only (hipFree waits for the device; steady use never gets here)
+static int inject_scratch(psamd_ctx *c, int64_t max_count)
+{
+    if (max_count <= c->inj_cap) return PSAMD_OK;
+    for (void *p : {(void *)c->inj.ent, (void *)c->inj.tcount, (void *)c->inj.tile_out}) if (p) PS_HIP(c, hipFree(p));
+    c->inj.ent = nullptr; c->inj.tcount = nullptr; c->inj.tile_out = nullptr;
+    c->inj_cap = 0;
+    const int64_t tiles = (max_count + INJECT_TILE - 1) / INJECT_TILE;
+    PS_HIP(c, hipMalloc((void **)&c->inj.ent, (size_t)(tiles * INJECT_TILE) * sizeof(int2)));
+    PS_HIP(c, hipMalloc((void **)&c->inj.tcount, (size_t)tiles * (size_t)c->geo.queue_infos * sizeof(int)));
+    PS_HIP(c, hipMalloc((void **)&c->inj.tile_out, (size_t)tiles * sizeof(int)));
+    c->inj_cap = tiles * INJECT_TILE;
+    return PSAMD_OK;
+}
+
+int psamd_inject(psamd_ctx *c, const psamd_inject_spec *spec)
+{
+    if (!c || !spec) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    if (spec->flags != 0 || spec->reserved != 0) return fail(c, PSAMD_ERR_INVALID_ARG, "inject: flags and reserved must be 0");
+    if (spec->max_count < 0 || spec->max_count > INT32_MAX) return fail(c, PSAMD_ERR_INVALID_ARG, "inject: max_count outside [0, 2^31)");
+    if (!spec->pos4 || !aligned(spec->pos4, 16) || !aligned(spec->vel4, 16) || !aligned(spec->fert_age, 4) || !aligned(spec->ids_dev, 4) ||
+        !aligned(spec->count_dev, 8) || !aligned(spec->result_dev, 8))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "inject: pos4 missing, or an array misaligned");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    PS_HIP(c, hipStreamIsCapturing(c->stream, &cs));
+    if (cs != hipStreamCaptureStatusNone)
+        return fail(c, PSAMD_ERR_STATE, "inject: the context's stream is being captured (the host's bound of the live count is "
+                                        "kept at the call: a replay would bypass it)");
+    psamd_inject_result *res = spec->result_dev ? spec->result_dev : c->inj.own;
+    if (spec->max_count == 0) {
+        PS_HIP(c, hipMemsetAsync(c->inj.own, 0, sizeof(psamd_inject_result), c->stream));
+        if (res != c->inj.own) PS_HIP(c, hipMemsetAsync(res, 0, sizeof(psamd_inject_result), c->stream));
+        return PSAMD_OK;
+    }
+    const int rc = inject_scratch(c, spec->max_count);
+    if (rc != PSAMD_OK) return rc;
+    const InjectArgs a{(const float4 *)spec->pos4, (const float4 *)spec->vel4, spec->fert_age, spec->max_count, spec->count_dev,
+                       spec->ids_dev, res};
+    PS_HIP(c, launch_inject(c->stream, c->P, c->S, c->d, c->geo.queue_infos, a, c->inj));
+    // fill's transitions; the device's queues are ahead of the host's mirror; every entry counts in the live bound,
+    // also when the record of a step enqueued before this call is read later (consume_scalars)
+    c->host_queues_valid = false;
+    c->grid_built = false; c->pairs_done = false; c->slab_stage = 0;
+    if (c->live_bound >= 0) c->live_bound = std::min<int64_t>(c->P.slots_total, c->live_bound + spec->max_count);
+    c->inject_tally[c->scalars_seq] += spec->max_count;
+    return PSAMD_OK;
+}
+
+int psamd_inject_result_get(psamd_ctx *c, psamd_inject_result *out)
+{
+    if (!c || !out) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    PS_HIP(c, hipMemcpyAsync(out, c->inj.own, sizeof *out, hipMemcpyDeviceToHost, c->stream));
     PS_HIP(c, hipStreamSynchronize(c->stream));
     return PSAMD_OK;
 }

@@ -1,0 +1,267 @@
+// inject.hip -- psamd_inject: particles from device arrays into their segments' free slots, on the stream.
+//
+// The device-side counterpart of psamd_fill_particles (capi.hip), byte for byte: entry i takes the next free slot of
+// its segment's queue in entry order (q_remove), and the stop rule is fill's.  A deterministic stable multisplit of the
+// entries by queue record, then the closed-form FIFO removal (the k-th remove of a record takes logical element k, as
+// k_replay_commit does), in five launches ordered by the launch boundaries only (no hand-off between workgroups):
+//   k_inject_locate  one workgroup per tile of INJECT_TILE entries: Geometry::locate in fp64, the segment record, the
+//                    ownership rule; the tile's per-record counts and every entry's stable rank inside the tile (the 16
+//                    waves take turns in entry order; inside a wave ballot + mbcnt per distinct record); the tile's
+//                    first entry outside the box
+//   k_inject_scan    one workgroup: per record, the exclusive prefix of the tile counts (in place) and the first
+//                    outside entry of all tiles
+//   k_inject_fail    per entry: its rank k among the earlier entries of its record; k == the queue's count is the
+//                    record's first queue failure (atomicMin: order-independent)
+//   k_inject_place   per entry below F = min(first outside, first failure, n): slot = queue[front + k], the slot written
+//                    as k_place writes it, the queue word -1, the id; per record how many it removed
+//   k_inject_commit  one workgroup: front / count / rear as host_q_remove leaves them, and the result record
+// The kernels touch the entries, the scratch, the queues and the slots they hand out: nothing a step in flight owns
+// (stream order puts them between steps).
+#include "kernels_common.hpp"
+
+#include <climits>
+
+namespace psamd {
+
+constexpr int INJECT_THREADS = 1024;          // k_inject_locate: 16 waves, 4 groups of 64 entries each
+constexpr int INJECT_WAVES = INJECT_THREADS / 64;
+constexpr int INJECT_GROUPS = INJECT_TILE / INJECT_THREADS;
+static_assert(INJECT_GROUPS * INJECT_THREADS == INJECT_TILE, "a wave ranks INJECT_GROUPS consecutive groups of 64 entries");
+constexpr int INJECT_LDS_RECORDS = 8192;      // records counted in LDS (32 KB); more: in the tile's row in global memory
+constexpr int INJ_NOT_MINE = -1, INJ_OUTSIDE = -2;
+
+__device__ __forceinline__ int inject_n(const int64_t *count_dev, int64_t max_count)
+{
+    if (!count_dev) return (int)max_count;
+    const int64_t v = *count_dev;
+    return (int)(v < 0 ? 0 : v > max_count ? max_count : v);
+}
+
+// Geometry::locate: the same fp64 floor((+-1.0 * c) / cell_size) + G / 2.  On x86 the host's out-of-range (int)
+// conversion gives INT_MIN (rejected); here it would saturate and NaN would become 0, so the range is tested on the
+// double: an integer-valued d converts into [0, G) exactly when 0 <= d < G, and NaN / +-inf fail the test.
+__device__ __forceinline__ bool inject_locate(const DevParams &P, float x, float y, float z, int &cell)
+{
+    const double cs = P.cell_size, h = (double)(P.G / 2), g = (double)P.G;
+    const double d1 = floor((-1.0 * (double)y) / cs) + h;
+    const double d2 = floor((1.0 * (double)x) / cs) + h;
+    const double d3 = floor((-1.0 * (double)z) / cs) + h;
+    if (!(d1 >= 0.0 && d1 < g && d2 >= 0.0 && d2 < g && d3 >= 0.0 && d3 < g)) return false;
+    cell = ((int)d3 * P.G + (int)d1) * P.G + (int)d2;
+    return true;
+}
+
+template <bool LDS>
+__global__ void __launch_bounds__(INJECT_THREADS) k_inject_locate(DevParams P, SegLayout S, int nrec, const CellInfo *__restrict__ celltab,
+                                                                  const float4 *__restrict__ pos4, int64_t max_count, const int64_t *count_dev,
+                                                                  int2 *__restrict__ ent, int *__restrict__ tcount, int *__restrict__ tile_out)
+{
+    extern __shared__ int lds_cnt[];
+    __shared__ int s_first_out;
+    const int n = inject_n(count_dev, max_count);
+    const int t = (int)blockIdx.x, base = t * INJECT_TILE;
+    if (base >= n) return;
+    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    int *cnt = LDS ? lds_cnt : tcount + (size_t)t * nrec;
+    for (int r = tid; r < nrec; r += INJECT_THREADS) cnt[r] = 0;
+    if (tid == 0) s_first_out = INT_MAX;
+    if (!LDS) __threadfence();
+    __syncthreads();
+
+    // every group's records and, per lane, its rank among the group's lanes of the same record (ballot + mbcnt per
+    // distinct record), the group's count of that record and the lane that will account for it (the lowest)
+    int rec[INJECT_GROUPS], in_rank[INJECT_GROUPS], pop[INJECT_GROUPS], lead[INJECT_GROUPS];
+    int first_out = INT_MAX;
+#pragma unroll
+    for (int g = 0; g < INJECT_GROUPS; g++) {
+        const int i = base + (wave * INJECT_GROUPS + g) * 64 + lane;
+        int r = INJ_NOT_MINE;
+        if (i < n) {
+            const float4 p = pos4[i];
+            int cell;
+            if (!inject_locate(P, p.x, p.y, p.z, cell)) { r = INJ_OUTSIDE; first_out = min(first_out, i); }
+            else {
+                const CellInfo ci = celltab[cell];
+                const int sr = segment_record(S, ci.seg_type, ci.seg_tid);
+                r = owns_record(P, sr) ? sr : INJ_NOT_MINE;
+            }
+        }
+        rec[g] = r; in_rank[g] = 0; pop[g] = 0; lead[g] = lane;
+        unsigned long long todo = __ballot(r >= 0);
+        while (todo) {
+            const int l = __ffsll((long long)todo) - 1;
+            const int r0 = __builtin_amdgcn_readlane(r, l);
+            const unsigned long long m = __ballot(r == r0);
+            if (r == r0) {
+                in_rank[g] = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                pop[g] = __popcll(m);
+                lead[g] = l;
+            }
+            todo &= ~m;
+        }
+    }
+    if (first_out != INT_MAX) atomicMin(&s_first_out, first_out);
+
+    // the waves take turns in entry order; a group's lowest lane of each record takes the record's running count
+    // (leaders of one group hold distinct records; a wave's groups follow one another)
+    int at[INJECT_GROUPS];
+    for (int w = 0; w < INJECT_WAVES; w++) {
+        if (wave == w) {
+#pragma unroll
+            for (int g = 0; g < INJECT_GROUPS; g++) {
+                int b = 0;
+                if (rec[g] >= 0 && lead[g] == lane) b = atomicAdd(&cnt[rec[g]], pop[g]);
+                at[g] = __shfl(b, lead[g]) + in_rank[g];
+            }
+        }
+        if (!LDS) __threadfence();
+        __syncthreads();
+    }
+#pragma unroll
+    for (int g = 0; g < INJECT_GROUPS; g++) {
+        const int i = base + (wave * INJECT_GROUPS + g) * 64 + lane;
+        if (i < n) ent[i] = make_int2(rec[g], rec[g] >= 0 ? at[g] : 0);
+    }
+    if (LDS) for (int r = tid; r < nrec; r += INJECT_THREADS) tcount[(size_t)t * nrec + r] = cnt[r];
+    if (tid == 0) tile_out[t] = s_first_out;
+}
+
+// one workgroup: per record the exclusive prefix of the tiles' counts, in tile order, in place; the first entry outside
+// the box; the first queue failure's word made ready for k_inject_fail; the removal counts zeroed
+__global__ void __launch_bounds__(1024) k_inject_scan(int nrec, int64_t max_count, const int64_t *count_dev, int *__restrict__ tcount,
+                                                      const int *__restrict__ tile_out, int *__restrict__ removed, int *__restrict__ hdr)
+{
+    __shared__ int s_min;
+    const int n = inject_n(count_dev, max_count), tiles = (int)(((int64_t)n + INJECT_TILE - 1) / INJECT_TILE);
+    const int tid = (int)threadIdx.x;
+    if (tid == 0) s_min = INT_MAX;
+    __syncthreads();
+    int m = INT_MAX;
+    for (int t = tid; t < tiles; t += 1024) m = min(m, tile_out[t]);
+    if (m != INT_MAX) atomicMin(&s_min, m);
+    for (int r = tid; r < nrec; r += 1024) {
+        int run = 0;
+        for (int t = 0; t < tiles; t++) {
+            int *p = tcount + (size_t)t * nrec + r;
+            const int c = *p;
+            *p = run;
+            run += c;
+        }
+        removed[r] = 0;
+    }
+    __syncthreads();
+    if (tid == 0) { hdr[0] = s_min; hdr[1] = INT_MAX; }
+}
+
+__global__ void k_inject_fail(int nrec, int64_t max_count, const int64_t *count_dev, const int *__restrict__ tcount,
+                              const QueueInfo *__restrict__ qinfo, int2 *__restrict__ ent, int *__restrict__ hdr)
+{
+    const int n = inject_n(count_dev, max_count);
+    const int64_t i64 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i64 >= n) return;
+    const int i = (int)i64;
+    int2 e = ent[i];
+    if (e.x < 0) return;
+    e.y += tcount[(size_t)(i / INJECT_TILE) * nrec + e.x];
+    ent[i] = e;
+    if (e.y == qinfo[e.x].count) atomicMin(&hdr[1], i);
+}
+
+__global__ void k_inject_place(DevParams P, int64_t max_count, const int64_t *count_dev, const float4 *__restrict__ pos4,
+                               const float4 *__restrict__ vel4, const float *__restrict__ fert, const int2 *__restrict__ ent,
+                               const int *__restrict__ hdr, const QueueInfo *__restrict__ qinfo, int *__restrict__ queue,
+                               int *__restrict__ ids, int *__restrict__ removed, float4 *d_pos4, float4 *d_vel4, float4 *d_acc4,
+                               int *d_cell, uint8_t *d_pflags)
+{
+    const int n = inject_n(count_dev, max_count);
+    const int64_t i64 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i64 >= n) return;
+    const int i = (int)i64;
+    const int F = min(min(hdr[0], hdr[1]), n);
+    const int2 e = ent[i];
+    int slot = -1;
+    if (i < F && e.x >= 0) {
+        const QueueInfo q = qinfo[e.x];
+        const int k = e.y;                                          // < q.count: the first failure is at or after F
+        const int off = (q.front - q.rloc + k) % q.seg_size;        // logical element k
+        const int qi = slot_index(P, q.rloc) + off;                 // the queue is stored like the slots
+        slot = queue[qi];
+        queue[qi] = -1;
+        const int si = slot_index(P, slot);
+        if (si >= 0) {
+            const float4 p = pos4[i];
+            int cell = -1;
+            (void)inject_locate(P, p.x, p.y, p.z, cell);
+            d_pos4[si] = p;                                         // create_particle_s, as k_place writes it
+            d_vel4[si] = vel4 ? vel4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+            d_acc4[si] = make_float4(0.f, 0.f, 0.f, fert ? fert[i] : 0.f);
+            d_cell[si] = cell;
+            d_pflags[si] = 0;
+        }
+        atomicMax(&removed[e.x], k + 1);
+    }
+    if (ids) ids[i] = slot;
+}
+
+// one workgroup: every record the entries took slots from, as host_q_remove leaves it after that many removals; the
+// result record (the context's own, and the caller's)
+__global__ void __launch_bounds__(1024) k_inject_commit(int nrec, int64_t max_count, const int64_t *count_dev, const int *__restrict__ hdr,
+                                                        const int *__restrict__ removed, QueueInfo *qinfo, psamd_inject_result *own,
+                                                        psamd_inject_result *out)
+{
+    __shared__ unsigned long long s_placed;
+    const int n = inject_n(count_dev, max_count);
+    const int tid = (int)threadIdx.x;
+    if (tid == 0) s_placed = 0;
+    __syncthreads();
+    unsigned long long placed = 0;
+    for (int r = tid; r < nrec; r += 1024) {
+        const int R = removed[r];
+        if (R <= 0) continue;
+        QueueInfo q = qinfo[r];
+        q.count -= R;
+        if (q.count == 0) { q.front = -1; q.rear = -1; }
+        else q.front = q.rloc + (q.front - q.rloc + R) % q.seg_size;
+        qinfo[r] = q;
+        placed += (unsigned long long)R;
+    }
+    if (placed) atomicAdd(&s_placed, placed);
+    __syncthreads();
+    if (tid == 0) {
+        const int fo = hdr[0], ff = hdr[1];
+        const int F = min(min(fo, ff), n);
+        psamd_inject_result res;
+        res.done = F;
+        res.placed = (int64_t)s_placed;
+        res.status = F == n ? PSAMD_OK : F == fo ? PSAMD_ERR_OUTSIDE_BOX : PSAMD_ERR_QUEUE_EMPTY;
+        res.reserved = 0;
+        *own = res;
+        if (out && out != own) *out = res;
+    }
+}
+
+hipError_t launch_inject(hipStream_t st, const DevParams &P, const SegLayout &S, const DeviceState &d, int nrec, const InjectArgs &a,
+                         const InjectScratch &s)
+{
+    const int64_t tiles = (a.max_count + INJECT_TILE - 1) / INJECT_TILE;
+    if (nrec <= INJECT_LDS_RECORDS)
+        k_inject_locate<true><<<(unsigned)tiles, INJECT_THREADS, (size_t)nrec * sizeof(int), st>>>(P, S, nrec, d.celltab, a.pos4, a.max_count,
+                                                                                                 a.count_dev, s.ent, s.tcount, s.tile_out);
+    else
+        k_inject_locate<false><<<(unsigned)tiles, INJECT_THREADS, 0, st>>>(P, S, nrec, d.celltab, a.pos4, a.max_count, a.count_dev,
+                                                                         s.ent, s.tcount, s.tile_out);
+    PS_LAUNCH_CHECK();
+    k_inject_scan<<<1, 1024, 0, st>>>(nrec, a.max_count, a.count_dev, s.tcount, s.tile_out, s.removed, s.hdr);
+    PS_LAUNCH_CHECK();
+    const unsigned blocks = (unsigned)((a.max_count + 255) / 256);
+    k_inject_fail<<<blocks, 256, 0, st>>>(nrec, a.max_count, a.count_dev, s.tcount, d.qinfo, s.ent, s.hdr);
+    PS_LAUNCH_CHECK();
+    k_inject_place<<<blocks, 256, 0, st>>>(P, a.max_count, a.count_dev, a.pos4, a.vel4, a.fert_age, s.ent, s.hdr, d.qinfo, d.queue,
+                                           a.ids, s.removed, d.pos4, d.vel4, d.acc4, d.cell, d.pflags);
+    PS_LAUNCH_CHECK();
+    k_inject_commit<<<1, 1024, 0, st>>>(nrec, a.max_count, a.count_dev, s.hdr, s.removed, d.qinfo, s.own, a.result);
+    PS_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+}  // namespace psamd

@@ -31,6 +31,26 @@ struct ExportOut {
     psamd_live_stats stats;
 };
 
+// psamd_inject (inject.hip): the entries in tiles of INJECT_TILE; the caller's arrays and the scratch (grown by the host
+// when max_count exceeds what it was sized for)
+constexpr int INJECT_TILE = 4096;
+struct InjectArgs {
+    const float4 *pos4, *vel4;
+    const float *fert_age;
+    int64_t max_count;
+    const int64_t *count_dev;
+    int *ids;
+    psamd_inject_result *result;
+};
+struct InjectScratch {
+    int2 *ent;        // [max_count] per entry: the record (-1 not this rank's, -2 outside the box) and its rank in the record
+    int *tcount;      // [tiles * nrec] per tile and record: the count, then the exclusive prefix over the tiles
+    int *tile_out;    // [tiles] the tile's first entry outside the box (INT_MAX: none)
+    int *removed;     // [nrec] slots the inject took from the record's queue
+    int *hdr;         // [2] first entry outside the box, first queue failure
+    psamd_inject_result *own;   // the context's own result record (psamd_inject_result_get)
+};
+
 // Container layout by segment type (slots and QUEUE_INFO records), device copy.
 struct SegLayout {
     int32_t seg_base[5];
@@ -169,5 +189,10 @@ hipError_t launch_status_merge(hipStream_t st, const DevParams &P, const DeviceS
 // slot order; workgroup 0 writes the count and the statistics)
 hipError_t launch_export_live(hipStream_t st, const DevParams &P, const DeviceState &d, const ExportFields &out,
                               int64_t capacity, int64_t *count_out, psamd_live_stats *stats_out);
+
+// psamd_inject: locate + rank, the records' prefix, the first queue failure, the placement, the commit of the queues and
+// the result record (max_count > 0)
+hipError_t launch_inject(hipStream_t st, const DevParams &P, const SegLayout &S, const DeviceState &d, int nrec, const InjectArgs &a,
+                         const InjectScratch &s);
 
 }  // namespace psamd

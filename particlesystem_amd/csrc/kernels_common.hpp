@@ -16,6 +16,7 @@
 //                  app_common.cu:305-376): k_ops_hist / k_ops_scatter / k_replay_commit (lists of any length), k_moves_stage
 //   slab.hip       the messages of a multi-GPU step: halo snapshots, force records, status records, all-pairs snapshot
 //   export.hip     not part of the step: psamd_export_live, the live particles as compact arrays and their statistics
+//   inject.hip     not part of the step: psamd_inject, particles from device arrays into their segments' free slots
 //
 // Reference arithmetic is reproduced operation for operation: every file is built with
 // -ffp-contract=off; where the reference evaluates in double (EPS2 add, 0.5*a*t*t) so

@@ -16,6 +16,11 @@ import os
 import numpy as np
 
 from . import build as _build
+# psamd_slab_msg_download / _upload `which`: slab.py's message slots, under the names of the C header
+from .slab import (HALO_OUT as MSG_HALO_OUT, HALO_IN as MSG_HALO_IN, FORCE_OUT as MSG_FORCE_OUT, FORCE_IN as MSG_FORCE_IN,
+                   XFER_OUT as MSG_XFER_OUT, XFER_IN as MSG_XFER_IN, STATUS_OUT as MSG_STATUS_OUT, STATUS_IN as MSG_STATUS_IN,
+                   ALLG_OUT as MSG_ALLG_OUT, ALLG_IN as MSG_ALLG_IN, XFER2_OUT as MSG_XFER2_OUT, XFER2_IN as MSG_XFER2_IN,
+                   FAR_OUT as MSG_FAR_OUT, FAR_IN as MSG_FAR_IN)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PSAMD_LIB") or os.path.join(HERE, "libpsamd.so")   # PSAMD_LIB: another build, for A/B measurements
@@ -160,13 +165,6 @@ def merge_live_stats(stats):
                 v = v + x
         out[n] = int(v) if n in ("live", "nonfinite") else (v if v.ndim else float(v))
     return out
-
-
-# psamd_slab_msg_download / _upload `which`
-MSG_HALO_OUT, MSG_HALO_IN, MSG_FORCE_OUT, MSG_FORCE_IN, MSG_XFER_OUT, MSG_XFER_IN, MSG_STATUS_OUT, MSG_STATUS_IN = 0, 2, 4, 5, 6, 8, 10, 11
-MSG_ALLG_OUT, MSG_ALLG_IN = 12, 13
-MSG_XFER2_OUT, MSG_XFER2_IN = 14, 16
-MSG_FAR_OUT, MSG_FAR_IN = 18, 19
 
 
 class PsamdError(RuntimeError):
@@ -477,19 +475,26 @@ class ParticleSystem:
     def slab_finish(self):
         self._ck(self.lib.psamd_slab_finish(self.h))
 
+    def msg_table(self):
+        """For every `which` of psamd_slab_msg_download: (device pointer, bytes that travel, bytes of room), read once.  Only
+        the transfer messages (6-9) travel with less than their room, and that may grow: msg_bytes() asks for it afresh."""
+        if getattr(self, "_msg_table", None) is None:
+            b, w = self.slab_buffers(), max(1, self.cfg.world)
+            t = [(b.halo_out[k], b.halo_out_bytes[k]) for k in (0, 1)] + [(b.halo_in[k], b.halo_in_bytes[k]) for k in (0, 1)]
+            t += [(b.force_out, b.force_out_bytes), (b.force_in, b.force_in_bytes)]
+            t += [(p, b.xfer_bytes, b.xfer_bytes_max) for p in (*b.xfer_out, *b.xfer_in)]
+            t += [(b.status_out, b.status_bytes), (b.status_in, b.status_bytes * w), (b.allg_out, b.allg_bytes), (b.allg_in, b.allg_bytes * w)]
+            t += [(p, b.xfer2_bytes) for p in (*b.xfer2_out, *b.xfer2_in)]
+            t += [(b.far_out, b.far_bytes), (b.far_in, b.far_bytes * w)]
+            self._msg_table = [(e[0] or 0, e[1], e[-1]) for e in t]
+        return self._msg_table
+
     def msg_bytes(self, which):
         """Size of message buffer `which` (psamd_slab_msg_download numbering); 0: no such message.  The transfer messages
         (6-9) may grow from step to step (config.xfer_cap_max): their size is asked for afresh."""
         if 6 <= which <= 9:
             return self.slab_buffers().xfer_bytes
-        if getattr(self, "_msg_bytes", None) is None:
-            b = self.slab_buffers()
-            self._msg_bytes = [b.halo_out_bytes[0], b.halo_out_bytes[1], b.halo_in_bytes[0], b.halo_in_bytes[1],
-                               b.force_out_bytes, b.force_in_bytes] + [b.xfer_bytes] * 4 + \
-                              [b.status_bytes, b.status_bytes * max(1, self.cfg.world),
-                               b.allg_bytes, b.allg_bytes * max(1, self.cfg.world)] + [b.xfer2_bytes] * 4 + \
-                              [b.far_bytes, b.far_bytes * max(1, self.cfg.world)]
-        return self._msg_bytes[which]
+        return self.msg_table()[which][1]
 
     def msg_download(self, which, nbytes=None):
         nbytes = self.msg_bytes(which) if nbytes is None else nbytes

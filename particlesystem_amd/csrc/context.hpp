@@ -1,0 +1,172 @@
+// context.hpp -- the psamd context and what the host units share (create.hip, step.hip, io.hip).
+//
+// Host side of the drop-in boundary, C++ like the reference's host code.  It mirrors
+// the reference driver's view of the path: nine buffers (ps.cpp:70-78), one-off setup
+// stages, then per step init_iframe -> build_grid -> calc_forces (ps.cpp:1843-1928).
+// All arithmetic of the step runs in the HIP kernels (kernels_common.hpp holds the map); there
+// is no CPU fallback: without a HIP device psamd_create fails with PSAMD_ERR_NO_DEVICE.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../../include/psamd.h"
+#include "device_types.h"
+#include "geometry.hpp"
+#include "kernels.h"
+#include "partition.hpp"
+
+namespace psamd {
+// A slab message (device), by the ABI's `which` numbering (psamd_slab_msg_download in include/psamd.h); in a pair,
+// + 0 = the rank below, + 1 = the rank above.  The *_IN of status, allg and far hold every rank's message, all-gathered.
+enum { MSG_HALO_OUT = 0, MSG_HALO_IN = 2, MSG_FORCE_OUT = 4, MSG_FORCE_IN, MSG_XFER_OUT = 6, MSG_XFER_IN = 8, MSG_STATUS_OUT = 10, MSG_STATUS_IN,
+       MSG_ALLG_OUT, MSG_ALLG_IN, MSG_XFER2_OUT = 14, MSG_XFER2_IN = 16, MSG_FAR_OUT = 18, MSG_FAR_IN, MSG_COUNT };
+struct SlabMsg {
+    int *ptr = nullptr;
+    size_t bytes = 0, alloc = 0;    // what travels now; the buffer's room (they differ for MSG_XFER_*: bytes grows with P.xfer_cap)
+};
+// bytes of a transfer message with room for `recs` records
+inline size_t xfer_msg_bytes(size_t recs) { return ((size_t)MSG_HEADER_WORDS + recs * (sizeof(XferRec) / sizeof(int))) * sizeof(int); }
+}  // namespace psamd
+
+using namespace psamd;      // (a private header: every host unit speaks these types)
+
+struct psamd_ctx {
+    Geometry geo;
+    DevParams P{};
+    DevParams P_int{}, P_rest{};      // the pair stage cut in two: interior own cells (no halo needed), the rest
+    bool have_interior = false, interior_done = false;
+    SegLayout S{};
+    DeviceState d;
+    hipStream_t stream = nullptr;       // stream in use
+    hipStream_t own_stream = nullptr;   // the one this context created
+    SlabPlan plan;
+    SlabMsg msg[MSG_COUNT];
+    int halo_out_c0[2] = {0, 0}, halo_out_cells[2] = {0, 0}, halo_in_cells[2] = {0, 0};
+    std::map<int, int> cap_decisions; // slab: record number -> the transfer capacity all ranks agreed on in that step (adopted two steps on)
+    int *pack_off[2] = {nullptr, nullptr}, *unpack_off[2] = {nullptr, nullptr};
+    int slab_stage = 0;               // 0 idle, 1 built, 2 pairs done, 3 applied
+    size_t frame_ints = 0;            // ints zeroed by init_iframe
+    std::vector<void *> allocs;
+    std::string err;
+    // host mirrors
+    std::vector<CellInfo> celltab;
+    std::vector<QueueInfo> h_qinfo;   // valid while !queues_on_device_newer
+    std::vector<int32_t> h_queue;
+    bool host_queues_valid = true;    // host mirror == device copy
+    FrameScalars *h_fs = nullptr;     // pinned host copies of the per-frame scalars: TWO records, a step's number picks one
+    FrameScalars last{};              // the record of the last step the host has read (consume_scalars)
+    int64_t processed_total = 0;      // sum over steps of the live particles at build_grid
+    int64_t max_bucket_seen = 0;
+    int bucket_cap0 = 2048;           // the longest operation list the step's replay instance sorts in LDS (2048 / 4096 / 8192, from the last lists seen)
+    char *snapshot = nullptr;         // device image for snapshot_save / _restore
+    int snapshot_step = 0;
+    void *staging = nullptr;          // device staging for AoS transfers
+    size_t staging_bytes = 0;
+    // stage state machine
+    bool frame_reset = false, grid_built = false, pairs_done = false;
+    bool tdata_mirror = true;         // build_grid also writes the reference's T_DATA rows (psamd_set_tdata_mirror)
+    bool frame_clean = true;          // the per-frame counts are zero: a finished step leaves them so (its last kernel is the next init_iframe)
+    int step = 0;
+    int64_t steps_total = 0;
+    int live_at_build = -1;           // host copy of fs->live (valid after a sync)
+    bool interior_ran = false;        // this step's pair stage ran in two passes (the scalars hold the second pass's task count)
+    std::set<int> interior_steps;     // ... the numbers of such steps whose records have not been read yet
+    int64_t tasks_last = 0;           // force tasks of the last step (all passes), sizes the next step's balanced pass
+    int64_t packs_last = 0;           // ... of which packs of partly filled slices
+    // upper bound of the live count at the next build_grid, kept on the host so that the
+    // life-cycle kernels can be sized without a read-back (-1 = unknown)
+    int64_t live_bound = 0, snapshot_live_bound = 0;
+    // psamd_inject: max_count of the injects enqueued after step k (key k = scalars_seq at the call), until the record
+    // of step k + 1 -- the first that counts them -- has been read
+    std::map<int, int64_t> inject_tally;
+    InjectScratch inj{};              // its scratch: ent / tcount / tile_out grow with max_count (inj_cap), the rest is fixed
+    int64_t inj_cap = 0;
+    // timing
+    int timing = 0;                    // 0 off, 1 pair pass / apply / life cycle, 2 every stage
+    int timing_period = 1;             // events are recorded on every timing_period-th step since set_timing
+    int64_t timing_steps = 0;          // steps since set_timing
+    int timing_now = 0;                // the level in force for the step being run (0 on the steps in between)
+    // The step's scalars: the device numbers the records it hands out (StepState.seq), the host counts the steps it has
+    // enqueued (scalars_seq) and the records it has read (scalars_seen).  run_ahead = 1: step k + 1 is enqueued once the
+    // record of step k - 1 has been read -- the host is never on a step's critical path; 0: every step's own record is
+    // waited for before the call returns.
+    int scalars_seq = 0, scalars_seen = 0;
+    int run_ahead = 1;
+    int pending_status = PSAMD_OK;     // the verdict of a step whose record was read by a call that does not report verdicts (kept for the next that does)
+    std::string pending_err;
+    bool wedged = false;               // a step's scalars did not arrive within the wall-clock bound: the context refuses further work
+    // Timing events: two sets, a timed step takes the one that was read longest ago; a set is read when it is taken again
+    // or by psamd_get_timing -- never by the step that recorded it (the host runs ahead of the GPU).
+    enum { E_RESET = 0, E_HIST, E_SCAN, E_SCATTER, E_SORT, E_SORT_END, E_COLLIDE, E_FORCE, E_PAIRS_END, E_APPLY, E_LIFE, E_END, E_COUNT };
+    hipEvent_t ev[2][E_COUNT]{};
+    int ev_level[2] = {0, 0};          // level a set was recorded at, 0: nothing outstanding in it
+    int tset = 0;                      // the set of the step being run
+    int64_t timed_steps = 0;
+    bool ev_made = false;
+    double t_us[PSAMD_NUM_TIMERS]{};
+    std::vector<float> t_samples[PSAMD_NUM_TIMERS];
+    int64_t t_launches = 0;
+    // stage sequences as hipGraphs (psamd_set_graphs): per kind of sequence, the shapes captured so far
+    struct GraphSlot { uint64_t key; hipGraphExec_t exec; uint64_t stamp; };
+    bool graphs = false;
+    std::vector<GraphSlot> gcache[5];
+    uint64_t gstamp = 0;
+    int64_t graph_launches = 0, graph_captures = 0;
+    std::string graph_refused;         // why the runtime would not capture (the context then runs without graphs)
+    int64_t slab_bound = 0;            // the bound slab_apply sized its launches from; slab_finish uses the same
+    int wait_policy = 0;               // how the host waits for the step's scalars: 0 spin, 1 spin briefly, then nap
+    double wait_limit_s = 10.0;        // ... and for how long at most (PSAMD_WAIT_LIMIT_S)
+};
+
+namespace psamd {
+
+const char *status_text(int status);
+
+inline int fail(psamd_ctx *c, int status, const std::string &what)
+{
+    if (c) c->err = std::string(status_text(status)) + ": " + what;
+    return status;
+}
+
+inline int hip_fail(psamd_ctx *c, hipError_t e, const char *what)
+{
+    return fail(c, e == hipErrorOutOfMemory ? PSAMD_ERR_OUT_OF_MEMORY : PSAMD_ERR_HIP,
+                std::string(what) + ": " + hipGetErrorString(e));
+}
+
+#define PS_HIP(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail((c), e_, #call); } while (0)
+
+template <typename T>
+hipError_t dev_alloc(psamd_ctx *c, T **out, size_t n)
+{
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
+    if (e != hipSuccess) return e;
+    c->allocs.push_back(p);
+    *out = (T *)p;
+    // PSAMD_POISON (tests): fresh device memory is usually zero, reused memory is not -- fill every
+    // allocation with a pattern so that anything read before it is written shows up
+    static const bool poison = std::getenv("PSAMD_POISON") != nullptr;
+    if (poison) {
+        e = hipMemset(p, 0xA5, std::max<size_t>(n, 1) * sizeof(T));
+        if (e == hipSuccess) e = hipDeviceSynchronize();     // (the fill must not overtake the context's own stream)
+    }
+    return e;
+}
+
+// internals that cross the host units
+int pull_queues(psamd_ctx *c);                      // io.hip: device -> host mirror
+int push_queues(psamd_ctx *c);                      // ... host mirror -> device
+int check_device_errors(psamd_ctx *c);              // step.hip: after a sync, the sticky error bits raised by kernels
+int drain_scalars(psamd_ctx *c, bool quiet = false);
+int refuse_wedged(psamd_ctx *c);
+void drop_graphs(psamd_ctx *c);
+
+}  // namespace psamd

@@ -1,0 +1,589 @@
+// create.hip -- making and describing a context: psamd_create as a sequence of named parts, psamd_destroy,
+// psamd_describe and the getters of sizes, configuration and slab plan.
+#include <cmath>
+#include <new>
+
+#include "context.hpp"
+
+const char *psamd::status_text(int s)
+{
+    switch (s) {
+    case PSAMD_OK: return "ok";
+    case PSAMD_ERR_INVALID_ARG: return "invalid argument";
+    case PSAMD_ERR_NO_DEVICE: return "no usable HIP device (the HIP path is the only path)";
+    case PSAMD_ERR_HIP: return "HIP runtime error";
+    case PSAMD_ERR_OUT_OF_MEMORY: return "out of device memory";
+    case PSAMD_ERR_OUTSIDE_BOX: return "particle location outside box";
+    case PSAMD_ERR_QUEUE_EMPTY: return "overflow: reserved space of the segment is full";
+    case PSAMD_ERR_CELL_OVERFLOW: return "cell or queue-op capacity exceeded on device";
+    case PSAMD_ERR_STATE: return "stage called out of order";
+    case PSAMD_ERR_UNSUPPORTED: return "unsupported";
+    }
+    return "unknown status";
+}
+
+extern "C" {
+
+int psamd_abi_version(void) { return PSAMD_ABI_VERSION; }
+const char *psamd_status_string(int status) { return status_text(status); }
+const char *psamd_last_error(const psamd_ctx *c) { return c ? c->err.c_str() : "null context"; }
+
+int psamd_default_config(psamd_config *cfg)
+{
+    if (!cfg) return PSAMD_ERR_INVALID_ARG;
+    std::memset(cfg, 0, sizeof *cfg);
+    cfg->max_particles_num = 1024 * 1024;  // common.h:12
+    cfg->x_factor = 2;                     // common.h:13
+    cfg->chunk_factor = 4;                 // common.h:29
+    cfg->chunk_dim = 4;                    // common.h:30
+    cfg->cell_size = 5.0;                  // common.h:52
+    cfg->eps2 = 0.2;                       // common.h:53
+    cfg->collision_radius = 0.4;           // common.h:54
+    cfg->particle_weight = 60.0;           // common.h:55
+    cfg->dt = 0.05;                        // common.h:69
+    cfg->max_v = 10.0;                     // common.h:66
+    cfg->explosion_speed = 3.0;            // common.h:67
+    cfg->life_steps = 300.0;               // common.h:58
+    cfg->device = 0;
+    cfg->flags = 0;
+    cfg->seed = 1;                         // RAND_SEED, common.h:56
+    cfg->rank = 0;
+    cfg->world = 1;
+    cfg->drag = 0.0;
+    cfg->force_sign = 1.0;
+    return PSAMD_OK;
+}
+
+static SlabPlan plan_for(const Geometry &g, const psamd_config &cfg)
+{
+    const bool given = cfg.world >= 1 && cfg.world <= PSAMD_MAX_RANKS && cfg.cuts[cfg.world] != 0;
+    return make_slab_plan(g.F, g.D, g.seg_base, g.seg_size_t, g.info_base, cfg.rank, cfg.world, given ? cfg.cuts : nullptr);
+}
+
+// DevParams fields that describe what this rank holds (partition.hpp -> device_types.h)
+static void fill_slab_params(const Geometry &g, const SlabPlan &pl, const psamd_config &cfg, DevParams &P)
+{
+    const int GG = g.G * g.G;
+    P.rank = pl.rank; P.world = pl.world; P.num_cells_global = g.num_cells;
+    const int first[4] = {pl.state_lo, pl.below_lo, pl.lentin_lo, pl.above_lo};
+    const int layers[4] = {pl.state_hi - pl.state_lo, pl.lentin_lo - pl.below_lo, pl.lentin_hi - pl.lentin_lo, pl.above_hi - pl.above_lo};
+    P.halo_cap_cell = (cfg.halo_cap_cell > 0 && cfg.halo_cap_cell < g.max_per_cell) ? cfg.halo_cap_cell : g.max_per_cell;
+    P.xfer_cap = pl.world > 1 ? (cfg.xfer_cap > 0 ? cfg.xfer_cap : std::max(4096, GG * g.max_per_cell / 4)) : 0;
+    // how far the transfer messages may grow (their buffers' room): by default a step's worst case -- everything two cell
+    // layers hold, and a child of each (a particle moves one layer a step, two when the rounded sum lands on the far face)
+    P.xfer_cap0 = P.xfer_cap;
+    P.xfer_cap_max = pl.world > 1 ? std::max(P.xfer_cap, cfg.xfer_cap_max > 0 ? cfg.xfer_cap_max
+                                                         : (int)std::min<int64_t>(4ll * GG * g.max_per_cell, INT32_MAX / 256)) : 0;
+    int64_t slots = 0;
+    for (int t = 0; t < 4; t++) { P.slot_lo[t] = pl.slot_lo[t]; P.slot_n[t] = pl.slot_hi[t] - pl.slot_lo[t]; slots += P.slot_n[t];
+                                  P.rec_lo[t] = pl.rec_lo[t]; P.rec_hi[t] = pl.rec_hi[t]; }
+    P.slots_total = (int)slots;
+    int base = 0;
+    int64_t sorted = 0;
+    for (int r = 0; r < 4; r++) {
+        P.reg_first[r] = first[r]; P.reg_layers[r] = layers[r]; P.reg_base[r] = base; P.reg_sorted[r] = (int)sorted;
+        base += layers[r] * GG + 1;                                     // + the gap cell
+        // the own block can hold every owned slot (overflow-killed entries keep their place in
+        // the sorted order for the frame); a remote block what its messages can carry
+        sorted += r == 0 ? slots : (int64_t)layers[r] * GG * P.halo_cap_cell;
+    }
+    P.n_local_cells = base; P.n_own_cells = layers[0] * GG;
+    P.sorted_cap = (int)sorted;
+    P.own_comp0 = (std::max(pl.cut_lo, pl.state_lo) - pl.state_lo) * GG;
+    P.own_comp1 = (std::min(pl.cut_hi, pl.state_hi) - pl.state_lo) * GG;
+    if (P.own_comp1 < P.own_comp0) P.own_comp1 = P.own_comp0;
+    // the whole pair stage in one pass: the lent cells, then the own ones
+    P.comp_lo[0] = P.reg_base[2]; P.comp_hi[0] = P.reg_base[2] + layers[2] * GG;
+    P.comp_lo[1] = P.own_comp0; P.comp_hi[1] = P.own_comp1;
+    P.comp_lo[2] = P.comp_hi[2] = 0;
+    P.lentout_c0 = (pl.lentout_lo - pl.state_lo) * GG; P.lentout_c1 = (pl.lentout_hi - pl.state_lo) * GG;
+}
+
+// the largest squared distance two in-box particles can have, with slack for one wrap of drift
+static double max_d2(const Geometry &g) { const double L = (double)g.G * g.cfg.cell_size; return 3.0 * (2.0 * L) * (2.0 * L); }
+
+// Everything the kernels' parameters (c->P, c->S) take from the configuration, the geometry and the ranks' plans:
+// host arithmetic only, no HIP call.
+static int derive_params(psamd_ctx *c, const psamd_config *cfg)
+{
+    const Geometry &g = c->geo; DevParams &P = c->P;
+    P.G = g.G; P.num_cells = g.num_cells; P.num_chunks = g.num_chunks; P.container = g.container;
+    P.max_per_cell = g.max_per_cell; P.max_per_chunk = g.max_per_chunk;
+    P.slices = (g.max_per_cell + 63) / 64;
+    P.flags = cfg->flags;
+    P.t = (float)cfg->dt;
+    P.kid_thr = float_ceil(g.kid_age);
+    P.life_thr = float_floor(g.particle_life);
+    // every pair whose fp32 squared distance is at or below this gets the exact
+    // collision test; the margin only has to cover the rounding of sqrtf
+    P.coll_d2_gate = (float)(cfg->collision_radius * cfg->collision_radius * 1.001 + 1e-30);
+    P.dmax = (float)cfg->cell_size;   // MAX_DX = CELL_SIZE, common.h:65
+    P.vmax = (float)cfg->max_v;
+    P.w_default = (float)cfg->particle_weight;
+    P.fert_lo = (float)g.min_fert; P.fert_hi = (float)g.max_fert;
+    P.cell_size = cfg->cell_size; P.eps2 = cfg->eps2; P.coll_radius = cfg->collision_radius;
+    P.kid_age = g.kid_age; P.life = g.particle_life; P.expl_speed = cfg->explosion_speed;
+    P.seed = cfg->seed;
+    P.drag = (float)cfg->drag;
+    P.force_sign = cfg->force_sign < 0 ? -1.0f : 1.0f;
+    if (cfg->drag < 0) return fail(c, PSAMD_ERR_INVALID_ARG, "drag must be >= 0");
+    fill_slab_params(g, c->plan, *cfg, P);
+    P.status_words = STATUS_CHUNK_OFF + 4 * g.num_chunks;
+    if (cfg->world > 1) {
+        // the ring neighbours' queue records; and whether any rank's whole state is ONE cell layer: a particle
+        // that crosses two layers in a step (from one ulp below a face, moved by exactly CELL_SIZE) can fly over
+        // such a rank, to the rank beyond it -- those records get outboxes of their own, sent straight to rank +-2.
+        // All-pairs: every rank's block of the all-gathered snapshot has the same size, room for the rank with the
+        // most cells / slots.
+        bool single = false;
+        int cells = 0;
+        int64_t slots = 0;
+        psamd_config rc = *cfg;
+        for (int r = 0; r < cfg->world; r++) {
+            rc.rank = r;
+            const SlabPlan pr = plan_for(g, rc);
+            if (!pr.valid) return fail(c, PSAMD_ERR_UNSUPPORTED, "no slab partition for this grid and world size");
+            single |= pr.state_hi - pr.state_lo < 2;
+            const int which = r == (cfg->rank + cfg->world - 1) % cfg->world ? 0 : -1, which2 = r == (cfg->rank + 1) % cfg->world ? 1 : -1;
+            for (int w : {which, which2})
+                if (w >= 0) for (int t = 0; t < 4; t++) { P.nbr_rec_lo[w][t] = pr.rec_lo[t]; P.nbr_rec_hi[w][t] = pr.rec_hi[t]; }
+            int64_t sl = 0;
+            for (int t = 0; t < 4; t++) sl += pr.slot_hi[t] - pr.slot_lo[t];
+            cells = std::max(cells, (pr.state_hi - pr.state_lo) * g.G * g.G);
+            slots = std::max(slots, sl);
+        }
+        P.xfer2_cap = (single && cfg->world >= 4) ? 1024 : 0;       // (a ring of two or three has no rank beyond the neighbours)
+        // A record for a rank further away: only a particle whose position stopped being a number travels that far (it is
+        // filed under one fixed cell wherever it was), and only births make such particles (a child with the direction
+        // (0, 0, 0)): with births on, a world of four or more all-gathers a small far outbox in the transfer phase.
+        P.far_cap = (cfg->world >= 4 && (cfg->flags & PSAMD_FLAG_EXPLOSIONS)) ? 16 : 0;
+        if (cfg->flags & PSAMD_FLAG_ALL_PAIRS) {
+            P.allg_cells = cells;
+            P.allg_cap = (int)((slots + 63) & ~(int64_t)63);
+            P.allg_block = MSG_HEADER_WORDS + P.allg_cells + 4 * P.allg_cap;
+        }
+    }
+    auto bits_for = [](int64_t n) { int b = 1; while (((int64_t)1 << b) < n) b++; return b; };
+    P.key_chunk_shift = 2 + bits_for(g.container);
+    P.key_rec_shift = P.key_chunk_shift + bits_for((int64_t)g.num_chunks + 1);
+    P.key_bits = P.key_rec_shift + bits_for(g.queue_infos);
+    {
+        // (r.r + eps2)^3 over every pair of in-box positions, with slack for one wrap of drift
+        const double lo = cfg->eps2 * cfg->eps2 * cfg->eps2, hi = std::pow(max_d2(g) + cfg->eps2, 3.0);
+        P.lean_math = (lo > std::ldexp(1.0, -60) && hi < std::ldexp(1.0, 60)) ? 1 : 0;
+        // Collision flags before forces (lean modes): a collision needs two bodies within
+        // COLLISION_RADIUS, so only bodies that close to a cell face concern the cell beyond it;
+        // 2.5 % + 1e-3 of slack covers every rounding between here and the exact test.  Needs
+        // the radius to be small against the cell (else the halo is the whole neighbour).
+        P.halo_reach = (float)(cfg->collision_radius * 1.025 + 1e-3);
+        {   // largest float t with (double)sqrtf(t) <= COLLISION_RADIUS (sqrtf: correctly rounded, monotone)
+            auto collides = [&](float t) { return !((double)std::sqrt(t) > cfg->collision_radius); };
+            uint32_t lo_b = 0u, hi_b = 0x7f7fffffu;                 // bit patterns of non-negative floats order like the floats
+            auto as_f = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
+            if (!collides(0.0f)) P.coll_d2_max = -1.0f;
+            else {
+                while (lo_b < hi_b) { const uint32_t mid = lo_b + (hi_b - lo_b + 1) / 2; if (collides(as_f(mid))) lo_b = mid; else hi_b = mid - 1; }
+                P.coll_d2_max = as_f(lo_b);
+            }
+        }
+        P.two_pass = (P.lean_math && P.halo_reach < 0.25 * cfg->cell_size && !std::getenv("PSAMD_ONE_PASS")) ? 1 : 0;
+    }
+    if (P.key_bits > 63) return fail(c, PSAMD_ERR_UNSUPPORTED, "queue-op key does not fit 64 bits for this configuration");
+    if ((cfg->flags & PSAMD_FLAG_ALL_PAIRS) && !P.lean_math) return fail(c, PSAMD_ERR_UNSUPPORTED, "all-pairs forces are built for the lean pair arithmetic only (EPS2 in its validated range)");
+    if ((cfg->flags & PSAMD_FLAG_ALL_PAIRS) && !P.two_pass) return fail(c, PSAMD_ERR_UNSUPPORTED, "all-pairs forces need the two-pass pair stage (collision radius small against the cell)");
+    for (int k = 0; k < 5; k++) { c->S.seg_base[k] = g.seg_base[k]; c->S.info_base[k] = g.info_base[k]; }
+    for (int k = 0; k < 4; k++) c->S.seg_size_t[k] = g.seg_size_t[k];
+    P.eps2f = (float)cfg->eps2;
+    P.eps_f32_from = INFINITY;   // always add EPS2 in double, unless probe_eps_f32 finds a threshold
+    return PSAMD_OK;
+}
+
+// room of a neighbour transfer message, in records: the most a step can ask for (also sizes the op and move lists)
+static size_t xfer_room(const DevParams &P) { return (size_t)P.xfer_cap_max + (size_t)P.xfer2_cap + (size_t)P.far_cap * (size_t)std::max(1, P.world) / 2 + 1; }
+
+// The step's device arrays.  The SEQUENCE of the HIP calls here is load-bearing, the copies and fills between the
+// allocations included (the runtime allocates on their first use): with the three fills and the chunk_segs copy moved
+// behind the last allocation the all-pairs step measured 0.15-0.17 % slower, with the same kernels (see also ctask_start).
+static int alloc_step_arrays(psamd_ctx *c)
+{
+    const Geometry &g = c->geo; const DevParams &P = c->P; DeviceState &d = c->d;
+    const size_t C = (size_t)P.slots_total;          // owned slots
+    const size_t SC = (size_t)P.sorted_cap + 64;     // sorted-order arrays (+ slack: scalar loads fetch whole groups)
+    const size_t LC = (size_t)P.n_local_cells;
+    const size_t xf = xfer_room(P);
+    d.ops_cap = (int)std::min<size_t>(3 * C + 2 * xf + 64 + (P.world > 1 ? (size_t)P.world * STATUS_KILL_CAP : 0), (size_t)INT32_MAX / 2);
+    d.moves_cap = (int)std::min<size_t>(2 * C + 2 * xf + 64, (size_t)INT32_MAX / 2);
+    int *frame = nullptr;
+    // cell counts, chunk counts, queue-op counts and cursors per record, halo counts, active-list lengths, hand-off flags of the force pass
+    const size_t frame_ints = LC + g.num_chunks + 2 * (size_t)g.queue_infos + LC + LC + 2 * LC * P.slices;   // (flags: one block per pass of the pair stage)
+    PS_HIP(c, dev_alloc(c, &d.pos4, C));
+    PS_HIP(c, dev_alloc(c, &d.vel4, C));
+    PS_HIP(c, dev_alloc(c, &d.acc4, C));
+    PS_HIP(c, dev_alloc(c, &d.cell, C));
+    PS_HIP(c, dev_alloc(c, &d.pflags, C));
+    PS_HIP(c, dev_alloc(c, &d.tdata, 6 * C));
+    PS_HIP(c, dev_alloc(c, &d.qinfo, (size_t)g.queue_infos));
+    PS_HIP(c, dev_alloc(c, &d.queue, C));
+    PS_HIP(c, dev_alloc(c, &frame, frame_ints));
+    d.cell_count = frame; d.chunk_count = frame + LC; d.rec_count = d.chunk_count + g.num_chunks;
+    d.rec_cursor = d.rec_count + g.queue_infos;
+    d.halo_count = d.rec_cursor + g.queue_infos;
+    d.active_count = d.halo_count + LC;
+    d.task_ready = d.active_count + LC;
+    c->frame_ints = frame_ints;
+    PS_HIP(c, dev_alloc(c, &d.halo_f, (size_t)3 * LC * HALO_CAP + 64));   // + slack: scalar loads fetch whole groups
+    PS_HIP(c, dev_alloc(c, &d.halo_id, LC * HALO_CAP + 64));
+    PS_HIP(c, dev_alloc(c, &d.active_list, SC));
+    PS_HIP(c, dev_alloc(c, &d.snap_cid, SC));
+    PS_HIP(c, dev_alloc(c, &d.task_list2, LC * P.slices));
+    PS_HIP(c, dev_alloc(c, &d.merged_tasks, LC));
+    PS_HIP(c, dev_alloc(c, &d.task_cost, LC));
+    // (LC + 1 entries are used.  At LC + 1 the later allocations move and the all-pairs step measured 0.1-0.2 % slower,
+    // with the same kernels.)
+    PS_HIP(c, dev_alloc(c, &d.ctask_start, 2 * LC + 2));
+    PS_HIP(c, dev_alloc(c, &d.cost_start, 2 * LC + 2));
+    PS_HIP(c, dev_alloc(c, &d.wave_pos, (size_t)MAX_PAIR_WAVES + 1));
+    PS_HIP(c, dev_alloc(c, &d.rec_start, (size_t)g.queue_infos + 1));
+    PS_HIP(c, dev_alloc(c, &d.fs, 1));
+    PS_HIP(c, dev_alloc(c, &d.st, 1));
+    PS_HIP(c, hipMemsetAsync(d.st, 0, sizeof(StepState), c->stream));
+    PS_HIP(c, dev_alloc(c, &d.cell_start, LC + 1));
+    PS_HIP(c, dev_alloc(c, &d.cursor, LC));
+    PS_HIP(c, dev_alloc(c, &d.task_start, LC + 1));
+    PS_HIP(c, dev_alloc(c, &d.task_list, LC * P.slices));
+    PS_HIP(c, dev_alloc(c, &d.sorted_id, SC));
+    PS_HIP(c, dev_alloc(c, &d.flag_slot, C));
+    PS_HIP(c, dev_alloc(c, &d.snap_soa, 4 * (size_t)P.sorted_cap + 64));
+    PS_HIP(c, dev_alloc(c, &d.snap_age, SC));
+    PS_HIP(c, dev_alloc(c, &d.force4, SC));
+    PS_HIP(c, dev_alloc(c, &d.celltab, (size_t)g.num_cells));
+    if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
+        // partial sums of the all-pairs far pass: one float4 per (part, particle that needs a force) -- dense, 64 to a task;
+        // every entry of the sorted order could be one
+        d.part_tasks = (int)(SC / 64 + 1);
+        PS_HIP(c, dev_alloc(c, &d.part_acc, (size_t)ALLP_PARTS * d.part_tasks * 64));
+        PS_HIP(c, dev_alloc(c, &d.act_start, LC + 1));
+        PS_HIP(c, dev_alloc(c, &d.dense_gi, SC));
+        PS_HIP(c, dev_alloc(c, &d.dense_cell, SC));
+    }
+    PS_HIP(c, dev_alloc(c, &d.chunk_skip, C));               // the chunk lists' capacity rule (chunk_cap_block)
+    PS_HIP(c, dev_alloc(c, &d.chunk_segs, (size_t)g.num_chunks * 27));
+    {
+        std::vector<int2> segs((size_t)g.num_chunks * 27);
+        for (int ch = 0; ch < g.num_chunks; ch++) {
+            Pair pk[27];
+            g.chunk_segments(ch, pk);
+            for (int j = 0; j < 27; j++) {
+                const int k = seg_index(pk[j].c);
+                segs[(size_t)ch * 27 + j] = make_int2(g.seg_base[k] + pk[j].p * g.seg_size_t[k], g.seg_size_t[k]);
+            }
+            // slot order (set_pkg_segments lists them so already; the walk must not depend on it)
+            std::sort(segs.begin() + (size_t)ch * 27, segs.begin() + (size_t)ch * 27 + 27, [](const int2 &a, const int2 &b) { return a.x < b.x; });
+        }
+        PS_HIP(c, hipMemcpy(d.chunk_segs, segs.data(), segs.size() * sizeof(int2), hipMemcpyHostToDevice));
+    }
+    PS_HIP(c, dev_alloc(c, &d.op_keys, (size_t)d.ops_cap));
+    PS_HIP(c, dev_alloc(c, &d.op_keys_sorted, (size_t)d.ops_cap));
+    PS_HIP(c, dev_alloc(c, &d.op_args, (size_t)d.ops_cap));
+    PS_HIP(c, dev_alloc(c, &d.op_args_sorted, (size_t)d.ops_cap));
+    // the host polls these records (wait_scalars): coherent mapping whatever HIP_HOST_COHERENT says, and zeroed --
+    // hipHostMalloc does not promise zeroed pages, and a recycled page whose seq word happened to hold the number
+    // the first step waits for would be taken for that step's scalars
+    PS_HIP(c, hipHostMalloc((void **)&c->h_fs, 2 * sizeof(FrameScalars), hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(c->h_fs, 0, 2 * sizeof(FrameScalars));
+    PS_HIP(c, hipHostGetDevicePointer((void **)&c->d.fs_host, c->h_fs, 0));
+    PS_HIP(c, dev_alloc(c, &d.moves, (size_t)d.moves_cap));
+    PS_HIP(c, dev_alloc(c, &d.stage, 3 * (size_t)d.moves_cap));
+    PS_HIP(c, dev_alloc(c, &d.ctr, (size_t)COUNTER_COPIES));
+    PS_HIP(c, dev_alloc(c, &d.exp_count, (size_t)export_tiles(P.slots_total)));     // psamd_export_live's scratch
+    PS_HIP(c, dev_alloc(c, &d.exp_tiles, (size_t)export_tiles(P.slots_total)));
+    PS_HIP(c, dev_alloc(c, &d.exp_out, 1));
+    PS_HIP(c, dev_alloc(c, &c->inj.removed, (size_t)g.queue_infos));    // psamd_inject's fixed scratch and result record
+    PS_HIP(c, dev_alloc(c, &c->inj.hdr, 2));
+    PS_HIP(c, dev_alloc(c, &c->inj.own, 1));
+    PS_HIP(c, hipMemsetAsync(c->inj.own, 0, sizeof(psamd_inject_result), c->stream));
+    PS_HIP(c, dev_alloc(c, &d.trace, 3 * (LC * P.slices + 4)));
+    PS_HIP(c, hipMemsetAsync(d.trace, 0, 3 * (LC * P.slices + 4) * sizeof(unsigned long long), c->stream));
+    return PSAMD_OK;
+}
+
+// a slab message's buffer, zeroed: `bytes` travel, `alloc` is the buffer's room (0: the same)
+static hipError_t alloc_msg(psamd_ctx *c, int which, size_t bytes, size_t alloc = 0)
+{
+    SlabMsg &m = c->msg[which];
+    m.bytes = bytes; m.alloc = alloc ? alloc : bytes;
+    const hipError_t e = dev_alloc(c, &m.ptr, m.alloc / sizeof(int));
+    return e != hipSuccess ? e : hipMemsetAsync(m.ptr, 0, m.alloc, c->stream);
+}
+
+// slab messages: sizes fixed by the plan (see slab.hip "slab exchange")
+static int alloc_slab_msgs(psamd_ctx *c)
+{
+    const Geometry &g = c->geo; const DevParams &P = c->P; const SlabPlan &pl = c->plan; DeviceState &d = c->d;
+    if (P.world <= 1) return PSAMD_OK;
+    const int GG = g.G * g.G;
+    auto halo_bytes = [&](int cells) { return ((size_t)MSG_HEADER_WORDS + (size_t)cells + 6 * (size_t)cells * P.halo_cap_cell) * sizeof(int); };
+        // out: own layers for the rank below / above; in: what they hold for this rank
+        c->halo_out_cells[0] = (pl.send_down_hi - pl.send_down_lo) * GG; c->halo_out_c0[0] = (pl.send_down_lo - pl.state_lo) * GG;
+        c->halo_out_cells[1] = (pl.send_up_hi - pl.send_up_lo) * GG;     c->halo_out_c0[1] = (pl.send_up_lo - pl.state_lo) * GG;
+        c->halo_in_cells[0] = (pl.below_hi - pl.below_lo) * GG;
+        c->halo_in_cells[1] = (pl.above_hi - pl.above_lo) * GG;
+    for (int k = 0; k < 2; k++) {
+        if (c->halo_out_cells[k] > 0) {
+            PS_HIP(c, alloc_msg(c, MSG_HALO_OUT + k, halo_bytes(c->halo_out_cells[k])));
+            PS_HIP(c, dev_alloc(c, &c->pack_off[k], (size_t)c->halo_out_cells[k] + 1));
+        }
+        if (c->halo_in_cells[k] > 0) {
+            PS_HIP(c, alloc_msg(c, MSG_HALO_IN + k, halo_bytes(c->halo_in_cells[k])));
+            PS_HIP(c, dev_alloc(c, &c->unpack_off[k], (size_t)c->halo_in_cells[k] + 1));
+        }
+    }
+    auto force_bytes = [&](int cells) { return ((size_t)MSG_HEADER_WORDS + 4 * (size_t)cells * P.halo_cap_cell) * sizeof(int); };
+    if (P.reg_layers[2] > 0) PS_HIP(c, alloc_msg(c, MSG_FORCE_OUT, force_bytes(P.reg_layers[2] * GG)));
+    if (P.lentout_c1 > P.lentout_c0) PS_HIP(c, alloc_msg(c, MSG_FORCE_IN, force_bytes(P.lentout_c1 - P.lentout_c0)));
+    // to the neighbours (what travels follows P.xfer_cap, psamd_slab_build; room for a step's worst case), then two ranks away
+    for (int k = 0; k < 2; k++) {
+        PS_HIP(c, alloc_msg(c, MSG_XFER_OUT + k, xfer_msg_bytes((size_t)P.xfer_cap + 1), xfer_msg_bytes(xfer_room(P))));
+        PS_HIP(c, alloc_msg(c, MSG_XFER_IN + k, xfer_msg_bytes((size_t)P.xfer_cap + 1), xfer_msg_bytes(xfer_room(P))));
+    }
+    for (int k = 0; k < 2 && P.xfer2_cap > 0; k++) {
+        PS_HIP(c, alloc_msg(c, MSG_XFER2_OUT + k, xfer_msg_bytes((size_t)P.xfer2_cap)));
+        PS_HIP(c, alloc_msg(c, MSG_XFER2_IN + k, xfer_msg_bytes((size_t)P.xfer2_cap)));
+    }
+    if (P.far_cap > 0) {
+        PS_HIP(c, alloc_msg(c, MSG_FAR_OUT, xfer_msg_bytes((size_t)P.far_cap)));
+        PS_HIP(c, alloc_msg(c, MSG_FAR_IN, xfer_msg_bytes((size_t)P.far_cap) * (size_t)P.world));
+    }
+    const int outbox[5] = {MSG_XFER_OUT, MSG_XFER_OUT + 1, MSG_XFER2_OUT, MSG_XFER2_OUT + 1, MSG_FAR_OUT};
+    for (int k = 0; k < 5; k++)
+        if (c->msg[outbox[k]].ptr) d.xfer_out[k] = reinterpret_cast<XferRec *>(c->msg[outbox[k]].ptr + MSG_HEADER_WORDS);
+    if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
+        const size_t block = (size_t)P.allg_block * sizeof(int);
+        PS_HIP(c, alloc_msg(c, MSG_ALLG_OUT, block));
+        PS_HIP(c, alloc_msg(c, MSG_ALLG_IN, block * P.world, block * P.world + 64 * sizeof(int)));      // + slack: scalar loads fetch whole groups
+            PS_HIP(c, dev_alloc(c, &d.gstart, (size_t)g.num_cells + 1));
+            PS_HIP(c, dev_alloc(c, &d.gn, (size_t)g.num_cells + 1));
+            PS_HIP(c, hipMemsetAsync(d.gstart, 0, ((size_t)g.num_cells + 1) * sizeof(int), c->stream));
+            PS_HIP(c, hipMemsetAsync(d.gn, 0, ((size_t)g.num_cells + 1) * sizeof(int), c->stream));
+        d.allg_in = c->msg[MSG_ALLG_IN].ptr;
+    }
+    PS_HIP(c, alloc_msg(c, MSG_STATUS_OUT, (size_t)P.status_words * sizeof(int)));
+    PS_HIP(c, alloc_msg(c, MSG_STATUS_IN, (size_t)P.status_words * sizeof(int) * P.world));
+    d.status_out = c->msg[MSG_STATUS_OUT].ptr;
+    return PSAMD_OK;
+}
+
+// From which squared distance on is the fp32 add of EPS2 bit-identical to the
+// reference's double add?  Try a few candidates, each checked on the device for
+// every float up to the largest squared distance two in-box particles can have.
+static int probe_eps_f32(psamd_ctx *c, const psamd_config *cfg)
+{
+    DevParams &P = c->P;
+    if (P.lean_math && cfg->eps2 > 0) {
+        const float d2_max = (float)max_d2(c->geo);
+        unsigned long long *bad = (unsigned long long *)c->d.fs;   // scratch, zeroed again by init_state
+        auto fbits = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
+        // (below 1.5 x EPS2 the sum lies under 0.5, a binade finer, and the rounding error of (float)EPS2 shows: 838 861 of the floats
+        // in [1.25 EPS2, 1.5 EPS2) differ at the reference's EPS2 -- lower multiples are not worth a try)
+        for (double mult : {1.5, 2.0, 4.0, 8.0, 16.0, 64.0}) {
+            const float from = (float)(mult * cfg->eps2);
+            if (!(from < d2_max)) break;
+            unsigned long long h_bad = 1;
+            PS_HIP(c, hipMemsetAsync(bad, 0, sizeof(unsigned long long), c->stream));
+            PS_HIP(c, launch_validate_eps(c->stream, fbits(from), fbits(d2_max), cfg->eps2, P.eps2f, bad));
+            PS_HIP(c, hipMemcpyAsync(&h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, c->stream));
+            PS_HIP(c, hipStreamSynchronize(c->stream));
+            if (h_bad == 0) { P.eps_f32_from = from; break; }
+        }
+    }
+    P.slow_below = std::max(P.eps_f32_from, std::nextafterf(P.coll_d2_gate, INFINITY));
+    return PSAMD_OK;
+}
+
+// Interior own cells: computed layers whose neighbour layers are both own state (or outside
+// the grid): their collision flags and forces need nothing from another rank, so that
+// pass can run while the halo messages travel (two-pass mode; slab_pairs_interior).
+static void split_interior(psamd_ctx *c)
+{
+    const Geometry &g = c->geo; const DevParams &P = c->P; const SlabPlan &pl = c->plan;
+    const int GG = g.G * g.G, lo = std::max(pl.cut_lo, pl.state_lo), hi = std::min(pl.cut_hi, pl.state_hi);
+    auto own = [&](int l) { return l < 0 || l >= g.G || (l >= pl.state_lo && l < pl.state_hi); };
+    int i0 = lo, i1 = lo;
+    for (int l = lo; l < hi; l++) if (own(l - 1) && own(l + 1)) { if (i1 == i0) i0 = l; i1 = l + 1; } else if (i1 > i0) break;
+    c->P_int = P; c->P_rest = P;
+    c->have_interior = P.world > 1 && P.two_pass && P.lean_math && i1 > i0 && (i1 - i0) < (hi - lo) + (pl.lentin_hi - pl.lentin_lo)
+                       && !(P.flags & PSAMD_FLAG_ALL_PAIRS);      // (an all-pairs pass needs the gathered snapshot: nothing to do before it lands)
+    if (c->have_interior) {
+        const int a = (i0 - pl.state_lo) * GG, b = (i1 - pl.state_lo) * GG;
+        c->P_int.comp_lo[0] = a; c->P_int.comp_hi[0] = b;
+        c->P_int.comp_lo[1] = c->P_int.comp_hi[1] = c->P_int.comp_lo[2] = c->P_int.comp_hi[2] = 0;
+        c->P_rest.comp_lo[1] = P.own_comp0; c->P_rest.comp_hi[1] = a;
+        c->P_rest.comp_lo[2] = b; c->P_rest.comp_hi[2] = P.own_comp1;
+    }
+}
+
+// The state a fresh context starts from, and the tables that never change.
+static int init_state(psamd_ctx *c)
+{
+    const Geometry &g = c->geo; const DevParams &P = c->P; DeviceState &d = c->d;
+    const size_t C = (size_t)P.slots_total, SC = (size_t)P.sorted_cap + 64, LC = (size_t)P.n_local_cells;
+    c->wait_policy = P.world > 1 ? 1 : 0;
+    if (const char *lim = std::getenv("PSAMD_WAIT_LIMIT_S")) c->wait_limit_s = std::max(0.05, std::atof(lim));
+    // init_particles (ps.cpp:722-753): every slot reset, cell = -1
+    for (float4 *a : {d.pos4, d.vel4, d.acc4}) PS_HIP(c, hipMemsetAsync(a, 0, std::max<size_t>(C, 1) * sizeof(float4), c->stream));
+    PS_HIP(c, hipMemsetAsync(d.pflags, 0, std::max<size_t>(C, 1), c->stream));
+    PS_HIP(c, hipMemsetAsync(d.force4, 0, SC * sizeof(float4), c->stream));
+    PS_HIP(c, hipMemsetAsync(d.flag_slot, 0, std::max<size_t>(C, 1), c->stream));
+    PS_HIP(c, hipMemsetAsync(d.fs, 0, sizeof(FrameScalars), c->stream));
+    PS_HIP(c, hipMemsetAsync(d.ctr, 0, sizeof(DevCounters) * COUNTER_COPIES, c->stream));
+    PS_HIP(c, hipMemsetAsync(d.cell_count, 0, c->frame_ints * sizeof(int), c->stream));     // (the frame's counts: one allocation)
+    PS_HIP(c, hipMemsetAsync(d.cell_start, 0, (LC + 1) * sizeof(int), c->stream));
+    PS_HIP(c, launch_fill_int(c->stream, d.cell, -1, C));
+    PS_HIP(c, launch_init_tdata(c->stream, P, d));
+    // q_start_fast (ps.cpp:814-871) and the cell table
+    g.initial_queues(c->h_qinfo, c->h_queue);
+    c->celltab = g.cell_table();
+    PS_HIP(c, hipMemcpyAsync(d.celltab, c->celltab.data(), c->celltab.size() * sizeof(CellInfo), hipMemcpyHostToDevice, c->stream));
+    {   // k_sort_cells' order of the own cells: the cells of one segment (they share its slots, so their gathers share
+        // cache lines) side by side -- one XCD's L2 then sees a segment's lines once
+        const int cell_off = P.reg_first[0] * g.G * g.G;
+        std::vector<int> order((size_t)std::max(P.n_own_cells, 1), 0);
+        for (int lc = 0; lc < P.n_own_cells; lc++) order[(size_t)lc] = lc;
+        std::stable_sort(order.begin(), order.begin() + P.n_own_cells, [&](int a, int b) {
+            const CellInfo &x = c->celltab[(size_t)(a + cell_off)], &y = c->celltab[(size_t)(b + cell_off)];
+            if (x.chunk != y.chunk) return x.chunk < y.chunk;
+            if (x.seg_type != y.seg_type) return x.seg_type < y.seg_type;
+            return x.seg_tid < y.seg_tid;
+        });
+        PS_HIP(c, dev_alloc(c, &d.cell_order, order.size()));
+        PS_HIP(c, hipMemcpy(d.cell_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    return push_queues(c);       // (host_queues_valid: the mirror is what the device now holds)
+}
+
+int psamd_create(const psamd_config *cfg, psamd_ctx **out)
+{
+    if (!cfg || !out) return PSAMD_ERR_INVALID_ARG;
+    *out = nullptr;
+    psamd_ctx *c = new (std::nothrow) psamd_ctx();
+    if (!c) return PSAMD_ERR_OUT_OF_MEMORY;
+    *out = c;  // returned even on failure so psamd_last_error can explain; caller destroys it
+    if (!c->geo.init(*cfg)) return fail(c, PSAMD_ERR_INVALID_ARG, "bad configuration (chunk_dim >= 3, sizes > 0, container < 2^31)");
+    if (cfg->world < 1 || cfg->world > PSAMD_MAX_RANKS || cfg->rank < 0 || cfg->rank >= cfg->world) return fail(c, PSAMD_ERR_INVALID_ARG, "rank/world");
+    const Geometry &g = c->geo;
+    c->plan = plan_for(g, *cfg);
+    if (!c->plan.valid) return fail(c, PSAMD_ERR_UNSUPPORTED, "no slab partition for this grid and world size (every rank needs >= 2 cell layers "
+                                                                "and its neighbours must hold every layer it reads)");
+
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(c, PSAMD_ERR_NO_DEVICE, "hipGetDeviceCount found none");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(c, PSAMD_ERR_NO_DEVICE, "device ordinal out of range");
+    PS_HIP(c, hipSetDevice(cfg->device));
+    PS_HIP(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
+    c->stream = c->own_stream;
+    PS_HIP(c, hipStreamCreateWithFlags(&c->d.side_stream, hipStreamNonBlocking));
+    PS_HIP(c, hipEventCreateWithFlags(&c->d.ev_fork, hipEventDisableTiming));
+    PS_HIP(c, hipEventCreateWithFlags(&c->d.ev_join, hipEventDisableTiming));
+
+    int rc = derive_params(c, cfg);
+    if (rc == PSAMD_OK) rc = alloc_step_arrays(c);
+    if (rc == PSAMD_OK) rc = alloc_slab_msgs(c);
+    if (rc == PSAMD_OK) rc = probe_eps_f32(c, cfg);      // (on the device: after the allocations, as ever)
+    if (rc != PSAMD_OK) return rc;
+    split_interior(c);
+    return init_state(c);
+}
+
+int psamd_destroy(psamd_ctx *c)
+{
+    if (!c) return PSAMD_OK;
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    drop_graphs(c);
+    for (void *p : c->allocs) (void)hipFree(p);
+    if (c->staging) (void)hipFree(c->staging);
+    for (void *p : {(void *)c->inj.ent, (void *)c->inj.tcount, (void *)c->inj.tile_out}) if (p) (void)hipFree(p);
+    if (c->h_fs) (void)hipHostFree(c->h_fs);
+    if (c->ev_made) for (auto &set : c->ev) for (auto &e : set) (void)hipEventDestroy(e);
+    if (c->d.ev_fork) (void)hipEventDestroy(c->d.ev_fork);
+    if (c->d.ev_join) (void)hipEventDestroy(c->d.ev_join);
+    if (c->d.side_stream) (void)hipStreamDestroy(c->d.side_stream);
+    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+    delete c;
+    return PSAMD_OK;
+}
+
+static void fill_sizes(const Geometry &g, psamd_sizes *o)
+{
+    std::memset(o, 0, sizeof *o);
+    o->grid_dim = g.G; o->num_cells = g.num_cells; o->num_chunks = g.num_chunks;
+    o->cells_per_chunk = g.cells_per_chunk; o->max_per_cell = g.max_per_cell; o->max_per_chunk = g.max_per_chunk;
+    o->container_size = g.container; o->queue_info_size = g.queue_infos;
+    o->n_chunkgrid = (int64_t)g.num_chunks * (1 + (int64_t)g.max_per_chunk);
+    o->n_cellgrid = (int64_t)g.num_cells * (1 + (int64_t)g.max_per_cell);
+    o->n_pkgdistrib = g.num_chunks * 27;
+    for (int k = 0; k < 4; k++) { o->seg_count[k] = g.seg_count[k]; o->seg_size_t[k] = g.seg_size_t[k]; o->seg_size[k] = g.seg_size[k]; }
+}
+
+int psamd_describe(const psamd_config *cfg, psamd_sizes *sizes, int32_t *cell_table3, int32_t *pkg,
+                   void *queue_info24, int32_t *queue)
+{
+    if (!cfg) return PSAMD_ERR_INVALID_ARG;
+    Geometry g;
+    if (!g.init(*cfg)) return PSAMD_ERR_INVALID_ARG;
+    if (sizes) fill_sizes(g, sizes);
+    if (cell_table3)
+        for (int i = 0; i < g.num_cells; i++) {
+            const CellInfo ci = g.cell_info(i);
+            cell_table3[3 * i] = ci.chunk; cell_table3[3 * i + 1] = ci.seg_type; cell_table3[3 * i + 2] = ci.seg_tid;
+        }
+    if (pkg) for (int ch = 0; ch < g.num_chunks; ch++) g.chunk_segments(ch, (Pair *)pkg + (size_t)ch * 27);
+    if (queue_info24 || queue) {
+        std::vector<QueueInfo> qi;
+        std::vector<int32_t> q;
+        g.initial_queues(qi, q);
+        if (queue_info24) std::memcpy(queue_info24, qi.data(), qi.size() * sizeof(QueueInfo));
+        if (queue) std::memcpy(queue, q.data(), q.size() * sizeof(int32_t));
+    }
+    return PSAMD_OK;
+}
+
+int psamd_get_sizes(const psamd_ctx *c, psamd_sizes *o)
+{
+    if (!c || !o) return PSAMD_ERR_INVALID_ARG;
+    fill_sizes(c->geo, o);
+    return PSAMD_OK;
+}
+
+int psamd_get_config(const psamd_ctx *c, psamd_config *o)
+{
+    if (!c || !o) return PSAMD_ERR_INVALID_ARG;
+    *o = c->geo.cfg;
+    return PSAMD_OK;
+}
+
+int psamd_slab_plan_describe(const psamd_config *cfg, psamd_slab_plan *o)
+{
+    if (!cfg || !o) return PSAMD_ERR_INVALID_ARG;
+    Geometry g;
+    if (!g.init(*cfg)) return PSAMD_ERR_INVALID_ARG;
+    if (cfg->world < 1 || cfg->world > PSAMD_MAX_RANKS || cfg->rank < 0 || cfg->rank >= cfg->world) return PSAMD_ERR_INVALID_ARG;
+    const SlabPlan p = plan_for(g, *cfg);
+    if (!p.valid) return PSAMD_ERR_UNSUPPORTED;
+    std::memset(o, 0, sizeof *o);
+    o->world = p.world; o->rank = p.rank; o->grid_dim = p.G;
+    o->cut_lo = p.cut_lo; o->cut_hi = p.cut_hi; o->state_lo = p.state_lo; o->state_hi = p.state_hi;
+    o->below_lo = p.below_lo; o->below_hi = p.below_hi; o->above_lo = p.above_lo; o->above_hi = p.above_hi;
+    o->lentin_lo = p.lentin_lo; o->lentin_hi = p.lentin_hi; o->lentout_lo = p.lentout_lo; o->lentout_hi = p.lentout_hi;
+    o->send_up_lo = p.send_up_lo; o->send_up_hi = p.send_up_hi; o->send_down_lo = p.send_down_lo; o->send_down_hi = p.send_down_hi;
+    for (int t = 0; t < 4; t++) { o->slot_lo[t] = p.slot_lo[t]; o->slot_hi[t] = p.slot_hi[t]; o->rec_lo[t] = p.rec_lo[t]; o->rec_hi[t] = p.rec_hi[t]; }
+    o->up_rank = p.up_rank; o->down_rank = p.down_rank;
+    return PSAMD_OK;
+}
+
+int psamd_get_slab_plan(const psamd_ctx *c, psamd_slab_plan *o)
+{
+    if (!c || !o) return PSAMD_ERR_INVALID_ARG;
+    return psamd_slab_plan_describe(&c->geo.cfg, o);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // inject.hip -- psamd_inject: particles from device arrays into their segments' free slots, on the stream.
 //
-// The device-side counterpart of psamd_fill_particles (capi.hip), byte for byte: entry i takes the next free slot of
+// The device-side counterpart of psamd_fill_particles (io.hip), byte for byte: entry i takes the next free slot of
 // its segment's queue in entry order (q_remove), and the stop rule is fill's.  A deterministic stable multisplit of the
 // entries by queue record, then the closed-form FIFO removal (the k-th remove of a record takes logical element k, as
 // k_replay_commit does), in five launches ordered by the launch boundaries only (no hand-off between workgroups):

@@ -1244,7 +1244,7 @@ __global__ __launch_bounds__(256, BALANCED_WAVES) void k_allp_far(DevParams P, c
 {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n_act = act_start[comp_count(P)];
-    const int ntask = min((n_act + 63) >> 6, (int)(far.part_plane >> 6));      // (the partial sums' room: never short, see capi.hip)
+    const int ntask = min((n_act + 63) >> 6, (int)(far.part_plane >> 6));      // (the partial sums' room: never short, see create.hip)
     const int nitem = ntask * ALLP_PARTS, nwg = (nitem + 3) >> 2;
     // (the launch is sized from the host's bound of the live count, the items from the device's own count: a launch
     // that is too small for them -- it should not be -- takes several rounds instead of leaving particles out)
@@ -1787,7 +1787,7 @@ constexpr double PACK_COST = 1.4;      // a pack's walk in ordinary tasks: four 
 
 static PairShape pair_shape(const DevParams &P, bool lean, int64_t hint)
 {
-    const int64_t tasks_hint = hint & 0xffffffffll, packs_hint = hint >> 32;      // (capi.hip, pairs_hint)
+    const int64_t tasks_hint = hint & 0xffffffffll, packs_hint = hint >> 32;      // (step.hip, pairs_hint)
     PairShape s{};
     s.two = lean && P.two_pass;
     if (!s.two) return s;

@@ -1,0 +1,710 @@
+// step.hip -- the stage engine: timing events, the enq_* stages, the hipGraph cache, the scalar-record pipeline, the
+// one-GPU stage calls, psamd_step, the slab stages, psamd_synchronize and the setters that steer them.
+#include <atomic>
+#include <ctime>
+
+#include <sys/prctl.h>
+
+#include "context.hpp"
+
+int psamd::check_device_errors(psamd_ctx *c)
+{
+    FrameScalars fs{};
+    PS_HIP(c, hipMemcpy(&fs, c->d.fs, sizeof fs, hipMemcpyDeviceToHost));
+    if (!c->grid_built) for (int k = 0; k < 5; k++) fs.n_out[k] = c->last.n_out[k];      // (between steps the device's record is the next frame's, zeroed)
+    if (fs.error & (ERR_BAD_ID | ERR_BAD_POS)) {
+        // an upload error is reported once and then cleared: the rejected records stay in the
+        // container, the caller is expected to upload valid ones over them
+        const int bits = fs.error;
+        const int cleared = fs.error & ~(ERR_BAD_ID | ERR_BAD_POS);
+        (void)hipMemcpy(&c->d.fs->error, &cleared, sizeof(int), hipMemcpyHostToDevice);
+        return fail(c, PSAMD_ERR_INVALID_ARG, (bits & ERR_BAD_ID) ? "uploaded particle with id != slot index"
+                                                                  : "uploaded live particle outside the box or with cell >= NUM_CELLS");
+    }
+    if (fs.error & ERR_CELL_TOO_BIG) return fail(c, PSAMD_ERR_CELL_OVERFLOW, "a cell holds more particles than the sort kernel ranks");
+    if (fs.error & ERR_FOREIGN_CELL) return fail(c, PSAMD_ERR_STATE, "a particle stored on this rank sits in a cell layer the rank holds no state for");
+    if (fs.error & ERR_HALO_OVERFLOW) {
+        // say what was asked for, so that the caller can size the messages (the error may also have come in with a
+        // neighbour's message header: then the numbers below are this rank's own and may all fit)
+        char buf[512];
+        std::snprintf(buf, sizeof buf, "a slab message had no room (raise halo_cap_cell / xfer_cap): this step this rank wanted to send %d / %d "
+                      "transfer records down / up (room: %d each now -- it follows the traffic two steps behind, up to xfer_cap_max), %d / %d two ranks away (room %d), %d to a far rank (room %d); "
+                      "a halo message holds halo_cap_cell = %d bodies per cell on average over a cell layer",
+                      fs.n_out[0], fs.n_out[1], c->P.xfer_cap, fs.n_out[2], fs.n_out[3], c->P.xfer2_cap, fs.n_out[4], c->P.far_cap, c->P.halo_cap_cell);
+        return fail(c, PSAMD_ERR_CELL_OVERFLOW, buf);
+    }
+    if (fs.error & ERR_SLAB_MISMATCH) return fail(c, PSAMD_ERR_STATE, "a slab message does not match the receiver's plan or counts");
+    if (fs.error & ERR_REMOTE_RECORD0) return fail(c, PSAMD_ERR_CELL_OVERFLOW, "more cell-overflow kills in one step than a slab's status message carries (ps.cpp:1523-1526 frees them into queue record 0)");
+    if (fs.error & ERR_CHUNK_CAP) return fail(c, PSAMD_ERR_CELL_OVERFLOW, "a chunk list passed MAX_PARTICLES_PER_CHUNK: the reference skips its tail (ps.cpp:1502-1508), this library does not reproduce that");
+    if (fs.error & ERR_OPS_OVERFLOW) return fail(c, PSAMD_ERR_CELL_OVERFLOW, "lifecycle op buffer overflow");
+    if (fs.error & ERR_HANDOFF_TIMEOUT) return fail(c, PSAMD_ERR_STATE, "force pass: a wave never saw the partial sums of the task it continues");
+    if (fs.error) return fail(c, PSAMD_ERR_STATE, "device error bits " + std::to_string(fs.error));
+    return PSAMD_OK;
+}
+
+static void make_events(psamd_ctx *c)
+{
+    if (c->ev_made) return;
+    for (auto &set : c->ev) for (auto &e : set) (void)hipEventCreate(&e);
+    c->ev_made = true;
+}
+
+// read a set of timing events (waits for its step's last kernel: a set is read when it is taken again, two timed
+// steps later, or by psamd_get_timing)
+static void collect_timing(psamd_ctx *c, int set)
+{
+    const int level = c->ev_level[set];
+    if (!level) return;
+    c->ev_level[set] = 0;
+    if (hipEventSynchronize(c->ev[set][psamd_ctx::E_END]) != hipSuccess) return;
+    // timers: hist scan scatter sort | force pass, apply, life cycle | frame reset | flags + active lists (two-pass prologue)
+    using X = psamd_ctx;
+    const int a[PSAMD_NUM_TIMERS] = {X::E_HIST, X::E_SCAN, X::E_SCATTER, X::E_SORT, X::E_FORCE, X::E_APPLY, X::E_LIFE, X::E_RESET, X::E_COLLIDE};
+    const int b[PSAMD_NUM_TIMERS] = {X::E_SCAN, X::E_SCATTER, X::E_SORT, X::E_SORT_END, X::E_PAIRS_END, X::E_LIFE, X::E_END, X::E_HIST, X::E_FORCE};
+    for (int k = 0; k < PSAMD_NUM_TIMERS; k++) {
+        if (level < 2 && (k < 4 || k == 7)) continue;
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, c->ev[set][a[k]], c->ev[set][b[k]]) == hipSuccess) {
+            c->t_us[k] += 1000.0 * ms;
+            c->t_samples[k].push_back(1000.0f * ms);
+        }
+    }
+    c->t_launches++;
+}
+
+static void tick(psamd_ctx *c, int e)        // a timing event on the context's stream, if this step carries them
+{
+    if (c->timing_now) (void)hipEventRecord(c->ev[c->tset][e], c->stream);
+}
+
+// ---- stages ---------------------------------------------------------------------
+//
+// Every stage is a fixed sequence of kernel launches whose arguments do not change from step to step
+// (sizes live on the device; the step's number and the scalar records' sequence number too: StepState).
+// enq_* functions only enqueue; the host-side state machine is advanced by their callers -- so that a
+// sequence can be captured once into a hipGraph and replayed (psamd_set_graphs): one submission per stage
+// instead of one per kernel.  A graph is keyed by what shapes its launches: the size of the balanced force
+// pass (from the last task count the host has seen) and the hint of the live count the life-cycle grids are sized
+// from, rounded up to 64 Ki so that a free-running population does not mean a capture per step.  Steps
+// that carry timing events run eagerly (the events sit between the kernels).
+//
+// NOTHING in a step waits for the host: the step's tail decides everything on the device (lifecycle.hip), and the
+// one read-back of a step -- live count, sticky errors, list sizes: what the reference's driver fetches as
+// hostGridMax, ps.cpp:1878-1900 -- lands in a pinned record that the host reads a step late (consume_scalars).
+
+static int slab_only(psamd_ctx *c, const char *what)
+{
+    return fail(c, PSAMD_ERR_STATE, std::string(what) + ": this context is one slab of a multi-rank system; step it with psamd_slab_build / "
+                                                         "_pairs / _apply / _finish and exchange the messages in between");
+}
+
+int psamd::refuse_wedged(psamd_ctx *c)
+{
+    return fail(c, PSAMD_ERR_STATE, "the GPU stopped answering (a step's scalars did not arrive within " + std::to_string((int)c->wait_limit_s) +
+                                    " s while its stream stayed busy): this context takes no further work; destroy it");
+}
+
+// which steps carry timing events is settled when the step begins (before anything is enqueued or replayed)
+static void begin_step(psamd_ctx *c)
+{
+    // (an event between two kernels costs ~6 us of idle GPU: a long timed run records them on every n-th step)
+    c->timing_now = (c->timing && c->timing_steps++ % c->timing_period == 0) ? c->timing : 0;
+    if (c->timing_now) {
+        make_events(c);
+        c->tset = (int)(c->timed_steps & 1);
+        collect_timing(c, c->tset);          // (the set's last use is two timed steps old: this returns at once)
+    }
+}
+
+static int enq_init_iframe(psamd_ctx *c)
+{
+    tick(c, psamd_ctx::E_RESET);
+    // cell / chunk / queue-record counts and the per-frame scalars (the sticky error word stays): the last kernel of
+    // the step before did it, unless there was none
+    if (!c->frame_clean) PS_HIP(c, launch_frame_reset(c->stream, c->d, c->frame_ints, c->P.world > 1 ? 4 * c->geo.num_chunks : 0));
+    return PSAMD_OK;
+}
+
+// is a cell with more than 1024 ids to be expected?  (the last frames the host has read; a wrong guess only costs time:
+// without the crowded cells' instance the ordinary one ranks such a cell through global memory)
+static bool big_cells_hint(const psamd_ctx *c) { return c->scalars_seen > 0 && c->last.max_cell_raw > 960; }
+static uint64_t build_key(const psamd_ctx *c) { return (c->frame_clean ? 0ull : 1ull) | (c->tdata_mirror ? 2ull : 0ull) | (big_cells_hint(c) ? 4ull : 0ull); }
+
+static int enq_build_grid(psamd_ctx *c)
+{
+    PS_HIP(c, launch_build_grid(c->stream, c->P, c->d, c->timing_now >= 2 ? &c->ev[c->tset][psamd_ctx::E_HIST] : nullptr, c->tdata_mirror, big_cells_hint(c)));
+    return PSAMD_OK;
+}
+
+// An upper bound of the particles alive at the NEXT build_grid, as far as the host can know it (< 0 inside: unknown --
+// state was uploaded -- every owned slot).  The host's figure comes from the scalars of the last step it has READ,
+// which with run-ahead is not the last step enqueued: every step in between may have added a child per particle
+// (explosions on) and a slab its arrivals.  Only the all-pairs far pass sizes a launch from this that must cover
+// every particle; everything else takes it as a hint.
+static int64_t live_bound_of(const psamd_ctx *c)
+{
+    int64_t b = c->live_bound >= 0 ? c->live_bound : (int64_t)c->P.slots_total;
+    for (int k = c->scalars_seen; k < c->scalars_seq && b < c->P.slots_total; k++) {
+        if (c->P.flags & PSAMD_FLAG_EXPLOSIONS) b *= 2;
+        b += 2 * (int64_t)c->P.xfer_cap + 2 * (int64_t)c->P.xfer2_cap + (int64_t)c->P.far_cap * c->P.world;
+    }
+    b = std::min<int64_t>(b, c->P.slots_total);
+    return c->graphs ? std::min<int64_t>((b + 65535) & ~(int64_t)65535, std::max<int64_t>(c->P.slots_total, 65536)) : b;
+}
+
+// size of the balanced force pass: the tasks of the last step whose scalars the host has read, else the bound of the
+// live count (a pass over part of the cells gets its share of the hint)
+static int64_t pairs_hint(const psamd_ctx *c, const DevParams &P)
+{
+    int64_t tasks_hint = (c->scalars_seen > 0 && c->tasks_last > 0) ? c->tasks_last
+                         : (c->live_bound >= 0 ? c->live_bound : (int64_t)c->P.slots_total) / 64 + comp_count(c->P);
+    // (high word: about how many packs of partly filled slices the pass will have -- their workgroups hold residency
+    // slots of the same launch; in steps of 64 so that the launch shape does not change with every step)
+    const int64_t packs = ((c->scalars_seen > 0 ? c->packs_last : 0) + 63) & ~(int64_t)63;
+    return (tasks_hint * comp_count(P) / std::max(1, comp_count(c->P))) | ((packs * comp_count(P) / std::max(1, comp_count(c->P))) << 32);
+}
+
+static int enq_pairs(psamd_ctx *c, const DevParams &P, int64_t tasks_hint, bool last = true, bool first = true)
+{
+    if (first) tick(c, psamd_ctx::E_COLLIDE);
+    PS_HIP(c, launch_pairs(c->stream, P, c->d, (c->timing_now && first) ? c->ev[c->tset][psamd_ctx::E_FORCE] : nullptr, tasks_hint, first ? 0 : 1, live_bound_of(c)));
+    if (last) tick(c, psamd_ctx::E_PAIRS_END);
+    return PSAMD_OK;
+}
+
+// kill / survive / integrate / explosion for every own particle; in slab mode the particles
+// that leave for a neighbour's segment are in the outboxes when this has run
+static int enq_apply(psamd_ctx *c, int64_t bound)
+{
+    tick(c, psamd_ctx::E_APPLY);
+    PS_HIP(c, launch_apply(c->stream, c->P, c->S, c->d));
+    const SlabMsg *m = c->msg;       // the outboxes: below, above, two below, two above, far
+    int *const out[5] = {m[MSG_XFER_OUT].ptr, m[MSG_XFER_OUT + 1].ptr, m[MSG_XFER2_OUT].ptr, m[MSG_XFER2_OUT + 1].ptr, m[MSG_FAR_OUT].ptr};
+    if (c->P.world > 1) PS_HIP(c, launch_outbox_close(c->stream, c->P, c->d, bound, out));
+    return PSAMD_OK;
+}
+
+// arrivals on top of the own particles: about what the op lists and move records of a step hold at most
+static int64_t lifecycle_bound(const psamd_ctx *c, int64_t bound)
+{
+    return bound + 2 * (int64_t)c->P.xfer_cap + 2 * (int64_t)c->P.xfer2_cap + (int64_t)c->P.far_cap * c->P.world
+           + (c->P.world > 1 ? (int64_t)c->P.world * STATUS_KILL_CAP : 0);
+}
+
+// Which instance replays the lists this step: the longest list of the last step the host has read is the hint (lists
+// longer than the instance sorts in LDS are sorted in global memory by the same workgroup: a wrong hint only costs time).
+static uint64_t pick_bucket_cap(psamd_ctx *c)
+{
+    const int last = c->scalars_seen > 0 ? c->last.max_bucket : 0;
+    c->bucket_cap0 = last > 4096 ? BUCKET_MAX : last > 2048 ? 4096 : 2048;
+    return c->bucket_cap0 > 4096 ? 2ull << 61 : c->bucket_cap0 > 2048 ? 1ull << 61 : 0ull;       // (part of a captured graph's key)
+}
+
+// free-slot queues and relocation (in slab mode: after the arrivals were merged in): census, bucketing -- the last
+// bucketing workgroup hands the step's scalars to the host's pinned record --, replay + commit; the last launch
+// is also the next frame's init_iframe
+static int enq_lifecycle(psamd_ctx *c, int64_t bound)
+{
+    tick(c, psamd_ctx::E_LIFE);
+    const SlabMsg *m = c->msg;
+    const int *const in[5] = {m[MSG_XFER_IN].ptr, m[MSG_XFER_IN + 1].ptr, m[MSG_XFER2_IN].ptr, m[MSG_XFER2_IN + 1].ptr, m[MSG_FAR_IN].ptr};
+    if (c->P.world > 1) PS_HIP(c, launch_inbox_merge(c->stream, c->P, c->d, in));
+    PS_HIP(c, launch_lifecycle(c->stream, c->P, c->d, c->geo.queue_infos, lifecycle_bound(c, bound), c->bucket_cap0,
+                               c->frame_ints, c->P.world > 1 ? 4 * c->geo.num_chunks : 0));
+    tick(c, psamd_ctx::E_END);
+    return PSAMD_OK;
+}
+
+// ---- hipGraph cache ----
+enum { SEG_BUILD = 0, SEG_PAIRS, SEG_APPLY, SEG_FINISH, SEG_STEP, NSEG };
+
+void psamd::drop_graphs(psamd_ctx *c)
+{
+    for (auto &cache : c->gcache) {
+        for (auto &g : cache) if (g.exec) (void)hipGraphExecDestroy(g.exec);
+        cache.clear();
+    }
+}
+
+template <typename F>
+static int run_segment(psamd_ctx *c, int seg, uint64_t key, F enqueue)
+{
+    if (!c->graphs || c->timing_now) return enqueue();
+    auto &cache = c->gcache[seg];
+    for (auto &g : cache)
+        if (g.key == key) {
+            g.stamp = ++c->gstamp;
+            PS_HIP(c, hipGraphLaunch(g.exec, c->stream));
+            c->graph_launches++;
+            return PSAMD_OK;
+        }
+    // not seen with this shape: capture the sequence once, then replay it
+    hipError_t e = hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed);
+    if (e == hipSuccess) {
+        const int rc = enqueue();
+        hipGraph_t graph = nullptr;
+        e = hipStreamEndCapture(c->stream, &graph);
+        hipGraphExec_t exec = nullptr;
+        if (rc == PSAMD_OK && e == hipSuccess && graph) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        if (graph) (void)hipGraphDestroy(graph);
+        if (rc != PSAMD_OK) return rc;
+        if (e == hipSuccess && exec) {
+            if (cache.size() >= 8) {                      // the shape that was used longest ago makes room
+                size_t old = 0;
+                for (size_t k = 1; k < cache.size(); k++) if (cache[k].stamp < cache[old].stamp) old = k;
+                (void)hipGraphExecDestroy(cache[old].exec);
+                cache.erase(cache.begin() + (long)old);
+            }
+            cache.push_back({key, exec, ++c->gstamp});
+            c->graph_captures++;
+            PS_HIP(c, hipGraphLaunch(exec, c->stream));
+            c->graph_launches++;
+            return PSAMD_OK;
+        }
+    }
+    // the runtime would not capture this: the context goes on without graphs (nothing was executed so far)
+    (void)hipGetLastError();
+    c->graphs = false;
+    c->graph_refused = std::string(hipGetErrorString(e));
+    return enqueue();
+}
+
+// The host's and the device's count of the scalar records part ways if a launch fails between the kernel that
+// publishes a record and the host's bookkeeping of the step: after an error both are set to what the device holds.
+static void resync_scalars(psamd_ctx *c)
+{
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return;
+    StepState st{};
+    if (hipMemcpy(&st, c->d.st, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) return;
+    c->scalars_seq = c->scalars_seen = st.seq;
+}
+
+// Wait until the scalars of step `seq` are in the host's record: the publishing workgroup stores the record's
+// number last.  The stream is looked at now and then so that a failed launch cannot leave the host waiting, and
+// the wall clock too: a stream that stays busy without ever publishing is a wedged GPU, reported as such
+// (PSAMD_ERR_STATE, sticky) instead of a host thread that never comes back.
+// Policy 0 spins on the word (lowest latency); policy 1, the default of a slab, spins for a few microseconds and
+// then sleeps in short naps -- eight ranks of a node do not pin eight cores for the whole run.  The naps need a
+// timer slack of ~1 us (the default 50 us would BE the nap): set for the wait, restored before it returns.
+static int wait_scalars(psamd_ctx *c, int seq)
+{
+    volatile int32_t *word = &c->h_fs[seq & 1].seq;
+    if (*word == seq) { std::atomic_thread_fence(std::memory_order_acquire); return PSAMD_OK; }
+    const bool naps = c->wait_policy == 1;
+    long old_slack = -1;
+    int rc = PSAMD_OK;
+    struct timespec t0;
+    (void)clock_gettime(CLOCK_MONOTONIC, &t0);
+    for (uint64_t spins = 1; *word != seq; spins++) {
+        if (naps && spins > 2000) {
+            if (old_slack < 0) { old_slack = prctl(PR_GET_TIMERSLACK, 0UL, 0UL, 0UL, 0UL); (void)prctl(PR_SET_TIMERSLACK, 1000UL, 0UL, 0UL, 0UL); }
+            struct timespec ts = {0, 5000};
+            (void)nanosleep(&ts, nullptr);
+        } else
+            __builtin_ia32_pause();
+        if ((spins & (naps ? 0x3ff : 0x3fff)) == 0) {
+            const hipError_t e = hipStreamQuery(c->stream);
+            if (e == hipSuccess) {
+                if (*word == seq) break;
+                rc = fail(c, PSAMD_ERR_STATE, "the step's scalars never arrived on the host");
+                break;
+            }
+            if (e != hipErrorNotReady) { rc = hip_fail(c, e, "waiting for the step's scalars"); break; }
+            struct timespec t1;
+            (void)clock_gettime(CLOCK_MONOTONIC, &t1);
+            if ((double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec) > c->wait_limit_s) { c->wedged = true; rc = refuse_wedged(c); break; }
+        }
+    }
+    if (old_slack >= 0) (void)prctl(PR_SET_TIMERSLACK, (unsigned long)old_slack, 0UL, 0UL, 0UL);
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return rc;
+}
+
+// Read the records of the steps up to number `upto` (waiting for them) and whatever has arrived beyond: the host's
+// bookkeeping of a step -- hints for the launches to come, the counters, and the step's verdict.
+// A slab fails COLLECTIVELY: only on error bits that were in a step's all-gathered status records,
+// which every rank sees alike (status_error) -- all ranks return the error from the same call.  An error this
+// rank raised after its status record was closed (a message that did not fit, an arrival for a queue it does not
+// hold) stays sticky, goes out with the next step's record and stops every rank there; returning it at once would
+// leave the ranks that have not heard of it waiting in the next exchange.  (psamd_synchronize reports whatever is pending.)
+static int consume_scalars(psamd_ctx *c, int upto)
+{
+    int verdict = PSAMD_OK;
+    while (c->scalars_seen < c->scalars_seq) {
+        const int s = c->scalars_seen + 1;
+        if (s <= upto) { const int st = wait_scalars(c, s); if (st != PSAMD_OK) { if (!c->wedged) resync_scalars(c); return st; } }
+        else if (*(volatile int32_t *)&c->h_fs[s & 1].seq != s) break;
+        std::atomic_thread_fence(std::memory_order_acquire);
+        const FrameScalars r = c->h_fs[s & 1];
+        c->scalars_seen = s;
+        c->last = r;
+        c->live_at_build = r.live;
+        const int64_t tasks_now = (int64_t)r.n_tasks2 + r.n_merged;       // ordinary tasks + packs of partial slices
+        // (a pair stage in two passes -- interior_ran is noted per step below -- reports the second pass's task count)
+        const bool two = c->interior_steps.count(s) != 0;
+        c->interior_steps.erase(s);
+        c->tasks_last = two ? tasks_now * comp_count(c->P) / std::max(1, comp_count(c->P_rest)) : tasks_now;
+        c->packs_last = two ? (int64_t)r.n_merged * comp_count(c->P) / std::max(1, comp_count(c->P_rest)) : r.n_merged;
+        c->live_bound = std::min<int64_t>(c->P.slots_total, (int64_t)r.live + r.n_moves);   // births and arrivals <= moves
+        // ... and what was injected after this step was enqueued (the record's live count does not include it)
+        for (auto it = c->inject_tally.begin(); it != c->inject_tally.end();) {
+            if (it->first < s) { it = c->inject_tally.erase(it); continue; }
+            c->live_bound = std::min<int64_t>(c->P.slots_total, c->live_bound + it->second);
+            ++it;
+        }
+        c->processed_total += r.live;
+        c->max_bucket_seen = std::max<int64_t>(c->max_bucket_seen, r.max_bucket);
+        if (c->P.world > 1 && r.xfer_cap_next > 0) c->cap_decisions[s] = r.xfer_cap_next;      // (every step's: an absolute number, the same on every rank)
+        if (verdict == PSAMD_OK && (c->P.world > 1 ? r.status_error != 0 : r.error != 0)) verdict = check_device_errors(c);
+    }
+    if (verdict != PSAMD_OK && c->pending_status == PSAMD_OK) { c->pending_status = verdict; c->pending_err = c->err; }
+    return PSAMD_OK;
+}
+
+static int take_verdict(psamd_ctx *c)
+{
+    if (c->pending_status == PSAMD_OK) return PSAMD_OK;
+    const int st = c->pending_status;
+    c->err = c->pending_err;
+    c->pending_status = PSAMD_OK;
+    return st;
+}
+
+// the rest of the step, once enq_lifecycle is enqueued (or replayed): the host's bookkeeping
+static int finish_step(psamd_ctx *c)
+{
+    c->host_queues_valid = false;
+    const int seq = ++c->scalars_seq;
+    if (c->interior_ran) c->interior_steps.insert(seq);
+    c->interior_ran = false;
+    if (c->timing_now) { c->ev_level[c->tset] = c->timing_now; c->timed_steps++; }
+    c->grid_built = false; c->pairs_done = false;
+    c->frame_clean = true;                       // (the step's last kernel zeroed the counts for the frame that follows)
+    c->step++; c->steps_total++;
+    // run-ahead: this step's record is read when the NEXT step has been enqueued (the record of the step before must be
+    // out of the way by then: the two pinned records alternate); else now
+    const int rc = consume_scalars(c, c->run_ahead ? seq - 1 : seq);
+    return rc != PSAMD_OK ? rc : take_verdict(c);
+}
+
+// everything enqueued so far has run: read every record outstanding (psamd_synchronize and the calls that hand
+// state or counters to the caller)
+int psamd::drain_scalars(psamd_ctx *c, bool quiet)
+{
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    const int rc = consume_scalars(c, c->scalars_seq);
+    return rc != PSAMD_OK ? rc : quiet ? (int)PSAMD_OK : take_verdict(c);
+}
+
+extern "C" {
+
+int psamd_init_iframe(psamd_ctx *c)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    if (c->P.world > 1) return slab_only(c, "init_iframe");
+    begin_step(c);
+    if (c->grid_built) c->frame_clean = false;      // (a frame abandoned after its build: its counts are in the way)
+    const int rc = enq_init_iframe(c);
+    if (rc != PSAMD_OK) return rc;
+    c->frame_clean = true;
+    c->frame_reset = true; c->grid_built = false; c->pairs_done = false;
+    return PSAMD_OK;
+}
+
+int psamd_build_grid(psamd_ctx *c)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    if (c->P.world > 1) return slab_only(c, "build_grid");
+    if (!c->frame_reset) return fail(c, PSAMD_ERR_STATE, "build_grid needs init_iframe first");
+    const int rc = enq_build_grid(c);
+    if (rc != PSAMD_OK) return rc;
+    c->frame_reset = false; c->grid_built = true; c->pairs_done = false; c->frame_clean = false;
+    return PSAMD_OK;
+}
+
+int psamd_calc_forces_pairs(psamd_ctx *c)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    if (c->P.world > 1) return slab_only(c, "calc_forces");
+    if (!c->grid_built) return fail(c, PSAMD_ERR_STATE, "calc_forces needs build_grid first");
+    const int rc = enq_pairs(c, c->P, pairs_hint(c, c->P));
+    if (rc != PSAMD_OK) return rc;
+    c->pairs_done = true;
+    return PSAMD_OK;
+}
+
+int psamd_calc_forces_apply(psamd_ctx *c)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    if (c->P.world > 1) return slab_only(c, "calc_forces");
+    if (!c->grid_built || !c->pairs_done) return fail(c, PSAMD_ERR_STATE, "apply needs build_grid and the pair pass first");
+    const int64_t bound = live_bound_of(c);
+    (void)pick_bucket_cap(c);
+    int rc = enq_apply(c, bound);
+    if (rc == PSAMD_OK) rc = enq_lifecycle(c, bound);
+    if (rc != PSAMD_OK) { resync_scalars(c); return rc; }
+    return finish_step(c);
+}
+
+int psamd_calc_forces(psamd_ctx *c)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    int rc = psamd_calc_forces_pairs(c);
+    if (rc != PSAMD_OK) return rc;
+    return psamd_calc_forces_apply(c);
+}
+
+int psamd_step(psamd_ctx *c, int32_t nsteps)
+{
+    if (!c || nsteps < 0) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    if (c->P.world > 1 && nsteps > 0) return slab_only(c, "step");
+    for (int k = 0; k < nsteps; k++) {
+        // init_iframe, build_grid, calc_forces: one sequence of launches (one graph)
+        begin_step(c);
+        if (c->grid_built) c->frame_clean = false;
+        const int64_t hint = pairs_hint(c, c->P), bound = live_bound_of(c);
+        const uint64_t key = launch_pairs_shape(c->P, hint) | ((uint64_t)bound << 24) | pick_bucket_cap(c) | (build_key(c) << 58);
+        int rc = run_segment(c, SEG_STEP, key, [&]() {
+            int r = enq_init_iframe(c);
+            if (r == PSAMD_OK) r = enq_build_grid(c);
+            if (r == PSAMD_OK) r = enq_pairs(c, c->P, hint);
+            if (r == PSAMD_OK) r = enq_apply(c, bound);
+            if (r == PSAMD_OK) r = enq_lifecycle(c, bound);
+            return r;
+        });
+        c->frame_clean = false;
+        if (rc != PSAMD_OK) { resync_scalars(c); return rc; }
+        c->frame_reset = false; c->grid_built = true; c->pairs_done = true;
+        rc = finish_step(c);
+        if (rc != PSAMD_OK) return rc;
+    }
+    return PSAMD_OK;
+}
+
+// ---- slab stages: the step cut where neighbouring ranks exchange messages -----------------
+
+int psamd_slab_build(psamd_ctx *c)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    begin_step(c);
+    if (c->grid_built) c->frame_clean = false;
+    {   // The transfer messages' capacity the ranks agreed on two steps ago (k_status_merge) takes effect now, on every rank
+        // in this same step: the record of step s - 2 has been read by every host that starts step s, whatever its run-ahead.
+        // A decision is an absolute number (grown, kept or shrunk: the rule is k_status_merge's), the same on every rank.
+        const int s = c->scalars_seq + 1;
+        int cap = c->P.xfer_cap;
+        for (auto it = c->cap_decisions.begin(); it != c->cap_decisions.end() && it->first <= s - 2; it = c->cap_decisions.erase(it)) cap = it->second;
+        cap = std::max(c->P.xfer_cap0, std::min(cap, c->P.xfer_cap_max));
+        if (cap != c->P.xfer_cap) {
+            c->P.xfer_cap = c->P_int.xfer_cap = c->P_rest.xfer_cap = cap;
+            for (int k = MSG_XFER_OUT; k < MSG_XFER_IN + 2; k++) c->msg[k].bytes = xfer_msg_bytes((size_t)cap + 1);
+        }
+    }
+    const int rc = run_segment(c, SEG_BUILD, build_key(c), [&]() {
+        int r = enq_init_iframe(c);
+        if (r == PSAMD_OK) r = enq_build_grid(c);
+        if (r != PSAMD_OK) return r;
+        if (c->msg[MSG_ALLG_OUT].ptr) PS_HIP(c, launch_allg_pack(c->stream, c->P, c->d, c->msg[MSG_ALLG_OUT].ptr));
+        int *const halo_out[2] = {c->msg[MSG_HALO_OUT].ptr, c->msg[MSG_HALO_OUT + 1].ptr};
+        if (c->P.world > 1) PS_HIP(c, launch_pack_halos(c->stream, c->P, c->d, c->halo_out_c0, c->halo_out_cells, halo_out, c->pack_off));
+        return (int)PSAMD_OK;
+    });
+    if (rc != PSAMD_OK) return rc;
+    c->frame_reset = false; c->grid_built = true; c->pairs_done = false; c->frame_clean = false;
+    c->slab_stage = 1;
+    return PSAMD_OK;
+}
+
+// optional, between slab_build and the arrival of the halo: the pair stage of the cells whose
+// stencil lies inside this rank's own layers
+int psamd_slab_pairs_interior(psamd_ctx *c)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (c->slab_stage != 1) return fail(c, PSAMD_ERR_STATE, "slab_pairs_interior belongs between slab_build and slab_pairs");
+    if (!c->have_interior || c->interior_done) return PSAMD_OK;
+    const int64_t hint = pairs_hint(c, c->P_int);
+    const int rc = run_segment(c, SEG_PAIRS, launch_pairs_shape(c->P_int, hint) | (1ull << 40), [&]() {
+        // (the status records have landed: the chunk lists' capacity rule over all ranks decides which particles the stage leaves alone)
+        PS_HIP(c, launch_chunk_census(c->stream, c->P, c->d, c->msg[MSG_STATUS_IN].ptr));
+        return enq_pairs(c, c->P_int, hint, false, true);
+    });
+    if (rc != PSAMD_OK) return rc;
+    c->interior_done = true; c->interior_ran = true;
+    return PSAMD_OK;
+}
+
+int psamd_slab_pairs(psamd_ctx *c)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (c->slab_stage != 1) return fail(c, PSAMD_ERR_STATE, "slab_pairs needs slab_build (and the halo exchange) first");
+    const DevParams &P = c->P;
+    const DevParams &Pp = c->interior_done ? c->P_rest : c->P;
+    const bool second = c->interior_done;
+    const int64_t hint = pairs_hint(c, Pp);
+    // (the all-pairs far pass sizes its launch from the live bound on one GPU only -- a slab takes every entry of the
+    // sorted order, see launch_pairs -- so the bound is no part of this key)
+    const int rc = run_segment(c, SEG_PAIRS, launch_pairs_shape(Pp, hint) | (second ? 2ull << 40 : 0ull), [&]() {
+        const int GG = P.G * P.G;
+        // from the rank below: halo layer (region 1), then lent layers (region 2); from the rank above: halo layer (region 3)
+        PS_HIP(c, launch_unpack_halos(c->stream, P, c->d, c->halo_in_cells[0], c->msg[MSG_HALO_IN].ptr, c->unpack_off[0],
+                                      c->halo_in_cells[1], c->msg[MSG_HALO_IN + 1].ptr, c->unpack_off[1]));
+        if (c->msg[MSG_ALLG_IN].ptr) PS_HIP(c, launch_allg_index(c->stream, P, c->d));      // all-pairs: the gathered snapshot, by global cell
+        // the chunk lists' capacity rule over all ranks (the status records have landed): which particles the step leaves alone
+        if (!second) PS_HIP(c, launch_chunk_census(c->stream, P, c->d, c->msg[MSG_STATUS_IN].ptr));
+        const int r = enq_pairs(c, Pp, hint, true, !second);
+        if (r != PSAMD_OK) return r;
+        if (c->msg[MSG_FORCE_OUT].ptr) PS_HIP(c, launch_pack_force(c->stream, P, c->d, c->msg[MSG_FORCE_OUT].ptr, P.reg_layers[2] * GG * P.halo_cap_cell));
+        return (int)PSAMD_OK;
+    });
+    c->interior_done = false;
+    if (rc != PSAMD_OK) return rc;
+    c->pairs_done = true;
+    c->slab_stage = 2;
+    return PSAMD_OK;
+}
+
+int psamd_slab_apply(psamd_ctx *c)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (c->slab_stage != 2) return fail(c, PSAMD_ERR_STATE, "slab_apply needs slab_pairs (and the force exchange) first");
+    const int64_t bound = live_bound_of(c);
+    const int rc = run_segment(c, SEG_APPLY, (uint64_t)bound | ((uint64_t)c->P.xfer_cap << 32), [&]() {
+        // the status records of all ranks (all-gathered since slab_build): error bits, cell-overflow kills for the
+        // owner of queue record 0, the transfer messages' next capacity; in
+        // the same launch the force records of the lent-out layers (the tail of the snapshot that went up)
+        PS_HIP(c, launch_status_merge(c->stream, c->P, c->d, c->msg[MSG_STATUS_IN].ptr, c->halo_out_cells[1] - (c->P.lentout_c1 - c->P.lentout_c0),
+                                      c->msg[MSG_FORCE_IN].ptr, c->pack_off[1]));
+        return enq_apply(c, bound);
+    });
+    if (rc != PSAMD_OK) return rc;
+    c->slab_bound = bound;
+    c->slab_stage = 3;
+    return PSAMD_OK;
+}
+
+int psamd_slab_finish(psamd_ctx *c)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (c->slab_stage != 3) return fail(c, PSAMD_ERR_STATE, "slab_finish needs slab_apply (and the transfer exchange) first");
+    c->slab_stage = 0;
+    const int64_t bound = c->slab_bound;
+    const int rc = run_segment(c, SEG_FINISH, (uint64_t)bound | ((uint64_t)(c->P.xfer_cap & 0x1fffffff) << 32) | pick_bucket_cap(c), [&]() { return enq_lifecycle(c, bound); });
+    if (rc != PSAMD_OK) { resync_scalars(c); return rc; }
+    return finish_step(c);
+}
+
+int psamd_synchronize(psamd_ctx *c)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    const int rc = drain_scalars(c);             // (the verdict of every step whose record had not been read yet)
+    if (rc != PSAMD_OK) return rc;
+    return check_device_errors(c);
+}
+
+int psamd_set_stream(psamd_ctx *c, void *hip_stream)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    c->stream = hip_stream ? (hipStream_t)hip_stream : c->own_stream;
+    return PSAMD_OK;
+}
+
+int psamd_get_stream(psamd_ctx *c, void **out)
+{
+    if (!c || !out) return PSAMD_ERR_INVALID_ARG;
+    *out = (void *)c->stream;
+    return PSAMD_OK;
+}
+
+int psamd_set_graphs(psamd_ctx *c, int enabled)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    if (!enabled) drop_graphs(c);
+    c->graphs = enabled != 0;
+    c->graph_refused.clear();
+    return PSAMD_OK;
+}
+
+int psamd_get_graph_stats(psamd_ctx *c, int64_t *launches, int64_t *captures)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (launches) *launches = c->graph_launches;
+    if (captures) *captures = c->graph_captures;
+    if (!c->graph_refused.empty()) return fail(c, PSAMD_ERR_UNSUPPORTED, "the HIP runtime would not capture a stage sequence (" + c->graph_refused + "); the context runs without graphs");
+    return PSAMD_OK;
+}
+
+int psamd_set_wait_policy(psamd_ctx *c, int policy)
+{
+    if (!c || policy < 0 || policy > 1) return PSAMD_ERR_INVALID_ARG;
+    c->wait_policy = policy;
+    return PSAMD_OK;
+}
+
+int psamd_set_tdata_mirror(psamd_ctx *c, int enabled)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    c->tdata_mirror = enabled != 0;
+    return PSAMD_OK;
+}
+
+int psamd_set_run_ahead(psamd_ctx *c, int steps)
+{
+    if (!c || steps < 0 || steps > 1) return PSAMD_ERR_INVALID_ARG;
+    c->run_ahead = steps;
+    return PSAMD_OK;
+}
+
+int psamd_set_timing(psamd_ctx *c, int enabled)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    collect_timing(c, 0); collect_timing(c, 1);          // (whatever is outstanding belongs to the setting that ends here)
+    c->timing = enabled < 0 ? 0 : enabled > 2 ? 2 : enabled;
+    c->timing_steps = 0; c->timing_now = 0;
+    if (c->timing) make_events(c);
+    for (double &v : c->t_us) v = 0.0;
+    for (auto &v : c->t_samples) v.clear();
+    c->t_launches = 0;
+    return PSAMD_OK;
+}
+
+int psamd_set_timing_period(psamd_ctx *c, int every)
+{
+    if (!c || every < 1) return PSAMD_ERR_INVALID_ARG;
+    c->timing_period = every;
+    c->timing_steps = 0;
+    return PSAMD_OK;
+}
+
+int psamd_get_timing(psamd_ctx *c, double us_out[PSAMD_NUM_TIMERS], int64_t *launches)
+{
+    if (!c || !us_out) return PSAMD_ERR_INVALID_ARG;
+    collect_timing(c, 0); collect_timing(c, 1);
+    for (int k = 0; k < PSAMD_NUM_TIMERS; k++) us_out[k] = c->t_us[k];
+    if (launches) *launches = c->t_launches;
+    return PSAMD_OK;
+}
+
+int psamd_get_timing_stats(psamd_ctx *c, double median_us[PSAMD_NUM_TIMERS], double max_us[PSAMD_NUM_TIMERS], int64_t *samples)
+{
+    if (!c || !median_us || !max_us) return PSAMD_ERR_INVALID_ARG;
+    collect_timing(c, 0); collect_timing(c, 1);
+    for (int k = 0; k < PSAMD_NUM_TIMERS; k++) {
+        std::vector<float> v = c->t_samples[k];
+        median_us[k] = max_us[k] = 0.0;
+        if (v.empty()) continue;
+        std::sort(v.begin(), v.end());
+        median_us[k] = v[v.size() / 2]; max_us[k] = v.back();
+    }
+    if (samples) *samples = c->t_launches;
+    return PSAMD_OK;
+}
+
+}  // extern "C"

@@ -204,18 +204,8 @@ class DeviceRing(_Ring):
         super().__init__(sysr, dist, rank, world)
         self.overlap_interior = overlap_interior
         import torch
-        b = sysr.slab_buffers()
-        ptrs = {HALO_OUT + 0: (b.halo_out[0], b.halo_out_bytes[0]), HALO_OUT + 1: (b.halo_out[1], b.halo_out_bytes[1]),
-                HALO_IN + 0: (b.halo_in[0], b.halo_in_bytes[0]), HALO_IN + 1: (b.halo_in[1], b.halo_in_bytes[1]),
-                FORCE_OUT: (b.force_out, b.force_out_bytes), FORCE_IN: (b.force_in, b.force_in_bytes),
-                XFER_OUT + 0: (b.xfer_out[0], b.xfer_bytes_max), XFER_OUT + 1: (b.xfer_out[1], b.xfer_bytes_max),
-                XFER_IN + 0: (b.xfer_in[0], b.xfer_bytes_max), XFER_IN + 1: (b.xfer_in[1], b.xfer_bytes_max),
-                STATUS_OUT: (b.status_out, b.status_bytes), STATUS_IN: (b.status_in, b.status_bytes * world),
-                ALLG_OUT: (b.allg_out, b.allg_bytes), ALLG_IN: (b.allg_in, b.allg_bytes * world),
-                XFER2_OUT + 0: (b.xfer2_out[0], b.xfer2_bytes), XFER2_OUT + 1: (b.xfer2_out[1], b.xfer2_bytes),
-                XFER2_IN + 0: (b.xfer2_in[0], b.xfer2_bytes), XFER2_IN + 1: (b.xfer2_in[1], b.xfer2_bytes),
-                FAR_OUT: (b.far_out, b.far_bytes), FAR_IN: (b.far_in, b.far_bytes * world)}
-        self.t = {slot: torch.as_tensor(_DevPtr(p, n), device="cuda") for slot, (p, n) in ptrs.items() if p and n}
+        # the whole of every buffer (of the transfer messages a prefix travels, see start)
+        self.t = {slot: torch.as_tensor(_DevPtr(p, room), device="cuda") for slot, (p, _, room) in enumerate(sysr.msg_table()) if p and room}
         self.stream = torch_stream
         sysr.set_stream(torch_stream.cuda_stream)
         self._phase_ops = {}     # the operations of a phase never change (fixed buffers, fixed peers): built once, on first use

@@ -92,7 +92,7 @@ struct DevParams {
 // ALLP_PARTS partial sums, each by a wave of its own (or a lone rank of eight would have half a wave per SIMD
 // walking the whole cloud): part p covers its share of the 64-cell blocks of the global cell order; partial sums
 // land in part_acc[p * part_plane + r], r = the particle's place among those that need a force, and
-// k_allpairs_combine adds them to the stencil's chain in part order (pairs.hip, k_allp_far).
+// k_allpairs_combine adds them to the stencil's chain in part order (allpairs.hip, k_allp_far).
 struct FarCells {
     unsigned long long plane = 0;
     float4 *part_acc = nullptr;
@@ -220,7 +220,7 @@ struct StepState {
     int32_t step, pending, seq;
     int32_t last_departures;   // slab mode: most records this rank sent in one direction in the step before (goes out with the next status record)
     int32_t peak_prev, pad_st; // slab mode: the busiest rank's count in the status records of the step before (the same number on every rank)
-    // The balanced force pass paces its waves against the clock (pairs.hip, WavePace): per pass of a frame (0 / 1), when
+    // The balanced force pass paces its waves against the clock (balanced.hpp, WavePace): per pass of a frame (0 / 1), when
     // the pass's planning ended (100 MHz real-time counter), when its last wave ended, and how long the last such pass
     // took -- what this one expects to take.
     unsigned long long pairs_t0[2], pairs_end[2];

@@ -1,4 +1,4 @@
-// kernels.h -- host-visible launch wrappers of kernels.hip.
+// kernels.h -- host-visible launch wrappers of the kernel files.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -160,6 +160,12 @@ hipError_t launch_force_gather(hipStream_t st, const DevParams &P, const DeviceS
 hipError_t launch_pairs(hipStream_t st, const DevParams &P, const DeviceState &d, hipEvent_t ev_force, int64_t tasks_hint, int pass, int64_t live_bound);
 // what shapes launch_pairs' launches for this hint, as a number below 2^24 (the key of a captured graph)
 uint64_t launch_pairs_shape(const DevParams &P, int64_t tasks_hint);
+// launch_pairs' launches outside force.hip, in the order it makes them (their errors are launch_pairs' to collect):
+// the collision flags (collide.hip), the plan of the balanced force pass (plan.hip: nw wave slots, merge: with packs),
+// the far field of the all-pairs forces and its sum (allpairs.hip; fast: the tolerance mode's arithmetic)
+void launch_collide(hipStream_t st, const DevParams &P, const DeviceState &d);
+void launch_plan_force(hipStream_t st, const DevParams &P, const DeviceState &d, int nw, bool merge, int pass);
+void launch_allpairs_far(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound);
 hipError_t launch_apply(hipStream_t st, const DevParams &P, const SegLayout &S, const DeviceState &d);
 hipError_t launch_frame_reset(hipStream_t st, const DeviceState &d, size_t frame_ints, int status_table);   // also clears the status record's header and census table
 // The step's tail behind k_apply: census of the queue operations (+ relocation phase 1), bucketing (the step's scalars go

@@ -1,4 +1,4 @@
-// kernels_common.hpp -- device helpers shared by the stage files (grid.hip, pairs.hip, apply.hip, lifecycle.hip, slab.hip).
+// kernels_common.hpp -- device helpers shared by the stage files (grid.hip, the pair stage's, apply.hip, lifecycle.hip, slab.hip).
 //
 // The step's kernels, hand-written for gfx950 (MI355X, CDNA4), by stage:
 //   grid.hip       AoS <-> SoA, init_iframe (the per-frame counts are zeroed by the last kernel of the step before;
@@ -6,11 +6,17 @@
 //                  k_scatter_lds counting sort of the live slots by cell (streaming, HBM), k_sort_cells: the reference's
 //                  cell-list order (ps.cpp:1510-1516), the snapshot in that order, the cell-overflow rule, the collision
 //                  halo lists
-//   pairs.hip      calc_forces' two neighbour loops (ps.cpp:1182-1263): k_collide_cell (collision flags from LDS bins),
-//                  k_plan_force, k_pairs_balanced / k_pairs: 27-cell softened gravity, one wave per 64
-//                  particles of one cell, neighbour bodies as scalar operands of packed fp32 instructions (or LDS tiles on
-//                  a small share), serial fp32 accumulation in the reference's order (fp32 VALU bound; no MFMA: no
-//                  contraction here, every pair needs its own rsqrt)
+//   the pair stage: calc_forces' two neighbour loops (ps.cpp:1182-1263), launched in this order by force.hip's launch_pairs
+//     pair_math.hpp  the pair arithmetic all of them share (device-inline only)
+//     collide.hip    k_collide_cell: collision flags from LDS bins, the lists of the particles that need a force
+//     plan.hip       k_plan_force: task list, packs, the wave slots' shares; balanced.hpp is what it shares with the pass
+//                    it plans (the wave_pos word, the hand-off of a cut task's sums, the waves' pacing)
+//     force.hip      k_pairs_balanced / k_pairs: 27-cell softened gravity, one wave per 64 particles of one cell,
+//                    neighbour bodies as scalar operands of packed fp32 instructions (or LDS tiles on a small share and
+//                    for the packs: tile_walk.hpp), serial fp32 accumulation in the reference's order (fp32 VALU bound;
+//                    no MFMA: no contraction here, every pair needs its own rsqrt)
+//     allpairs.hip   the far field of the all-pairs forces, beyond the stencil
+//     selftest.hip   the short sqrt / reciprocal against the compiler's over whole float ranges
 //   apply.hip      k_apply: death / survive / integrate / wrap / re-hash in slot order (ps.cpp:1210-1333; streaming, HBM)
 //   lifecycle.hip  free-slot queues + relocation replayed in the reference's serial order (ps.cpp:1335-1374,
 //                  app_common.cu:305-376): k_ops_hist / k_ops_scatter / k_replay_commit (lists of any length), k_moves_stage
@@ -20,7 +26,7 @@
 //
 // Reference arithmetic is reproduced operation for operation: every file is built with
 // -ffp-contract=off; where the reference evaluates in double (EPS2 add, 0.5*a*t*t) so
-// does this, except where an fp32 form is proven bit-identical (see pairs.hip).
+// does this, except where an fp32 form is proven bit-identical (see pair_math.hpp).
 // Citations: ps.cpp = source/code/src/particleSystem.cpp of the reference.
 #pragma once
 
@@ -45,6 +51,9 @@ static inline int blocks_for(size_t n, int threads, int cap = 4096)
     if (b > (size_t)cap) b = cap;
     return b < 1 ? 1 : (int)b;
 }
+
+// (force.hip's k_pairs_balanced and allpairs.hip's k_allp_far are launched for it)
+constexpr int BALANCED_WAVES = 7;      // resident waves per SIMD the scalar-walk force pass is built for (70 VGPRs; measured, exact / tolerance arithmetic: 6 waves 2.15 / 1.25 ms, 7 waves 2.11 / 1.22 ms)
 
 // (d_i2, d_i1, d_i3): the cell itself, then the reference's 26 candidates in the
 // order fill_cells probes them (app.cu:375-408).

@@ -90,6 +90,8 @@ def build_driver(force=False):
 
 
 RING_SRC = os.path.join(os.path.dirname(HERE), "host", "ps_ring_rccl.cpp")
+# ... and the headers it alone includes: the routes and buffers, the ring step, the benchmark protocol, the command line
+RING_DEPS = [RING_SRC] + [os.path.join(os.path.dirname(HERE), "host", h) for h in ("ring_routes.hpp", "ring_step.hpp", "ring_bench.hpp", "ring_options.hpp")]
 RING = os.path.join(os.path.dirname(HERE), "host", "ps_ring_rccl")
 
 
@@ -98,7 +100,7 @@ def build_ring(force=False):
     the HIP runtime and rccl.h; links libpsamd.so by relative rpath and the image's librccl)."""
     inc = os.path.join(os.path.dirname(HERE), "include")
     if not force and os.path.exists(RING) and os.path.getmtime(RING) > max(
-            os.path.getmtime(RING_SRC), os.path.getmtime(os.path.join(inc, "psamd.h")), os.path.getmtime(LIB)):
+            os.path.getmtime(f) for f in RING_DEPS + [os.path.join(inc, "psamd.h"), LIB]):
         return RING
     # linked beside its final name and renamed: another rank that sees the file sees a whole program
     tmp = RING + ".tmp.%d" % os.getpid()

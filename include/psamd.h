@@ -205,6 +205,23 @@ typedef struct psamd_inject_spec {
     psamd_inject_result *result_dev;   /* optional out (device); NULL: the context's own record only         */
 } psamd_inject_spec;
 
+/* What psamd_potential found (see "energy" below). */
+typedef struct psamd_potential_result {
+    int64_t listed;           /* particles phi was formed for                                                 */
+    int64_t nonfinite;        /* of them, with a phi that is not finite                                       */
+    double  potential;        /* U                                                                            */
+    double  phi_min, phi_max; /* over the finite ones; +inf / -inf if there is none                           */
+} psamd_potential_result;     /* 40 bytes */
+
+/* What psamd_potential writes and where (device pointers). */
+typedef struct psamd_potential_spec {
+    uint32_t flags;           /* 0 (reserved for later)                                                       */
+    int32_t  reserved;        /* 0                                                                            */
+    float   *phi;             /* optional out, float[capacity], 4-byte aligned; required if capacity > 0      */
+    int64_t  capacity;        /* entries phi holds                                                            */
+    psamd_potential_result *result_dev;   /* optional out (device), 8-byte aligned; NULL: the context's own record only */
+} psamd_potential_spec;       /* 32 bytes */
+
 typedef struct psamd_ctx psamd_ctx;
 
 /* ---- lifetime ------------------------------------------------------------ */
@@ -485,6 +502,54 @@ int psamd_live_stats_get(psamd_ctx *ctx, psamd_live_stats *out);
  * psamd_inject_result_get: the last inject's record, into host memory; waits for the context's stream. */
 int psamd_inject(psamd_ctx *ctx, const psamd_inject_spec *spec);
 int psamd_inject_result_get(psamd_ctx *ctx, psamd_inject_result *out);
+
+/* ---- energy ------------------------------------------------------------------ */
+/* The potential of every particle in the frame's cell lists, and the potential energy, formed on the device from what
+ * psamd_build_grid left (cell_start, sorted_id, the snap_soa planes).  Not in the reference: like drag, repulsion, Euler
+ * and all-pairs it changes nothing in the step's arithmetic.  For every entry i of the sorted order of the own cells
+ *     phi_i = - s * sum over j != i of  w_eff_j / sqrt(|x_j - x_i|^2 + eps2),     s = force_sign (0 reads as +1)
+ * over exactly the bodies the force pass walks for i's cell: the 27-cell non-periodic stencil in the reference's order,
+ * of each cell its first min(count, MAX_PARTICLES_PER_CELL) bodies; with PSAMD_FLAG_ALL_PAIRS every other cell of the box
+ * behind them, in global index order.  A kid has w_eff = 0: it adds nothing to anybody and is given the potential at
+ * its own position.  j is left out BY SORTED INDEX, not by distance: two particles at one point see each other at
+ * -w / sqrt(eps2).  w_eff in these formulas is the unsigned mass (w, or 0 for a kid): the sign s appears in phi alone,
+ * so repulsion flips phi and U together.  U = 1/2 * sum_i w_eff_i * phi_i in fp64; a particle whose phi is not finite (its own position, or
+ * that of a body of its stencil, is not a number) counts in `nonfinite` and in no sum.
+ *
+ * Arithmetic: the differences and r.r in fp32 as the force pass forms them, the hardware reciprocal square root, the
+ * terms added in list order in fp32 chains of at most 64 that start with every cell and are carried on in fp64.  The
+ * association depends on the cell order and the lists' lengths alone: phi and U are the same bits from run to run, with
+ * graphs on or off, and phi_i is the same on one context and on the slab that holds particle i.  Against an fp64 direct
+ * sum phi and U stay within 1e-5 relative (tests/test_gpu_potential.py; measured: 1.5e-7 and 1e-8).
+ *
+ * psamd_potential: enqueued on the context's stream (psamd_get_stream) and nothing else -- it allocates nothing, waits
+ * for nothing and reads nothing back (its scratch is the context's, sized at creation), so it may be captured into a
+ * graph.  phi[k] belongs to the k-th live particle in ascending global slot id, the first min(count, capacity) of them:
+ * entry for entry the arrays of a psamd_export_live made at the same point of the stream.  A live particle that is in no
+ * list of the frame gets a quiet NaN there and does not count in `listed`.  *result_dev and the context's own record
+ * (psamd_potential_result_get) are written by the time the stream reaches the end of the call.
+ *
+ * Valid while a frame is built and its particles have not moved: world == 1 from psamd_build_grid until the frame ends
+ * (before or after psamd_calc_forces_pairs: the pair stage does not disturb what the pass reads); world > 1 from
+ * psamd_slab_pairs, which unpacks the halos, until psamd_slab_apply.  Elsewhere PSAMD_ERR_STATE, also for a wedged
+ * context.  psamd_step cannot be interposed: use the stage calls.
+ *
+ * A slab forms phi for the particles of its own state layers from its own snapshot and the received halos (all-pairs:
+ * the gathered snapshot), and only if its plan lends nothing -- lentin and lentout empty, which holds for group-aligned
+ * cuts; else PSAMD_ERR_UNSUPPORTED (the context stays usable): shipping phi of lent layers home would need a message of
+ * its own.  The ranks' results combine like psamd_live_stats: counts and U add, the extrema take min and max.
+ *
+ * PSAMD_ERR_INVALID_ARG: a NULL context or spec, flags or reserved not 0, capacity < 0, phi not 4-byte aligned, phi NULL
+ * with capacity > 0, result_dev not 8-byte aligned.
+ *
+ * psamd_potential_result_get: the last call's record, into host memory; waits for the context's stream.
+ * psamd_download_potential: the same pass into host memory (phi: `capacity` floats or NULL with capacity 0; out may be
+ * NULL); only the min(count, capacity) entries cross PCIe and are written, count being the live count that
+ * psamd_download_live reports at the same point (with no fields and capacity 0 it costs two small launches).  Waits for
+ * the context's stream. */
+int psamd_potential(psamd_ctx *ctx, const psamd_potential_spec *spec);
+int psamd_potential_result_get(psamd_ctx *ctx, psamd_potential_result *out);
+int psamd_download_potential(psamd_ctx *ctx, float *phi, int64_t capacity, psamd_potential_result *out);
 
 /* ---- introspection -------------------------------------------------------- */
 int psamd_get_counters(psamd_ctx *ctx, psamd_counters *out);

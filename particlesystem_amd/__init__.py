@@ -148,6 +148,31 @@ class Inject(C.Structure):
                 ("result_dev", C.c_void_p)]
 
 
+class PotentialResult(C.Structure):
+    """psamd_potential_result: counts, the potential energy U and the extrema of phi."""
+    _fields_ = [("listed", C.c_int64), ("nonfinite", C.c_int64), ("potential", C.c_double),
+                ("phi_min", C.c_double), ("phi_max", C.c_double)]
+
+    def to_dict(self):
+        return {"listed": int(self.listed), "nonfinite": int(self.nonfinite), "potential": float(self.potential),
+                "phi_min": float(self.phi_min), "phi_max": float(self.phi_max)}
+
+
+class Potential(C.Structure):
+    """psamd_potential_spec: what psamd_potential writes and where (device pointers)."""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_int32), ("phi", C.c_void_p), ("capacity", C.c_int64),
+                ("result_dev", C.c_void_p)]
+
+
+def merge_potential(results):
+    """The potential of a system from its ranks' (dicts of potential() / download_potential()): counts and U add, in
+    rank order; the extrema take the minimum and the maximum.  (No "phi": the ranks' arrays pair with their own exports.)"""
+    results = list(results)
+    return {"listed": sum(int(r["listed"]) for r in results), "nonfinite": sum(int(r["nonfinite"]) for r in results),
+            "potential": float(sum(float(r["potential"]) for r in results)),
+            "phi_min": float(min(float(r["phi_min"]) for r in results)), "phi_max": float(max(float(r["phi_max"]) for r in results))}
+
+
 def merge_live_stats(stats):
     """The statistics of a system from its ranks' (dicts of live_stats() / export_live()["stats"]): counts and sums
     add, in rank order; the box and the ages take the minima and maxima."""
@@ -241,6 +266,9 @@ ABI = [
     ("psamd_live_stats_get", C.c_int, [_vp, C.POINTER(LiveStats)]),
     ("psamd_inject", C.c_int, [_vp, C.POINTER(Inject)]),
     ("psamd_inject_result_get", C.c_int, [_vp, C.POINTER(InjectResult)]),
+    ("psamd_potential", C.c_int, [_vp, C.POINTER(Potential)]),
+    ("psamd_potential_result_get", C.c_int, [_vp, C.POINTER(PotentialResult)]),
+    ("psamd_download_potential", C.c_int, [_vp, _vp, _i64, C.POINTER(PotentialResult)]),
 ]
 
 _lib = None
@@ -635,6 +663,62 @@ class ParticleSystem:
         r = InjectResult()
         self._ck(self.lib.psamd_inject_result_get(self.h, C.byref(r)))
         return r.to_dict()
+
+    # ---- energy (include/psamd.h) -----------------------------------------------
+    def potential(self, phi=False, capacity=None):
+        """psamd_potential: {"listed", "nonfinite", "potential", "phi_min", "phi_max"} of the frame that is built (after
+        build_grid; a slab: between slab_pairs and slab_apply) and, with phi=True, "phi": a float32 torch device tensor of
+        min(live count, capacity) entries that pairs, entry for entry, with export_live() at the same point of the stream.
+        Waits for the context's stream.  torch must have been imported before the library was loaded."""
+        import torch
+        dev = torch.device("cuda", int(self.cfg.device))
+        spec = Potential()
+        result = torch.zeros(C.sizeof(PotentialResult), dtype=torch.uint8, device=dev)
+        spec.result_dev = result.data_ptr()
+        out = count = None
+        if phi:
+            capacity = self.owned_slots() if capacity is None else int(capacity)
+            out = torch.empty(max(capacity, 1), dtype=torch.float32, device=dev)
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            spec.phi, spec.capacity = out.data_ptr(), capacity
+        st = torch.cuda.ExternalStream(self.stream(), device=dev)
+        st.wait_stream(torch.cuda.current_stream(dev))        # (the tensors are torch's: the pass follows their allocation)
+        self._ck(self.lib.psamd_potential(self.h, C.byref(spec)))
+        if phi:      # how many entries were written: the live count at this point of the stream
+            self._ck(self.lib.psamd_export_live(self.h, C.byref(Export(fields=0, capacity=0, count_dev=count.data_ptr()))))
+        st.synchronize()
+        res = PotentialResult.from_buffer_copy(result.cpu().numpy().tobytes()).to_dict()
+        if phi:
+            res["phi"] = out[:min(int(count.item()), capacity)]
+        return res
+
+    def potential_result(self):
+        """psamd_potential_result_get: the last potential call's record"""
+        r = PotentialResult()
+        self._ck(self.lib.psamd_potential_result_get(self.h, C.byref(r)))
+        return r.to_dict()
+
+    def download_potential(self, phi=True, capacity=None):
+        """psamd_download_potential, the numpy form of potential(): "phi" is a float32 array of min(live count, capacity)"""
+        r = PotentialResult()
+        if not phi:
+            self._ck(self.lib.psamd_download_potential(self.h, None, 0, C.byref(r)))
+            return r.to_dict()
+        capacity = self.owned_slots() if capacity is None else int(capacity)
+        out = np.full(max(capacity, 1), np.nan, np.float32)
+        self._ck(self.lib.psamd_download_potential(self.h, _ptr(out), capacity, C.byref(r)))
+        res = r.to_dict()
+        n = C.c_int64()        # how many entries were written: the export's count at this point (no fields, nothing copied)
+        self._ck(self.lib.psamd_download_live(self.h, 0, None, None, None, None, None, 0, C.byref(n)))
+        res["phi"] = out[:min(n.value, capacity)]
+        return res
+
+    def energy(self):
+        """{"kinetic", "potential", "total"} of the frame that is built: one potential() and one live_stats() at the same
+        point of the stream (kinetic: psamd_live_stats.kinetic, sum 0.5 w |v|^2 over the live particles)"""
+        u = self.potential()["potential"]
+        k = float(self.live_stats()["kinetic"])
+        return {"kinetic": k, "potential": u, "total": k + u}
 
     def device_view(self):
         v = DeviceView()

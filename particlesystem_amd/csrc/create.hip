@@ -298,6 +298,12 @@ static int alloc_step_arrays(psamd_ctx *c)
     PS_HIP(c, dev_alloc(c, &d.exp_count, (size_t)export_tiles(P.slots_total)));     // psamd_export_live's scratch
     PS_HIP(c, dev_alloc(c, &d.exp_tiles, (size_t)export_tiles(P.slots_total)));
     PS_HIP(c, dev_alloc(c, &d.exp_out, 1));
+    PS_HIP(c, dev_alloc(c, &d.pot_sorted, SC));                                      // psamd_potential's scratch and result record
+    PS_HIP(c, dev_alloc(c, &d.pot_slot, C));
+    PS_HIP(c, dev_alloc(c, &d.pot_tiles, (size_t)pot_tiles(P.slots_total)));
+    PS_HIP(c, dev_alloc(c, &d.pot_count, (size_t)pot_tiles(P.slots_total)));
+    PS_HIP(c, dev_alloc(c, &d.pot_out, 1));
+    PS_HIP(c, hipMemsetAsync(d.pot_out, 0, sizeof(PotOut), c->stream));
     PS_HIP(c, dev_alloc(c, &c->inj.removed, (size_t)g.queue_infos));    // psamd_inject's fixed scratch and result record
     PS_HIP(c, dev_alloc(c, &c->inj.hdr, 2));
     PS_HIP(c, dev_alloc(c, &c->inj.own, 1));

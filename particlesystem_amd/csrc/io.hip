@@ -556,6 +556,65 @@ int psamd_inject_result_get(psamd_ctx *c, psamd_inject_result *out)
     return PSAMD_OK;
 }
 
+// ---- energy (potential.hip) ----
+// a frame is built, its particles have not moved, and -- a slab -- the halos are in and nothing of the plan is lent
+static int potential_ready(psamd_ctx *c)
+{
+    if (c->wedged) return refuse_wedged(c);
+    const bool ok = c->P.world > 1 ? c->slab_stage == 2 : (c->grid_built && c->slab_stage != 3);
+    if (!ok) return fail(c, PSAMD_ERR_STATE, c->P.world > 1 ? "potential belongs between slab_pairs and slab_apply"
+                                                             : "potential needs build_grid first, and a frame that has not been applied");
+    const SlabPlan &pl = c->plan;
+    if (c->P.world > 1 && (pl.lentin_lo < pl.lentin_hi || pl.lentout_lo < pl.lentout_hi))
+        return fail(c, PSAMD_ERR_UNSUPPORTED, "potential: this rank's plan lends cell layers (lentin / lentout not empty); only plans "
+                                              "with group-aligned cuts are served");
+    return PSAMD_OK;
+}
+
+int psamd_potential(psamd_ctx *c, const psamd_potential_spec *spec)
+{
+    if (!c || !spec) return PSAMD_ERR_INVALID_ARG;
+    if (spec->flags != 0 || spec->reserved != 0) return fail(c, PSAMD_ERR_INVALID_ARG, "potential: flags and reserved must be 0");
+    if (spec->capacity < 0) return fail(c, PSAMD_ERR_INVALID_ARG, "potential: capacity < 0");
+    if (!aligned(spec->phi, 4) || (!spec->phi && spec->capacity > 0) || !aligned(spec->result_dev, 8))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "potential: phi missing or misaligned, or result_dev misaligned");
+    const int rc = potential_ready(c);
+    if (rc != PSAMD_OK) return rc;
+    PS_HIP(c, launch_potential(c->stream, c->P, c->d, spec->phi, spec->capacity, spec->result_dev));
+    return PSAMD_OK;
+}
+
+int psamd_potential_result_get(psamd_ctx *c, psamd_potential_result *out)
+{
+    if (!c || !out) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    PS_HIP(c, hipMemcpyAsync(out, &c->d.pot_out->result, sizeof *out, hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    return PSAMD_OK;
+}
+
+int psamd_download_potential(psamd_ctx *c, float *phi, int64_t capacity, psamd_potential_result *out)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (capacity < 0 || (!phi && capacity > 0)) return fail(c, PSAMD_ERR_INVALID_ARG, "download_potential: capacity < 0, or no array for it");
+    int rc = potential_ready(c);
+    if (rc != PSAMD_OK) return rc;
+    const int64_t n = std::min<int64_t>(capacity, c->P.slots_total);
+    rc = ensure_staging(c, std::max<size_t>((size_t)n * sizeof(float), 256));
+    if (rc != PSAMD_OK) return rc;
+    PS_HIP(c, launch_potential(c->stream, c->P, c->d, n > 0 ? (float *)c->staging : nullptr, n, nullptr));
+    PotOut got{};
+    PS_HIP(c, hipMemcpyAsync(&got, c->d.pot_out, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t m = (size_t)std::min<int64_t>(got.live, n);
+    if (m > 0) {
+        PS_HIP(c, hipMemcpyAsync(phi, c->staging, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        PS_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    if (out) *out = got.result;
+    return PSAMD_OK;
+}
+
 int psamd_download_force4(psamd_ctx *c, void *out, int64_t first, int64_t count)
 {
     if (!c || !out || first < 0 || count < 0 || first + count > c->P.sorted_cap) return PSAMD_ERR_INVALID_ARG;

@@ -51,6 +51,22 @@ struct InjectScratch {
     psamd_inject_result *own;   // the context's own result record (psamd_inject_result_get)
 };
 
+// psamd_potential (potential.hip): the sorted order of the own cells, and the owned slots, in tiles of POT_TILE; per tile of
+// the sorted order the partials of U (fp64), of phi's extrema and of the counts
+constexpr int POT_TILE = 4096;
+struct __align__(16) PotTile {
+    double u;
+    float lo, hi;
+    int listed, nonfinite;
+    int pad[2];
+};
+inline int pot_tiles(int slots_total) { return (slots_total + POT_TILE - 1) / POT_TILE; }
+// the context's own result record (psamd_potential_result_get), and the live count psamd_download_potential copies by
+struct PotOut {
+    psamd_potential_result result;
+    int64_t live;
+};
+
 // Container layout by segment type (slots and QUEUE_INFO records), device copy.
 struct SegLayout {
     int32_t seg_base[5];
@@ -132,6 +148,12 @@ struct DeviceState {
     int *exp_count = nullptr;
     ExportTile *exp_tiles = nullptr;
     ExportOut *exp_out = nullptr;
+    // psamd_potential: phi by sorted index and by slot, per tile the partials and the live count, the context's own result record
+    float *pot_sorted = nullptr;
+    float *pot_slot = nullptr;
+    PotTile *pot_tiles = nullptr;
+    int *pot_count = nullptr;
+    PotOut *pot_out = nullptr;
     unsigned long long *trace = nullptr;  // 3 words per pair-kernel wave slot (diagnostic builds only)
 };
 
@@ -195,6 +217,11 @@ hipError_t launch_status_merge(hipStream_t st, const DevParams &P, const DeviceS
 // slot order; workgroup 0 writes the count and the statistics)
 hipError_t launch_export_live(hipStream_t st, const DevParams &P, const DeviceState &d, const ExportFields &out,
                               int64_t capacity, int64_t *count_out, psamd_live_stats *stats_out);
+
+// psamd_potential: phi of every particle in the own cells' lists (k_pot_pairs), U and the extrema in a fixed tree, phi of the
+// first `capacity` live particles in slot order (phi null or capacity 0: the result alone); result_dev may be null
+hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceState &d, float *phi, int64_t capacity,
+                            psamd_potential_result *result_dev);
 
 // psamd_inject: locate + rank, the records' prefix, the first queue failure, the placement, the commit of the queues and
 // the result record (max_count > 0)

@@ -1,0 +1,391 @@
+// potential.hip -- psamd_potential: every listed particle's potential and the potential energy, on the device.
+//
+// Not part of the step and not in the reference.  The pass reads the frame psamd_build_grid left
+// (cell_start, sorted_id, the snap_soa planes) and walks, for every particle of the own cells' lists, exactly the
+// bodies the force pass walks for its cell:
+//   phi_i = - sum over j != i of w_j / sqrt(|x_j - x_i|^2 + eps2)        (w_j: the snapshot's w_eff -- force_sign is
+//                                                                         in it, a kid's is 0)
+//   U     = 1/2 sum_i |w_i| phi_i                                        (fp64)
+// in three launches that nothing in between has to wait for:
+//   k_pot_pairs   one wave per (own cell, 64-particle slice), one lane per particle: the 27-cell stencil in the
+//                 reference's order, the bodies as wave-uniform (scalar) loads of the four planes, eight to a group in
+//                 pair_math.hpp's packed forms; all-pairs contexts go on over every other cell in global order.  The
+//                 lane's own entry is left out BY SORTED INDEX: two particles at one point see each other.
+//                 phi by sorted index.
+//   k_pot_reduce  per tile of POT_TILE sorted entries: phi scattered to slot order through sorted_id; U, the extrema and
+//                 the counts of the tile in a fixed tree; and -- tile t of the owned SLOTS -- its live count.
+//   k_pot_finish  workgroup 0: the tiles in index order, the result record; workgroup 1 + t: slot tile t of phi
+//                 compacted to export order (ascending slot id: entry k pairs with psamd_export_live's entry k).
+// The launch boundaries are the only ordering between the workgroups (as in export.hip).
+//
+// Accumulation.  Terms are fp32 (differences and r.r as the force pass forms them, v_rsq_f32, one multiply).  They are
+// added in list order in fp32 CHAINS of at most POT_CHAIN terms; a chain starts at +0 with every cell (and every
+// POT_CHAIN bodies inside a cell) and its sum is carried on in fp64.  A particle's association therefore depends on
+// nothing but the cell order and the cells' list lengths: the same bits from run to run, with graphs or without, on one
+// context and on the slab that holds the particle.  Against an fp64 direct sum: 1.5e-7 relative for phi, 1e-8 for U
+// (tests/test_gpu_potential.py prints the largest error of every case).
+#include "pair_math.hpp"
+
+namespace psamd {
+
+constexpr int POT_THREADS = 256;
+constexpr int POT_WAVES = POT_THREADS / 64;
+constexpr int POT_ITEMS = POT_TILE / POT_THREADS;        // 16 batches of 64 entries per wave
+constexpr int POT_CHAIN = 64;                            // fp32 additions in one chain, a multiple of the group's 8
+static_assert(POT_ITEMS * POT_THREADS == POT_TILE, "a wave walks POT_ITEMS batches of 64 entries");
+
+__device__ __forceinline__ bool pot_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// Eight bodies from jj on, their terms added to the chain `a` in list order.  TAIL: only the first `rem` of them are
+// bodies of the list (the others are read -- inside the buffer, see pot_walk -- and dropped).  SELF: the list is the
+// lane's own cell's, body 0 has sorted index gj0: the lane's own entry is dropped.
+template <bool SELF, bool TAIL>
+__device__ __forceinline__ void pot_group(const PairCtx &ctx, const float *__restrict__ sx, const float *__restrict__ sy,
+                                          const float *__restrict__ sz, const float *__restrict__ sw, int jj, int rem,
+                                          int gj0, float eps2f, float &a)
+{
+    constexpr int NQ = 8;
+    v2f qx[NQ / 2], qy[NQ / 2], qz[NQ / 2], qw[NQ / 2];
+#pragma unroll
+    for (int i = 0; i < NQ / 2; i++) {
+        qx[i] = v2f{sx[jj + 2 * i], sx[jj + 2 * i + 1]};
+        qy[i] = v2f{sy[jj + 2 * i], sy[jj + 2 * i + 1]};
+        qz[i] = v2f{sz[jj + 2 * i], sz[jj + 2 * i + 1]};
+        qw[i] = v2f{sw[jj + 2 * i], sw[jj + 2 * i + 1]};
+    }
+    PairRows<NQ> r;
+    pairs_dist<NQ, false>(ctx, qx, qy, qz, 0.f, r);
+    const v2f eps = {eps2f, eps2f};
+    v2f t[NQ / 2];
+#pragma unroll
+    for (int i = 0; i < NQ / 2; i++) {
+        const v2f e = r.d[i] + eps;
+        v2f s; s.x = __builtin_amdgcn_rsqf(e.x); s.y = __builtin_amdgcn_rsqf(e.y);
+        t[i] = qw[i] * s;
+    }
+#pragma unroll
+    for (int i = 0; i < NQ; i++) {
+        float ti = (i & 1) ? t[i >> 1].y : t[i >> 1].x;
+        if (TAIL && i >= rem) ti = 0.f;
+        if (SELF && gj0 + jj + i == ctx.gi) ti = 0.f;
+        a += ti;
+    }
+}
+
+// n bodies from four planes of a snapshot (wave-uniform pointers: scalar loads), their terms carried on in acc.
+// padded: eight floats past the list's end can be read in every plane (the own snapshot: create.hip allocates it so;
+// not the gathered one) -- the ragged tail is then one group with its surplus dropped instead of up to seven single
+// bodies.  Both forms add the same terms in the same order.
+template <bool SELF>
+__device__ __forceinline__ void pot_walk(const PairCtx &ctx, const float *__restrict__ sx, const float *__restrict__ sy,
+                                         const float *__restrict__ sz, const float *__restrict__ sw, int n, int gj0,
+                                         float eps2f, bool padded, double &acc)
+{
+    for (int j0 = 0; j0 < n; j0 += POT_CHAIN) {
+        const int m = min(POT_CHAIN, n - j0);
+        float a = 0.f;
+        int jj = 0;
+        for (; jj + 8 <= m; jj += 8) pot_group<SELF, false>(ctx, sx, sy, sz, sw, j0 + jj, 8, gj0, eps2f, a);
+        if (jj < m) {
+            if (padded) pot_group<SELF, true>(ctx, sx, sy, sz, sw, j0 + jj, m - jj, gj0, eps2f, a);
+            else {
+                // (one body at a time: each term is pot_group's -- pairs_dist<NQ, false>'s unfused r.r, the same eps add, rsq and
+                // multiply -- and must stay so, or a slab's all-pairs phi leaves the single context's bits;
+                // tests/test_gpu_potential.py holds the two against each other on a world of two)
+                for (; jj < m; jj++) {
+                    const int j = j0 + jj;
+                    const float rx = sx[j] - ctx.xi, ry = sy[j] - ctx.yi, rz = sz[j] - ctx.zi;
+                    const float d2 = rx * rx + ry * ry + rz * rz;
+                    float ti = sw[j] * __builtin_amdgcn_rsqf(d2 + eps2f);
+                    if (SELF && gj0 + j == ctx.gi) ti = 0.f;
+                    a += ti;
+                }
+            }
+        }
+        acc += (double)a;
+    }
+}
+
+// where an all-pairs context finds the cells beyond the stencil (allpairs.hip, launch_allpairs_far)
+struct PotFar {
+    const float *buf;
+    const int *start, *n;
+    unsigned long long plane;
+    int padded;
+};
+
+template <bool ALLP>
+__global__ __launch_bounds__(POT_THREADS) void k_pot_pairs(DevParams P, const int *__restrict__ cell_start,
+                                                           const float *__restrict__ snap_soa,
+                                                           const float *__restrict__ snap_age,
+                                                           const int *__restrict__ sorted_id,
+                                                           const float4 *__restrict__ pos4, const PotFar far,
+                                                           float *__restrict__ phi_sorted)
+{
+    // (cell, slice) tasks of every own cell, cell-major; four independent waves per workgroup, an XCD's workgroups a
+    // contiguous run of cells (force.hip, k_pairs).  Slices past a cell's count end at once.
+    const int lane = threadIdx.x & 63;
+    const int ntask = P.n_own_cells * P.slices, nwg = (ntask + 3) >> 2;
+    if ((int)blockIdx.x >= nwg) return;
+    const int slot = __builtin_amdgcn_readfirstlane(xcd_contiguous(blockIdx.x, nwg) * 4 + (int)(threadIdx.x >> 6));
+    if (slot >= ntask) return;
+    const int c = slot / P.slices, slice = slot - c * P.slices;
+    const int base = cell_start[c];
+    const int cnt = min(cell_start[c + 1] - base, P.max_per_cell);
+    const int first = slice * 64;
+    if (first >= cnt) return;
+    const bool valid = lane < min(64, cnt - first);
+    const int gi = base + first + (valid ? lane : 0);
+    const size_t cap = (size_t)P.sorted_cap;
+    float mx = snap_soa[gi], my = snap_soa[cap + gi], mz = snap_soa[2 * cap + gi];
+    if (snap_age[gi] < P.kid_thr) {              // a kid's snapshot position is the origin (grid.hip): its own is in its slot
+        const int si = slot_index(P, sorted_id[gi]);
+        if (si >= 0) { const float4 p = pos4[si]; mx = p.x; my = p.y; mz = p.z; }
+    }
+    int i1, i2, i3;
+    cell_coords(P, c, i1, i2, i3);
+    const float eps2f = (float)P.eps2;
+    const PairCtx ctx = {mx, my, mz, 0.f, 0, gi, false};
+    int my_nb = 0, my_cnt = 0;
+    if (lane < STENCIL) {
+        const int nc = local_cell(P, i3 + c_stencil[lane][2], i1 + c_stencil[lane][1], i2 + c_stencil[lane][0]);
+        if (nc >= 0) {
+            my_nb = cell_start[nc];
+            my_cnt = min(cell_start[nc + 1] - my_nb, P.max_per_cell);
+        }
+    }
+    double acc = 0.0;
+    {   // the own cell first, as the stencil has it
+        const float *sx = snap_soa + base;
+        pot_walk<true>(ctx, sx, sx + cap, sx + 2 * cap, sx + 3 * cap, cnt, base, eps2f, true, acc);
+    }
+    for (int k = 1; k < STENCIL; k++) {
+        const int nb = __builtin_amdgcn_readlane(my_nb, k), n = __builtin_amdgcn_readlane(my_cnt, k);
+        const float *sx = snap_soa + nb;
+        pot_walk<false>(ctx, sx, sx + cap, sx + 2 * cap, sx + 3 * cap, n, 0, eps2f, true, acc);
+    }
+    if (ALLP) {
+        // every other cell of the box in global index order, 64 cell ranges to a vector load (allpairs.hip); the wave's
+        // particles share one cell, so the cells of its stencil are left out for the whole wave
+        const size_t plane = (size_t)far.plane;
+        const int nblk = (P.num_cells_global + 63) >> 6, GG = P.G * P.G;
+        for (int blk = 0; blk < nblk; blk++) {
+            const int c2 = blk * 64 + lane;
+            int f_nb = 0, f_cnt = 0;
+            if (c2 < P.num_cells_global) {
+                const int j3 = c2 / GG, rem = c2 - j3 * GG, j1 = rem / P.G, j2 = rem - j1 * P.G;
+                f_nb = far.start[c2];
+                f_cnt = far.n ? far.n[c2] : min(far.start[c2 + 1] - f_nb, P.max_per_cell);
+                if (abs(j3 - i3) <= 1 && abs(j1 - i1) <= 1 && abs(j2 - i2) <= 1) f_cnt = 0;
+            }
+            for (unsigned long long todo = __ballot(f_cnt > 0); todo; todo &= todo - 1) {
+                const int q = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+                const int nb = __builtin_amdgcn_readlane(f_nb, q), n = __builtin_amdgcn_readlane(f_cnt, q);
+                const float *sx = far.buf + nb;
+                pot_walk<false>(ctx, sx, sx + plane, sx + 2 * plane, sx + 3 * plane, n, 0, eps2f, far.padded != 0, acc);
+            }
+        }
+    }
+    if (valid) phi_sorted[gi] = (float)(-acc);
+}
+
+// What a tile, a wave or a lane has seen of the listed particles.
+struct PotAcc {
+    double u;
+    float lo, hi;
+    int listed, nonfinite;
+    __device__ __forceinline__ void init() { u = 0.0; lo = __int_as_float(0x7f800000); hi = -lo; listed = 0; nonfinite = 0; }
+    __device__ __forceinline__ void add(float w, float phi)
+    {
+        listed++;
+        if (!pot_finite(phi)) { nonfinite++; return; }
+        u += 0.5 * (double)fabsf(w) * (double)phi;
+        lo = fminf(lo, phi); hi = fmaxf(hi, phi);
+    }
+    __device__ __forceinline__ void merge(const PotAcc &o)
+    {
+        u += o.u; lo = fminf(lo, o.lo); hi = fmaxf(hi, o.hi); listed += o.listed; nonfinite += o.nonfinite;
+    }
+    __device__ __forceinline__ void wave_reduce()          // a butterfly: the same fixed tree on every run
+    {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            PotAcc o;
+            o.u = __shfl_xor(u, m); o.lo = __shfl_xor(lo, m); o.hi = __shfl_xor(hi, m);
+            o.listed = __shfl_xor(listed, m); o.nonfinite = __shfl_xor(nonfinite, m);
+            merge(o);
+        }
+    }
+};
+
+// Tile t of the sorted order of the own cells (entries cell_start[0] + t * POT_TILE ...; an entry whose id is -1 was
+// ranked past its cell's list capacity: no particle) and tile t of the owned slots.
+__global__ __launch_bounds__(POT_THREADS) void k_pot_reduce(DevParams P, const int *__restrict__ cell_start,
+                                                            const int *__restrict__ sorted_id,
+                                                            const float *__restrict__ snap_soa,
+                                                            const float *__restrict__ phi_sorted,
+                                                            const int *__restrict__ cell, float *__restrict__ phi_slot,
+                                                            PotTile *__restrict__ tiles, int *__restrict__ tile_count)
+{
+    __shared__ PotAcc s_acc[POT_WAVES];
+    __shared__ int s_live[POT_WAVES];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, t = blockIdx.x;
+    const int g0 = cell_start[0], g1 = min(cell_start[P.n_own_cells], P.sorted_cap);
+    const int off = t * POT_TILE + wv * 64 * POT_ITEMS + lane;
+    const float *sw = snap_soa + 3 * (size_t)P.sorted_cap;
+    PotAcc a;
+    a.init();
+    int live = 0;
+#pragma unroll 4
+    for (int k = 0; k < POT_ITEMS; k++) {
+        const int gi = g0 + off + 64 * k;
+        const int id = gi < g1 ? sorted_id[gi] : -1;
+        if (id >= 0) {
+            const float phi = phi_sorted[gi];
+            a.add(sw[gi], phi);
+            const int si = slot_index(P, id);
+            if (phi_slot && si >= 0) phi_slot[si] = phi;
+        }
+        const int i = off + 64 * k;
+        const int cl = i < P.slots_total ? cell[i] : -1;
+        live += __popcll(__ballot(cl >= 0 && cl < P.num_cells_global));
+    }
+    a.wave_reduce();
+    if (lane == 0) { s_acc[wv] = a; s_live[wv] = live; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        PotAcc b = s_acc[0];
+        int n = s_live[0];
+        for (int w = 1; w < POT_WAVES; w++) { b.merge(s_acc[w]); n += s_live[w]; }
+        PotTile &r = tiles[t];
+        r.u = b.u; r.lo = b.lo; r.hi = b.hi; r.listed = b.listed; r.nonfinite = b.nonfinite;
+        tile_count[t] = n;
+    }
+}
+
+// Workgroup 0: U over the tiles in index order -- one serial fp64 chain, the tiles' partials through LDS a round of
+// POT_THREADS at a time (export.hip, export_finish) -- and the extrema and counts, which do not depend on the order.
+__device__ __forceinline__ void pot_finish(int ntiles, const PotTile *__restrict__ tiles, const int *__restrict__ tile_count,
+                                           psamd_potential_result *__restrict__ result_out, PotOut *__restrict__ own)
+{
+    __shared__ double s_u[POT_THREADS];
+    __shared__ PotAcc s_acc[POT_WAVES];
+    __shared__ long long s_live[POT_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    PotAcc a;
+    a.init();
+    long long live = 0;
+    double sum = 0.0;
+    for (int base = 0; base < ntiles; base += POT_THREADS) {
+        const int t = base + tid;
+        if (t < ntiles) {
+            const PotTile r = tiles[t];
+            s_u[tid] = r.u;
+            a.lo = fminf(a.lo, r.lo); a.hi = fmaxf(a.hi, r.hi); a.listed += r.listed; a.nonfinite += r.nonfinite;
+            live += tile_count[t];
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const int m = min(POT_THREADS, ntiles - base);
+            int j = 0;
+            for (; j + 8 <= m; j += 8) {               // eight reads in flight, then their adds in order
+                double x[8];
+#pragma unroll
+                for (int i = 0; i < 8; i++) x[i] = s_u[j + i];
+#pragma unroll
+                for (int i = 0; i < 8; i++) sum += x[i];
+            }
+            for (; j < m; j++) sum += s_u[j];
+        }
+        __syncthreads();
+    }
+    a.wave_reduce();
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) live += __shfl_xor(live, m);
+    if (lane == 0) { s_acc[wv] = a; s_live[wv] = live; }
+    __syncthreads();
+    if (tid == 0) {
+        long long listed = 0, nonfinite = 0, n = 0;
+        float lo = __int_as_float(0x7f800000), hi = -lo;
+        for (int w = 0; w < POT_WAVES; w++) {
+            listed += s_acc[w].listed; nonfinite += s_acc[w].nonfinite; n += s_live[w];
+            lo = fminf(lo, s_acc[w].lo); hi = fmaxf(hi, s_acc[w].hi);
+        }
+        psamd_potential_result r;
+        r.listed = listed; r.nonfinite = nonfinite; r.potential = sum; r.phi_min = (double)lo; r.phi_max = (double)hi;
+        own->result = r; own->live = n;
+        if (result_out) *result_out = r;
+    }
+}
+
+// Workgroup 1 + t: slot tile t of phi to export order (export.hip, k_export_write: the tile's offset from the tile
+// counts, a wave's from the four wave counts, a lane's from the ballot).
+__global__ __launch_bounds__(POT_THREADS) void k_pot_finish(DevParams P, int ntiles, const int *__restrict__ cell,
+                                                            const float *__restrict__ phi_slot,
+                                                            const PotTile *__restrict__ tiles, const int *__restrict__ tile_count,
+                                                            float *__restrict__ phi_out, int64_t capacity,
+                                                            psamd_potential_result *__restrict__ result_out, PotOut *__restrict__ own)
+{
+    if (blockIdx.x == 0) { pot_finish(ntiles, tiles, tile_count, result_out, own); return; }
+    __shared__ int s_before[POT_WAVES], s_live[POT_WAVES];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, t = blockIdx.x - 1;
+    int before = 0;
+    for (int i = threadIdx.x; i < t; i += POT_THREADS) before += tile_count[i];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) before += __shfl_xor(before, m);
+    const int first = t * POT_TILE + wv * 64 * POT_ITEMS + lane;
+    unsigned long long mask[POT_ITEMS];
+    int live = 0;
+#pragma unroll
+    for (int k = 0; k < POT_ITEMS; k++) {
+        const int i = first + 64 * k;
+        const int cl = i < P.slots_total ? cell[i] : -1;
+        mask[k] = __ballot(cl >= 0 && cl < P.num_cells_global);
+        live += __popcll(mask[k]);
+    }
+    if (lane == 0) { s_before[wv] = before; s_live[wv] = live; }
+    __syncthreads();
+    int64_t at = 0;
+    for (int w = 0; w < POT_WAVES; w++) at += s_before[w] + (w < wv ? s_live[w] : 0);
+    if (at >= capacity) return;
+#pragma unroll
+    for (int k = 0; k < POT_ITEMS; k++) {
+        const unsigned long long m = mask[k];
+        const int64_t o = at + (int64_t)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        at += __popcll(m);
+        if (((m >> lane) & 1ull) && o < capacity) phi_out[o] = phi_slot[first + 64 * k];
+    }
+}
+
+hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceState &d, float *phi, int64_t capacity,
+                            psamd_potential_result *result_dev)
+{
+    const int ntiles = pot_tiles(P.slots_total);
+    const bool want_phi = phi && capacity > 0 && ntiles > 0;
+    // a live particle that is in no list of the frame keeps this quiet NaN
+    if (want_phi) { const hipError_t e = launch_fill_int(st, reinterpret_cast<int *>(d.pot_slot), 0x7fc00000, (size_t)P.slots_total); if (e != hipSuccess) return e; }
+    const int ntask = P.n_own_cells * P.slices;
+    if (ntask > 0) {
+        if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
+            // the own snapshot (cells by local == global index) or the gathered one with its index by global cell
+            const bool gathered = P.world > 1;
+            const PotFar far{gathered ? reinterpret_cast<const float *>(d.allg_in) : d.snap_soa, gathered ? d.gstart : d.cell_start,
+                             gathered ? d.gn : nullptr, gathered ? (unsigned long long)P.allg_cap : (unsigned long long)P.sorted_cap,
+                             gathered ? 0 : 1};
+            k_pot_pairs<true><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, far, d.pot_sorted);
+        } else
+            k_pot_pairs<false><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, PotFar{}, d.pot_sorted);
+        PS_LAUNCH_CHECK();
+    }
+    if (ntiles > 0) {
+        k_pot_reduce<<<ntiles, POT_THREADS, 0, st>>>(P, d.cell_start, d.sorted_id, d.snap_soa, d.pot_sorted, d.cell,
+                                                     want_phi ? d.pot_slot : nullptr, d.pot_tiles, d.pot_count);
+        PS_LAUNCH_CHECK();
+    }
+    k_pot_finish<<<want_phi ? ntiles + 1 : 1, POT_THREADS, 0, st>>>(P, ntiles, d.cell, d.pot_slot, d.pot_tiles, d.pot_count, phi, capacity,
+                                                                    result_dev, d.pot_out);
+    PS_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+}  // namespace psamd

@@ -205,6 +205,29 @@ typedef struct psamd_inject_spec {
     psamd_inject_result *result_dev;   /* optional out (device); NULL: the context's own record only         */
 } psamd_inject_spec;
 
+/* What psamd_remove did (see "taking particles out" below). */
+#define PSAMD_REMOVE_BOX     0x1u   /* the candidates are the live particles inside [lo, hi), not an id list          */
+#define PSAMD_REMOVE_OUTSIDE 0x2u   /* with BOX only: the live particles NOT inside                                    */
+typedef struct psamd_remove_result {
+    int64_t done;             /* by id: n; by box: live owned particles examined                              */
+    int64_t removed;          /* particles reset (outcomes 0 and 4)                                           */
+    int64_t not_live, foreign, invalid;   /* by id: entries with the outcomes 1, 2, 3; by box: 0              */
+    int64_t dropped;          /* of `removed`, slots a full queue did not take (outcome 4)                    */
+} psamd_remove_result;        /* 48 bytes */
+
+/* What psamd_remove reads and where it writes (device pointers). */
+typedef struct psamd_remove_spec {
+    uint32_t flags;           /* 0: by id; PSAMD_REMOVE_BOX [| PSAMD_REMOVE_OUTSIDE]: by box                  */
+    int32_t  reserved;        /* 0                                                                            */
+    const int32_t *ids;       /* by id: int32[max_count] slot ids, 4-byte aligned; required if max_count > 0  */
+    int64_t  max_count;       /* by id: entries the arrays hold; sizes the launches; 0 <= max_count < 2^31    */
+    const int64_t *count_dev; /* by id, optional device int64: n = clamp(*count_dev, 0, max_count), read by
+                                 the kernels; NULL: n = max_count                                             */
+    int32_t *outcome_dev;     /* by id, optional out, int32[max_count]: every entry's outcome code            */
+    float    lo[3], hi[3];    /* by box: inside is lo.x <= x < hi.x, and likewise y and z, in fp32            */
+    psamd_remove_result *result_dev;   /* optional out (device), 8-byte aligned; NULL: the context's own record only */
+} psamd_remove_spec;          /* 72 bytes */
+
 /* What psamd_potential found (see "energy" below). */
 typedef struct psamd_potential_result {
     int64_t listed;           /* particles phi was formed for                                                 */
@@ -502,6 +525,56 @@ int psamd_live_stats_get(psamd_ctx *ctx, psamd_live_stats *out);
  * psamd_inject_result_get: the last inject's record, into host memory; waits for the context's stream. */
 int psamd_inject(psamd_ctx *ctx, const psamd_inject_spec *spec);
 int psamd_inject_result_get(psamd_ctx *ctx, psamd_inject_result *out);
+
+/* ---- taking particles out -------------------------------------------------- */
+/* psamd_remove: the device-side, stream-ordered counterpart of the reference's kill (reset_particle, then q_insert of
+ * the slot id into the queue of the slot's own segment: ps.cpp:1210-1242).  A set of candidate slots is processed in a
+ * defined serial order.  A candidate whose slot is live at its turn (0 <= cell < num_cells, what psamd_live_count counts)
+ * is removed: the slot becomes a free slot's record (cell -1, position, velocity, acceleration and flags zero) and its id
+ * goes to the rear of the queue of the segment the SLOT belongs to (get_id_info of the id, not the particle's cell),
+ * exactly as q_insert does it: an empty record restarts at front = rear = rloc whatever the two held, rear wraps from
+ * rloc + seg_size - 1 to rloc, and a record with count == seg_size takes nothing -- the particle is reset all the same
+ * and counts in `dropped` (the cell-overflow rule frees foreign slots into record 0, so a queue can be full while one of
+ * its slots is live).  After the call psamd_download_particles and psamd_download_queues return, byte for byte, what the
+ * reference's serial reset + q_insert over the same candidates leave, and the steps that follow stay equal.  T_DATA
+ * mirror rows are not touched (the reference's reset does not touch them either).
+ *
+ * By id (flags == 0): the candidates are the entries [0, n) of `ids`, in entry order.  Every entry gets an outcome,
+ * written to outcome_dev if given:
+ *     0  removed
+ *     1  the slot is not live at the entry's turn -- a free slot, and the second and later occurrences of a
+ *        duplicated id (that is the whole duplicate rule)
+ *     2  a valid id whose slot this context does not own (a slab is given all entries and removes its own)
+ *     3  an id outside [0, container_size)
+ *     4  removed, but the full queue did not take the slot
+ * By box (PSAMD_REMOVE_BOX): the candidates are the live owned particles with lo.x <= x < hi.x, and likewise y and z
+ * (fp32 comparisons: a coordinate that is not a number is not inside), or with PSAMD_REMOVE_OUTSIDE those that are
+ * not inside, in ascending global slot id: what by id does when given the ids of a psamd_export_live filtered by the
+ * same predicate.  ids, count_dev and outcome_dev must be NULL and max_count 0; the launches cover every owned slot.
+ * In a world larger than 1 the ranks' results add, and the union of the ranks' states is the state of one context
+ * given the same call.
+ *
+ * Everything is enqueued on the context's stream (psamd_get_stream): nothing waits and nothing is read back.  Scratch
+ * for the entries is allocated when max_count exceeds what an earlier call allocated for (that growth may wait for the
+ * device); steady use neither allocates nor waits.  Like psamd_inject, the call ends a frame in progress
+ * (psamd_calc_forces refuses with PSAMD_ERR_STATE until psamd_build_grid runs again) and is refused while the context's
+ * stream is being captured (PSAMD_ERR_STATE: a replayed graph would bypass that bookkeeping).  The host's bound of the
+ * live count stays as it is: it is an upper bound.  The call returns PSAMD_OK once the work is enqueued; only the
+ * result record reports what happened.
+ *
+ * Cost on an MI355X at N = 2^20 (profiles/remove_cost.txt): 61 us by id for 65 536 live ids, 45 us by box
+ * for as many; the host route (download_particles, download_queues, edit, two uploads) takes 156 ms there, 41 ms of it
+ * in the four transfers.
+ *
+ * PSAMD_ERR_INVALID_ARG: a NULL context or spec, unknown flag bits, OUTSIDE without BOX, reserved != 0, max_count
+ * outside [0, 2^31), by id ids NULL with max_count > 0, ids or outcome_dev not 4-byte aligned, count_dev or result_dev
+ * not 8-byte aligned, by box any of ids / count_dev / outcome_dev set or max_count != 0.  PSAMD_ERR_STATE: the context
+ * is wedged, or its stream is being captured.  By id with max_count == 0 the call writes a zero result and launches
+ * nothing else.
+ *
+ * psamd_remove_result_get: the last remove's record, into host memory; waits for the context's stream. */
+int psamd_remove(psamd_ctx *ctx, const psamd_remove_spec *spec);
+int psamd_remove_result_get(psamd_ctx *ctx, psamd_remove_result *out);
 
 /* ---- energy ------------------------------------------------------------------ */
 /* The potential of every particle in the frame's cell lists, and the potential energy, formed on the device from what

@@ -148,6 +148,33 @@ class Inject(C.Structure):
                 ("result_dev", C.c_void_p)]
 
 
+# psamd_remove: the flags, and the outcome codes of the entries of a removal by id
+REMOVE_BOX, REMOVE_OUTSIDE = 0x1, 0x2
+REMOVED, REMOVE_NOT_LIVE, REMOVE_FOREIGN, REMOVE_INVALID, REMOVE_DROPPED = 0, 1, 2, 3, 4
+
+
+class RemoveResult(C.Structure):
+    """psamd_remove_result: what psamd_remove did."""
+    _fields_ = [(n, C.c_int64) for n in ("done", "removed", "not_live", "foreign", "invalid", "dropped")]
+
+    def to_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class Remove(C.Structure):
+    """psamd_remove_spec: what psamd_remove reads and where it writes (device pointers)."""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_int32), ("ids", C.c_void_p), ("max_count", C.c_int64),
+                ("count_dev", C.c_void_p), ("outcome_dev", C.c_void_p), ("lo", C.c_float * 3), ("hi", C.c_float * 3),
+                ("result_dev", C.c_void_p)]
+
+
+def merge_remove(results):
+    """The result of a removal on a system from its ranks' (dicts of remove() / remove_result()): every count adds (by id
+    each rank is given all entries, so `done` adds up to world * n)."""
+    results = list(results)
+    return {n: sum(int(r[n]) for r in results) for n, _ in RemoveResult._fields_}
+
+
 class PotentialResult(C.Structure):
     """psamd_potential_result: counts, the potential energy U and the extrema of phi."""
     _fields_ = [("listed", C.c_int64), ("nonfinite", C.c_int64), ("potential", C.c_double),
@@ -266,6 +293,8 @@ ABI = [
     ("psamd_live_stats_get", C.c_int, [_vp, C.POINTER(LiveStats)]),
     ("psamd_inject", C.c_int, [_vp, C.POINTER(Inject)]),
     ("psamd_inject_result_get", C.c_int, [_vp, C.POINTER(InjectResult)]),
+    ("psamd_remove", C.c_int, [_vp, C.POINTER(Remove)]),
+    ("psamd_remove_result_get", C.c_int, [_vp, C.POINTER(RemoveResult)]),
     ("psamd_potential", C.c_int, [_vp, C.POINTER(Potential)]),
     ("psamd_potential_result_get", C.c_int, [_vp, C.POINTER(PotentialResult)]),
     ("psamd_download_potential", C.c_int, [_vp, _vp, _i64, C.POINTER(PotentialResult)]),
@@ -662,6 +691,50 @@ class ParticleSystem:
         """psamd_inject_result_get: the last inject's {"done", "placed", "status"}"""
         r = InjectResult()
         self._ck(self.lib.psamd_inject_result_get(self.h, C.byref(r)))
+        return r.to_dict()
+
+    # ---- taking particles out (include/psamd.h) ---------------------------------
+    def remove(self, ids=None, count=None, box=None, outside=False, outcome=False):
+        """psamd_remove.  By id: ids is an int32 [m] torch device tensor of slot ids, count None (all m entries) or a
+        1-element int64 device tensor that work on torch's current stream may write just before; with outcome=True the
+        result has "outcome": an int32 device tensor of m entries (the codes REMOVED .. REMOVE_DROPPED).  By box:
+        box=(lo, hi), two triples; outside=True removes the live particles that are NOT inside.  Returns the result
+        record as a dict (done, removed, not_live, foreign, invalid, dropped).  Waits for the context's stream.  torch must
+        have been imported before the library was loaded."""
+        import torch
+        dev = torch.device("cuda", int(self.cfg.device))
+        spec = Remove()
+        out = None
+        if box is not None:
+            assert ids is None and count is None and not outcome, "remove: by box takes no ids, count or outcome"
+            spec.flags = REMOVE_BOX | (REMOVE_OUTSIDE if outside else 0)
+            for k in range(3):
+                spec.lo[k], spec.hi[k] = float(box[0][k]), float(box[1][k])
+        else:
+            assert ids is not None and not outside, "remove: ids or box"
+            m = int(ids.shape[0])
+            assert ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous() and ids.is_cuda, "remove: bad ids tensor"
+            spec.max_count = m
+            spec.ids = ids.data_ptr() if m > 0 else None
+            if count is not None:
+                assert count.dtype == torch.int64 and tuple(count.shape) == (1,) and count.is_cuda, "remove: bad count tensor"
+                spec.count_dev = count.data_ptr()
+            if outcome:
+                out = torch.full((max(m, 1),), -1, dtype=torch.int32, device=dev)
+                spec.outcome_dev = out.data_ptr()
+        st = torch.cuda.ExternalStream(self.stream(), device=dev)
+        st.wait_stream(torch.cuda.current_stream(dev))        # (the inputs are written on torch's stream)
+        self._ck(self.lib.psamd_remove(self.h, C.byref(spec)))
+        st.synchronize()
+        res = self.remove_result()
+        if out is not None:
+            res["outcome"] = out[:int(ids.shape[0])]
+        return res
+
+    def remove_result(self):
+        """psamd_remove_result_get: the last remove's record as a dict"""
+        r = RemoveResult()
+        self._ck(self.lib.psamd_remove_result_get(self.h, C.byref(r)))
         return r.to_dict()
 
     # ---- energy (include/psamd.h) -----------------------------------------------

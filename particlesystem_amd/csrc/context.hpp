@@ -88,6 +88,8 @@ struct psamd_ctx {
     std::map<int, int64_t> inject_tally;
     InjectScratch inj{};              // its scratch: ent / tcount / tile_out grow with max_count (inj_cap), the rest is fixed
     int64_t inj_cap = 0;
+    RemoveScratch rem{};              // psamd_remove's scratch: ent / tcount / tile_out grow with max_count (rem_cap), the rest is fixed
+    int64_t rem_cap = 0;
     // timing
     int timing = 0;                    // 0 off, 1 pair pass / apply / life cycle, 2 every stage
     int timing_period = 1;             // events are recorded on every timing_period-th step since set_timing

@@ -308,6 +308,13 @@ static int alloc_step_arrays(psamd_ctx *c)
     PS_HIP(c, dev_alloc(c, &c->inj.hdr, 2));
     PS_HIP(c, dev_alloc(c, &c->inj.own, 1));
     PS_HIP(c, hipMemsetAsync(c->inj.own, 0, sizeof(psamd_inject_result), c->stream));
+    PS_HIP(c, dev_alloc(c, &c->rem.claim, C));                          // psamd_remove's fixed scratch and result record
+    PS_HIP(c, dev_alloc(c, &c->rem.ins, (size_t)g.queue_infos));
+    PS_HIP(c, dev_alloc(c, &c->rem.prefix, C + 1));
+    PS_HIP(c, dev_alloc(c, &c->rem.tile_sel, (size_t)remove_tiles(P.slots_total)));
+    PS_HIP(c, dev_alloc(c, &c->rem.tile_live, (size_t)remove_tiles(P.slots_total)));
+    PS_HIP(c, dev_alloc(c, &c->rem.own, 1));
+    PS_HIP(c, hipMemsetAsync(c->rem.own, 0, sizeof(psamd_remove_result), c->stream));
     PS_HIP(c, dev_alloc(c, &d.trace, 3 * (LC * P.slices + 4)));
     PS_HIP(c, hipMemsetAsync(d.trace, 0, 3 * (LC * P.slices + 4) * sizeof(unsigned long long), c->stream));
     return PSAMD_OK;
@@ -445,6 +452,7 @@ static int init_state(psamd_ctx *c)
     PS_HIP(c, hipMemsetAsync(d.cell_count, 0, c->frame_ints * sizeof(int), c->stream));     // (the frame's counts: one allocation)
     PS_HIP(c, hipMemsetAsync(d.cell_start, 0, (LC + 1) * sizeof(int), c->stream));
     PS_HIP(c, launch_fill_int(c->stream, d.cell, -1, C));
+    PS_HIP(c, launch_fill_int(c->stream, c->rem.claim, INT32_MAX, C));      // psamd_remove: no slot is claimed between calls
     PS_HIP(c, launch_init_tdata(c->stream, P, d));
     // q_start_fast (ps.cpp:814-871) and the cell table
     g.initial_queues(c->h_qinfo, c->h_queue);
@@ -508,6 +516,7 @@ int psamd_destroy(psamd_ctx *c)
     for (void *p : c->allocs) (void)hipFree(p);
     if (c->staging) (void)hipFree(c->staging);
     for (void *p : {(void *)c->inj.ent, (void *)c->inj.tcount, (void *)c->inj.tile_out}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->rem.ent, (void *)c->rem.tcount, (void *)c->rem.tile_out}) if (p) (void)hipFree(p);
     if (c->h_fs) (void)hipHostFree(c->h_fs);
     if (c->ev_made) for (auto &set : c->ev) for (auto &e : set) (void)hipEventDestroy(e);
     if (c->d.ev_fork) (void)hipEventDestroy(c->d.ev_fork);

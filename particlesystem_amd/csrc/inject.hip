@@ -5,9 +5,8 @@
 // entries by queue record, then the closed-form FIFO removal (the k-th remove of a record takes logical element k, as
 // k_replay_commit does), in five launches ordered by the launch boundaries only (no hand-off between workgroups):
 //   k_inject_locate  one workgroup per tile of INJECT_TILE entries: Geometry::locate in fp64, the segment record, the
-//                    ownership rule; the tile's per-record counts and every entry's stable rank inside the tile (the 16
-//                    waves take turns in entry order; inside a wave ballot + mbcnt per distinct record); the tile's
-//                    first entry outside the box
+//                    ownership rule; the tile's per-record counts and every entry's stable rank inside the tile
+//                    (multisplit.hpp, shared with remove.hip); the tile's first entry outside the box
 //   k_inject_scan    one workgroup: per record, the exclusive prefix of the tile counts (in place) and the first
 //                    outside entry of all tiles
 //   k_inject_fail    per entry: its rank k among the earlier entries of its record; k == the queue's count is the
@@ -17,14 +16,13 @@
 //   k_inject_commit  one workgroup: front / count / rear as host_q_remove leaves them, and the result record
 // The kernels touch the entries, the scratch, the queues and the slots they hand out: nothing a step in flight owns
 // (stream order puts them between steps).
-#include "kernels_common.hpp"
+#include "multisplit.hpp"
 
 #include <climits>
 
 namespace psamd {
 
-constexpr int INJECT_THREADS = 1024;          // k_inject_locate: 16 waves, 4 groups of 64 entries each
-constexpr int INJECT_WAVES = INJECT_THREADS / 64;
+constexpr int INJECT_THREADS = SPLIT_THREADS;  // k_inject_locate: 16 waves, 4 groups of 64 entries each (multisplit.hpp)
 constexpr int INJECT_GROUPS = INJECT_TILE / INJECT_THREADS;
 static_assert(INJECT_GROUPS * INJECT_THREADS == INJECT_TILE, "a wave ranks INJECT_GROUPS consecutive groups of 64 entries");
 constexpr int INJECT_LDS_RECORDS = 8192;      // records counted in LDS (32 KB); more: in the tile's row in global memory
@@ -86,37 +84,13 @@ __global__ void __launch_bounds__(INJECT_THREADS) k_inject_locate(DevParams P, S
                 r = owns_record(P, sr) ? sr : INJ_NOT_MINE;
             }
         }
-        rec[g] = r; in_rank[g] = 0; pop[g] = 0; lead[g] = lane;
-        unsigned long long todo = __ballot(r >= 0);
-        while (todo) {
-            const int l = __ffsll((long long)todo) - 1;
-            const int r0 = __builtin_amdgcn_readlane(r, l);
-            const unsigned long long m = __ballot(r == r0);
-            if (r == r0) {
-                in_rank[g] = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-                pop[g] = __popcll(m);
-                lead[g] = l;
-            }
-            todo &= ~m;
-        }
+        rec[g] = r;
+        split_group_rank(r, lane, in_rank[g], pop[g], lead[g]);
     }
     if (first_out != INT_MAX) atomicMin(&s_first_out, first_out);
 
-    // the waves take turns in entry order; a group's lowest lane of each record takes the record's running count
-    // (leaders of one group hold distinct records; a wave's groups follow one another)
     int at[INJECT_GROUPS];
-    for (int w = 0; w < INJECT_WAVES; w++) {
-        if (wave == w) {
-#pragma unroll
-            for (int g = 0; g < INJECT_GROUPS; g++) {
-                int b = 0;
-                if (rec[g] >= 0 && lead[g] == lane) b = atomicAdd(&cnt[rec[g]], pop[g]);
-                at[g] = __shfl(b, lead[g]) + in_rank[g];
-            }
-        }
-        if (!LDS) __threadfence();
-        __syncthreads();
-    }
+    split_take_turns<INJECT_GROUPS, !LDS>(rec, in_rank, pop, lead, cnt, wave, lane, at);
 #pragma unroll
     for (int g = 0; g < INJECT_GROUPS; g++) {
         const int i = base + (wave * INJECT_GROUPS + g) * 64 + lane;
@@ -140,13 +114,7 @@ __global__ void __launch_bounds__(1024) k_inject_scan(int nrec, int64_t max_coun
     for (int t = tid; t < tiles; t += 1024) m = min(m, tile_out[t]);
     if (m != INT_MAX) atomicMin(&s_min, m);
     for (int r = tid; r < nrec; r += 1024) {
-        int run = 0;
-        for (int t = 0; t < tiles; t++) {
-            int *p = tcount + (size_t)t * nrec + r;
-            const int c = *p;
-            *p = run;
-            run += c;
-        }
+        (void)split_tile_prefix(tcount, nrec, tiles, r);
         removed[r] = 0;
     }
     __syncthreads();

@@ -556,6 +556,71 @@ int psamd_inject_result_get(psamd_ctx *c, psamd_inject_result *out)
     return PSAMD_OK;
 }
 
+// ---- taking particles out (remove.hip) ----
+// the entries' scratch for max_count entries: grows only, like inject's
+static int remove_scratch(psamd_ctx *c, int64_t max_count)
+{
+    if (max_count <= c->rem_cap) return PSAMD_OK;
+    for (void *p : {(void *)c->rem.ent, (void *)c->rem.tcount, (void *)c->rem.tile_out}) if (p) PS_HIP(c, hipFree(p));
+    c->rem.ent = nullptr; c->rem.tcount = nullptr; c->rem.tile_out = nullptr;
+    c->rem_cap = 0;
+    const int64_t tiles = (max_count + REMOVE_TILE - 1) / REMOVE_TILE;
+    PS_HIP(c, hipMalloc((void **)&c->rem.ent, (size_t)(tiles * REMOVE_TILE) * sizeof(int2)));
+    PS_HIP(c, hipMalloc((void **)&c->rem.tcount, (size_t)tiles * (size_t)c->geo.queue_infos * sizeof(int)));
+    PS_HIP(c, hipMalloc((void **)&c->rem.tile_out, (size_t)tiles * 3 * sizeof(int)));
+    c->rem_cap = tiles * REMOVE_TILE;
+    return PSAMD_OK;
+}
+
+int psamd_remove(psamd_ctx *c, const psamd_remove_spec *spec)
+{
+    if (!c || !spec) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    const bool box = (spec->flags & PSAMD_REMOVE_BOX) != 0;
+    if ((spec->flags & ~(PSAMD_REMOVE_BOX | PSAMD_REMOVE_OUTSIDE)) || (!box && (spec->flags & PSAMD_REMOVE_OUTSIDE)) || spec->reserved != 0)
+        return fail(c, PSAMD_ERR_INVALID_ARG, "remove: unknown flag bits, OUTSIDE without BOX, or reserved not 0");
+    if (spec->max_count < 0 || spec->max_count > INT32_MAX) return fail(c, PSAMD_ERR_INVALID_ARG, "remove: max_count outside [0, 2^31)");
+    if (!aligned(spec->ids, 4) || !aligned(spec->outcome_dev, 4) || !aligned(spec->count_dev, 8) || !aligned(spec->result_dev, 8))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "remove: an array misaligned");
+    if (box && (spec->ids || spec->count_dev || spec->outcome_dev || spec->max_count != 0))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "remove: by box, ids, count_dev and outcome_dev must be NULL and max_count 0");
+    if (!box && !spec->ids && spec->max_count > 0) return fail(c, PSAMD_ERR_INVALID_ARG, "remove: ids missing");
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    PS_HIP(c, hipStreamIsCapturing(c->stream, &cs));
+    if (cs != hipStreamCaptureStatusNone)
+        return fail(c, PSAMD_ERR_STATE, "remove: the context's stream is being captured (the call ends the host's frame in "
+                                        "progress: a replay would bypass that)");
+    psamd_remove_result *res = spec->result_dev ? spec->result_dev : c->rem.own;
+    if (!box && spec->max_count == 0) {
+        PS_HIP(c, hipMemsetAsync(c->rem.own, 0, sizeof(psamd_remove_result), c->stream));
+        if (res != c->rem.own) PS_HIP(c, hipMemsetAsync(res, 0, sizeof(psamd_remove_result), c->stream));
+        return PSAMD_OK;
+    }
+    if (box) {
+        PS_HIP(c, launch_remove_box(c->stream, c->P, c->S, c->d, c->geo.queue_infos, spec->lo, spec->hi,
+                                    (spec->flags & PSAMD_REMOVE_OUTSIDE) != 0, res, c->rem));
+    } else {
+        const int rc = remove_scratch(c, spec->max_count);
+        if (rc != PSAMD_OK) return rc;
+        const RemoveArgs a{spec->ids, spec->max_count, spec->count_dev, spec->outcome_dev, res};
+        PS_HIP(c, launch_remove_ids(c->stream, c->P, c->S, c->d, c->geo.queue_infos, a, c->rem));
+    }
+    // inject's transitions; the device's queues are ahead of the host's mirror.  The host's bound of the live count stays:
+    // it is an upper bound.
+    c->host_queues_valid = false;
+    c->grid_built = false; c->pairs_done = false; c->slab_stage = 0;
+    return PSAMD_OK;
+}
+
+int psamd_remove_result_get(psamd_ctx *c, psamd_remove_result *out)
+{
+    if (!c || !out) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    PS_HIP(c, hipMemcpyAsync(out, c->rem.own, sizeof *out, hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    return PSAMD_OK;
+}
+
 // ---- energy (potential.hip) ----
 // a frame is built, its particles have not moved, and -- a slab -- the halos are in and nothing of the plan is lent
 static int potential_ready(psamd_ctx *c)

@@ -51,6 +51,28 @@ struct InjectScratch {
     psamd_inject_result *own;   // the context's own result record (psamd_inject_result_get)
 };
 
+// psamd_remove (remove.hip): by id, the entries in tiles of REMOVE_TILE (ranked like inject's: multisplit.hpp); by box, the
+// owned slots in tiles of REMOVE_TILE.  ent / tcount / tile_out grow with max_count (the host), the rest is sized at creation.
+constexpr int REMOVE_TILE = INJECT_TILE;
+inline int remove_tiles(int slots_total) { return (slots_total + REMOVE_TILE - 1) / REMOVE_TILE; }
+struct RemoveArgs {
+    const int *ids;
+    int64_t max_count;
+    const int64_t *count_dev;
+    int *outcome;
+    psamd_remove_result *result;
+};
+struct RemoveScratch {
+    int2 *ent;        // [max_count] per entry: the record of a slot's first live occurrence (else -1 - outcome) and its rank in the record
+    int *tcount;      // [tiles * nrec] per tile and record: the count, then the exclusive prefix over the tiles
+    int *tile_out;    // [tiles * 3] the tile's entries with the outcomes 1, 2, 3
+    int *claim;       // [slots] the lowest entry index that names the slot; INT_MAX between calls (a call restores what it claimed)
+    int2 *ins;        // [nrec] the insert rule of a record the call adds to: offset of its first insert behind rloc, inserts the queue takes
+    int *prefix;      // [slots + 1] by box: selected slots before this one in storage order
+    int *tile_sel, *tile_live;   // [tiles of slots] by box: the tile's selected / live slots
+    psamd_remove_result *own;    // the context's own result record (psamd_remove_result_get)
+};
+
 // psamd_potential (potential.hip): the sorted order of the own cells, and the owned slots, in tiles of POT_TILE; per tile of
 // the sorted order the partials of U (fp64), of phi's extrema and of the counts
 constexpr int POT_TILE = 4096;
@@ -227,5 +249,12 @@ hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceStat
 // the result record (max_count > 0)
 hipError_t launch_inject(hipStream_t st, const DevParams &P, const SegLayout &S, const DeviceState &d, int nrec, const InjectArgs &a,
                          const InjectScratch &s);
+
+// psamd_remove by id (max_count > 0): the first occurrences' claims, the entries' ranks, the records' commit and the result
+// record, the placement; by box: the tiles' counts, the slots' prefix, the commit, the placement (every owned slot)
+hipError_t launch_remove_ids(hipStream_t st, const DevParams &P, const SegLayout &S, const DeviceState &d, int nrec, const RemoveArgs &a,
+                             const RemoveScratch &s);
+hipError_t launch_remove_box(hipStream_t st, const DevParams &P, const SegLayout &S, const DeviceState &d, int nrec, const float lo[3],
+                             const float hi[3], bool outside, psamd_remove_result *result, const RemoveScratch &s);
 
 }  // namespace psamd

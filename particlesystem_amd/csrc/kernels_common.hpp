@@ -23,6 +23,7 @@
 //   slab.hip       the messages of a multi-GPU step: halo snapshots, force records, status records, all-pairs snapshot
 //   export.hip     not part of the step: psamd_export_live, the live particles as compact arrays and their statistics
 //   inject.hip     not part of the step: psamd_inject, particles from device arrays into their segments' free slots
+//   remove.hip     not part of the step: psamd_remove, particles out of their slots and the slots back into the queues
 //   potential.hip  not part of the step: psamd_potential, every listed particle's potential and the potential energy
 //
 // Reference arithmetic is reproduced operation for operation: every file is built with

@@ -10,6 +10,7 @@ Stage names follow the reference's task list (particleSystem.cpp:2269-2282):
 ``init_iframe`` (task 3), ``build_grid`` (task 8), ``calc_forces`` (task 6),
 ``fill_particles`` (task 5).
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -112,18 +113,29 @@ _EXPORT_FIELDS = (("pos4", EXPORT_POS, 4, np.float32), ("vel4", EXPORT_VEL, 4, n
                   ("id", EXPORT_ID, 1, np.int32), ("cell", EXPORT_CELL, 1, np.int32))
 
 
-class LiveStats(C.Structure):
-    """psamd_live_stats: count and fp64 statistics of the live particles."""
-    _fields_ = [("live", C.c_int64), ("nonfinite", C.c_int64), ("mass", C.c_double), ("momentum", C.c_double * 3),
-                ("kinetic", C.c_double), ("mass_moment", C.c_double * 3), ("lo", C.c_double * 3), ("hi", C.c_double * 3),
-                ("age_min", C.c_double), ("age_max", C.c_double), ("age_sum", C.c_double)]
+class _Record(C.Structure):
+    """A result record of the C header.  to_dict: every field but the reserved ones, an integer field as int, a double as
+    float, an array of doubles as a float64 array."""
 
     def to_dict(self):
         out = {}
         for n, t in self._fields_:
-            v = getattr(self, n)
-            out[n] = np.array(v[:], np.float64) if hasattr(t, "_length_") else v
+            if not n.startswith("reserved"):
+                v = getattr(self, n)
+                out[n] = np.array(v[:], np.float64) if hasattr(t, "_length_") else float(v) if t is C.c_double else int(v)
         return out
+
+    @classmethod
+    def from_device(cls, t):
+        """the record a service left in a uint8 torch device tensor of sizeof(cls) bytes"""
+        return cls.from_buffer_copy(t.cpu().numpy().tobytes())
+
+
+class LiveStats(_Record):
+    """psamd_live_stats: count and fp64 statistics of the live particles."""
+    _fields_ = [("live", C.c_int64), ("nonfinite", C.c_int64), ("mass", C.c_double), ("momentum", C.c_double * 3),
+                ("kinetic", C.c_double), ("mass_moment", C.c_double * 3), ("lo", C.c_double * 3), ("hi", C.c_double * 3),
+                ("age_min", C.c_double), ("age_max", C.c_double), ("age_sum", C.c_double)]
 
 
 class Export(C.Structure):
@@ -133,12 +145,9 @@ class Export(C.Structure):
                 ("capacity", C.c_int64), ("count_dev", C.c_void_p), ("stats_dev", C.c_void_p)]
 
 
-class InjectResult(C.Structure):
+class InjectResult(_Record):
     """psamd_inject_result: what psamd_inject did (done, placed, status)."""
     _fields_ = [("done", C.c_int64), ("placed", C.c_int64), ("status", C.c_int32), ("reserved", C.c_int32)]
-
-    def to_dict(self):
-        return {"done": int(self.done), "placed": int(self.placed), "status": int(self.status)}
 
 
 class Inject(C.Structure):
@@ -153,12 +162,9 @@ REMOVE_BOX, REMOVE_OUTSIDE = 0x1, 0x2
 REMOVED, REMOVE_NOT_LIVE, REMOVE_FOREIGN, REMOVE_INVALID, REMOVE_DROPPED = 0, 1, 2, 3, 4
 
 
-class RemoveResult(C.Structure):
+class RemoveResult(_Record):
     """psamd_remove_result: what psamd_remove did."""
     _fields_ = [(n, C.c_int64) for n in ("done", "removed", "not_live", "foreign", "invalid", "dropped")]
-
-    def to_dict(self):
-        return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
 
 class Remove(C.Structure):
@@ -175,14 +181,10 @@ def merge_remove(results):
     return {n: sum(int(r[n]) for r in results) for n, _ in RemoveResult._fields_}
 
 
-class PotentialResult(C.Structure):
+class PotentialResult(_Record):
     """psamd_potential_result: counts, the potential energy U and the extrema of phi."""
     _fields_ = [("listed", C.c_int64), ("nonfinite", C.c_int64), ("potential", C.c_double),
                 ("phi_min", C.c_double), ("phi_max", C.c_double)]
-
-    def to_dict(self):
-        return {"listed": int(self.listed), "nonfinite": int(self.nonfinite), "potential": float(self.potential),
-                "phi_min": float(self.phi_min), "phi_max": float(self.phi_max)}
 
 
 class Potential(C.Structure):
@@ -602,6 +604,16 @@ class ParticleSystem:
         self._ck(self.lib.psamd_get_stream(self.h, C.byref(p)))
         return p.value or 0
 
+    @contextlib.contextmanager
+    def _on_stream(self, dev):
+        """Calls enqueued inside follow what torch's current stream holds so far (the tensors they use are torch's: allocated,
+        maybe written, there); leaving waits for the context's stream."""
+        import torch
+        st = torch.cuda.ExternalStream(self.stream(), device=dev)
+        st.wait_stream(torch.cuda.current_stream(dev))
+        yield
+        st.synchronize()
+
     def owned_slots(self):
         """slots this context holds (the whole container on one context): the most live particles it can have"""
         return int(self.device_view().container_size)
@@ -625,14 +637,12 @@ class ParticleSystem:
         count = torch.zeros(1, dtype=torch.int64, device=dev)
         stats = torch.zeros(C.sizeof(LiveStats), dtype=torch.uint8, device=dev)
         spec.count_dev, spec.stats_dev = count.data_ptr(), stats.data_ptr()
-        st = torch.cuda.ExternalStream(self.stream(), device=dev)
-        st.wait_stream(torch.cuda.current_stream(dev))        # (the tensors are torch's: the export follows their allocation)
-        self._ck(self.lib.psamd_export_live(self.h, C.byref(spec)))
-        st.synchronize()
+        with self._on_stream(dev):
+            self._ck(self.lib.psamd_export_live(self.h, C.byref(spec)))
         n = int(count.item())
         res = {name: t[:min(n, capacity)] for name, t in out.items()}
         res["count"] = n
-        res["stats"] = LiveStats.from_buffer_copy(stats.cpu().numpy().tobytes()).to_dict()
+        res["stats"] = LiveStats.from_device(stats).to_dict()
         return res
 
     def download_live(self, fields, capacity=None):
@@ -678,10 +688,8 @@ class ParticleSystem:
         spec.count_dev = ptr(count, torch.int64, (1,))
         out_ids = torch.full((max(m, 1),), -1, dtype=torch.int32, device=dev) if ids else None
         spec.ids_dev = None if out_ids is None else out_ids.data_ptr()
-        st = torch.cuda.ExternalStream(self.stream(), device=dev)
-        st.wait_stream(torch.cuda.current_stream(dev))        # (the inputs are written on torch's stream)
-        self._ck(self.lib.psamd_inject(self.h, C.byref(spec)))
-        st.synchronize()
+        with self._on_stream(dev):
+            self._ck(self.lib.psamd_inject(self.h, C.byref(spec)))
         res = self.inject_result()
         if ids:
             res["ids"] = out_ids[:m]
@@ -722,10 +730,8 @@ class ParticleSystem:
             if outcome:
                 out = torch.full((max(m, 1),), -1, dtype=torch.int32, device=dev)
                 spec.outcome_dev = out.data_ptr()
-        st = torch.cuda.ExternalStream(self.stream(), device=dev)
-        st.wait_stream(torch.cuda.current_stream(dev))        # (the inputs are written on torch's stream)
-        self._ck(self.lib.psamd_remove(self.h, C.byref(spec)))
-        st.synchronize()
+        with self._on_stream(dev):
+            self._ck(self.lib.psamd_remove(self.h, C.byref(spec)))
         res = self.remove_result()
         if out is not None:
             res["outcome"] = out[:int(ids.shape[0])]
@@ -754,13 +760,11 @@ class ParticleSystem:
             out = torch.empty(max(capacity, 1), dtype=torch.float32, device=dev)
             count = torch.zeros(1, dtype=torch.int64, device=dev)
             spec.phi, spec.capacity = out.data_ptr(), capacity
-        st = torch.cuda.ExternalStream(self.stream(), device=dev)
-        st.wait_stream(torch.cuda.current_stream(dev))        # (the tensors are torch's: the pass follows their allocation)
-        self._ck(self.lib.psamd_potential(self.h, C.byref(spec)))
-        if phi:      # how many entries were written: the live count at this point of the stream
-            self._ck(self.lib.psamd_export_live(self.h, C.byref(Export(fields=0, capacity=0, count_dev=count.data_ptr()))))
-        st.synchronize()
-        res = PotentialResult.from_buffer_copy(result.cpu().numpy().tobytes()).to_dict()
+        with self._on_stream(dev):
+            self._ck(self.lib.psamd_potential(self.h, C.byref(spec)))
+            if phi:      # how many entries were written: the live count at this point of the stream
+                self._ck(self.lib.psamd_export_live(self.h, C.byref(Export(fields=0, capacity=0, count_dev=count.data_ptr()))))
+        res = PotentialResult.from_device(result).to_dict()
         if phi:
             res["phi"] = out[:min(int(count.item()), capacity)]
         return res

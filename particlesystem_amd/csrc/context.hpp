@@ -1,4 +1,4 @@
-// context.hpp -- the psamd context and what the host units share (create.hip, step.hip, io.hip).
+// context.hpp -- the psamd context and what the host units share (create.hip, step.hip, io.hip, services.hip).
 //
 // Host side of the drop-in boundary, C++ like the reference's host code.  It mirrors
 // the reference driver's view of the path: nine buffers (ps.cpp:70-78), one-off setup
@@ -86,10 +86,8 @@ struct psamd_ctx {
     // psamd_inject: max_count of the injects enqueued after step k (key k = scalars_seq at the call), until the record
     // of step k + 1 -- the first that counts them -- has been read
     std::map<int, int64_t> inject_tally;
-    InjectScratch inj{};              // its scratch: ent / tcount / tile_out grow with max_count (inj_cap), the rest is fixed
-    int64_t inj_cap = 0;
-    RemoveScratch rem{};              // psamd_remove's scratch: ent / tcount / tile_out grow with max_count (rem_cap), the rest is fixed
-    int64_t rem_cap = 0;
+    InjectScratch inj{};              // its scratch: inj.e grows with max_count, the rest is fixed
+    RemoveScratch rem{};              // psamd_remove's scratch: rem.e grows with max_count, the rest is fixed
     // timing
     int timing = 0;                    // 0 off, 1 pair pass / apply / life cycle, 2 every stage
     int timing_period = 1;             // events are recorded on every timing_period-th step since set_timing
@@ -144,6 +142,7 @@ inline int hip_fail(psamd_ctx *c, hipError_t e, const char *what)
 }
 
 #define PS_HIP(c, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return hip_fail((c), e_, #call); } while (0)
+#define PS_TRY(call) do { const int rc_ = (call); if (rc_ != PSAMD_OK) return rc_; } while (0)     // a status passed up
 
 template <typename T>
 hipError_t dev_alloc(psamd_ctx *c, T **out, size_t n)
@@ -169,6 +168,8 @@ int push_queues(psamd_ctx *c);                      // ... host mirror -> device
 int check_device_errors(psamd_ctx *c);              // step.hip: after a sync, the sticky error bits raised by kernels
 int drain_scalars(psamd_ctx *c, bool quiet = false);
 int refuse_wedged(psamd_ctx *c);
+int ensure_staging(psamd_ctx *c, size_t bytes);     // io.hip: the device staging buffer holds at least so many bytes
+void end_frame(psamd_ctx *c);                       // services.hip: the slots or queues changed under the host's frame
 void drop_graphs(psamd_ctx *c);
 
 }  // namespace psamd

@@ -295,13 +295,13 @@ static int alloc_step_arrays(psamd_ctx *c)
     PS_HIP(c, dev_alloc(c, &d.moves, (size_t)d.moves_cap));
     PS_HIP(c, dev_alloc(c, &d.stage, 3 * (size_t)d.moves_cap));
     PS_HIP(c, dev_alloc(c, &d.ctr, (size_t)COUNTER_COPIES));
-    PS_HIP(c, dev_alloc(c, &d.exp_count, (size_t)export_tiles(P.slots_total)));     // psamd_export_live's scratch
-    PS_HIP(c, dev_alloc(c, &d.exp_tiles, (size_t)export_tiles(P.slots_total)));
+    PS_HIP(c, dev_alloc(c, &d.exp_count, (size_t)slot_tiles(P.slots_total)));     // psamd_export_live's scratch
+    PS_HIP(c, dev_alloc(c, &d.exp_tiles, (size_t)slot_tiles(P.slots_total)));
     PS_HIP(c, dev_alloc(c, &d.exp_out, 1));
     PS_HIP(c, dev_alloc(c, &d.pot_sorted, SC));                                      // psamd_potential's scratch and result record
     PS_HIP(c, dev_alloc(c, &d.pot_slot, C));
-    PS_HIP(c, dev_alloc(c, &d.pot_tiles, (size_t)pot_tiles(P.slots_total)));
-    PS_HIP(c, dev_alloc(c, &d.pot_count, (size_t)pot_tiles(P.slots_total)));
+    PS_HIP(c, dev_alloc(c, &d.pot_tiles, (size_t)slot_tiles(P.slots_total)));
+    PS_HIP(c, dev_alloc(c, &d.pot_count, (size_t)slot_tiles(P.slots_total)));
     PS_HIP(c, dev_alloc(c, &d.pot_out, 1));
     PS_HIP(c, hipMemsetAsync(d.pot_out, 0, sizeof(PotOut), c->stream));
     PS_HIP(c, dev_alloc(c, &c->inj.removed, (size_t)g.queue_infos));    // psamd_inject's fixed scratch and result record
@@ -311,8 +311,8 @@ static int alloc_step_arrays(psamd_ctx *c)
     PS_HIP(c, dev_alloc(c, &c->rem.claim, C));                          // psamd_remove's fixed scratch and result record
     PS_HIP(c, dev_alloc(c, &c->rem.ins, (size_t)g.queue_infos));
     PS_HIP(c, dev_alloc(c, &c->rem.prefix, C + 1));
-    PS_HIP(c, dev_alloc(c, &c->rem.tile_sel, (size_t)remove_tiles(P.slots_total)));
-    PS_HIP(c, dev_alloc(c, &c->rem.tile_live, (size_t)remove_tiles(P.slots_total)));
+    PS_HIP(c, dev_alloc(c, &c->rem.tile_sel, (size_t)slot_tiles(P.slots_total)));
+    PS_HIP(c, dev_alloc(c, &c->rem.tile_live, (size_t)slot_tiles(P.slots_total)));
     PS_HIP(c, dev_alloc(c, &c->rem.own, 1));
     PS_HIP(c, hipMemsetAsync(c->rem.own, 0, sizeof(psamd_remove_result), c->stream));
     PS_HIP(c, dev_alloc(c, &d.trace, 3 * (LC * P.slices + 4)));
@@ -515,8 +515,8 @@ int psamd_destroy(psamd_ctx *c)
     drop_graphs(c);
     for (void *p : c->allocs) (void)hipFree(p);
     if (c->staging) (void)hipFree(c->staging);
-    for (void *p : {(void *)c->inj.ent, (void *)c->inj.tcount, (void *)c->inj.tile_out}) if (p) (void)hipFree(p);
-    for (void *p : {(void *)c->rem.ent, (void *)c->rem.tcount, (void *)c->rem.tile_out}) if (p) (void)hipFree(p);
+    for (const EntryScratch &e : {c->inj.e, c->rem.e})
+        for (void *p : {(void *)e.ent, (void *)e.tcount, (void *)e.tile_out}) if (p) (void)hipFree(p);
     if (c->h_fs) (void)hipHostFree(c->h_fs);
     if (c->ev_made) for (auto &set : c->ev) for (auto &e : set) (void)hipEventDestroy(e);
     if (c->d.ev_fork) (void)hipEventDestroy(c->d.ev_fork);

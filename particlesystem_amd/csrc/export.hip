@@ -2,32 +2,25 @@
 //
 // A deterministic stream compaction of the owned slots in slot order, plus a deterministic reduction over the same
 // particles, in two launches that nothing in between has to wait for:
-//   k_export_count  pass A, one workgroup per tile of EXPORT_TILE owned slots: the tile's live count (wave64 ballot +
+//   k_export_count  pass A, one workgroup per tile of SLOT_TILE owned slots: the tile's live count (wave64 ballot +
 //                   popcount) and its statistics partials (fp64 sums, fp32 extrema)
 //   k_export_write  pass B, workgroup 1 + t for tile t: the tile's output offset (the exclusive prefix of the tile
 //                   counts, rebuilt in the workgroup: fewer than 1000 tiles at N = 2^20), a wave's offset inside the
-//                   tile (the four wave counts in LDS), a lane's rank inside the wave (ballot + mbcnt); then the
-//                   chosen fields, one 16-byte store per float4.  Workgroup 0 sums the tiles' partials in tile order
-//                   and writes the count and the statistics.
+//                   tile, a lane's rank inside the wave (slot_walk.hpp); then the chosen fields, one 16-byte store
+//                   per float4.  Workgroup 0 sums the tiles' partials in tile order and writes the count and the
+//                   statistics.
 // There is no hand-off between the workgroups of one launch (no flag, no ticket, no spin): the launch boundary between
 // the passes is the only ordering (a last-arriver ticket on this part cost 7 -> 251 us).
 // The launches cover every owned slot (slots_total); no host-side bound of the live count is used for sizing, since
 // such a bound can be stale after an upload or a restore.
 //
-// Live: 0 <= cell < num_cells_global, what psamd_live_count counts; the mid-step encodings cell <= -2 are not live.
 // A rank's storage order is its slot order (kernels_common.hpp, own_local_cell), so the output is in ascending global
 // slot id, and slot_of_index gives the global id.
-#include "kernels_common.hpp"
+#include "slot_walk.hpp"
 
 namespace psamd {
 
-constexpr int EXPORT_THREADS = 256;
-constexpr int EXPORT_WAVES = EXPORT_THREADS / 64;
-constexpr int EXPORT_ITEMS = EXPORT_TILE / EXPORT_THREADS;     // 16 batches of 64 slots per wave
 constexpr int EXPORT_BATCH = 8;                                 // slots per lane whose loads are in flight together
-static_assert(EXPORT_ITEMS * EXPORT_THREADS == EXPORT_TILE, "a wave walks EXPORT_ITEMS batches of 64 slots");
-
-__device__ __forceinline__ bool export_live(const DevParams &P, int c) { return c >= 0 && c < P.num_cells_global; }
 
 // The statistics of some live particles: every term formed in fp64 from the fp32 fields; a particle whose position or
 // velocity is not a finite number is counted and left out of everything else.
@@ -70,39 +63,36 @@ struct ExportAcc {
     }
 };
 
-// Pass A.  Wave w of tile t walks the slots [t * EXPORT_TILE + w * 64 * EXPORT_ITEMS, + 64 * EXPORT_ITEMS), 64 at a
+// Pass A.  Wave w of tile t walks the slots [t * SLOT_TILE + w * 64 * SLOT_ITEMS, + 64 * SLOT_ITEMS), 64 at a
 // time; a lane sums its own slots in order, then the wave's butterfly, then the waves in order.
-__global__ __launch_bounds__(EXPORT_THREADS) void k_export_count(DevParams P, const int *__restrict__ cell,
-                                                                 const float4 *__restrict__ pos4,
-                                                                 const float4 *__restrict__ vel4,
-                                                                 int *__restrict__ tile_count,
-                                                                 ExportTile *__restrict__ tiles)
+__global__ __launch_bounds__(SLOT_THREADS) void k_export_count(DevParams P, const int *__restrict__ cell,
+                                                               const float4 *__restrict__ pos4,
+                                                               const float4 *__restrict__ vel4,
+                                                               int *__restrict__ tile_count,
+                                                               ExportTile *__restrict__ tiles)
 {
-    __shared__ ExportAcc s_acc[EXPORT_WAVES];
-    __shared__ int s_live[EXPORT_WAVES];
+    __shared__ ExportAcc s_acc[SLOT_WAVES];
+    __shared__ int s_live[SLOT_WAVES];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, t = blockIdx.x;
-    const int first = t * EXPORT_TILE + wv * 64 * EXPORT_ITEMS + lane;
-    int c[EXPORT_ITEMS];
+    const int first = slot_first(t, wv, lane);
+    int c[SLOT_ITEMS];
 #pragma unroll
-    for (int k = 0; k < EXPORT_ITEMS; k++) {
-        const int i = first + 64 * k;
-        c[k] = i < P.slots_total ? cell[i] : -1;
-    }
+    for (int k = 0; k < SLOT_ITEMS; k++) c[k] = slot_cell(P, cell, first + 64 * k);
     ExportAcc a;
     a.init();
     int live = 0;
     // the loads of a batch are issued together, then summed in slot order
 #pragma unroll
-    for (int k0 = 0; k0 < EXPORT_ITEMS; k0 += EXPORT_BATCH) {
+    for (int k0 = 0; k0 < SLOT_ITEMS; k0 += EXPORT_BATCH) {
         float4 p[EXPORT_BATCH], v[EXPORT_BATCH];
 #pragma unroll
         for (int k = 0; k < EXPORT_BATCH; k++) {
             const int i = first + 64 * (k0 + k);
-            if (export_live(P, c[k0 + k])) { p[k] = pos4[i]; v[k] = vel4[i]; }
+            if (slot_live(P, c[k0 + k])) { p[k] = pos4[i]; v[k] = vel4[i]; }
         }
 #pragma unroll
         for (int k = 0; k < EXPORT_BATCH; k++) {
-            const bool on = export_live(P, c[k0 + k]);
+            const bool on = slot_live(P, c[k0 + k]);
             live += __popcll(__ballot(on));
             if (on) a.add(p[k], v[k]);
         }
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(EXPORT_THREADS) void k_export_count(DevParams P, co
     if (threadIdx.x == 0) {
         ExportAcc b = s_acc[0];
         int n = s_live[0];
-        for (int w = 1; w < EXPORT_WAVES; w++) {
+        for (int w = 1; w < SLOT_WAVES; w++) {
             const ExportAcc &o = s_acc[w];
 #pragma unroll
             for (int k = 0; k < EXPORT_SUMS; k++) b.sum[k] += o.sum[k];
@@ -132,49 +122,28 @@ __global__ __launch_bounds__(EXPORT_THREADS) void k_export_count(DevParams P, co
     }
 }
 
-// Workgroup 0 of pass B.  The fp64 sums take the tiles in index order, one sum to a thread (a serial chain, so the same
-// bits on every run -- graphs or not -- for a given context geometry); the tiles' partials pass through LDS a round of
-// EXPORT_THREADS tiles at a time, read once by the whole workgroup.  The extrema and counts do not depend on the order:
-// every thread takes its tiles', then a tree.
+// Workgroup 0 of pass B.  The fp64 sums take the tiles in index order, one sum to a thread (tile_order_sums: a serial
+// chain, so the same bits on every run -- graphs or not -- for a given context geometry).  The extrema and counts do not
+// depend on the order: every thread takes its tiles', then a tree.
 __device__ __forceinline__ void export_finish(int ntiles, const int *__restrict__ tile_count, const ExportTile *__restrict__ tiles,
                                               int64_t *__restrict__ count_out, psamd_live_stats *__restrict__ stats_out)
 {
-    __shared__ double s_sum[EXPORT_SUMS][EXPORT_THREADS + 1];     // (+ 1: the sums' rows start in different banks)
-    __shared__ float s_lo[EXPORT_WAVES][4], s_hi[EXPORT_WAVES][4];
-    __shared__ int s_n[EXPORT_WAVES][2];
+    __shared__ float s_lo[SLOT_WAVES][4], s_hi[SLOT_WAVES][4];
+    __shared__ int s_n[SLOT_WAVES][2];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     float lo[4], hi[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) { lo[k] = __int_as_float(0x7f800000); hi[k] = -__int_as_float(0x7f800000); }
     int live = 0, nonfinite = 0;
-    double sum = 0.0;
-    for (int base = 0; base < ntiles; base += EXPORT_THREADS) {
-        const int t = base + tid;
-        if (t < ntiles) {
-            const ExportTile r = tiles[t];
+    const double sum = tile_order_sums<EXPORT_SUMS>(ntiles, [&](int t, double (&v)[EXPORT_SUMS]) {
+        const ExportTile r = tiles[t];
 #pragma unroll
-            for (int k = 0; k < EXPORT_SUMS; k++) s_sum[k][tid] = r.sum[k];
+        for (int k = 0; k < EXPORT_SUMS; k++) v[k] = r.sum[k];
 #pragma unroll
-            for (int k = 0; k < 4; k++) { lo[k] = fminf(lo[k], r.lo[k]); hi[k] = fmaxf(hi[k], r.hi[k]); }
-            nonfinite += r.nonfinite;
-            live += tile_count[t];
-        }
-        __syncthreads();
-        if (tid < EXPORT_SUMS) {
-            const int m = min(EXPORT_THREADS, ntiles - base);
-            const double *v = s_sum[tid];
-            int j = 0;
-            for (; j + 8 <= m; j += 8) {               // eight reads in flight, then their adds in order
-                double x[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++) x[i] = v[j + i];
-#pragma unroll
-                for (int i = 0; i < 8; i++) sum += x[i];
-            }
-            for (; j < m; j++) sum += v[j];
-        }
-        __syncthreads();
-    }
+        for (int k = 0; k < 4; k++) { lo[k] = fminf(lo[k], r.lo[k]); hi[k] = fmaxf(hi[k], r.hi[k]); }
+        nonfinite += r.nonfinite;
+        live += tile_count[t];
+    });
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
 #pragma unroll
@@ -197,7 +166,7 @@ __device__ __forceinline__ void export_finish(int ntiles, const int *__restrict_
     case 8: o->age_sum = sum; break;
     case 64: {
         long long n = 0, nf = 0;
-        for (int w = 0; w < EXPORT_WAVES; w++) {
+        for (int w = 0; w < SLOT_WAVES; w++) {
             n += s_n[w][0]; nf += s_n[w][1];
 #pragma unroll
             for (int k = 0; k < 4; k++) { lo[k] = fminf(lo[k], s_lo[w][k]); hi[k] = fmaxf(hi[k], s_hi[w][k]); }
@@ -213,48 +182,39 @@ __device__ __forceinline__ void export_finish(int ntiles, const int *__restrict_
 }
 
 // Pass B.  The same walk as pass A over tile blockIdx.x - 1.
-__global__ __launch_bounds__(EXPORT_THREADS) void k_export_write(DevParams P, int ntiles, const int *__restrict__ cell,
-                                                                 const float4 *__restrict__ pos4,
-                                                                 const float4 *__restrict__ vel4,
-                                                                 const float4 *__restrict__ acc4,
-                                                                 const int *__restrict__ tile_count,
-                                                                 const ExportTile *__restrict__ tiles, ExportFields out,
-                                                                 int64_t capacity, int64_t *__restrict__ count_out,
-                                                                 psamd_live_stats *__restrict__ stats_out)
+__global__ __launch_bounds__(SLOT_THREADS) void k_export_write(DevParams P, int ntiles, const int *__restrict__ cell,
+                                                               const float4 *__restrict__ pos4,
+                                                               const float4 *__restrict__ vel4,
+                                                               const float4 *__restrict__ acc4,
+                                                               const int *__restrict__ tile_count,
+                                                               const ExportTile *__restrict__ tiles, ExportFields out,
+                                                               int64_t capacity, int64_t *__restrict__ count_out,
+                                                               psamd_live_stats *__restrict__ stats_out)
 {
     if (blockIdx.x == 0) { export_finish(ntiles, tile_count, tiles, count_out, stats_out); return; }
     if (!out.pos4 && !out.vel4 && !out.acc4 && !out.id && !out.cell) return;
-    __shared__ int s_before[EXPORT_WAVES], s_live[EXPORT_WAVES];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, t = blockIdx.x - 1;
-    // the live particles of the tiles before this one
-    int before = 0;
-    for (int i = threadIdx.x; i < t; i += EXPORT_THREADS) before += tile_count[i];
+    const int before = tiles_before(tile_count, t);       // the live particles of the tiles before this one
+    const int first = slot_first(t, wv, lane);
+    unsigned long long mask[SLOT_ITEMS];
+    int c[SLOT_ITEMS], live = 0;
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) before += __shfl_xor(before, m);
-    const int first = t * EXPORT_TILE + wv * 64 * EXPORT_ITEMS + lane;
-    unsigned long long mask[EXPORT_ITEMS];
-    int c[EXPORT_ITEMS], live = 0;
-#pragma unroll
-    for (int k = 0; k < EXPORT_ITEMS; k++) {
-        const int i = first + 64 * k;
-        c[k] = i < P.slots_total ? cell[i] : -1;
-        mask[k] = __ballot(export_live(P, c[k]));
+    for (int k = 0; k < SLOT_ITEMS; k++) {
+        c[k] = slot_cell(P, cell, first + 64 * k);
+        mask[k] = __ballot(slot_live(P, c[k]));
         live += __popcll(mask[k]);
     }
-    if (lane == 0) { s_before[wv] = before; s_live[wv] = live; }
-    __syncthreads();
-    int64_t at = 0;
-    for (int w = 0; w < EXPORT_WAVES; w++) at += s_before[w] + (w < wv ? s_live[w] : 0);
+    int64_t at = wave_offset<int64_t>(before, live, wv, lane);
     if (at >= capacity) return;                           // (the wave's slots all fall past the caller's capacity)
-    // a batch's loads together, then its stores; a lane's rank in the wave: mbcnt over the batch's ballot
+    // a batch's loads together, then its stores
 #pragma unroll
-    for (int k0 = 0; k0 < EXPORT_ITEMS; k0 += EXPORT_BATCH) {
+    for (int k0 = 0; k0 < SLOT_ITEMS; k0 += EXPORT_BATCH) {
         float4 p[EXPORT_BATCH], v[EXPORT_BATCH], a[EXPORT_BATCH];
         int64_t o[EXPORT_BATCH];
 #pragma unroll
         for (int k = 0; k < EXPORT_BATCH; k++) {
             const unsigned long long m = mask[k0 + k];
-            o[k] = at + (int64_t)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            o[k] = at + (int64_t)lane_rank(m);
             at += __popcll(m);
             if (((m >> lane) & 1ull) && o[k] < capacity) {
                 const int i = first + 64 * (k0 + k);
@@ -280,12 +240,12 @@ __global__ __launch_bounds__(EXPORT_THREADS) void k_export_write(DevParams P, in
 hipError_t launch_export_live(hipStream_t st, const DevParams &P, const DeviceState &d, const ExportFields &out,
                               int64_t capacity, int64_t *count_out, psamd_live_stats *stats_out)
 {
-    const int ntiles = export_tiles(P.slots_total);
+    const int ntiles = slot_tiles(P.slots_total);
     if (ntiles > 0) {
-        k_export_count<<<ntiles, EXPORT_THREADS, 0, st>>>(P, d.cell, d.pos4, d.vel4, d.exp_count, d.exp_tiles);
+        k_export_count<<<ntiles, SLOT_THREADS, 0, st>>>(P, d.cell, d.pos4, d.vel4, d.exp_count, d.exp_tiles);
         PS_LAUNCH_CHECK();
     }
-    k_export_write<<<ntiles + 1, EXPORT_THREADS, 0, st>>>(P, ntiles, d.cell, d.pos4, d.vel4, d.acc4, d.exp_count, d.exp_tiles,
+    k_export_write<<<ntiles + 1, SLOT_THREADS, 0, st>>>(P, ntiles, d.cell, d.pos4, d.vel4, d.acc4, d.exp_count, d.exp_tiles,
                                                           out, capacity, count_out, stats_out);
     PS_LAUNCH_CHECK();
     return hipSuccess;

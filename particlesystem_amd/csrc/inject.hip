@@ -4,7 +4,7 @@
 // its segment's queue in entry order (q_remove), and the stop rule is fill's.  A deterministic stable multisplit of the
 // entries by queue record, then the closed-form FIFO removal (the k-th remove of a record takes logical element k, as
 // k_replay_commit does), in five launches ordered by the launch boundaries only (no hand-off between workgroups):
-//   k_inject_locate  one workgroup per tile of INJECT_TILE entries: Geometry::locate in fp64, the segment record, the
+//   k_inject_locate  one workgroup per tile of ENTRY_TILE entries: Geometry::locate in fp64, the segment record, the
 //                    ownership rule; the tile's per-record counts and every entry's stable rank inside the tile
 //                    (multisplit.hpp, shared with remove.hip); the tile's first entry outside the box
 //   k_inject_scan    one workgroup: per record, the exclusive prefix of the tile counts (in place) and the first
@@ -18,22 +18,9 @@
 // (stream order puts them between steps).
 #include "multisplit.hpp"
 
-#include <climits>
-
 namespace psamd {
 
-constexpr int INJECT_THREADS = SPLIT_THREADS;  // k_inject_locate: 16 waves, 4 groups of 64 entries each (multisplit.hpp)
-constexpr int INJECT_GROUPS = INJECT_TILE / INJECT_THREADS;
-static_assert(INJECT_GROUPS * INJECT_THREADS == INJECT_TILE, "a wave ranks INJECT_GROUPS consecutive groups of 64 entries");
-constexpr int INJECT_LDS_RECORDS = 8192;      // records counted in LDS (32 KB); more: in the tile's row in global memory
 constexpr int INJ_NOT_MINE = -1, INJ_OUTSIDE = -2;
-
-__device__ __forceinline__ int inject_n(const int64_t *count_dev, int64_t max_count)
-{
-    if (!count_dev) return (int)max_count;
-    const int64_t v = *count_dev;
-    return (int)(v < 0 ? 0 : v > max_count ? max_count : v);
-}
 
 // Geometry::locate: the same fp64 floor((+-1.0 * c) / cell_size) + G / 2.  On x86 the host's out-of-range (int)
 // conversion gives INT_MIN (rejected); here it would saturate and NaN would become 0, so the range is tested on the
@@ -50,29 +37,22 @@ __device__ __forceinline__ bool inject_locate(const DevParams &P, float x, float
 }
 
 template <bool LDS>
-__global__ void __launch_bounds__(INJECT_THREADS) k_inject_locate(DevParams P, SegLayout S, int nrec, const CellInfo *__restrict__ celltab,
-                                                                  const float4 *__restrict__ pos4, int64_t max_count, const int64_t *count_dev,
-                                                                  int2 *__restrict__ ent, int *__restrict__ tcount, int *__restrict__ tile_out)
+__global__ void __launch_bounds__(SPLIT_THREADS) k_inject_locate(DevParams P, SegLayout S, int nrec, const CellInfo *__restrict__ celltab,
+                                                                 const float4 *__restrict__ pos4, int64_t max_count, const int64_t *count_dev,
+                                                                 int2 *__restrict__ ent, int *__restrict__ tcount, int *__restrict__ tile_out)
 {
     extern __shared__ int lds_cnt[];
     __shared__ int s_first_out;
-    const int n = inject_n(count_dev, max_count);
-    const int t = (int)blockIdx.x, base = t * INJECT_TILE;
-    if (base >= n) return;
-    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    int *cnt = LDS ? lds_cnt : tcount + (size_t)t * nrec;
-    for (int r = tid; r < nrec; r += INJECT_THREADS) cnt[r] = 0;
-    if (tid == 0) s_first_out = INT_MAX;
-    if (!LDS) __threadfence();
-    __syncthreads();
-
-    // every group's records and, per lane, its rank among the group's lanes of the same record (ballot + mbcnt per
-    // distinct record), the group's count of that record and the lane that will account for it (the lowest)
-    int rec[INJECT_GROUPS], in_rank[INJECT_GROUPS], pop[INJECT_GROUPS], lead[INJECT_GROUPS];
+    const int n = entry_count(count_dev, max_count);
+    const int t = (int)blockIdx.x;
+    if (t * ENTRY_TILE >= n) return;
+    if (threadIdx.x == 0) s_first_out = INT_MAX;
+    SplitKeys k;
+    split_tile_begin<LDS>(t, nrec, lds_cnt, tcount, k);
     int first_out = INT_MAX;
 #pragma unroll
-    for (int g = 0; g < INJECT_GROUPS; g++) {
-        const int i = base + (wave * INJECT_GROUPS + g) * 64 + lane;
+    for (int g = 0; g < SPLIT_GROUPS; g++) {
+        const int i = split_entry(t, g);
         int r = INJ_NOT_MINE;
         if (i < n) {
             const float4 p = pos4[i];
@@ -84,20 +64,12 @@ __global__ void __launch_bounds__(INJECT_THREADS) k_inject_locate(DevParams P, S
                 r = owns_record(P, sr) ? sr : INJ_NOT_MINE;
             }
         }
-        rec[g] = r;
-        split_group_rank(r, lane, in_rank[g], pop[g], lead[g]);
+        k.rec[g] = r;
+        split_group_rank(r, (int)threadIdx.x & 63, k.in_rank[g], k.pop[g], k.lead[g]);
     }
     if (first_out != INT_MAX) atomicMin(&s_first_out, first_out);
-
-    int at[INJECT_GROUPS];
-    split_take_turns<INJECT_GROUPS, !LDS>(rec, in_rank, pop, lead, cnt, wave, lane, at);
-#pragma unroll
-    for (int g = 0; g < INJECT_GROUPS; g++) {
-        const int i = base + (wave * INJECT_GROUPS + g) * 64 + lane;
-        if (i < n) ent[i] = make_int2(rec[g], rec[g] >= 0 ? at[g] : 0);
-    }
-    if (LDS) for (int r = tid; r < nrec; r += INJECT_THREADS) tcount[(size_t)t * nrec + r] = cnt[r];
-    if (tid == 0) tile_out[t] = s_first_out;
+    split_tile_store<LDS>(t, n, nrec, k, ent, tcount);
+    if (threadIdx.x == 0) tile_out[t] = s_first_out;
 }
 
 // one workgroup: per record the exclusive prefix of the tiles' counts, in tile order, in place; the first entry outside
@@ -106,7 +78,7 @@ __global__ void __launch_bounds__(1024) k_inject_scan(int nrec, int64_t max_coun
                                                       const int *__restrict__ tile_out, int *__restrict__ removed, int *__restrict__ hdr)
 {
     __shared__ int s_min;
-    const int n = inject_n(count_dev, max_count), tiles = (int)(((int64_t)n + INJECT_TILE - 1) / INJECT_TILE);
+    const int n = entry_count(count_dev, max_count), tiles = entry_tiles(n);
     const int tid = (int)threadIdx.x;
     if (tid == 0) s_min = INT_MAX;
     __syncthreads();
@@ -124,13 +96,13 @@ __global__ void __launch_bounds__(1024) k_inject_scan(int nrec, int64_t max_coun
 __global__ void k_inject_fail(int nrec, int64_t max_count, const int64_t *count_dev, const int *__restrict__ tcount,
                               const QueueInfo *__restrict__ qinfo, int2 *__restrict__ ent, int *__restrict__ hdr)
 {
-    const int n = inject_n(count_dev, max_count);
+    const int n = entry_count(count_dev, max_count);
     const int64_t i64 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i64 >= n) return;
     const int i = (int)i64;
     int2 e = ent[i];
     if (e.x < 0) return;
-    e.y += tcount[(size_t)(i / INJECT_TILE) * nrec + e.x];
+    e.y += tcount[(size_t)(i / ENTRY_TILE) * nrec + e.x];
     ent[i] = e;
     if (e.y == qinfo[e.x].count) atomicMin(&hdr[1], i);
 }
@@ -141,7 +113,7 @@ __global__ void k_inject_place(DevParams P, int64_t max_count, const int64_t *co
                                int *__restrict__ ids, int *__restrict__ removed, float4 *d_pos4, float4 *d_vel4, float4 *d_acc4,
                                int *d_cell, uint8_t *d_pflags)
 {
-    const int n = inject_n(count_dev, max_count);
+    const int n = entry_count(count_dev, max_count);
     const int64_t i64 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i64 >= n) return;
     const int i = (int)i64;
@@ -177,12 +149,10 @@ __global__ void __launch_bounds__(1024) k_inject_commit(int nrec, int64_t max_co
                                                         const int *__restrict__ removed, QueueInfo *qinfo, psamd_inject_result *own,
                                                         psamd_inject_result *out)
 {
-    __shared__ unsigned long long s_placed;
-    const int n = inject_n(count_dev, max_count);
+    __shared__ unsigned long long s_placed[1];
+    const int n = entry_count(count_dev, max_count);
     const int tid = (int)threadIdx.x;
-    if (tid == 0) s_placed = 0;
-    __syncthreads();
-    unsigned long long placed = 0;
+    long long placed[1] = {0}, sum[1];
     for (int r = tid; r < nrec; r += 1024) {
         const int R = removed[r];
         if (R <= 0) continue;
@@ -191,40 +161,38 @@ __global__ void __launch_bounds__(1024) k_inject_commit(int nrec, int64_t max_co
         if (q.count == 0) { q.front = -1; q.rear = -1; }
         else q.front = q.rloc + (q.front - q.rloc + R) % q.seg_size;
         qinfo[r] = q;
-        placed += (unsigned long long)R;
+        placed[0] += R;
     }
-    if (placed) atomicAdd(&s_placed, placed);
-    __syncthreads();
+    block_sum(placed, s_placed, sum);
     if (tid == 0) {
         const int fo = hdr[0], ff = hdr[1];
         const int F = min(min(fo, ff), n);
         psamd_inject_result res;
         res.done = F;
-        res.placed = (int64_t)s_placed;
+        res.placed = sum[0];
         res.status = F == n ? PSAMD_OK : F == fo ? PSAMD_ERR_OUTSIDE_BOX : PSAMD_ERR_QUEUE_EMPTY;
         res.reserved = 0;
-        *own = res;
-        if (out && out != own) *out = res;
+        write_result(own, out, res);
     }
 }
 
 hipError_t launch_inject(hipStream_t st, const DevParams &P, const SegLayout &S, const DeviceState &d, int nrec, const InjectArgs &a,
                          const InjectScratch &s)
 {
-    const int64_t tiles = (a.max_count + INJECT_TILE - 1) / INJECT_TILE;
-    if (nrec <= INJECT_LDS_RECORDS)
-        k_inject_locate<true><<<(unsigned)tiles, INJECT_THREADS, (size_t)nrec * sizeof(int), st>>>(P, S, nrec, d.celltab, a.pos4, a.max_count,
-                                                                                                 a.count_dev, s.ent, s.tcount, s.tile_out);
+    const int64_t tiles = (a.max_count + ENTRY_TILE - 1) / ENTRY_TILE;
+    if (nrec <= SPLIT_LDS_RECORDS)
+        k_inject_locate<true><<<(unsigned)tiles, SPLIT_THREADS, (size_t)nrec * sizeof(int), st>>>(P, S, nrec, d.celltab, a.pos4, a.max_count,
+                                                                                                a.count_dev, s.e.ent, s.e.tcount, s.e.tile_out);
     else
-        k_inject_locate<false><<<(unsigned)tiles, INJECT_THREADS, 0, st>>>(P, S, nrec, d.celltab, a.pos4, a.max_count, a.count_dev,
-                                                                         s.ent, s.tcount, s.tile_out);
+        k_inject_locate<false><<<(unsigned)tiles, SPLIT_THREADS, 0, st>>>(P, S, nrec, d.celltab, a.pos4, a.max_count, a.count_dev,
+                                                                        s.e.ent, s.e.tcount, s.e.tile_out);
     PS_LAUNCH_CHECK();
-    k_inject_scan<<<1, 1024, 0, st>>>(nrec, a.max_count, a.count_dev, s.tcount, s.tile_out, s.removed, s.hdr);
+    k_inject_scan<<<1, 1024, 0, st>>>(nrec, a.max_count, a.count_dev, s.e.tcount, s.e.tile_out, s.removed, s.hdr);
     PS_LAUNCH_CHECK();
     const unsigned blocks = (unsigned)((a.max_count + 255) / 256);
-    k_inject_fail<<<blocks, 256, 0, st>>>(nrec, a.max_count, a.count_dev, s.tcount, d.qinfo, s.ent, s.hdr);
+    k_inject_fail<<<blocks, 256, 0, st>>>(nrec, a.max_count, a.count_dev, s.e.tcount, d.qinfo, s.e.ent, s.hdr);
     PS_LAUNCH_CHECK();
-    k_inject_place<<<blocks, 256, 0, st>>>(P, a.max_count, a.count_dev, a.pos4, a.vel4, a.fert_age, s.ent, s.hdr, d.qinfo, d.queue,
+    k_inject_place<<<blocks, 256, 0, st>>>(P, a.max_count, a.count_dev, a.pos4, a.vel4, a.fert_age, s.e.ent, s.hdr, d.qinfo, d.queue,
                                            a.ids, s.removed, d.pos4, d.vel4, d.acc4, d.cell, d.pflags);
     PS_LAUNCH_CHECK();
     k_inject_commit<<<1, 1024, 0, st>>>(nrec, a.max_count, a.count_dev, s.hdr, s.removed, d.qinfo, s.own, a.result);

@@ -1,10 +1,11 @@
-// io.hip -- state in and out of a context: fill / upload / download, export, inject, snapshot, the slab message
-// buffers, and the debug / self-test calls.  Nothing here enqueues a stage of the step.
+// io.hip -- state in and out of a context: fill / upload / download, snapshot, the slab message buffers, and the debug /
+// self-test calls (the on-stream services -- export, inject, remove, potential -- are services.hip's).  Nothing here
+// enqueues a stage of the step.
 #include <random>
 
 #include "context.hpp"
 
-static int ensure_staging(psamd_ctx *c, size_t bytes)
+int psamd::ensure_staging(psamd_ctx *c, size_t bytes)
 {
     if (bytes <= c->staging_bytes) return PSAMD_OK;
     if (c->staging) (void)hipFree(c->staging);
@@ -418,268 +419,6 @@ int psamd_device_view_get(psamd_ctx *c, psamd_device_view *o)
     return PSAMD_OK;
 }
 
-// ---- getting frames out (export.hip) ----
-static const uint32_t export_bits[5] = {PSAMD_EXPORT_POS, PSAMD_EXPORT_VEL, PSAMD_EXPORT_ACC, PSAMD_EXPORT_ID, PSAMD_EXPORT_CELL};
-static const size_t export_size[5] = {sizeof(float4), sizeof(float4), sizeof(float4), sizeof(int32_t), sizeof(int32_t)};
-
-// device: the kernel stores to the arrays (float4 and int32 stores want their natural alignment); host arrays are copied into
-static int export_args(psamd_ctx *c, uint32_t fields, void *const ptr[5], int64_t capacity, bool device)
-{
-    if (fields & ~PSAMD_EXPORT_ALL) return fail(c, PSAMD_ERR_INVALID_ARG, "export: unknown field bits");
-    if (capacity < 0) return fail(c, PSAMD_ERR_INVALID_ARG, "export: capacity < 0");
-    for (int k = 0; k < 5; k++)
-        if ((fields & export_bits[k]) && (!ptr[k] || (device && (uintptr_t)ptr[k] % export_size[k] != 0)))
-            return fail(c, PSAMD_ERR_INVALID_ARG, "export: a field asked for has a null or misaligned pointer");
-    return PSAMD_OK;
-}
-
-static ExportFields export_fields(uint32_t fields, void *const ptr[5])
-{
-    void *p[5];
-    for (int k = 0; k < 5; k++) p[k] = (fields & export_bits[k]) ? ptr[k] : nullptr;
-    return ExportFields{(float4 *)p[0], (float4 *)p[1], (float4 *)p[2], (int *)p[3], (int *)p[4]};
-}
-
-int psamd_export_live(psamd_ctx *c, const psamd_export *spec)
-{
-    if (!c || !spec) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
-    void *const ptr[5] = {spec->pos4, spec->vel4, spec->acc4, spec->id, spec->cell};
-    if (spec->reserved != 0) return fail(c, PSAMD_ERR_INVALID_ARG, "export: reserved must be 0");
-    const int rc = export_args(c, spec->fields, ptr, spec->capacity, true);
-    if (rc != PSAMD_OK) return rc;
-    PS_HIP(c, launch_export_live(c->stream, c->P, c->d, export_fields(spec->fields, ptr), spec->capacity,
-                                 spec->count_dev ? spec->count_dev : &c->d.exp_out->count,
-                                 spec->stats_dev ? spec->stats_dev : &c->d.exp_out->stats));
-    return PSAMD_OK;
-}
-
-int psamd_download_live(psamd_ctx *c, uint32_t fields, void *pos4, void *vel4, void *acc4, int32_t *id, int32_t *cell,
-                        int64_t capacity, int64_t *count)
-{
-    if (!c || !count) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
-    void *const host[5] = {pos4, vel4, acc4, id, cell};
-    int rc = export_args(c, fields, host, capacity, false);
-    if (rc != PSAMD_OK) return rc;
-    // the chosen fields of at most min(capacity, owned slots) particles, one after the other in the staging buffer
-    const int64_t n = std::min<int64_t>(capacity, c->P.slots_total);
-    size_t off[5] = {0, 0, 0, 0, 0}, bytes = 0;
-    for (int k = 0; k < 5; k++)
-        if (fields & export_bits[k]) { off[k] = bytes; bytes += ((size_t)n * export_size[k] + 255) / 256 * 256; }
-    rc = ensure_staging(c, std::max<size_t>(bytes, 256));
-    if (rc != PSAMD_OK) return rc;
-    void *dev[5];
-    for (int k = 0; k < 5; k++) dev[k] = (char *)c->staging + off[k];
-    PS_HIP(c, launch_export_live(c->stream, c->P, c->d, export_fields(fields, dev), n, &c->d.exp_out->count, &c->d.exp_out->stats));
-    int64_t total = 0;
-    PS_HIP(c, hipMemcpyAsync(&total, &c->d.exp_out->count, sizeof total, hipMemcpyDeviceToHost, c->stream));
-    PS_HIP(c, hipStreamSynchronize(c->stream));
-    const size_t got = (size_t)std::min<int64_t>(total, n);
-    if (got > 0)
-        for (int k = 0; k < 5; k++)
-            if (fields & export_bits[k]) PS_HIP(c, hipMemcpyAsync(host[k], dev[k], got * export_size[k], hipMemcpyDeviceToHost, c->stream));
-    PS_HIP(c, hipStreamSynchronize(c->stream));
-    *count = total;
-    return PSAMD_OK;
-}
-
-int psamd_live_stats_get(psamd_ctx *c, psamd_live_stats *out)
-{
-    if (!c || !out) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
-    PS_HIP(c, launch_export_live(c->stream, c->P, c->d, ExportFields{nullptr, nullptr, nullptr, nullptr, nullptr}, 0,
-                                 &c->d.exp_out->count, &c->d.exp_out->stats));
-    PS_HIP(c, hipMemcpyAsync(out, &c->d.exp_out->stats, sizeof *out, hipMemcpyDeviceToHost, c->stream));
-    PS_HIP(c, hipStreamSynchronize(c->stream));
-    return PSAMD_OK;
-}
-
-// ---- putting particles in (inject.hip) ----
-static bool aligned(const void *p, size_t a) { return (uintptr_t)p % a == 0; }
-
-// the entries' scratch for max_count entries: grows only (hipFree waits for the device; steady use never gets here)
-static int inject_scratch(psamd_ctx *c, int64_t max_count)
-{
-    if (max_count <= c->inj_cap) return PSAMD_OK;
-    for (void *p : {(void *)c->inj.ent, (void *)c->inj.tcount, (void *)c->inj.tile_out}) if (p) PS_HIP(c, hipFree(p));
-    c->inj.ent = nullptr; c->inj.tcount = nullptr; c->inj.tile_out = nullptr;
-    c->inj_cap = 0;
-    const int64_t tiles = (max_count + INJECT_TILE - 1) / INJECT_TILE;
-    PS_HIP(c, hipMalloc((void **)&c->inj.ent, (size_t)(tiles * INJECT_TILE) * sizeof(int2)));
-    PS_HIP(c, hipMalloc((void **)&c->inj.tcount, (size_t)tiles * (size_t)c->geo.queue_infos * sizeof(int)));
-    PS_HIP(c, hipMalloc((void **)&c->inj.tile_out, (size_t)tiles * sizeof(int)));
-    c->inj_cap = tiles * INJECT_TILE;
-    return PSAMD_OK;
-}
-
-int psamd_inject(psamd_ctx *c, const psamd_inject_spec *spec)
-{
-    if (!c || !spec) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
-    if (spec->flags != 0 || spec->reserved != 0) return fail(c, PSAMD_ERR_INVALID_ARG, "inject: flags and reserved must be 0");
-    if (spec->max_count < 0 || spec->max_count > INT32_MAX) return fail(c, PSAMD_ERR_INVALID_ARG, "inject: max_count outside [0, 2^31)");
-    if (!spec->pos4 || !aligned(spec->pos4, 16) || !aligned(spec->vel4, 16) || !aligned(spec->fert_age, 4) || !aligned(spec->ids_dev, 4) ||
-        !aligned(spec->count_dev, 8) || !aligned(spec->result_dev, 8))
-        return fail(c, PSAMD_ERR_INVALID_ARG, "inject: pos4 missing, or an array misaligned");
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    PS_HIP(c, hipStreamIsCapturing(c->stream, &cs));
-    if (cs != hipStreamCaptureStatusNone)
-        return fail(c, PSAMD_ERR_STATE, "inject: the context's stream is being captured (the host's bound of the live count is "
-                                        "kept at the call: a replay would bypass it)");
-    psamd_inject_result *res = spec->result_dev ? spec->result_dev : c->inj.own;
-    if (spec->max_count == 0) {
-        PS_HIP(c, hipMemsetAsync(c->inj.own, 0, sizeof(psamd_inject_result), c->stream));
-        if (res != c->inj.own) PS_HIP(c, hipMemsetAsync(res, 0, sizeof(psamd_inject_result), c->stream));
-        return PSAMD_OK;
-    }
-    const int rc = inject_scratch(c, spec->max_count);
-    if (rc != PSAMD_OK) return rc;
-    const InjectArgs a{(const float4 *)spec->pos4, (const float4 *)spec->vel4, spec->fert_age, spec->max_count, spec->count_dev,
-                       spec->ids_dev, res};
-    PS_HIP(c, launch_inject(c->stream, c->P, c->S, c->d, c->geo.queue_infos, a, c->inj));
-    // fill's transitions; the device's queues are ahead of the host's mirror; every entry counts in the live bound,
-    // also when the record of a step enqueued before this call is read later (consume_scalars)
-    c->host_queues_valid = false;
-    c->grid_built = false; c->pairs_done = false; c->slab_stage = 0;
-    if (c->live_bound >= 0) c->live_bound = std::min<int64_t>(c->P.slots_total, c->live_bound + spec->max_count);
-    c->inject_tally[c->scalars_seq] += spec->max_count;
-    return PSAMD_OK;
-}
-
-int psamd_inject_result_get(psamd_ctx *c, psamd_inject_result *out)
-{
-    if (!c || !out) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
-    PS_HIP(c, hipMemcpyAsync(out, c->inj.own, sizeof *out, hipMemcpyDeviceToHost, c->stream));
-    PS_HIP(c, hipStreamSynchronize(c->stream));
-    return PSAMD_OK;
-}
-
-// ---- taking particles out (remove.hip) ----
-// the entries' scratch for max_count entries: grows only, like inject's
-static int remove_scratch(psamd_ctx *c, int64_t max_count)
-{
-    if (max_count <= c->rem_cap) return PSAMD_OK;
-    for (void *p : {(void *)c->rem.ent, (void *)c->rem.tcount, (void *)c->rem.tile_out}) if (p) PS_HIP(c, hipFree(p));
-    c->rem.ent = nullptr; c->rem.tcount = nullptr; c->rem.tile_out = nullptr;
-    c->rem_cap = 0;
-    const int64_t tiles = (max_count + REMOVE_TILE - 1) / REMOVE_TILE;
-    PS_HIP(c, hipMalloc((void **)&c->rem.ent, (size_t)(tiles * REMOVE_TILE) * sizeof(int2)));
-    PS_HIP(c, hipMalloc((void **)&c->rem.tcount, (size_t)tiles * (size_t)c->geo.queue_infos * sizeof(int)));
-    PS_HIP(c, hipMalloc((void **)&c->rem.tile_out, (size_t)tiles * 3 * sizeof(int)));
-    c->rem_cap = tiles * REMOVE_TILE;
-    return PSAMD_OK;
-}
-
-int psamd_remove(psamd_ctx *c, const psamd_remove_spec *spec)
-{
-    if (!c || !spec) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
-    const bool box = (spec->flags & PSAMD_REMOVE_BOX) != 0;
-    if ((spec->flags & ~(PSAMD_REMOVE_BOX | PSAMD_REMOVE_OUTSIDE)) || (!box && (spec->flags & PSAMD_REMOVE_OUTSIDE)) || spec->reserved != 0)
-        return fail(c, PSAMD_ERR_INVALID_ARG, "remove: unknown flag bits, OUTSIDE without BOX, or reserved not 0");
-    if (spec->max_count < 0 || spec->max_count > INT32_MAX) return fail(c, PSAMD_ERR_INVALID_ARG, "remove: max_count outside [0, 2^31)");
-    if (!aligned(spec->ids, 4) || !aligned(spec->outcome_dev, 4) || !aligned(spec->count_dev, 8) || !aligned(spec->result_dev, 8))
-        return fail(c, PSAMD_ERR_INVALID_ARG, "remove: an array misaligned");
-    if (box && (spec->ids || spec->count_dev || spec->outcome_dev || spec->max_count != 0))
-        return fail(c, PSAMD_ERR_INVALID_ARG, "remove: by box, ids, count_dev and outcome_dev must be NULL and max_count 0");
-    if (!box && !spec->ids && spec->max_count > 0) return fail(c, PSAMD_ERR_INVALID_ARG, "remove: ids missing");
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    PS_HIP(c, hipStreamIsCapturing(c->stream, &cs));
-    if (cs != hipStreamCaptureStatusNone)
-        return fail(c, PSAMD_ERR_STATE, "remove: the context's stream is being captured (the call ends the host's frame in "
-                                        "progress: a replay would bypass that)");
-    psamd_remove_result *res = spec->result_dev ? spec->result_dev : c->rem.own;
-    if (!box && spec->max_count == 0) {
-        PS_HIP(c, hipMemsetAsync(c->rem.own, 0, sizeof(psamd_remove_result), c->stream));
-        if (res != c->rem.own) PS_HIP(c, hipMemsetAsync(res, 0, sizeof(psamd_remove_result), c->stream));
-        return PSAMD_OK;
-    }
-    if (box) {
-        PS_HIP(c, launch_remove_box(c->stream, c->P, c->S, c->d, c->geo.queue_infos, spec->lo, spec->hi,
-                                    (spec->flags & PSAMD_REMOVE_OUTSIDE) != 0, res, c->rem));
-    } else {
-        const int rc = remove_scratch(c, spec->max_count);
-        if (rc != PSAMD_OK) return rc;
-        const RemoveArgs a{spec->ids, spec->max_count, spec->count_dev, spec->outcome_dev, res};
-        PS_HIP(c, launch_remove_ids(c->stream, c->P, c->S, c->d, c->geo.queue_infos, a, c->rem));
-    }
-    // inject's transitions; the device's queues are ahead of the host's mirror.  The host's bound of the live count stays:
-    // it is an upper bound.
-    c->host_queues_valid = false;
-    c->grid_built = false; c->pairs_done = false; c->slab_stage = 0;
-    return PSAMD_OK;
-}
-
-int psamd_remove_result_get(psamd_ctx *c, psamd_remove_result *out)
-{
-    if (!c || !out) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
-    PS_HIP(c, hipMemcpyAsync(out, c->rem.own, sizeof *out, hipMemcpyDeviceToHost, c->stream));
-    PS_HIP(c, hipStreamSynchronize(c->stream));
-    return PSAMD_OK;
-}
-
-// ---- energy (potential.hip) ----
-// a frame is built, its particles have not moved, and -- a slab -- the halos are in and nothing of the plan is lent
-static int potential_ready(psamd_ctx *c)
-{
-    if (c->wedged) return refuse_wedged(c);
-    const bool ok = c->P.world > 1 ? c->slab_stage == 2 : (c->grid_built && c->slab_stage != 3);
-    if (!ok) return fail(c, PSAMD_ERR_STATE, c->P.world > 1 ? "potential belongs between slab_pairs and slab_apply"
-                                                             : "potential needs build_grid first, and a frame that has not been applied");
-    const SlabPlan &pl = c->plan;
-    if (c->P.world > 1 && (pl.lentin_lo < pl.lentin_hi || pl.lentout_lo < pl.lentout_hi))
-        return fail(c, PSAMD_ERR_UNSUPPORTED, "potential: this rank's plan lends cell layers (lentin / lentout not empty); only plans "
-                                              "with group-aligned cuts are served");
-    return PSAMD_OK;
-}
-
-int psamd_potential(psamd_ctx *c, const psamd_potential_spec *spec)
-{
-    if (!c || !spec) return PSAMD_ERR_INVALID_ARG;
-    if (spec->flags != 0 || spec->reserved != 0) return fail(c, PSAMD_ERR_INVALID_ARG, "potential: flags and reserved must be 0");
-    if (spec->capacity < 0) return fail(c, PSAMD_ERR_INVALID_ARG, "potential: capacity < 0");
-    if (!aligned(spec->phi, 4) || (!spec->phi && spec->capacity > 0) || !aligned(spec->result_dev, 8))
-        return fail(c, PSAMD_ERR_INVALID_ARG, "potential: phi missing or misaligned, or result_dev misaligned");
-    const int rc = potential_ready(c);
-    if (rc != PSAMD_OK) return rc;
-    PS_HIP(c, launch_potential(c->stream, c->P, c->d, spec->phi, spec->capacity, spec->result_dev));
-    return PSAMD_OK;
-}
-
-int psamd_potential_result_get(psamd_ctx *c, psamd_potential_result *out)
-{
-    if (!c || !out) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
-    PS_HIP(c, hipMemcpyAsync(out, &c->d.pot_out->result, sizeof *out, hipMemcpyDeviceToHost, c->stream));
-    PS_HIP(c, hipStreamSynchronize(c->stream));
-    return PSAMD_OK;
-}
-
-int psamd_download_potential(psamd_ctx *c, float *phi, int64_t capacity, psamd_potential_result *out)
-{
-    if (!c) return PSAMD_ERR_INVALID_ARG;
-    if (capacity < 0 || (!phi && capacity > 0)) return fail(c, PSAMD_ERR_INVALID_ARG, "download_potential: capacity < 0, or no array for it");
-    int rc = potential_ready(c);
-    if (rc != PSAMD_OK) return rc;
-    const int64_t n = std::min<int64_t>(capacity, c->P.slots_total);
-    rc = ensure_staging(c, std::max<size_t>((size_t)n * sizeof(float), 256));
-    if (rc != PSAMD_OK) return rc;
-    PS_HIP(c, launch_potential(c->stream, c->P, c->d, n > 0 ? (float *)c->staging : nullptr, n, nullptr));
-    PotOut got{};
-    PS_HIP(c, hipMemcpyAsync(&got, c->d.pot_out, sizeof got, hipMemcpyDeviceToHost, c->stream));
-    PS_HIP(c, hipStreamSynchronize(c->stream));
-    const size_t m = (size_t)std::min<int64_t>(got.live, n);
-    if (m > 0) {
-        PS_HIP(c, hipMemcpyAsync(phi, c->staging, m * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        PS_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    if (out) *out = got.result;
-    return PSAMD_OK;
-}
-
 int psamd_download_force4(psamd_ctx *c, void *out, int64_t first, int64_t count)
 {
     if (!c || !out || first < 0 || count < 0 || first + count > c->P.sorted_cap) return PSAMD_ERR_INVALID_ARG;
@@ -739,8 +478,8 @@ int psamd_snapshot_restore(psamd_ctx *c)
     if (!c->snapshot) return fail(c, PSAMD_ERR_STATE, "snapshot_restore without a saved snapshot");
     c->step = c->snapshot_step;
     c->live_bound = c->snapshot_live_bound;
-    c->host_queues_valid = false;
-    c->frame_reset = false; c->grid_built = false; c->pairs_done = false; c->slab_stage = 0;
+    end_frame(c);
+    c->frame_reset = false;
     return snapshot_copy(c, false);
 }
 

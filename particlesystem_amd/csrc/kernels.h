@@ -9,17 +9,27 @@
 
 namespace psamd {
 
-// psamd_export_live (export.hip): the owned slots in tiles of EXPORT_TILE; pass A leaves per tile its live count
-// (DeviceState::exp_count) and these partials of the statistics (fp64 sums: mass, momentum x y z, kinetic energy,
-// mass moment x y z, age; fp32 extrema: x, y, z, age)
-constexpr int EXPORT_TILE = 4096;
+// The on-stream services walk the owned slots in tiles of SLOT_TILE (slot_walk.hpp: export, potential, remove by box) and
+// a caller's entries in tiles of ENTRY_TILE (multisplit.hpp: inject, remove by id)
+constexpr int SLOT_TILE = 4096;
+constexpr int ENTRY_TILE = 4096;
+inline int slot_tiles(int slots_total) { return (slots_total + SLOT_TILE - 1) / SLOT_TILE; }
+// what grows with a call's max_count (the host: grow_entry_scratch, services.hip)
+struct EntryScratch {
+    int2 *ent;        // [cap] per entry: its key -- the queue record, or a negative code of the service -- and its rank in the record
+    int *tcount;      // [tiles * nrec] per tile and record: the count, then the exclusive prefix over the tiles
+    int *tile_out;    // [tiles * words] the tile's side result (inject: its first entry outside the box; remove: three outcome counts)
+    int64_t cap;      // entries there is room for
+};
+
+// psamd_export_live (export.hip): pass A leaves per tile its live count (DeviceState::exp_count) and these partials of the
+// statistics (fp64 sums: mass, momentum x y z, kinetic energy, mass moment x y z, age; fp32 extrema: x, y, z, age)
 constexpr int EXPORT_SUMS = 9;
 struct __align__(16) ExportTile {
     double sum[EXPORT_SUMS];
     float lo[4], hi[4];
     int nonfinite, pad;
 };
-inline int export_tiles(int slots_total) { return (slots_total + EXPORT_TILE - 1) / EXPORT_TILE; }
 // where the chosen fields go (null: not wanted)
 struct ExportFields {
     float4 *pos4, *vel4, *acc4;
@@ -31,9 +41,7 @@ struct ExportOut {
     psamd_live_stats stats;
 };
 
-// psamd_inject (inject.hip): the entries in tiles of INJECT_TILE; the caller's arrays and the scratch (grown by the host
-// when max_count exceeds what it was sized for)
-constexpr int INJECT_TILE = 4096;
+// psamd_inject (inject.hip): the caller's arrays and the scratch
 struct InjectArgs {
     const float4 *pos4, *vel4;
     const float *fert_age;
@@ -43,18 +51,13 @@ struct InjectArgs {
     psamd_inject_result *result;
 };
 struct InjectScratch {
-    int2 *ent;        // [max_count] per entry: the record (-1 not this rank's, -2 outside the box) and its rank in the record
-    int *tcount;      // [tiles * nrec] per tile and record: the count, then the exclusive prefix over the tiles
-    int *tile_out;    // [tiles] the tile's first entry outside the box (INT_MAX: none)
+    EntryScratch e;   // keys: the record, -1 not this rank's, -2 outside the box; tile_out: [tiles], INT_MAX: none outside
     int *removed;     // [nrec] slots the inject took from the record's queue
     int *hdr;         // [2] first entry outside the box, first queue failure
     psamd_inject_result *own;   // the context's own result record (psamd_inject_result_get)
 };
 
-// psamd_remove (remove.hip): by id, the entries in tiles of REMOVE_TILE (ranked like inject's: multisplit.hpp); by box, the
-// owned slots in tiles of REMOVE_TILE.  ent / tcount / tile_out grow with max_count (the host), the rest is sized at creation.
-constexpr int REMOVE_TILE = INJECT_TILE;
-inline int remove_tiles(int slots_total) { return (slots_total + REMOVE_TILE - 1) / REMOVE_TILE; }
+// psamd_remove (remove.hip): by id the caller's entries, by box the owned slots.  All but `e` is sized at creation.
 struct RemoveArgs {
     const int *ids;
     int64_t max_count;
@@ -63,9 +66,7 @@ struct RemoveArgs {
     psamd_remove_result *result;
 };
 struct RemoveScratch {
-    int2 *ent;        // [max_count] per entry: the record of a slot's first live occurrence (else -1 - outcome) and its rank in the record
-    int *tcount;      // [tiles * nrec] per tile and record: the count, then the exclusive prefix over the tiles
-    int *tile_out;    // [tiles * 3] the tile's entries with the outcomes 1, 2, 3
+    EntryScratch e;   // keys: the record of a slot's first live occurrence, else -1 - outcome; tile_out: [tiles * 3] the outcomes 1, 2, 3
     int *claim;       // [slots] the lowest entry index that names the slot; INT_MAX between calls (a call restores what it claimed)
     int2 *ins;        // [nrec] the insert rule of a record the call adds to: offset of its first insert behind rloc, inserts the queue takes
     int *prefix;      // [slots + 1] by box: selected slots before this one in storage order
@@ -73,16 +74,15 @@ struct RemoveScratch {
     psamd_remove_result *own;    // the context's own result record (psamd_remove_result_get)
 };
 
-// psamd_potential (potential.hip): the sorted order of the own cells, and the owned slots, in tiles of POT_TILE; per tile of
-// the sorted order the partials of U (fp64), of phi's extrema and of the counts
-constexpr int POT_TILE = 4096;
+// psamd_potential (potential.hip): the sorted order of the own cells in tiles of POT_TILE (tile t goes with tile t of the
+// owned slots); per tile of the sorted order the partials of U (fp64), of phi's extrema and of the counts
+constexpr int POT_TILE = SLOT_TILE;
 struct __align__(16) PotTile {
     double u;
     float lo, hi;
     int listed, nonfinite;
     int pad[2];
 };
-inline int pot_tiles(int slots_total) { return (slots_total + POT_TILE - 1) / POT_TILE; }
 // the context's own result record (psamd_potential_result_get), and the live count psamd_download_potential copies by
 struct PotOut {
     psamd_potential_result result;
@@ -166,7 +166,7 @@ struct DeviceState {
     int *dense_gi = nullptr;      // all-pairs: [container] sorted index of the r-th particle that needs a force (cell order)
     int *dense_cell = nullptr;    // all-pairs: [container] its cell
     DevCounters *ctr = nullptr;
-    // psamd_export_live: per tile of EXPORT_TILE owned slots, the live count and the statistics' partials; the context's own result record
+    // psamd_export_live: per tile of SLOT_TILE owned slots, the live count and the statistics' partials; the context's own result record
     int *exp_count = nullptr;
     ExportTile *exp_tiles = nullptr;
     ExportOut *exp_out = nullptr;

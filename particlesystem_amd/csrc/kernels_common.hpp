@@ -21,10 +21,11 @@
 //   lifecycle.hip  free-slot queues + relocation replayed in the reference's serial order (ps.cpp:1335-1374,
 //                  app_common.cu:305-376): k_ops_hist / k_ops_scatter / k_replay_commit (lists of any length), k_moves_stage
 //   slab.hip       the messages of a multi-GPU step: halo snapshots, force records, status records, all-pairs snapshot
-//   export.hip     not part of the step: psamd_export_live, the live particles as compact arrays and their statistics
-//   inject.hip     not part of the step: psamd_inject, particles from device arrays into their segments' free slots
-//   remove.hip     not part of the step: psamd_remove, particles out of their slots and the slots back into the queues
-//   potential.hip  not part of the step: psamd_potential, every listed particle's potential and the potential energy
+//   the on-stream services, not part of the step (host side: services.hip; shared: slot_walk.hpp, multisplit.hpp)
+//   export.hip     psamd_export_live, the live particles as compact arrays and their statistics
+//   inject.hip     psamd_inject, particles from device arrays into their segments' free slots
+//   remove.hip     psamd_remove, particles out of their slots and the slots back into the queues
+//   potential.hip  psamd_potential, every listed particle's potential and the potential energy
 //
 // Reference arithmetic is reproduced operation for operation: every file is built with
 // -ffp-contract=off; where the reference evaluates in double (EPS2 add, 0.5*a*t*t) so

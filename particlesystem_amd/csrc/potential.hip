@@ -16,7 +16,7 @@
 //                 the counts of the tile in a fixed tree; and -- tile t of the owned SLOTS -- its live count.
 //   k_pot_finish  workgroup 0: the tiles in index order, the result record; workgroup 1 + t: slot tile t of phi
 //                 compacted to export order (ascending slot id: entry k pairs with psamd_export_live's entry k).
-// The launch boundaries are the only ordering between the workgroups (as in export.hip).
+// The launch boundaries are the only ordering between the workgroups; the walk over the owned slots is slot_walk.hpp's.
 //
 // Accumulation.  Terms are fp32 (differences and r.r as the force pass forms them, v_rsq_f32, one multiply).  They are
 // added in list order in fp32 CHAINS of at most POT_CHAIN terms; a chain starts at +0 with every cell (and every
@@ -25,14 +25,14 @@
 // context and on the slab that holds the particle.  Against an fp64 direct sum: 1.5e-7 relative for phi, 1e-8 for U
 // (tests/test_gpu_potential.py prints the largest error of every case).
 #include "pair_math.hpp"
+#include "slot_walk.hpp"
 
 namespace psamd {
 
-constexpr int POT_THREADS = 256;
-constexpr int POT_WAVES = POT_THREADS / 64;
+constexpr int POT_THREADS = SLOT_THREADS, POT_WAVES = SLOT_WAVES;   // (k_pot_reduce walks tile t of the sorted order and of the slots)
 constexpr int POT_ITEMS = POT_TILE / POT_THREADS;        // 16 batches of 64 entries per wave
 constexpr int POT_CHAIN = 64;                            // fp32 additions in one chain, a multiple of the group's 8
-static_assert(POT_ITEMS * POT_THREADS == POT_TILE, "a wave walks POT_ITEMS batches of 64 entries");
+static_assert(POT_ITEMS == SLOT_ITEMS, "a wave walks POT_ITEMS batches of 64 sorted entries and as many of 64 slots");
 
 __device__ __forceinline__ bool pot_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
@@ -246,9 +246,7 @@ __global__ __launch_bounds__(POT_THREADS) void k_pot_reduce(DevParams P, const i
             const int si = slot_index(P, id);
             if (phi_slot && si >= 0) phi_slot[si] = phi;
         }
-        const int i = off + 64 * k;
-        const int cl = i < P.slots_total ? cell[i] : -1;
-        live += __popcll(__ballot(cl >= 0 && cl < P.num_cells_global));
+        live += __popcll(__ballot(slot_live(P, slot_cell(P, cell, off + 64 * k))));
     }
     a.wave_reduce();
     if (lane == 0) { s_acc[wv] = a; s_live[wv] = live; }
@@ -263,42 +261,23 @@ __global__ __launch_bounds__(POT_THREADS) void k_pot_reduce(DevParams P, const i
     }
 }
 
-// Workgroup 0: U over the tiles in index order -- one serial fp64 chain, the tiles' partials through LDS a round of
-// POT_THREADS at a time (export.hip, export_finish) -- and the extrema and counts, which do not depend on the order.
+// Workgroup 0: U over the tiles in index order -- one serial fp64 chain (tile_order_sums) -- and the extrema and
+// counts, which do not depend on the order.
 __device__ __forceinline__ void pot_finish(int ntiles, const PotTile *__restrict__ tiles, const int *__restrict__ tile_count,
                                            psamd_potential_result *__restrict__ result_out, PotOut *__restrict__ own)
 {
-    __shared__ double s_u[POT_THREADS];
     __shared__ PotAcc s_acc[POT_WAVES];
     __shared__ long long s_live[POT_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     PotAcc a;
     a.init();
     long long live = 0;
-    double sum = 0.0;
-    for (int base = 0; base < ntiles; base += POT_THREADS) {
-        const int t = base + tid;
-        if (t < ntiles) {
-            const PotTile r = tiles[t];
-            s_u[tid] = r.u;
-            a.lo = fminf(a.lo, r.lo); a.hi = fmaxf(a.hi, r.hi); a.listed += r.listed; a.nonfinite += r.nonfinite;
-            live += tile_count[t];
-        }
-        __syncthreads();
-        if (tid == 0) {
-            const int m = min(POT_THREADS, ntiles - base);
-            int j = 0;
-            for (; j + 8 <= m; j += 8) {               // eight reads in flight, then their adds in order
-                double x[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++) x[i] = s_u[j + i];
-#pragma unroll
-                for (int i = 0; i < 8; i++) sum += x[i];
-            }
-            for (; j < m; j++) sum += s_u[j];
-        }
-        __syncthreads();
-    }
+    const double sum = tile_order_sums<1>(ntiles, [&](int t, double (&v)[1]) {
+        const PotTile r = tiles[t];
+        v[0] = r.u;
+        a.lo = fminf(a.lo, r.lo); a.hi = fmaxf(a.hi, r.hi); a.listed += r.listed; a.nonfinite += r.nonfinite;
+        live += tile_count[t];
+    });
     a.wave_reduce();
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) live += __shfl_xor(live, m);
@@ -318,8 +297,7 @@ __device__ __forceinline__ void pot_finish(int ntiles, const PotTile *__restrict
     }
 }
 
-// Workgroup 1 + t: slot tile t of phi to export order (export.hip, k_export_write: the tile's offset from the tile
-// counts, a wave's from the four wave counts, a lane's from the ballot).
+// Workgroup 1 + t: slot tile t of phi to export order (the walk of k_export_write).
 __global__ __launch_bounds__(POT_THREADS) void k_pot_finish(DevParams P, int ntiles, const int *__restrict__ cell,
                                                             const float *__restrict__ phi_slot,
                                                             const PotTile *__restrict__ tiles, const int *__restrict__ tile_count,
@@ -327,31 +305,22 @@ __global__ __launch_bounds__(POT_THREADS) void k_pot_finish(DevParams P, int nti
                                                             psamd_potential_result *__restrict__ result_out, PotOut *__restrict__ own)
 {
     if (blockIdx.x == 0) { pot_finish(ntiles, tiles, tile_count, result_out, own); return; }
-    __shared__ int s_before[POT_WAVES], s_live[POT_WAVES];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, t = blockIdx.x - 1;
-    int before = 0;
-    for (int i = threadIdx.x; i < t; i += POT_THREADS) before += tile_count[i];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) before += __shfl_xor(before, m);
-    const int first = t * POT_TILE + wv * 64 * POT_ITEMS + lane;
-    unsigned long long mask[POT_ITEMS];
+    const int before = tiles_before(tile_count, t);
+    const int first = slot_first(t, wv, lane);
+    unsigned long long mask[SLOT_ITEMS];
     int live = 0;
 #pragma unroll
-    for (int k = 0; k < POT_ITEMS; k++) {
-        const int i = first + 64 * k;
-        const int cl = i < P.slots_total ? cell[i] : -1;
-        mask[k] = __ballot(cl >= 0 && cl < P.num_cells_global);
+    for (int k = 0; k < SLOT_ITEMS; k++) {
+        mask[k] = __ballot(slot_live(P, slot_cell(P, cell, first + 64 * k)));
         live += __popcll(mask[k]);
     }
-    if (lane == 0) { s_before[wv] = before; s_live[wv] = live; }
-    __syncthreads();
-    int64_t at = 0;
-    for (int w = 0; w < POT_WAVES; w++) at += s_before[w] + (w < wv ? s_live[w] : 0);
+    int64_t at = wave_offset<int64_t>(before, live, wv, lane);
     if (at >= capacity) return;
 #pragma unroll
-    for (int k = 0; k < POT_ITEMS; k++) {
+    for (int k = 0; k < SLOT_ITEMS; k++) {
         const unsigned long long m = mask[k];
-        const int64_t o = at + (int64_t)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        const int64_t o = at + (int64_t)lane_rank(m);
         at += __popcll(m);
         if (((m >> lane) & 1ull) && o < capacity) phi_out[o] = phi_slot[first + 64 * k];
     }
@@ -360,7 +329,7 @@ __global__ __launch_bounds__(POT_THREADS) void k_pot_finish(DevParams P, int nti
 hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceState &d, float *phi, int64_t capacity,
                             psamd_potential_result *result_dev)
 {
-    const int ntiles = pot_tiles(P.slots_total);
+    const int ntiles = slot_tiles(P.slots_total);
     const bool want_phi = phi && capacity > 0 && ntiles > 0;
     // a live particle that is in no list of the frame keeps this quiet NaN
     if (want_phi) { const hipError_t e = launch_fill_int(st, reinterpret_cast<int *>(d.pot_slot), 0x7fc00000, (size_t)P.slots_total); if (e != hipSuccess) return e; }

@@ -12,7 +12,7 @@
 // (no hand-off between workgroups):
 //   k_remove_claim   per entry whose id is valid, owned and live: atomicMin of the entry's index into the slot's claim
 //                    word -- the slot's FIRST occurrence wins, whatever the order the atomics arrive in
-//   k_remove_rank    one workgroup per tile of REMOVE_TILE entries: the outcome of the entries that remove nothing, the
+//   k_remove_rank    one workgroup per tile of ENTRY_TILE entries: the outcome of the entries that remove nothing, the
 //                    record of the winners, their stable rank inside the tile and the tile's per-record counts
 //                    (multisplit.hpp, shared with inject.hip)
 //   k_remove_commit  one workgroup: per record the exclusive prefix of the tile counts; from the record's total its
@@ -20,8 +20,8 @@
 //   k_remove_place   per winner: the slot reset as k_unpack_aos writes a free slot, its claim word restored (the claim
 //                    array is never cleared as a whole), its id at the closed-form position of the queue, the outcome
 // By box, the candidates are the selected live particles in ascending slot id.  A record covers one contiguous slot range,
-// so a candidate's rank in its record is a prefix count in slot order, built like the export's compaction:
-//   k_remove_box_count   one workgroup per tile of REMOVE_TILE owned slots: the tile's selected and live counts
+// so a candidate's rank in its record is a prefix count in slot order (slot_walk.hpp):
+//   k_remove_box_count   one workgroup per tile of SLOT_TILE owned slots: the tile's selected and live counts
 //   k_remove_box_prefix  per slot the number of selected slots before it (the tiles' prefix rebuilt in the workgroup)
 //   k_remove_box_commit  one workgroup: per owned record its total from the prefix at its bounds, then as k_remove_commit
 //   k_remove_box_place   per selected slot: rank = prefix[slot] - prefix[record's first slot], then as k_remove_place
@@ -29,27 +29,10 @@
 // (stream order puts them between steps).  T_DATA mirror rows are left alone, as the reference's reset leaves them.
 #include "multisplit.hpp"
 
-#include <climits>
-
 namespace psamd {
 
-constexpr int REMOVE_GROUPS = REMOVE_TILE / SPLIT_THREADS;
-static_assert(REMOVE_GROUPS * SPLIT_THREADS == REMOVE_TILE, "a wave ranks REMOVE_GROUPS consecutive groups of 64 entries");
-constexpr int REMOVE_LDS_RECORDS = 8192;      // records counted in LDS (32 KB); more: in the tile's row in global memory
-constexpr int REMOVE_BOX_THREADS = 256;
-constexpr int REMOVE_BOX_WAVES = REMOVE_BOX_THREADS / 64;
-constexpr int REMOVE_BOX_ITEMS = REMOVE_TILE / REMOVE_BOX_THREADS;     // 16 batches of 64 slots per wave
 // outcome codes (include/psamd.h); an entry that removes nothing is kept as -1 - code in its record word
 enum { REM_REMOVED = 0, REM_NOT_LIVE = 1, REM_FOREIGN = 2, REM_INVALID = 3, REM_DROPPED = 4 };
-
-__device__ __forceinline__ int remove_n(const int64_t *count_dev, int64_t max_count)
-{
-    if (!count_dev) return (int)max_count;
-    const int64_t v = *count_dev;
-    return (int)(v < 0 ? 0 : v > max_count ? max_count : v);
-}
-
-__device__ __forceinline__ bool remove_live(const DevParams &P, int c) { return c >= 0 && c < P.num_cells_global; }
 
 // the storage index of an entry's slot if the entry can remove it (valid id, owned, live now), else -1 - outcome
 __device__ __forceinline__ int remove_classify(const DevParams &P, int id, const int *__restrict__ cell)
@@ -57,7 +40,7 @@ __device__ __forceinline__ int remove_classify(const DevParams &P, int id, const
     if (id < 0 || id >= P.container) return -1 - REM_INVALID;
     const int si = slot_index(P, id);
     if (si < 0) return -1 - REM_FOREIGN;
-    return remove_live(P, cell[si]) ? si : -1 - REM_NOT_LIVE;
+    return slot_live(P, cell[si]) ? si : -1 - REM_NOT_LIVE;
 }
 
 // a free slot as k_unpack_aos writes it (psamd_snapshot_restore relies on free slots being all-zero)
@@ -97,30 +80,12 @@ __device__ __forceinline__ int remove_insert(const DevParams &P, const QueueInfo
     return REM_REMOVED;
 }
 
-// sums `v` over the workgroup (int64, order-independent) into *out; s: one word of LDS per value, zeroed here
-template <int N>
-__device__ __forceinline__ void block_sum(const long long (&v)[N], unsigned long long *s, long long (&out)[N])
-{
-    if (threadIdx.x < N) s[threadIdx.x] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        long long x = v[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m);
-        if ((threadIdx.x & 63) == 0 && x) atomicAdd(&s[k], (unsigned long long)x);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) out[k] = (long long)s[k];
-}
-
 // ---- by id ----
 
 __global__ void k_remove_claim(DevParams P, int64_t max_count, const int64_t *count_dev, const int *__restrict__ ids,
                                const int *__restrict__ cell, int *__restrict__ claim)
 {
-    const int n = remove_n(count_dev, max_count);
+    const int n = entry_count(count_dev, max_count);
     const int64_t i64 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i64 >= n) return;
     const int si = remove_classify(P, ids[i64], cell);
@@ -135,20 +100,15 @@ __global__ void __launch_bounds__(SPLIT_THREADS) k_remove_rank(DevParams P, SegL
 {
     extern __shared__ int lds_cnt[];
     __shared__ int s_out[3];
-    const int n = remove_n(count_dev, max_count);
-    const int t = (int)blockIdx.x, base = t * REMOVE_TILE;
-    if (base >= n) return;
-    const int tid = (int)threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    int *cnt = LDS ? lds_cnt : tcount + (size_t)t * nrec;
-    for (int r = tid; r < nrec; r += SPLIT_THREADS) cnt[r] = 0;
+    const int n = entry_count(count_dev, max_count);
+    const int t = (int)blockIdx.x, tid = (int)threadIdx.x;
+    if (t * ENTRY_TILE >= n) return;
     if (tid < 3) s_out[tid] = 0;
-    if (!LDS) __threadfence();
-    __syncthreads();
-
-    int rec[REMOVE_GROUPS], in_rank[REMOVE_GROUPS], pop[REMOVE_GROUPS], lead[REMOVE_GROUPS];
+    SplitKeys k;
+    split_tile_begin<LDS>(t, nrec, lds_cnt, tcount, k);
 #pragma unroll
-    for (int g = 0; g < REMOVE_GROUPS; g++) {
-        const int i = base + (wave * REMOVE_GROUPS + g) * 64 + lane;
+    for (int g = 0; g < SPLIT_GROUPS; g++) {
+        const int i = split_entry(t, g), lane = tid & 63;
         int r = INT_MIN;                                           // past the last entry
         if (i < n) {
             const int id = ids[i];
@@ -156,22 +116,15 @@ __global__ void __launch_bounds__(SPLIT_THREADS) k_remove_rank(DevParams P, SegL
             // a later occurrence of a slot finds it gone at its turn: not live
             r = si < 0 ? si : claim[si] == i ? segment_record_of_slot(S, id) : -1 - REM_NOT_LIVE;
         }
-        rec[g] = r;
-        split_group_rank(r, lane, in_rank[g], pop[g], lead[g]);
+        k.rec[g] = r;
+        split_group_rank(r, lane, k.in_rank[g], k.pop[g], k.lead[g]);
 #pragma unroll
         for (int code = REM_NOT_LIVE; code <= REM_INVALID; code++) {
             const unsigned long long m = __ballot(r == -1 - code);
             if (lane == 0 && m) atomicAdd(&s_out[code - 1], __popcll(m));
         }
     }
-    int at[REMOVE_GROUPS];
-    split_take_turns<REMOVE_GROUPS, !LDS>(rec, in_rank, pop, lead, cnt, wave, lane, at);
-#pragma unroll
-    for (int g = 0; g < REMOVE_GROUPS; g++) {
-        const int i = base + (wave * REMOVE_GROUPS + g) * 64 + lane;
-        if (i < n) ent[i] = make_int2(rec[g], rec[g] >= 0 ? at[g] : 0);
-    }
-    if (LDS) for (int r = tid; r < nrec; r += SPLIT_THREADS) tcount[(size_t)t * nrec + r] = cnt[r];
+    split_tile_store<LDS>(t, n, nrec, k, ent, tcount);
     if (tid < 3) tile_out[3 * t + tid] = s_out[tid];
 }
 
@@ -179,8 +132,7 @@ __device__ __forceinline__ void remove_write_result(const long long (&v)[6], psa
 {
     psamd_remove_result res;
     res.done = v[0]; res.removed = v[1]; res.not_live = v[2]; res.foreign = v[3]; res.invalid = v[4]; res.dropped = v[5];
-    *own = res;
-    if (out && out != own) *out = res;
+    write_result(own, out, res);
 }
 
 __global__ void __launch_bounds__(1024) k_remove_commit(int nrec, int64_t max_count, const int64_t *count_dev, int *__restrict__ tcount,
@@ -188,7 +140,7 @@ __global__ void __launch_bounds__(1024) k_remove_commit(int nrec, int64_t max_co
                                                         psamd_remove_result *own, psamd_remove_result *out)
 {
     __shared__ unsigned long long s_sum[6];
-    const int n = remove_n(count_dev, max_count), tiles = (int)(((int64_t)n + REMOVE_TILE - 1) / REMOVE_TILE);
+    const int n = entry_count(count_dev, max_count), tiles = entry_tiles(n);
     const int tid = (int)threadIdx.x;
     long long v[6] = {0, 0, 0, 0, 0, 0}, sum[6];
     for (int r = tid; r < nrec; r += 1024) {
@@ -208,7 +160,7 @@ __global__ void k_remove_place(DevParams P, int nrec, int64_t max_count, const i
                                const int2 *__restrict__ ins, int *__restrict__ queue, int *__restrict__ claim,
                                int *__restrict__ outcome, float4 *d_pos4, float4 *d_vel4, float4 *d_acc4, int *d_cell, uint8_t *d_pflags)
 {
-    const int n = remove_n(count_dev, max_count);
+    const int n = entry_count(count_dev, max_count);
     const int64_t i64 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i64 >= n) return;
     const int i = (int)i64;
@@ -216,7 +168,7 @@ __global__ void k_remove_place(DevParams P, int nrec, int64_t max_count, const i
     int code = -1 - e.x;
     if (e.x >= 0) {
         const int id = ids[i], si = slot_index(P, id);
-        const int k = e.y + tcount[(size_t)(i / REMOVE_TILE) * nrec + e.x];
+        const int k = e.y + tcount[(size_t)(i / ENTRY_TILE) * nrec + e.x];
         remove_reset(si, d_pos4, d_vel4, d_acc4, d_cell, d_pflags);
         claim[si] = INT_MAX;
         code = remove_insert(P, qinfo, ins, queue, e.x, k, id);
@@ -237,24 +189,24 @@ struct RemoveBox {
     }
 };
 
-// wave w of tile t walks the slots [t * REMOVE_TILE + w * 64 * REMOVE_BOX_ITEMS, + 64 * REMOVE_BOX_ITEMS), 64 at a time
+// slot i (storage order) is live, and selected
 __device__ __forceinline__ bool remove_box_selected(const DevParams &P, const RemoveBox &B, int i, const int *cell, const float4 *pos4,
                                                     bool &live)
 {
-    live = i < P.slots_total && remove_live(P, cell[i]);
+    live = i < P.slots_total && slot_live(P, cell[i]);
     return live && B.selects(pos4[i]);
 }
 
-__global__ void __launch_bounds__(REMOVE_BOX_THREADS) k_remove_box_count(DevParams P, RemoveBox B, const int *__restrict__ cell,
+__global__ void __launch_bounds__(SLOT_THREADS) k_remove_box_count(DevParams P, RemoveBox B, const int *__restrict__ cell,
                                                                          const float4 *__restrict__ pos4, int *__restrict__ tile_sel,
                                                                          int *__restrict__ tile_live)
 {
-    __shared__ int s_n[REMOVE_BOX_WAVES][2];
+    __shared__ int s_n[SLOT_WAVES][2];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, t = blockIdx.x;
-    const int first = t * REMOVE_TILE + wv * 64 * REMOVE_BOX_ITEMS + lane;
+    const int first = slot_first(t, wv, lane);
     int sel = 0, live = 0;
 #pragma unroll 4
-    for (int k = 0; k < REMOVE_BOX_ITEMS; k++) {
+    for (int k = 0; k < SLOT_ITEMS; k++) {
         bool l;
         const bool s = remove_box_selected(P, B, first + 64 * k, cell, pos4, l);
         sel += __popcll(__ballot(s));
@@ -264,44 +216,37 @@ __global__ void __launch_bounds__(REMOVE_BOX_THREADS) k_remove_box_count(DevPara
     __syncthreads();
     if (threadIdx.x == 0) {
         int a = 0, b = 0;
-        for (int w = 0; w < REMOVE_BOX_WAVES; w++) { a += s_n[w][0]; b += s_n[w][1]; }
+        for (int w = 0; w < SLOT_WAVES; w++) { a += s_n[w][0]; b += s_n[w][1]; }
         tile_sel[t] = a; tile_live[t] = b;
     }
 }
 
 // prefix[i]: selected slots before storage index i; prefix[slots_total]: all of them
-__global__ void __launch_bounds__(REMOVE_BOX_THREADS) k_remove_box_prefix(DevParams P, RemoveBox B, int ntiles, const int *__restrict__ cell,
+__global__ void __launch_bounds__(SLOT_THREADS) k_remove_box_prefix(DevParams P, RemoveBox B, int ntiles, const int *__restrict__ cell,
                                                                           const float4 *__restrict__ pos4,
                                                                           const int *__restrict__ tile_sel, int *__restrict__ prefix)
 {
-    __shared__ int s_before[REMOVE_BOX_WAVES], s_sel[REMOVE_BOX_WAVES];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, t = blockIdx.x;
-    int before = 0;
-    for (int i = threadIdx.x; i < t; i += REMOVE_BOX_THREADS) before += tile_sel[i];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) before += __shfl_xor(before, m);
-    const int first = t * REMOVE_TILE + wv * 64 * REMOVE_BOX_ITEMS + lane;
-    unsigned long long mask[REMOVE_BOX_ITEMS];
+    const int before = tiles_before(tile_sel, t);
+    const int first = slot_first(t, wv, lane);
+    unsigned long long mask[SLOT_ITEMS];
     int sel = 0;
 #pragma unroll
-    for (int k = 0; k < REMOVE_BOX_ITEMS; k++) {
+    for (int k = 0; k < SLOT_ITEMS; k++) {
         bool l;
         mask[k] = __ballot(remove_box_selected(P, B, first + 64 * k, cell, pos4, l));
         sel += __popcll(mask[k]);
     }
-    if (lane == 0) { s_before[wv] = before; s_sel[wv] = sel; }
-    __syncthreads();
-    int at = 0;
-    for (int w = 0; w < REMOVE_BOX_WAVES; w++) at += s_before[w] + (w < wv ? s_sel[w] : 0);
+    int at = wave_offset<int>(before, sel, wv, lane);
 #pragma unroll
-    for (int k = 0; k < REMOVE_BOX_ITEMS; k++) {
+    for (int k = 0; k < SLOT_ITEMS; k++) {
         const unsigned long long m = mask[k];
         const int i = first + 64 * k;
-        if (i < P.slots_total) prefix[i] = at + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        if (i < P.slots_total) prefix[i] = at + lane_rank(m);
         at += __popcll(m);
     }
     // (the tile's last wave and lane have walked the whole tile)
-    if (t == ntiles - 1 && threadIdx.x == REMOVE_BOX_THREADS - 1) prefix[P.slots_total] = at;
+    if (t == ntiles - 1 && threadIdx.x == SLOT_THREADS - 1) prefix[P.slots_total] = at;
 }
 
 __global__ void __launch_bounds__(1024) k_remove_box_commit(DevParams P, int nrec, int ntiles, const int *__restrict__ prefix,
@@ -324,12 +269,12 @@ __global__ void __launch_bounds__(1024) k_remove_box_commit(DevParams P, int nre
     if (tid == 0) remove_write_result(sum, own, out);
 }
 
-__global__ void __launch_bounds__(REMOVE_BOX_THREADS) k_remove_box_place(DevParams P, SegLayout S, RemoveBox B, const int *__restrict__ prefix,
+__global__ void __launch_bounds__(SLOT_THREADS) k_remove_box_place(DevParams P, SegLayout S, RemoveBox B, const int *__restrict__ prefix,
                                                                          const QueueInfo *__restrict__ qinfo, const int2 *__restrict__ ins,
                                                                          int *__restrict__ queue, float4 *d_pos4, float4 *d_vel4,
                                                                          float4 *d_acc4, int *d_cell, uint8_t *d_pflags)
 {
-    const int i = (int)(blockIdx.x * REMOVE_BOX_THREADS + threadIdx.x);
+    const int i = (int)(blockIdx.x * SLOT_THREADS + threadIdx.x);
     bool live;
     if (!remove_box_selected(P, B, i, d_cell, d_pos4, live)) return;
     const int id = slot_of_index(P, i), r = segment_record_of_slot(S, id);
@@ -341,20 +286,20 @@ __global__ void __launch_bounds__(REMOVE_BOX_THREADS) k_remove_box_place(DevPara
 hipError_t launch_remove_ids(hipStream_t st, const DevParams &P, const SegLayout &S, const DeviceState &d, int nrec, const RemoveArgs &a,
                              const RemoveScratch &s)
 {
-    const int64_t tiles = (a.max_count + REMOVE_TILE - 1) / REMOVE_TILE;
+    const int64_t tiles = (a.max_count + ENTRY_TILE - 1) / ENTRY_TILE;
     const unsigned blocks = (unsigned)((a.max_count + 255) / 256);
     k_remove_claim<<<blocks, 256, 0, st>>>(P, a.max_count, a.count_dev, a.ids, d.cell, s.claim);
     PS_LAUNCH_CHECK();
-    if (nrec <= REMOVE_LDS_RECORDS)
+    if (nrec <= SPLIT_LDS_RECORDS)
         k_remove_rank<true><<<(unsigned)tiles, SPLIT_THREADS, (size_t)nrec * sizeof(int), st>>>(P, S, nrec, a.max_count, a.count_dev, a.ids, d.cell,
-                                                                                              s.claim, s.ent, s.tcount, s.tile_out);
+                                                                                              s.claim, s.e.ent, s.e.tcount, s.e.tile_out);
     else
-        k_remove_rank<false><<<(unsigned)tiles, SPLIT_THREADS, 0, st>>>(P, S, nrec, a.max_count, a.count_dev, a.ids, d.cell, s.claim, s.ent,
-                                                                      s.tcount, s.tile_out);
+        k_remove_rank<false><<<(unsigned)tiles, SPLIT_THREADS, 0, st>>>(P, S, nrec, a.max_count, a.count_dev, a.ids, d.cell, s.claim, s.e.ent,
+                                                                      s.e.tcount, s.e.tile_out);
     PS_LAUNCH_CHECK();
-    k_remove_commit<<<1, 1024, 0, st>>>(nrec, a.max_count, a.count_dev, s.tcount, s.tile_out, d.qinfo, s.ins, s.own, a.result);
+    k_remove_commit<<<1, 1024, 0, st>>>(nrec, a.max_count, a.count_dev, s.e.tcount, s.e.tile_out, d.qinfo, s.ins, s.own, a.result);
     PS_LAUNCH_CHECK();
-    k_remove_place<<<blocks, 256, 0, st>>>(P, nrec, a.max_count, a.count_dev, a.ids, s.ent, s.tcount, d.qinfo, s.ins, d.queue, s.claim,
+    k_remove_place<<<blocks, 256, 0, st>>>(P, nrec, a.max_count, a.count_dev, a.ids, s.e.ent, s.e.tcount, d.qinfo, s.ins, d.queue, s.claim,
                                            a.outcome, d.pos4, d.vel4, d.acc4, d.cell, d.pflags);
     PS_LAUNCH_CHECK();
     return hipSuccess;
@@ -363,20 +308,20 @@ hipError_t launch_remove_ids(hipStream_t st, const DevParams &P, const SegLayout
 hipError_t launch_remove_box(hipStream_t st, const DevParams &P, const SegLayout &S, const DeviceState &d, int nrec, const float lo[3],
                              const float hi[3], bool outside, psamd_remove_result *result, const RemoveScratch &s)
 {
-    const int ntiles = remove_tiles(P.slots_total);
+    const int ntiles = slot_tiles(P.slots_total);
     RemoveBox B;
     for (int k = 0; k < 3; k++) { B.lo[k] = lo[k]; B.hi[k] = hi[k]; }
     B.outside = outside ? 1 : 0;
     if (ntiles > 0) {
-        k_remove_box_count<<<ntiles, REMOVE_BOX_THREADS, 0, st>>>(P, B, d.cell, d.pos4, s.tile_sel, s.tile_live);
+        k_remove_box_count<<<ntiles, SLOT_THREADS, 0, st>>>(P, B, d.cell, d.pos4, s.tile_sel, s.tile_live);
         PS_LAUNCH_CHECK();
-        k_remove_box_prefix<<<ntiles, REMOVE_BOX_THREADS, 0, st>>>(P, B, ntiles, d.cell, d.pos4, s.tile_sel, s.prefix);
+        k_remove_box_prefix<<<ntiles, SLOT_THREADS, 0, st>>>(P, B, ntiles, d.cell, d.pos4, s.tile_sel, s.prefix);
         PS_LAUNCH_CHECK();
     }
     k_remove_box_commit<<<1, 1024, 0, st>>>(P, ntiles > 0 ? nrec : 0, ntiles, s.prefix, s.tile_live, d.qinfo, s.ins, s.own, result);
     PS_LAUNCH_CHECK();
     if (ntiles > 0) {
-        k_remove_box_place<<<ntiles * (REMOVE_TILE / REMOVE_BOX_THREADS), REMOVE_BOX_THREADS, 0, st>>>(P, S, B, s.prefix, d.qinfo, s.ins, d.queue,
+        k_remove_box_place<<<ntiles * SLOT_ITEMS, SLOT_THREADS, 0, st>>>(P, S, B, s.prefix, d.qinfo, s.ins, d.queue,
                                                                                                       d.pos4, d.vel4, d.acc4, d.cell, d.pflags);
         PS_LAUNCH_CHECK();
     }

@@ -15,7 +15,7 @@ import torch
 import particlesystem_amd as ps
 from particlesystem_amd import _build as psbuild
 from particlesystem_amd.slab import step_local
-from util import GOLDEN, O, cloud, explosion_rng, g2_cloud, oracle_cfg_from
+from util import GOLDEN, O, SENTINEL, capacities, cloud, explosion_rng, g2_cloud, oracle_cfg_from, ragged
 
 pytestmark = pytest.mark.gpu
 
@@ -408,3 +408,42 @@ def test_driver_writes_frames(tmp_path):
     m = re.search(r"state-hash ([0-9a-f]{16}) live (\d+)", out)
     assert m and int(m.group(1), 16) == digest(o.particles) and int(m.group(2)) == len(want), out
     o.close()
+
+
+# ---- a container that is no whole number of slot tiles ------------------------------------------------------------------
+# The default container is 4096 * 514 slots.  This one has 125 segments of 144 slots = 18 000: four tiles of 4096 and one of
+# 1616, whose slots are corner segments -- every cell of a uniform cloud fills some of them (util.ragged).
+
+def test_ragged_last_tile():
+    g, rec = ragged()
+    got = g.export_live(ALL)
+    assert int(got["id"].max()) == rec["id"].max()
+    check_export(got, rec, "ragged last tile (export_live)")
+    check_stats(got["stats"], rec, "ragged last tile (stats)")
+    check_export(g.download_live(ALL), rec, "ragged last tile (download_live)")
+    g.close()
+
+
+def test_ragged_capacity_cuts():
+    g, rec = ragged(seed=32)
+    live, want = len(rec), fields_of(rec)
+    dev = torch.device("cuda", 0)
+    for cap in capacities(live):
+        m = min(live, cap)
+        arrs = {name: torch.full((cap + 1, width) if width > 1 else (cap + 1,), SENTINEL, dtype=torch.int32, device=dev)
+                for name, _, width, _ in ps._EXPORT_FIELDS}
+        count = torch.full((1,), -1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        spec = ps.Export(fields=ALL, capacity=cap, count_dev=count.data_ptr(), **{k: t.data_ptr() for k, t in arrs.items()})
+        assert g.lib.psamd_export_live(g.h, C.byref(spec)) == 0
+        sync(g)
+        assert count.item() == live, (cap, count.item(), live)
+        for k, t in arrs.items():
+            a = t.cpu().numpy()
+            same_bits(a[:m].view(np.float32) if k.endswith("4") else a[:m], want[k][:m], "capacity %d: %s" % (cap, k))
+            assert (a[m:] == SENTINEL).all(), "capacity %d: %s written past entry %d" % (cap, k, m)
+        got = g.download_live(ALL, capacity=cap)
+        assert got["count"] == live
+        for k in arrs:
+            same_bits(got[k], want[k][:m], "download_live capacity %d: %s" % (cap, k))
+    g.close()

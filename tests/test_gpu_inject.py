@@ -386,3 +386,27 @@ def test_arguments_and_capture():
     same_state(a, b, "2 steps after the refused capture")
     for g in (a, b):
         g.close()
+
+
+# ---- more queue records than the tile's counts have room for in LDS ---------------------------------------------------------
+# queue_infos = (2 * chunk_factor + 1)^3 = 9261 > 8192: the tile counts live in the tile's row in global memory
+
+MANY_RECORDS = dict(chunk_factor=10, chunk_dim=3, x_factor=2, max_particles_num=27000)
+
+
+def many_records():
+    g = ps.ParticleSystem(ps.default_config(**MANY_RECORDS))
+    assert g.sizes.queue_info_size > 8192, g.sizes.queue_info_size
+    return g
+
+
+def test_more_than_8192_queue_records():
+    a, b = many_records(), many_records()
+    pos4, vel4, fert = batch(a, 8192 + 100, 41)          # three tiles of entries, the last one ragged
+    f = fill(a, pos4, vel4, fert)
+    r = inject(b, pos4, vel4, fert)
+    assert f[0] == OK and f[1] == len(pos4)
+    same_as_fill(f, r, "9261 records")
+    same_state(a, b, "9261 records")
+    a.close()
+    b.close()

@@ -21,7 +21,7 @@ import torch
 
 import particlesystem_amd as ps
 from particlesystem_amd import slab
-from util import cloud
+from util import SENTINEL, capacities, cloud, ragged
 
 pytestmark = pytest.mark.gpu
 
@@ -587,4 +587,49 @@ def test_state_and_arguments():
     g.calc_forces()
     assert call() == ERR_STATE                                   # the frame has ended
     g.synchronize()
+    g.close()
+
+
+# ---- a container that is no whole number of slot tiles (tests/test_gpu_export.py, ragged) ---------------------------------
+
+def test_ragged_last_tile_pairs_with_the_export():
+    g, rec = ragged(seed=33)
+    frame(g)
+    phi, ids, res = by_id(g)
+    fr = Frame(g)
+    live = g.live_count()
+    assert len(ids) == live == res["listed"] and ids.max() >= 16384 and (np.diff(ids) > 0).all()
+    check_against(fr, phi, res, fr.phi_cutoff(), "ragged last tile")
+    d = g.download_potential()
+    assert np.array_equal(bits(d["phi"]), bits(res["phi"]))
+    g.close()
+
+
+def test_ragged_capacity_cuts():
+    g, rec = ragged(seed=34)
+    frame(g)
+    full = g.potential(phi=True)
+    live = g.live_count()
+    assert len(full["phi"]) == live == full["listed"]
+    want = bits(full["phi"])
+    dev = torch.device("cuda", 0)
+    for cap in capacities(live):
+        m = min(live, cap)
+        out = torch.full((cap + 1,), SENTINEL, dtype=torch.int32, device=dev)
+        result = torch.zeros(C.sizeof(ps.PotentialResult), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        spec = ps.Potential(phi=out.data_ptr() if cap > 0 else None, capacity=cap, result_dev=result.data_ptr())
+        assert g.lib.psamd_potential(g.h, C.byref(spec)) == 0
+        torch.cuda.ExternalStream(g.stream()).synchronize()
+        a = out.cpu().numpy()
+        assert np.array_equal(a[:m].view(np.uint32), want[:m]), "capacity %d: phi differs" % cap
+        assert (a[m:] == SENTINEL).all(), "capacity %d: written past entry %d" % (cap, m)
+        r = ps.PotentialResult.from_buffer_copy(result.cpu().numpy().tobytes()).to_dict()
+        assert r == {k: full[k] for k in full if k != "phi"}, (cap, r)
+        # the wrappers: the count they cut by is the live count
+        short = g.potential(phi=True, capacity=cap)
+        assert len(short["phi"]) == m and np.array_equal(bits(short["phi"]), want[:m]), cap
+        if cap > 0:
+            d = g.download_potential(capacity=cap)
+            assert len(d["phi"]) == m and np.array_equal(bits(d["phi"]), want[:m]), cap
     g.close()

@@ -14,8 +14,8 @@ import torch
 import particlesystem_amd as ps
 import remove_model as M
 from particlesystem_amd.slab import merge_owned, step_local
-from test_gpu_inject import batch, dev, hip_runtime, inject, same_state, start, state
-from util import assert_same_particles, cloud
+from test_gpu_inject import batch, dev, hip_runtime, inject, many_records, same_state, start, state
+from util import SLOT_TILE, assert_same_particles, cloud, ragged
 
 pytestmark = pytest.mark.gpu
 
@@ -407,3 +407,44 @@ def test_snapshot_after_a_remove():
     assert qi.tobytes() == saved[1].tobytes() and np.array_equal(q, saved[2])
     g.close()
     o.close()
+
+
+def same_as_model(g, want, what):
+    for got, w, name in zip(state(g), want, ("particles", "QUEUE_INFO records", "queues")):
+        assert got.tobytes() == w.tobytes(), "%s: %s differ" % (what, name)
+
+
+@pytest.mark.parametrize("outside", [False, True])
+def test_by_box_ragged_last_tile(outside):
+    """18 000 owned slots: four slot tiles and one of 1616, the selection in all five"""
+    g, rec = ragged(seed=35)
+    lo, hi = (-12.5, -20.0, -3.0), (15.0, 9.25, 20.0)
+    sel = inside(np.stack([rec["x"], rec["y"], rec["z"]], 1), lo, hi) != outside
+    ids = rec["id"][sel].astype(np.int32)
+    assert set(ids // SLOT_TILE) == set(range((g.owned_slots() + SLOT_TILE - 1) // SLOT_TILE)) and 0 < len(ids) < len(rec)
+    p2, qi2, q2, out, want = M.closed_form(g.sizes, g.sizes.num_cells, *state(g), ids)
+    assert (out == M.REMOVED).all()
+    r = g.remove(box=(lo, hi), outside=outside)
+    assert r == dict(want, done=len(rec)) and g.remove_result() == r, (r, want)
+    same_as_model(g, (p2, qi2, q2), "by box, ragged last tile")
+    g.close()
+
+
+def test_by_id_with_more_than_8192_queue_records():
+    """9261 records: the tile counts in global memory; three tiles of entries, the last one ragged"""
+    g = many_records()
+    pos4, vel4, fert = batch(g, 8192 + 100, 42)
+    assert inject(g, pos4, vel4, fert)["placed"] == len(pos4)
+    p, qi, q = state(g)
+    live = np.nonzero(p["cell"] >= 0)[0]
+    free = np.nonzero(p["cell"] < 0)[0]
+    rng = np.random.default_rng(42)
+    ids = np.concatenate([live, rng.choice(live, 60), [g.sizes.container_size, int(free[len(free) // 2])]]).astype(np.int32)
+    rng.shuffle(ids)
+    assert len(ids) >= 8193 and len(ids) % TILE != 0
+    p2, qi2, q2, s_out, want = M.closed_form(g.sizes, g.sizes.num_cells, p, qi, q, ids)
+    r, out = remove_ids(g, ids)
+    assert np.array_equal(out, s_out), np.nonzero(out != s_out)[0][:10]
+    assert r == want and want["removed"] == len(live) and want["invalid"] == 1 and want["not_live"] == 61, (r, want)
+    same_as_model(g, (p2, qi2, q2), "by id, 9261 records")
+    g.close()

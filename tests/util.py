@@ -64,3 +64,30 @@ def assert_same_particles(gpu_p, ora_p, what=""):
     rows, cols = np.nonzero(ga != oa)
     raise AssertionError("%s records differ only in padding bytes: %d slots, first slot %d byte %d gpu %d oracle %d, cell there %d" %
                          (what, len(set(rows.tolist())), rows[0], cols[0], ga[rows[0], cols[0]], oa[rows[0], cols[0]], gpu_p["cell"][rows[0]]))
+
+
+# ---- a container that is no whole number of slot tiles (the GPU tests of export, potential and remove) ----------------------
+SLOT_TILE = 4096          # the slot walk's tile (slot_walk.hpp)
+RAGGED = dict(chunk_factor=2, chunk_dim=4, max_particles_num=4096)
+CAPACITIES = (0, 1, 63, 64, 65, -1, 0, +1)          # the last three: relative to the live count
+SENTINEL = -0x12345679
+
+
+def ragged(seed=31, **over):
+    """(context, its live records): uniform_cloud(4096, seed) in 125 segments of 144 slots = 18 000 slots, four tiles and
+    one of 1616, with a live particle in the partial tile"""
+    import particlesystem_amd as ps
+    g = ps.ParticleSystem(ps.default_config(**RAGGED, **over))
+    rng = np.random.default_rng(seed)
+    g.fill_particles(g.uniform_cloud(4096, seed), age=rng.uniform(0.2, 9.0, 4096).astype(np.float32), fert_age=np.float32(1e6),
+                     w=rng.uniform(20.0, 100.0, 4096).astype(np.float32), vxyz=rng.uniform(-20, 20, (4096, 3)).astype(np.float32))
+    slots = g.owned_slots()
+    assert slots % SLOT_TILE != 0 and slots > SLOT_TILE, slots
+    p = g.download_particles()
+    rec = p[(p["cell"] >= 0) & (p["cell"] < g.sizes.num_cells)]
+    assert rec["id"].max() >= max(8192, slots // SLOT_TILE * SLOT_TILE), (rec["id"].max(), slots)
+    return g, rec
+
+
+def capacities(live):
+    return [c if k < 5 else live + c for k, c in enumerate(CAPACITIES)]

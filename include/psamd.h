@@ -47,7 +47,10 @@ typedef enum psamd_status {
 
 /* config.flags */
 #define PSAMD_FLAG_EXPLOSIONS   0x1u  /* births enabled (ps.cpp:1306-1333) with the counter-based RNG below */
-#define PSAMD_FLAG_FAST_MATH    0x2u  /* FMA/rsq pair arithmetic: NOT bit-identical to the reference, see DESIGN.md */
+#define PSAMD_FLAG_FAST_MATH    0x2u  /* FMA/rsq pair arithmetic: NOT bit-identical to the reference, see DESIGN.md.  Only the pair
+                                         sums differ (everything after them is the exact path's); every pair is formed by the same
+                                         operations in the same order whatever the launch shape, so the mode gives the same bytes
+                                         from run to run, with graphs on or off, and as the union of slabs */
 #define PSAMD_FLAG_ALL_PAIRS    0x4u  /* force walk over EVERY cell, not only the 27-cell stencil (the reference has only the
                                          cutoff, app.cu:352-452): the stencil first, in the reference's order, then the other
                                          cells in index order -- so a cloud that fits a 2x2x2 block of cells gets the cutoff
@@ -55,7 +58,9 @@ typedef enum psamd_status {
                                          contributes the snapshot of its own cells to an all-gather once per step
                                          (allg_out -> allg_in below) and walks the gathered buffer in the same order. */
 #define PSAMD_FLAG_EULER        0x8u  /* position update x += v*dt (explicit Euler) instead of the reference's
-                                         x += v*dt + 0.5*a*dt*dt (ps.cpp:1274-1276); the velocity update is the same */
+                                         x += v*dt + 0.5*a*dt*dt (ps.cpp:1274-1276); the velocity update is the same.
+                                         dx is the fp32 product v*dt alone; the MAX_DX clamp, the wrap and the segment
+                                         change act on it as they do on the reference's dx */
 
 /* Runtime form of the reference's compile-time configuration, common.h:12-70.
  * psamd_default_config() fills in the shipped values. */
@@ -90,8 +95,14 @@ typedef struct psamd_config {
     int32_t  cuts[PSAMD_MAX_RANKS + 1];
     /* Not in the reference (BASELINE.json asks for them; nothing there can pin them): */
     double   drag;               /* linear drag k >= 0: the acceleration that is integrated and stored is a - k*v; 0 = the
-                                    reference's arithmetic, untouched                                          */
-    double   force_sign;         /* +1 gravity (reference), -1 repulsion: multiplies every mass in the force term; 0 reads as +1 */
+                                    reference's arithmetic, untouched.  For every particle the step integrates, per axis and in
+                                    fp32: a' = RN(a - RN(k*v)) with k = (float)drag -- two roundings, no fused multiply-add;
+                                    a' enters the position and the velocity update alike and is what ax, ay, az keep.  Where k*v is
+                                    not a number, a' is that not-a-number bit for bit (its sign is not left to the subtraction) */
+    double   force_sign;         /* +1 gravity (reference), -1 repulsion: multiplies every mass in the force term; 0 reads as +1.
+                                    The collision scan does not see it; w in the particle records and in the T_DATA rows stays
+                                    unsigned (the sign lives in the pair stage's own snapshot, in the halo messages and in the
+                                    all-gather block) */
     int32_t  xfer_cap_max;       /* how far the transfer messages may grow: their BUFFERS have this room from the start, the bytes that
                                     travel are xfer_cap's and follow the traffic.  Every rank reports in its status record how many records it
                                     sent in the step before; all ranks see all records and apply the same rule -- twice (the busiest rank's

@@ -110,6 +110,7 @@ def lib():
         L.pso_step.argtypes = [vp, ci]
         L.pso_set_rng.argtypes = [vp, RNG_FN, vp]
         L.pso_set_explosions.argtypes = [vp, ci]
+        L.pso_set_options.argtypes = [vp, C.c_double, C.c_double, ci]
         for n in ("pso_particles", "pso_tdata_buf", "pso_queue", "pso_queue_info_buf",
                   "pso_chunkgrid", "pso_cellgrid", "pso_gridmax", "pso_pkgdistrib"):
             getattr(L, n).argtypes = [vp]
@@ -183,6 +184,15 @@ def default_config(**over):
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg
+
+
+PSAMD_FLAG_EULER = 0x8      # include/psamd.h
+
+
+def options_from(cfg):
+    """psamd Config -> the arguments of System.set_options (what pso_config has no field for): drag, the force sign (0 reads
+    as +1) and the Euler switch.  The one place where the mapping is written."""
+    return dict(drag=float(cfg.drag), force_sign=-1.0 if cfg.force_sign < 0 else 1.0, euler=bool(cfg.flags & PSAMD_FLAG_EULER))
 
 
 def derive(cfg):
@@ -327,6 +337,10 @@ class System:
 
     def set_explosions(self, on):
         self.L.pso_set_explosions(self.h, 1 if on else 0)
+
+    def set_options(self, drag=0.0, force_sign=1.0, euler=False):
+        """include/psamd.h's config.drag, config.force_sign and PSAMD_FLAG_EULER; untouched = the pinned path"""
+        self.L.pso_set_options(self.h, float(drag), float(force_sign), 1 if euler else 0)
 
     def set_rng(self, fn):
         """fn(parent_id, step) -> ((i0,i1,i2), u)"""

@@ -40,6 +40,11 @@ struct pso_system {
     void           *rng_user;
     int             explosions;
     int             step;
+    /* the options nothing in the reference can pin (include/psamd.h: config.drag, config.force_sign,
+     * PSAMD_FLAG_EULER); pso_set_options.  As created: 0, +1, 0 -- the reference's arithmetic, untouched */
+    float           drag;
+    float           force_sign;
+    int             euler;
 };
 
 /* ------------------------------------------------------------------ config */
@@ -373,8 +378,8 @@ void pso_q_insert(pso_queue_info *qi, int *queue, const pso_derived *d, int seg_
 /* app_common.cu:236-267.  Softened gravity of snapshot body bj on bi.
  * distSq is fp32; EPS2 is a double literal, so the add is done in double and
  * rounded to float; the cube, sqrtf and the reciprocal are fp32. */
-void pso_body_body_interaction(const pso_config *c, const pso_derived *d,
-                               const pso_particle *bi, const pso_tdata *bj, float ai[3])
+static void interaction_signed(const pso_config *c, const pso_derived *d,
+                               const pso_particle *bi, const pso_tdata *bj, float sign, float ai[3])
 {
     float rx, ry, rz, distSq, distSqr, distSixth, invDistCube, s;
     if ((double)bi->age < d->kid_age || (double)bj->age < d->kid_age) return;
@@ -383,8 +388,15 @@ void pso_body_body_interaction(const pso_config *c, const pso_derived *d,
     distSqr = (float)((double)distSq + c->eps2);
     distSixth = distSqr * distSqr * distSqr;
     invDistCube = 1.0f / sqrtf(distSixth);
-    s = bj->w * invDistCube;
+    /* psamd.h, config.force_sign: "multiplies every mass in the force term" (sign = +1: w * 1 is w, to the bit) */
+    s = (sign * bj->w) * invDistCube;
     ai[0] += rx * s; ai[1] += ry * s; ai[2] += rz * s;
+}
+
+void pso_body_body_interaction(const pso_config *c, const pso_derived *d,
+                               const pso_particle *bi, const pso_tdata *bj, float ai[3])
+{
+    interaction_signed(c, d, bi, bj, 1.0f, ai);
 }
 
 /* app_common.cu:269-301.  0 none, 1 survive (bi has the higher id), 2 kill. */
@@ -408,7 +420,7 @@ static float clamp_mag(float v, float lim) /* ps.cpp:1279-1281, 1294-1296 */
 
 /* ps.cpp:1268-1302.  dx = v*t (fp32) + 0.5*a*t*t (double), rounded once to
  * float; v += a*t in fp32; both clamped per axis; age += t. */
-void pso_integrate(const pso_config *c, const pso_derived *d, pso_particle *p)
+static void integrate_opt(const pso_config *c, const pso_derived *d, pso_particle *p, int euler)
 {
     float t = (float)c->dt;
     float dx = (float)(p->vx * t + 0.5 * p->ax * t * t);
@@ -416,12 +428,39 @@ void pso_integrate(const pso_config *c, const pso_derived *d, pso_particle *p)
     float dz = (float)(p->vz * t + 0.5 * p->az * t * t);
     float dmaxr = (float)d->max_dx, maxv = (float)c->max_v;
     float rx, ry, rz, vx, vy, vz;
+    /* psamd.h, PSAMD_FLAG_EULER: x += v*dt -- the fp32 product alone, before the MAX_DX clamp */
+    if (euler) { dx = p->vx * t; dy = p->vy * t; dz = p->vz * t; }
     dx = clamp_mag(dx, dmaxr); dy = clamp_mag(dy, dmaxr); dz = clamp_mag(dz, dmaxr);
     rx = p->x + dx; ry = p->y + dy; rz = p->z + dz;
     pso_set_pos_x(c, d, p, rx, ry, rz);
     vx = p->vx + p->ax * t; vy = p->vy + p->ay * t; vz = p->vz + p->az * t;
     p->vx = clamp_mag(vx, maxv); p->vy = clamp_mag(vy, maxv); p->vz = clamp_mag(vz, maxv);
     p->age += t;
+}
+
+void pso_integrate(const pso_config *c, const pso_derived *d, pso_particle *p)
+{
+    integrate_opt(c, d, p, 0);
+}
+
+/* The acceleration a particle that is integrated keeps, and the integration itself, with the options
+ * (psamd.h, config.drag: "the acceleration that is integrated and stored is a - k*v").  k = (float)drag;
+ * per axis a' = RN(a - RN(k*v)) in fp32, two roundings (this file is built with -ffp-contract=off); a' goes
+ * into both updates and stays in ax, ay, az.  drag == 0: the reference's lines, untouched. */
+static void store_acc_and_integrate(pso_system *s, pso_particle *me, const float acc[3])
+{
+    me->ax = acc[0]; me->ay = acc[1]; me->az = acc[2];
+    if (s->drag > 0.0f) {
+        const float k = s->drag;
+        float kvx = k * me->vx, kvy = k * me->vy, kvz = k * me->vz;
+        me->ax = me->ax - kvx; me->ay = me->ay - kvy; me->az = me->az - kvz;
+        /* psamd.h: where k*v is not a number, a' is that not-a-number, bit for bit (the sign a subtraction gives it is
+         * the implementation's choice in IEEE 754) */
+        if (kvx != kvx) me->ax = kvx;
+        if (kvy != kvy) me->ay = kvy;
+        if (kvz != kvz) me->az = kvz;
+    }
+    integrate_opt(&s->cfg, &s->d, me, s->euler);
 }
 
 /* ------------------------------------------------------------ lifecycle */
@@ -444,6 +483,7 @@ pso_system *pso_create(const pso_config *cfg)
     if (!s->particles || !s->tdata || !s->queue || !s->queue_info || !s->chunkgrid ||
         !s->cellgrid || !s->pkgdistrib || !s->neib) { pso_destroy(s); return NULL; }
     s->explosions = 1;
+    s->drag = 0.0f; s->force_sign = 1.0f; s->euler = 0;
 
     /* init_particles_host, ps.cpp:722-753 */
     for (i = 0; i < s->d.container_size; i++) {
@@ -492,6 +532,12 @@ const pso_counters *pso_get_counters(const pso_system *s) { return &s->ctr; }
 int pso_step_index(const pso_system *s) { return s->step; }
 void pso_set_rng(pso_system *s, pso_rng_fn fn, void *user) { s->rng = fn; s->rng_user = user; }
 void pso_set_explosions(pso_system *s, int enabled) { s->explosions = enabled; }
+void pso_set_options(pso_system *s, double drag, double force_sign, int euler)
+{
+    s->drag = drag > 0.0 ? (float)drag : 0.0f;
+    s->force_sign = force_sign < 0.0 ? -1.0f : 1.0f;      /* 0 reads as +1 */
+    s->euler = euler != 0;
+}
 
 int pso_live_count(const pso_system *s)
 {
@@ -614,7 +660,7 @@ static int scan_and_accumulate(const pso_system *s, const pso_particle *me, cons
     if (collision_flag > 0) return collision_flag;
     for (i = 0; i < nn; i++) {
         const pso_tdata *nb = &s->tdata[neib[i]];
-        if (me->id != nb->id) pso_body_body_interaction(c, d, me, nb, acc);
+        if (me->id != nb->id) interaction_signed(c, d, me, nb, s->force_sign, acc);
     }
     return 0;
 }
@@ -638,8 +684,7 @@ static void finish_particle(pso_system *s, pso_particle *me, int collision_flag,
     }
     if (collision_flag == 1) { pso_survive_particle(me); s->ctr.survives++; return; }
 
-    me->ax = acc[0]; me->ay = acc[1]; me->az = acc[2];
-    pso_integrate(c, d, me);
+    store_acc_and_integrate(s, me, acc);
     s->ctr.integrated++;
 
     if (s->explosions && (me->age >= me->fertility_age) && !me->is_parent) {
@@ -877,8 +922,7 @@ int pso_apply_collect(pso_system *s, const float *force4, pso_op *ops, int cap)
                 continue;
             }
             if (bits.i == 1) { pso_survive_particle(me); s->ctr.survives++; continue; }
-            me->ax = force4[4 * k]; me->ay = force4[4 * k + 1]; me->az = force4[4 * k + 2];
-            pso_integrate(c, d, me);
+            store_acc_and_integrate(s, me, &force4[4 * k]);
             s->ctr.integrated++;
             if (s->explosions && (me->age >= me->fertility_age) && !me->is_parent) {   /* ps.cpp:1306-1333 */
                 if (!s->rng) s->ctr.explosions_skipped++;

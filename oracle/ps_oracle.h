@@ -147,6 +147,15 @@ void pso_advance_step(pso_system *s);   /* what pso_step does after calc_forces 
 
 void pso_set_rng(pso_system *s, pso_rng_fn fn, void *user);
 void pso_set_explosions(pso_system *s, int enabled);
+/* The three options nothing in the reference can pin, restated from include/psamd.h (NOT from the kernels):
+ *   drag        k = (float)drag >= 0, for integrated particles only: per axis a' = RN(a - RN(k*v)) in fp32 (unfused);
+ *               a' enters the position AND the velocity update and is what ax, ay, az keep (where k*v is not a number,
+ *               a' is that not-a-number bit for bit).  0: nothing changes.
+ *   force_sign  s = -1 if < 0, else +1: every mass in the force term is multiplied by s; the collision scan,
+ *               the T_DATA rows and the particle's w are untouched.
+ *   euler       != 0: dx = the fp32 product v*t alone, before the MAX_DX clamp; the velocity update is unchanged.
+ * A system that never calls this runs the pinned path: (0, +1, 0). */
+void pso_set_options(pso_system *s, double drag, double force_sign, int euler);
 
 /* borrowed views of the nine reference buffers (ps.cpp:70-78) */
 pso_particle   *pso_particles(pso_system *s);

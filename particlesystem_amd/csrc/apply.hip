@@ -93,7 +93,12 @@ __global__ __launch_bounds__(1024) void k_apply(DevParams P, SegLayout S, const 
     } else if (moved) {
         float axv = f.x, ayv = f.y, azv = f.z;
         const float t = P.t;
-        if (P.drag > 0.f) { axv -= P.drag * v.x; ayv -= P.drag * v.y; azv -= P.drag * v.z; }    // not in the reference
+        if (P.drag > 0.f) {                                                                     // not in the reference
+            // a' = RN(a - RN(k*v)), two roundings (psamd.h).  Where k*v is not a number a' IS that not-a-number, bit for
+            // bit: a subtraction may hand it on with its sign flipped (IEEE 754 leaves that open; this hardware does)
+            const float kx = P.drag * v.x, ky = P.drag * v.y, kz = P.drag * v.z;
+            axv = (kx != kx) ? kx : axv - kx; ayv = (ky != ky) ? ky : ayv - ky; azv = (kz != kz) ? kz : azv - kz;
+        }
         // dx = v*t (fp32) + 0.5*a*t*t (double, left to right), rounded once (ps.cpp:1274-1276)
         float dx = (float)((double)(v.x * t) + ((0.5 * (double)axv) * (double)t) * (double)t);
         float dy = (float)((double)(v.y * t) + ((0.5 * (double)ayv) * (double)t) * (double)t);

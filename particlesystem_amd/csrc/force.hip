@@ -126,7 +126,7 @@ __device__ __forceinline__ void pairs_task(const DevParams &P, const int *__rest
                 if (MODE == 1)
                     pair1_exact_lean(P, ctx, q, nb + jj, snap_age, sorted_id, ax, ay, az, flag);
                 else
-                    dmin = fminf(dmin, pair_fast(me.x, me.y, me.z, q, eps2f, ax, ay, az) + eps2f);
+                    dmin = fminf(dmin, pair_fast(me.x, me.y, me.z, q, eps2f, ax, ay, az));
             }
             // fast math, rare: someone in this cell is within the (widened) collision gate of
             // one of my lanes; the exact rule is then evaluated on unfused distances

@@ -89,13 +89,16 @@ __device__ __forceinline__ float pair_exact(float xi, float yi, float zi, const 
 __device__ __forceinline__ float pair_fast(float xi, float yi, float zi, const float4 q, float eps2,
                                            float &ax, float &ay, float &az)
 {
+    // One pair of pairsN_fast, operation for operation (the softened distance is ONE fma chain started at eps2): a body
+    // gets the same bits whether it falls into a group of NQ or into the tail behind the groups, so the result does not
+    // depend on NQ or on which walk the launch shape picked -- the same bytes from run to run and on any number of slabs.
+    // Returns the softened squared distance, as pairsN_fast does.
     const float rx = q.x - xi, ry = q.y - yi, rz = q.z - zi;
-    const float d2 = fmaf(rz, rz, fmaf(ry, ry, rx * rx));
-    const float dsq = d2 + eps2;
+    const float dsq = fmaf(rz, rz, fmaf(ry, ry, fmaf(rx, rx, eps2)));
     const float rinv = __builtin_amdgcn_rsqf(dsq);
     const float s = q.w * (rinv * rinv * rinv);
     ax = fmaf(rx, s, ax); ay = fmaf(ry, s, ay); az = fmaf(rz, s, az);
-    return d2;
+    return dsq;
 }
 
 // bodyBodyCollision, app_common.cu:269-301, evaluated exactly for the few pairs whose

@@ -107,11 +107,17 @@ def draw_case(rng, sizes, max_steps=6, worlds=(1, 1, 2, 3, 4), nan_draw=True):
                      (n, G, half, vmax, births, w is not None, world, cuts, interior, reupload, int(v is not None and bool(np.isnan(v).any())), over))
 
 
-def run_case(c, seed, graphs=False):
-    """graphs: the contexts replay their stage sequences as hipGraphs (psamd_set_graphs)"""
+def run_case(c, seed, graphs=False, options=None, counters_out=None):
+    """graphs: the contexts replay their stage sequences as hipGraphs (psamd_set_graphs)
+    options: dict(drag=, force_sign=, flags=) -- what the reference cannot pin (psamd.h: config.drag, config.force_sign,
+    PSAMD_FLAG_EULER and any further flag bits), given to every context and, restated, to the oracle; None: the case as drawn
+    counters_out: a dict that receives the oracle's event counters of the run (all of them)"""
     has_nan = c["v"] is not None and bool(np.isnan(c["v"]).any())
     flags = ps.FLAG_EXPLOSIONS if (c["births"] or has_nan) else 0      # (births on: the far outbox exists in worlds of four or more)
     extra = dict(seed=seed) if c["births"] else {}
+    if options:
+        flags |= int(options.get("flags", 0))
+        extra.update({k: options[k] for k in ("drag", "force_sign") if k in options})
     W = c["world"]
     if c["cuts"]:
         extra["cuts"] = c["cuts"]
@@ -129,6 +135,8 @@ def run_case(c, seed, graphs=False):
         raise
     carried = {}                                                 # counters of a context that handed its state on
     o = O.System(oracle_cfg_from(ranks[0].cfg))
+    if options:
+        o.set_options(**O.options_from(ranks[0].cfg))
     if c["births"]:
         o.set_rng(explosion_rng(seed))
     try:
@@ -206,6 +214,8 @@ def run_case(c, seed, graphs=False):
     cnt = {k: v // twice for k, v in cnt.items()}
     if graphs:
         cnt["graph_replays"] = sum(g.graph_stats()[0] for g in ranks)       # (raises if the runtime refused a capture)
+    if counters_out is not None:
+        counters_out.update(o.counters)
     for g in ranks:
         g.close()
     o.close()

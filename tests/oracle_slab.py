@@ -36,6 +36,9 @@ class OracleSlabRank:
                                    ("max_particles_num", "x_factor", "chunk_factor", "chunk_dim", "cell_size", "eps2",
                                     "collision_radius", "particle_weight", "dt", "max_v", "explosion_speed", "life_steps")})
         self.o = O.System(ocfg)
+        opts = O.options_from(cfg)
+        self.force_sign = opts["force_sign"]
+        self.o.set_options(**opts)
         d = self.o.d
         self.G, self.GG, self.mpc = d.grid_dim, d.grid_dim * d.grid_dim, d.max_per_cell
         self.D = cfg.chunk_dim
@@ -182,7 +185,7 @@ class OracleSlabRank:
             planes.append(b[16 + self.ag_cells:].reshape(5, self.ag_cap)[:, :nb].view(np.float32))
         bx, by, bz, bw, bage = np.concatenate(planes, axis=1)             # ranks hold ascending layers: global cell order
         kid = np.float32(self.cfg.life_steps * self.cfg.dt / 10.0)
-        w_eff = np.where(bage < kid, np.float32(0), bw).astype(np.float32)
+        w_eff = np.where(bage < kid, np.float32(0), np.float32(self.force_sign) * bw).astype(np.float32)
         start = np.concatenate([[0], np.cumsum(count)])
         cell_of_body = np.repeat(np.arange(ncells_total), count)
         b3, b1, b2 = cell_of_body // GG, (cell_of_body % GG) // G, cell_of_body % G

@@ -26,6 +26,13 @@ def oracle_cfg_from(cfg):
                                 "explosion_speed", "life_steps")})
 
 
+def oracle_from(cfg):
+    """an oracle system with the reference constants AND the options of a psamd Config"""
+    o = O.System(oracle_cfg_from(cfg))
+    o.set_options(**O.options_from(cfg))
+    return o
+
+
 def splitmix64(x):
     x = (x + 0x9E3779B97F4A7C15) & M64
     x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & M64

@@ -256,6 +256,33 @@ typedef struct psamd_potential_spec {
     psamd_potential_result *result_dev;   /* optional out (device), 8-byte aligned; NULL: the context's own record only */
 } psamd_potential_spec;       /* 32 bytes */
 
+/* psamd_probe: which components of the field are wanted (see "the field at chosen points" below). */
+#define PSAMD_PROBE_ACC 0x1u   /* out4.xyz = acceleration at the point            */
+#define PSAMD_PROBE_PHI 0x2u   /* out4.w   = potential at the point               */
+
+/* What psamd_probe did. */
+typedef struct psamd_probe_result {
+    int64_t done;             /* n: entries examined                                                          */
+    int64_t served;           /* outcome 0                                                                    */
+    int64_t outside;          /* outcome 1                                                                    */
+    int64_t foreign;          /* outcome 2                                                                    */
+    int64_t nonfinite;        /* of `served`, entries with a requested component not finite                   */
+} psamd_probe_result;         /* 40 bytes */
+
+/* What psamd_probe reads and where it writes (device pointers). */
+typedef struct psamd_probe_spec {
+    uint32_t fields;          /* PSAMD_PROBE_ACC | PSAMD_PROBE_PHI, at least one                              */
+    int32_t  reserved;        /* 0                                                                            */
+    const void *pos4;         /* float4[max_count] x, y, z (w ignored), 16-byte aligned: an export's pos4 can
+                                 be passed as it is                                                           */
+    int64_t  max_count;       /* 0 <= max_count < 2^31; sizes the launches                                    */
+    const int64_t *count_dev; /* optional device int64: n = clamp(*count_dev, 0, max_count), read by the
+                                 kernels; NULL: n = max_count                                                 */
+    void    *out4;            /* float4[max_count], 16-byte aligned, not pos4; required if max_count > 0      */
+    int32_t *outcome_dev;     /* optional out, int32[max_count]: every entry's outcome code                   */
+    psamd_probe_result *result_dev;   /* optional out (device), 8-byte aligned; NULL: the context's own record only */
+} psamd_probe_spec;           /* 56 bytes */
+
 typedef struct psamd_ctx psamd_ctx;
 
 /* ---- lifetime ------------------------------------------------------------ */
@@ -634,6 +661,70 @@ int psamd_remove_result_get(psamd_ctx *ctx, psamd_remove_result *out);
 int psamd_potential(psamd_ctx *ctx, const psamd_potential_spec *spec);
 int psamd_potential_result_get(psamd_ctx *ctx, psamd_potential_result *out);
 int psamd_download_potential(psamd_ctx *ctx, float *phi, int64_t capacity, psamd_potential_result *out);
+
+/* ---- the field at chosen points ------------------------------------------------ */
+/* psamd_probe: the acceleration and the potential of the frame's field at points of the caller's choosing -- under a
+ * cursor, on the nodes of a grid, along a field line, at massless tracers the caller integrates itself.  A probe is no
+ * particle: it has a position and nothing else, it enters no list and no life cycle.  Not in the reference; the step's
+ * arithmetic is untouched.
+ *
+ * Outcomes.  Every entry k < n has a cell by the rule psamd_inject uses (Geometry::locate, the fp64 floor test):
+ *     0  served
+ *     1  outside the box; coordinates that are not numbers, and huge ones, count as outside
+ *     2  a valid cell that is not one of this context's compute cells -- the cells its force pass walks, lent-in layers
+ *        included (world > 1 only: exactly one rank serves each in-box probe, on any plan)
+ * An entry with outcome 1 or 2 gets the quiet NaN 0x7fc00000 in all four words of out4[k]; a served entry gets 0.0f in
+ * the components that were not asked for.  Entries at or past n are not touched.
+ *
+ * Bodies.  A served probe at x sees exactly the bodies the force pass walks for its cell: the 27-cell non-periodic
+ * stencil in the reference's order, of each cell the first min(count, MAX_PARTICLES_PER_CELL) entries of the sorted
+ * snapshot with their w_eff.  A kid has w_eff = 0 and the origin as its snapshot position; force_sign is folded into
+ * w_eff.  Nothing is left out: a probe has no own entry.
+ *
+ * Acceleration.  One fp32 chain per component starts at +0 and every body is added in that order by the context's own
+ * pair form -- the exact forms of the force pass, or the fast ones on a PSAMD_FLAG_FAST_MATH context.  Consequence: on an
+ * exact-path cutoff context (a softening length in the lean range, which the default is) a probe at the position of an
+ * adult that the frame's force pass serves returns that particle's (ax, ay, az) BIT FOR BIT -- the particle's own term is
+ * r * s with r = 0, which adds a zero.  A softening length outside the lean range takes the generic exact form, which
+ * skips massless bodies and has no such promise for a probe on a particle (1/sqrt(eps2^3) need not be finite there).
+ *
+ * Potential.  psamd_potential's arithmetic and association, unchanged: fp32 chains of at most 64 that start with every
+ * cell and are carried on in fp64, phi = (float)(-sum).  Consequence: a probe at the true position of a listed kid (its
+ * pos4, not its snapshot entry) returns that kid's phi from psamd_potential bit for bit.  A probe on an adult returns
+ * that adult's phi plus its own term, -s * w / sqrt(eps2) up to rounding: psamd_potential leaves the own entry out, a
+ * probe has none to leave out.
+ *
+ * All-pairs contexts (PSAMD_FLAG_ALL_PAIRS), world == 1: every other cell of the box follows the stencil in global index
+ * order, psamd_potential's walk.  phi keeps the association above.  For the acceleration each far cell's terms go into
+ * fp32 chains per component that start at +0 with the cell, hold at most 64 terms and are carried on in fp64, and
+ * a = (float)((double)a_stencil + far).  This is NOT the force pass's far-field association (16 partial sums per
+ * particle): equality with the force record is promised for cutoff contexts only.  With empty far cells the result is
+ * the cutoff result bit for bit.  With world > 1 the call returns PSAMD_ERR_UNSUPPORTED; the context stays usable.
+ *
+ * Determinism.  A probe's four words depend on its position and the frame alone: not on the other probes, their order,
+ * max_count, graphs, or whether a slab or one context serves it.
+ *
+ * Valid in psamd_potential's window: world == 1 from psamd_build_grid until the frame ends, world > 1 between
+ * psamd_slab_pairs and psamd_slab_apply; elsewhere PSAMD_ERR_STATE, also for a wedged context.  psamd_potential's
+ * refusal of plans that lend layers does not apply: a rank serves the probes of the cells it computes.
+ *
+ * Everything is enqueued on the context's stream (psamd_get_stream): nothing waits, nothing is read back, the call ends
+ * no frame and keeps no host bookkeeping.  Scratch per entry grows only when max_count exceeds every earlier call's
+ * (that growth may wait for the device); so the call may be captured into a graph whenever no growth is needed, and
+ * returns PSAMD_ERR_STATE if growth is needed while the stream is being captured.  *result_dev and the context's own
+ * record (psamd_probe_result_get) are written by the time the stream reaches the end of the call.
+ *
+ * Cost on an MI355X at N = 2^20 (profiles/probe_cost.txt), ACC | PHI: 1.12 ms for 65 536 probes on particles' own
+ * positions, 0.89 ms for as many on a regular grid, beside 0.48 ms of psamd_potential and 0.39 ms of the force pass on
+ * the same frames.  The cost follows the (wave, distinct cell) walks: 16 probes to a cell use a quarter of the lanes.
+ *
+ * PSAMD_ERR_INVALID_ARG: a NULL context or spec, fields 0 or with unknown bits, reserved != 0, max_count outside
+ * [0, 2^31), pos4 or out4 NULL with max_count > 0 or not 16-byte aligned, outcome_dev not 4-byte aligned, count_dev or
+ * result_dev not 8-byte aligned.  max_count == 0 writes a zero result and launches nothing else.
+ *
+ * psamd_probe_result_get: the last probe's record, into host memory; waits for the context's stream. */
+int psamd_probe(psamd_ctx *ctx, const psamd_probe_spec *spec);
+int psamd_probe_result_get(psamd_ctx *ctx, psamd_probe_result *out);
 
 /* ---- introspection -------------------------------------------------------- */
 int psamd_get_counters(psamd_ctx *ctx, psamd_counters *out);

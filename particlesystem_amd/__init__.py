@@ -202,6 +202,46 @@ def merge_potential(results):
             "phi_min": float(min(float(r["phi_min"]) for r in results)), "phi_max": float(max(float(r["phi_max"]) for r in results))}
 
 
+# psamd_probe: the field bits, and the outcome codes of the entries
+PROBE_ACC, PROBE_PHI = 0x1, 0x2
+PROBE_SERVED, PROBE_OUTSIDE, PROBE_FOREIGN = 0, 1, 2
+
+
+class ProbeResult(_Record):
+    """psamd_probe_result: what psamd_probe did."""
+    _fields_ = [(n, C.c_int64) for n in ("done", "served", "outside", "foreign", "nonfinite")]
+
+
+class ProbeSpec(C.Structure):
+    """psamd_probe_spec: what psamd_probe reads and where it writes (device pointers)."""
+    _fields_ = [("fields", C.c_uint32), ("reserved", C.c_int32), ("pos4", C.c_void_p), ("max_count", C.c_int64),
+                ("count_dev", C.c_void_p), ("out4", C.c_void_p), ("outcome_dev", C.c_void_p), ("result_dev", C.c_void_p)]
+
+
+def merge_probe(results):
+    """The probes of a slab world from its ranks' (dicts of probe(outcome=True), every rank given all entries): each
+    entry's out4 from the rank whose outcome is 0 (the quiet NaN where no rank serves it), `served` and `nonfinite`
+    add, `outside` and `done` are any one rank's (every rank sees the same entries), `foreign` is what no rank served
+    inside the box: 0.  out4 / outcome may be torch tensors or numpy arrays; the merged ones are numpy arrays."""
+    results = list(results)
+
+    def host(a):
+        return np.asarray(a.cpu().numpy() if hasattr(a, "cpu") else a)
+    outs = [host(r["out4"]).astype(np.float32, copy=False) for r in results]
+    codes = [host(r["outcome"]).astype(np.int32, copy=False) for r in results]
+    out4 = np.full(outs[0].shape, np.float32(np.nan), np.float32).view(np.uint32)
+    out4[...] = 0x7fc00000
+    outcome = np.where(codes[0] == PROBE_OUTSIDE, PROBE_OUTSIDE, PROBE_FOREIGN).astype(np.int32)
+    for o, c in zip(outs, codes):
+        sel = c == PROBE_SERVED
+        out4[sel] = o.view(np.uint32)[sel]
+        outcome[sel] = PROBE_SERVED
+    served = sum(int(r["served"]) for r in results)
+    return {"out4": out4.view(np.float32), "outcome": outcome, "done": int(results[0]["done"]), "served": served,
+            "outside": int(results[0]["outside"]), "foreign": int(results[0]["done"]) - int(results[0]["outside"]) - served,
+            "nonfinite": sum(int(r["nonfinite"]) for r in results)}
+
+
 def merge_live_stats(stats):
     """The statistics of a system from its ranks' (dicts of live_stats() / export_live()["stats"]): counts and sums
     add, in rank order; the box and the ages take the minima and maxima."""
@@ -300,6 +340,8 @@ ABI = [
     ("psamd_potential", C.c_int, [_vp, C.POINTER(Potential)]),
     ("psamd_potential_result_get", C.c_int, [_vp, C.POINTER(PotentialResult)]),
     ("psamd_download_potential", C.c_int, [_vp, _vp, _i64, C.POINTER(PotentialResult)]),
+    ("psamd_probe", C.c_int, [_vp, C.POINTER(ProbeSpec)]),
+    ("psamd_probe_result_get", C.c_int, [_vp, C.POINTER(ProbeResult)]),
 ]
 
 _lib = None
@@ -796,6 +838,40 @@ class ParticleSystem:
         u = self.potential()["potential"]
         k = float(self.live_stats()["kinetic"])
         return {"kinetic": k, "potential": u, "total": k + u}
+
+    # ---- the field at chosen points (include/psamd.h) ---------------------------
+    def probe(self, pos4, count=None, acc=True, phi=True, outcome=False):
+        """psamd_probe from a torch device tensor: pos4 float32 [m, 4] (x, y, z; w ignored -- an export's "pos4" as it is);
+        count: None (all m entries) or a 1-element int64 device tensor that work on torch's current stream may write just
+        before.  Returns {"out4": float32 [m, 4] device tensor (acceleration in xyz, potential in w; quiet NaNs where the
+        entry was not served), "done", "served", "outside", "foreign", "nonfinite"} and, with outcome=True, "outcome": an
+        int32 device tensor of m entries (PROBE_SERVED, PROBE_OUTSIDE, PROBE_FOREIGN).  Entries at or past the count keep
+        the zeros (out4) and -1 (outcome) they were allocated with.  Waits for the context's stream."""
+        import torch
+        dev = pos4.device
+        m = int(pos4.shape[0])
+        assert pos4.dtype == torch.float32 and tuple(pos4.shape) == (m, 4) and pos4.is_contiguous() and pos4.is_cuda, "probe: bad pos4 tensor"
+        spec = ProbeSpec(fields=(PROBE_ACC if acc else 0) | (PROBE_PHI if phi else 0), max_count=m)
+        out4 = torch.zeros((max(m, 1), 4), dtype=torch.float32, device=dev)
+        spec.pos4, spec.out4 = (pos4.data_ptr(), out4.data_ptr()) if m > 0 else (None, None)
+        if count is not None:
+            assert count.dtype == torch.int64 and tuple(count.shape) == (1,) and count.device == dev, "probe: bad count tensor"
+            spec.count_dev = count.data_ptr()
+        codes = torch.full((max(m, 1),), -1, dtype=torch.int32, device=dev) if outcome else None
+        spec.outcome_dev = None if codes is None else codes.data_ptr()
+        with self._on_stream(dev):
+            self._ck(self.lib.psamd_probe(self.h, C.byref(spec)))
+        res = self.probe_result()
+        res["out4"] = out4[:m]
+        if outcome:
+            res["outcome"] = codes[:m]
+        return res
+
+    def probe_result(self):
+        """psamd_probe_result_get: the last probe's record as a dict"""
+        r = ProbeResult()
+        self._ck(self.lib.psamd_probe_result_get(self.h, C.byref(r)))
+        return r.to_dict()
 
     def device_view(self):
         v = DeviceView()

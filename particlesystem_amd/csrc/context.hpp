@@ -88,6 +88,7 @@ struct psamd_ctx {
     std::map<int, int64_t> inject_tally;
     InjectScratch inj{};              // its scratch: inj.e grows with max_count, the rest is fixed
     RemoveScratch rem{};              // psamd_remove's scratch: rem.e grows with max_count, the rest is fixed
+    ProbeScratch prb{};               // psamd_probe's scratch: code / order grow with max_count, the counters are fixed
     // timing
     int timing = 0;                    // 0 off, 1 pair pass / apply / life cycle, 2 every stage
     int timing_period = 1;             // events are recorded on every timing_period-th step since set_timing

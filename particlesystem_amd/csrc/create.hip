@@ -315,6 +315,11 @@ static int alloc_step_arrays(psamd_ctx *c)
     PS_HIP(c, dev_alloc(c, &c->rem.tile_live, (size_t)slot_tiles(P.slots_total)));
     PS_HIP(c, dev_alloc(c, &c->rem.own, 1));
     PS_HIP(c, hipMemsetAsync(c->rem.own, 0, sizeof(psamd_remove_result), c->stream));
+    // psamd_probe's fixed scratch and result record: a counter per local cell (a rank serves the cells it computes, lent-in
+    // layers included, so the own cells alone would not do), one word more, the header
+    PS_HIP(c, dev_alloc(c, &c->prb.counts, LC + 1 + PROBE_HDR_WORDS));
+    PS_HIP(c, dev_alloc(c, &c->prb.own, 1));
+    PS_HIP(c, hipMemsetAsync(c->prb.own, 0, sizeof(psamd_probe_result), c->stream));
     PS_HIP(c, dev_alloc(c, &d.trace, 3 * (LC * P.slices + 4)));
     PS_HIP(c, hipMemsetAsync(d.trace, 0, 3 * (LC * P.slices + 4) * sizeof(unsigned long long), c->stream));
     return PSAMD_OK;
@@ -517,6 +522,7 @@ int psamd_destroy(psamd_ctx *c)
     if (c->staging) (void)hipFree(c->staging);
     for (const EntryScratch &e : {c->inj.e, c->rem.e})
         for (void *p : {(void *)e.ent, (void *)e.tcount, (void *)e.tile_out}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->prb.code, (void *)c->prb.order}) if (p) (void)hipFree(p);
     if (c->h_fs) (void)hipHostFree(c->h_fs);
     if (c->ev_made) for (auto &set : c->ev) for (auto &e : set) (void)hipEventDestroy(e);
     if (c->d.ev_fork) (void)hipEventDestroy(c->d.ev_fork);

@@ -22,20 +22,6 @@ namespace psamd {
 
 constexpr int INJ_NOT_MINE = -1, INJ_OUTSIDE = -2;
 
-// Geometry::locate: the same fp64 floor((+-1.0 * c) / cell_size) + G / 2.  On x86 the host's out-of-range (int)
-// conversion gives INT_MIN (rejected); here it would saturate and NaN would become 0, so the range is tested on the
-// double: an integer-valued d converts into [0, G) exactly when 0 <= d < G, and NaN / +-inf fail the test.
-__device__ __forceinline__ bool inject_locate(const DevParams &P, float x, float y, float z, int &cell)
-{
-    const double cs = P.cell_size, h = (double)(P.G / 2), g = (double)P.G;
-    const double d1 = floor((-1.0 * (double)y) / cs) + h;
-    const double d2 = floor((1.0 * (double)x) / cs) + h;
-    const double d3 = floor((-1.0 * (double)z) / cs) + h;
-    if (!(d1 >= 0.0 && d1 < g && d2 >= 0.0 && d2 < g && d3 >= 0.0 && d3 < g)) return false;
-    cell = ((int)d3 * P.G + (int)d1) * P.G + (int)d2;
-    return true;
-}
-
 template <bool LDS>
 __global__ void __launch_bounds__(SPLIT_THREADS) k_inject_locate(DevParams P, SegLayout S, int nrec, const CellInfo *__restrict__ celltab,
                                                                  const float4 *__restrict__ pos4, int64_t max_count, const int64_t *count_dev,
@@ -57,7 +43,7 @@ __global__ void __launch_bounds__(SPLIT_THREADS) k_inject_locate(DevParams P, Se
         if (i < n) {
             const float4 p = pos4[i];
             int cell;
-            if (!inject_locate(P, p.x, p.y, p.z, cell)) { r = INJ_OUTSIDE; first_out = min(first_out, i); }
+            if (!locate_cell(P, p.x, p.y, p.z, cell)) { r = INJ_OUTSIDE; first_out = min(first_out, i); }
             else {
                 const CellInfo ci = celltab[cell];
                 const int sr = segment_record(S, ci.seg_type, ci.seg_tid);
@@ -131,7 +117,7 @@ __global__ void k_inject_place(DevParams P, int64_t max_count, const int64_t *co
         if (si >= 0) {
             const float4 p = pos4[i];
             int cell = -1;
-            (void)inject_locate(P, p.x, p.y, p.z, cell);
+            (void)locate_cell(P, p.x, p.y, p.z, cell);
             d_pos4[si] = p;                                         // create_particle_s, as k_place writes it
             d_vel4[si] = vel4 ? vel4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
             d_acc4[si] = make_float4(0.f, 0.f, 0.f, fert ? fert[i] : 0.f);

@@ -89,6 +89,26 @@ struct PotOut {
     int64_t live;
 };
 
+// psamd_probe (probe.hip): the caller's arrays and the scratch.  code / order grow with a call's max_count (the host:
+// grow_probe_scratch, services.hip); the counters are sized at creation
+constexpr int PROBE_HDR_WORDS = 4;
+struct ProbeArgs {
+    uint32_t fields;
+    const float4 *pos4;
+    int64_t max_count;
+    const int64_t *count_dev;
+    float4 *out4;
+    int *outcome;
+    psamd_probe_result *result;
+};
+struct ProbeScratch {
+    int *code;        // [cap] per entry: its local cell, or -1 - outcome
+    int *order;       // [cap] the served entries' indices, cell-major
+    int64_t cap;      // entries there is room for
+    int *counts;      // [n_local_cells + 1 + PROBE_HDR_WORDS] per cell: served entries, then their prefix; the header: nonfinite, served, outside, foreign
+    psamd_probe_result *own;    // the context's own result record (psamd_probe_result_get)
+};
+
 // Container layout by segment type (slots and QUEUE_INFO records), device copy.
 struct SegLayout {
     int32_t seg_base[5];
@@ -244,6 +264,10 @@ hipError_t launch_export_live(hipStream_t st, const DevParams &P, const DeviceSt
 // first `capacity` live particles in slot order (phi null or capacity 0: the result alone); result_dev may be null
 hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceState &d, float *phi, int64_t capacity,
                             psamd_potential_result *result_dev);
+
+// psamd_probe (max_count > 0): locate + count, the cells' prefix, the cell-major order, the pair pass (one probe to a lane), the
+// result record
+hipError_t launch_probe(hipStream_t st, const DevParams &P, const DeviceState &d, const ProbeArgs &a, const ProbeScratch &s);
 
 // psamd_inject: locate + rank, the records' prefix, the first queue failure, the placement, the commit of the queues and
 // the result record (max_count > 0)

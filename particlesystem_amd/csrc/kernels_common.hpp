@@ -26,6 +26,7 @@
 //   inject.hip     psamd_inject, particles from device arrays into their segments' free slots
 //   remove.hip     psamd_remove, particles out of their slots and the slots back into the queues
 //   potential.hip  psamd_potential, every listed particle's potential and the potential energy
+//   probe.hip      psamd_probe, the acceleration and the potential at points of the caller's choosing
 //
 // Reference arithmetic is reproduced operation for operation: every file is built with
 // -ffp-contract=off; where the reference evaluates in double (EPS2 add, 0.5*a*t*t) so
@@ -376,6 +377,20 @@ __device__ __forceinline__ int segment_record(const SegLayout &S, int seg_type, 
 {
     const int k = seg_type == 1 ? 0 : seg_type == 2 ? 1 : seg_type == 4 ? 2 : 3;
     return S.info_base[k] + seg_tid;
+}
+
+// Geometry::locate on the device (inject.hip places by it, probe.hip serves by it): the same fp64
+// floor((+-1.0 * c) / cell_size) + G / 2.  On x86 the host's out-of-range (int) conversion gives INT_MIN (rejected); here it would saturate and NaN would become 0, so the range is tested on the
+// double: an integer-valued d converts into [0, G) exactly when 0 <= d < G, and NaN / +-inf fail the test.
+__device__ __forceinline__ bool locate_cell(const DevParams &P, float x, float y, float z, int &cell)
+{
+    const double cs = P.cell_size, h = (double)(P.G / 2), g = (double)P.G;
+    const double d1 = floor((-1.0 * (double)y) / cs) + h;
+    const double d2 = floor((1.0 * (double)x) / cs) + h;
+    const double d3 = floor((-1.0 * (double)z) / cs) + h;
+    if (!(d1 >= 0.0 && d1 < g && d2 >= 0.0 && d2 < g && d3 >= 0.0 && d3 < g)) return false;
+    cell = ((int)d3 * P.G + (int)d1) * P.G + (int)d2;
+    return true;
 }
 
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x)

@@ -24,95 +24,16 @@
 // nothing but the cell order and the cells' list lengths: the same bits from run to run, with graphs or without, on one
 // context and on the slab that holds the particle.  Against an fp64 direct sum: 1.5e-7 relative for phi, 1e-8 for U
 // (tests/test_gpu_potential.py prints the largest error of every case).
-#include "pair_math.hpp"
+#include "pot_walk.hpp"
 #include "slot_walk.hpp"
 
 namespace psamd {
 
 constexpr int POT_THREADS = SLOT_THREADS, POT_WAVES = SLOT_WAVES;   // (k_pot_reduce walks tile t of the sorted order and of the slots)
 constexpr int POT_ITEMS = POT_TILE / POT_THREADS;        // 16 batches of 64 entries per wave
-constexpr int POT_CHAIN = 64;                            // fp32 additions in one chain, a multiple of the group's 8
 static_assert(POT_ITEMS == SLOT_ITEMS, "a wave walks POT_ITEMS batches of 64 sorted entries and as many of 64 slots");
 
 __device__ __forceinline__ bool pot_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// Eight bodies from jj on, their terms added to the chain `a` in list order.  TAIL: only the first `rem` of them are
-// bodies of the list (the others are read -- inside the buffer, see pot_walk -- and dropped).  SELF: the list is the
-// lane's own cell's, body 0 has sorted index gj0: the lane's own entry is dropped.
-template <bool SELF, bool TAIL>
-__device__ __forceinline__ void pot_group(const PairCtx &ctx, const float *__restrict__ sx, const float *__restrict__ sy,
-                                          const float *__restrict__ sz, const float *__restrict__ sw, int jj, int rem,
-                                          int gj0, float eps2f, float &a)
-{
-    constexpr int NQ = 8;
-    v2f qx[NQ / 2], qy[NQ / 2], qz[NQ / 2], qw[NQ / 2];
-#pragma unroll
-    for (int i = 0; i < NQ / 2; i++) {
-        qx[i] = v2f{sx[jj + 2 * i], sx[jj + 2 * i + 1]};
-        qy[i] = v2f{sy[jj + 2 * i], sy[jj + 2 * i + 1]};
-        qz[i] = v2f{sz[jj + 2 * i], sz[jj + 2 * i + 1]};
-        qw[i] = v2f{sw[jj + 2 * i], sw[jj + 2 * i + 1]};
-    }
-    PairRows<NQ> r;
-    pairs_dist<NQ, false>(ctx, qx, qy, qz, 0.f, r);
-    const v2f eps = {eps2f, eps2f};
-    v2f t[NQ / 2];
-#pragma unroll
-    for (int i = 0; i < NQ / 2; i++) {
-        const v2f e = r.d[i] + eps;
-        v2f s; s.x = __builtin_amdgcn_rsqf(e.x); s.y = __builtin_amdgcn_rsqf(e.y);
-        t[i] = qw[i] * s;
-    }
-#pragma unroll
-    for (int i = 0; i < NQ; i++) {
-        float ti = (i & 1) ? t[i >> 1].y : t[i >> 1].x;
-        if (TAIL && i >= rem) ti = 0.f;
-        if (SELF && gj0 + jj + i == ctx.gi) ti = 0.f;
-        a += ti;
-    }
-}
-
-// n bodies from four planes of a snapshot (wave-uniform pointers: scalar loads), their terms carried on in acc.
-// padded: eight floats past the list's end can be read in every plane (the own snapshot: create.hip allocates it so;
-// not the gathered one) -- the ragged tail is then one group with its surplus dropped instead of up to seven single
-// bodies.  Both forms add the same terms in the same order.
-template <bool SELF>
-__device__ __forceinline__ void pot_walk(const PairCtx &ctx, const float *__restrict__ sx, const float *__restrict__ sy,
-                                         const float *__restrict__ sz, const float *__restrict__ sw, int n, int gj0,
-                                         float eps2f, bool padded, double &acc)
-{
-    for (int j0 = 0; j0 < n; j0 += POT_CHAIN) {
-        const int m = min(POT_CHAIN, n - j0);
-        float a = 0.f;
-        int jj = 0;
-        for (; jj + 8 <= m; jj += 8) pot_group<SELF, false>(ctx, sx, sy, sz, sw, j0 + jj, 8, gj0, eps2f, a);
-        if (jj < m) {
-            if (padded) pot_group<SELF, true>(ctx, sx, sy, sz, sw, j0 + jj, m - jj, gj0, eps2f, a);
-            else {
-                // (one body at a time: each term is pot_group's -- pairs_dist<NQ, false>'s unfused r.r, the same eps add, rsq and
-                // multiply -- and must stay so, or a slab's all-pairs phi leaves the single context's bits;
-                // tests/test_gpu_potential.py holds the two against each other on a world of two)
-                for (; jj < m; jj++) {
-                    const int j = j0 + jj;
-                    const float rx = sx[j] - ctx.xi, ry = sy[j] - ctx.yi, rz = sz[j] - ctx.zi;
-                    const float d2 = rx * rx + ry * ry + rz * rz;
-                    float ti = sw[j] * __builtin_amdgcn_rsqf(d2 + eps2f);
-                    if (SELF && gj0 + j == ctx.gi) ti = 0.f;
-                    a += ti;
-                }
-            }
-        }
-        acc += (double)a;
-    }
-}
-
-// where an all-pairs context finds the cells beyond the stencil (allpairs.hip, launch_allpairs_far)
-struct PotFar {
-    const float *buf;
-    const int *start, *n;
-    unsigned long long plane;
-    int padded;
-};
 
 template <bool ALLP>
 __global__ __launch_bounds__(POT_THREADS) void k_pot_pairs(DevParams P, const int *__restrict__ cell_start,

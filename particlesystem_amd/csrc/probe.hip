@@ -1,0 +1,308 @@
+// probe.hip -- psamd_probe: the acceleration and the potential of the frame's field at points of the caller's choosing.
+//
+// Not part of the step and not in the reference.  A probe is no particle: it has a position and
+// nothing else.  A probe in compute cell c -- a cell this context's force pass walks -- sees exactly the bodies that pass
+// walks for c: the 27-cell stencil in the reference's order, of each cell the first min(count, MAX_PARTICLES_PER_CELL)
+// entries of the sorted snapshot with their w_eff; an all-pairs context (world 1) goes on over every other cell of the
+// box in global index order.  Six enqueues that nothing in between has to wait for:
+//   (memset)         the per-cell counters and the four header words
+//   k_probe_locate   one lane per entry: locate_cell, the outcome, the local cell; the cell's counter + 1 (an integer
+//                    atomic: nothing about a probe's result depends on where it lands in its cell's run); the entries that
+//                    are not served get their NaN words here, every entry its outcome
+//   k_probe_scan     one workgroup: the counters' exclusive prefix, in place
+//   k_probe_scatter  the served entries' indices into cell-major order
+//   k_probe_pairs    one wave per 64 consecutive entries of that order, one probe to a lane.  The wave takes the
+//                    distinct cells among its lanes one after the other; for each, ALL lanes walk that cell's stencil --
+//                    the bodies are wave-uniform (scalar) loads of the four planes, eight to a group, as in force.hip and
+//                    potential.hip -- and the lanes that belong to the cell store their four words at the end.  (No lane
+//                    is switched off during a walk: the stencil lookup is handed out by readlane from lanes 0..26, and
+//                    a lane of another cell only computes numbers nobody keeps.)
+//   k_probe_finish   the result record
+//
+// Acceleration: one fp32 chain per component from +0, every body added in list order by the context's own pair form
+// (pair_math.hpp; scan = false: no collision work).  On the lean exact path a probe on an adult of a cutoff context
+// repeats that particle's force chain operation for operation: the same bits as its force record (the own term is r * s
+// with r = 0).  Potential: pot_walk.hpp, potential.hip's association unchanged.  All-pairs: each far cell's terms in fp32
+// chains of at most POT_CHAIN that start at +0 with the cell and are carried on in fp64, a = (float)((double)a_stencil +
+// far) -- NOT the force pass's far-field association (allpairs.hip: 16 partial sums), so equality with the force record
+// is promised for cutoff contexts only; with empty far cells the result is the cutoff result bit for bit.
+//
+// The kernel is templated on acc / phi / both, generic exact / lean exact / fast, cutoff / all-pairs; the registers and
+// waves per SIMD of every instance are in the table at k_probe_pairs.
+#include "multisplit.hpp"
+#include "pot_walk.hpp"
+
+namespace psamd {
+
+constexpr int PROBE_THREADS = 256;
+constexpr int PROBE_OUTSIDE = -2, PROBE_FOREIGN = -3;      // an entry's code: its local cell, or -1 - outcome
+enum { PH_NONFINITE = 0, PH_SERVED, PH_OUTSIDE, PH_FOREIGN };   // the header words behind the counters (PROBE_HDR_WORDS)
+
+// a cell this context's force pass walks (the whole pair stage's ranges: lent-in layers, the own computed cells)
+__device__ __forceinline__ bool probe_computes(const DevParams &P, int lc)
+{
+    return (lc >= P.comp_lo[0] && lc < P.comp_hi[0]) || (lc >= P.comp_lo[1] && lc < P.comp_hi[1]) ||
+           (lc >= P.comp_lo[2] && lc < P.comp_hi[2]);
+}
+
+__global__ __launch_bounds__(PROBE_THREADS) void k_probe_locate(DevParams P, const float4 *__restrict__ pos4, int64_t max_count,
+                                                                const int64_t *count_dev, int *__restrict__ code,
+                                                                int *__restrict__ counts, int *__restrict__ hdr,
+                                                                float4 *__restrict__ out4, int *__restrict__ outcome)
+{
+    const int n = entry_count(count_dev, max_count);
+    const int64_t i64 = (int64_t)blockIdx.x * PROBE_THREADS + threadIdx.x;
+    int oc = -1;
+    if (i64 < n) {
+        const int i = (int)i64;
+        const float4 p = pos4[i];
+        int gc, lc = PROBE_OUTSIDE;
+        if (locate_cell(P, p.x, p.y, p.z, gc)) {
+            lc = local_of_global(P, gc);
+            if (lc < 0 || !probe_computes(P, lc)) lc = PROBE_FOREIGN;
+        }
+        code[i] = lc;
+        oc = lc >= 0 ? 0 : -1 - lc;
+        if (lc >= 0) atomicAdd(&counts[lc], 1);
+        else {
+            const float qnan = __int_as_float(0x7fc00000);
+            out4[i] = make_float4(qnan, qnan, qnan, qnan);
+        }
+        if (outcome) outcome[i] = oc;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const int cnt = __popcll(__ballot(oc == k));
+        if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&hdr[PH_SERVED + k], cnt);
+    }
+}
+
+// one workgroup: counts[c] becomes the number of served entries in the cells before c
+__global__ __launch_bounds__(1024) void k_probe_scan(int ncells, int *__restrict__ counts)
+{
+    __shared__ int s_w[16];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int run = 0;
+    for (int b = 0; b < ncells; b += 1024) {
+        const int c = b + tid;
+        const int v = c < ncells ? counts[c] : 0;
+        const int incl = wave_incl_scan(v);
+        if (lane == 63) s_w[wv] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < 16; k++) { if (k < wv) before += s_w[k]; total += s_w[k]; }
+        if (c < ncells) counts[c] = run + before + incl - v;
+        run += total;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(PROBE_THREADS) void k_probe_scatter(int64_t max_count, const int64_t *count_dev,
+                                                                 const int *__restrict__ code, int *__restrict__ counts,
+                                                                 int *__restrict__ order)
+{
+    const int n = entry_count(count_dev, max_count);
+    const int64_t i64 = (int64_t)blockIdx.x * PROBE_THREADS + threadIdx.x;
+    if (i64 >= n) return;
+    const int lc = code[(int)i64];
+    if (lc >= 0) order[atomicAdd(&counts[lc], 1)] = (int)i64;      // (below the served count, which is at most n <= the scratch's room)
+}
+
+// n bodies of one list (wave-uniform pointers: scalar loads) added to the chains in list order by the context's pair
+// form: force.hip's walk_cell without its collision work.  MATH 1: pairsN_exact_lean's three parts and pair1_exact_lean
+// for the ragged tail; 2: the fast forms; 0: pair_exact one body at a time, a massless body skipped as k_pairs<0> skips it.
+template <int MATH>
+__device__ __forceinline__ void probe_acc_walk(const DevParams &P, const PairCtx &ctx, const float *__restrict__ sx,
+                                               const float *__restrict__ sy, const float *__restrict__ sz,
+                                               const float *__restrict__ sw, int n, float eps2f, float &ax, float &ay, float &az)
+{
+    constexpr int NQ = 8;
+    int jj = 0, flag = 0;
+    if (MATH != 0) {
+        for (; jj + NQ <= n; jj += NQ) {
+            v2f qx[NQ / 2], qy[NQ / 2], qz[NQ / 2], qw[NQ / 2];
+#pragma unroll
+            for (int i = 0; i < NQ / 2; i++) {
+                qx[i] = v2f{sx[jj + 2 * i], sx[jj + 2 * i + 1]};
+                qy[i] = v2f{sy[jj + 2 * i], sy[jj + 2 * i + 1]};
+                qz[i] = v2f{sz[jj + 2 * i], sz[jj + 2 * i + 1]};
+                qw[i] = v2f{sw[jj + 2 * i], sw[jj + 2 * i + 1]};
+            }
+            PairRows<NQ> r;
+            if (MATH == 1) {
+                v2f sc[NQ / 2];
+                pairs_dist<NQ, false>(ctx, qx, qy, qz, 0.f, r);
+                pairs_scale_exact<NQ, true>(P, ctx, r, qw, 0, nullptr, nullptr, sc, flag);
+                pairs_add<NQ>(r, sc, ax, ay, az);
+            } else {
+                pairs_dist<NQ, true>(ctx, qx, qy, qz, eps2f, r);
+                pairs_finish_fast<NQ>(r, qw, ax, ay, az);
+            }
+        }
+    }
+    for (; jj < n; jj++) {
+        const float4 q = make_float4(sx[jj], sy[jj], sz[jj], sw[jj]);
+        if (MATH == 1) pair1_exact_lean(P, ctx, q, 0, nullptr, nullptr, ax, ay, az, flag);
+        else if (MATH == 2) (void)pair_fast(ctx.xi, ctx.yi, ctx.zi, q, eps2f, ax, ay, az);
+        else if (q.w != 0.0f) (void)pair_exact(ctx.xi, ctx.yi, ctx.zi, q, P.eps2, ax, ay, az);
+    }
+}
+
+__device__ __forceinline__ bool probe_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// VGPRs / waves per SIMD as the compiler reports them for gfx950, no instance with scratch (cutoff | all-pairs; the
+// generic exact form has no all-pairs instance):
+//                 generic exact      lean exact            fast
+//   acc           28 / 8             66 / 7 | 83 / 5       58 / 8 | 75 / 6
+//   phi           40 / 7             40 / 7 | 41 / 7       40 / 7 | 41 / 7
+//   acc and phi   44 / 7             72 / 7 | 87 / 5       62 / 7 | 77 / 6
+// (acc and phi walk a cell's list once each: the two passes share no registers, and their loads hit the scalar cache.)
+template <int FIELDS, int MATH, bool ALLP>
+__global__ __launch_bounds__(PROBE_THREADS) void k_probe_pairs(DevParams P, const int *__restrict__ cell_start,
+                                                               const float *__restrict__ snap_soa,
+                                                               const float4 *__restrict__ pos4, const int *__restrict__ code,
+                                                               const int *__restrict__ order, int *__restrict__ hdr,
+                                                               const PotFar far, float4 *__restrict__ out4)
+{
+    // waves of 64 consecutive served entries, four independent waves per workgroup, an XCD's workgroups a contiguous run
+    // of the cell-major order (force.hip, k_pairs).  The launch is sized by max_count, the work by the served count.
+    const int lane = threadIdx.x & 63;
+    const int served = hdr[PH_SERVED];
+    const int nwave = (int)(((int64_t)served + 63) >> 6), nwg = (nwave + 3) >> 2;
+    if ((int)blockIdx.x >= nwg) return;
+    const int slot = __builtin_amdgcn_readfirstlane(xcd_contiguous(blockIdx.x, nwg) * 4 + (int)(threadIdx.x >> 6));
+    if (slot >= nwave) return;
+    const int64_t j = (int64_t)slot * 64 + lane;
+    const bool valid = j < served;
+    const int i = valid ? order[j] : 0;
+    const int lc = valid ? code[i] : -1;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (valid) p = pos4[i];
+    const size_t cap = (size_t)P.sorted_cap;
+    const float eps2f = (float)P.eps2;
+    const PairCtx ctx = {p.x, p.y, p.z, 0.f, 0, -1, false};
+    int nonfinite = 0;
+    for (unsigned long long todo = __ballot(valid); todo;) {
+        const int first = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
+        const int c = __builtin_amdgcn_readlane(lc, first);
+        const unsigned long long mine = __ballot(valid && lc == c);
+        todo &= ~mine;
+        int i1, i2, i3;
+        cell_coords(P, c, i1, i2, i3);
+        int my_nb = 0, my_cnt = 0;
+        if (lane < STENCIL) {
+            const int nc = local_cell(P, i3 + c_stencil[lane][2], i1 + c_stencil[lane][1], i2 + c_stencil[lane][0]);
+            if (nc >= 0) {
+                my_nb = cell_start[nc];
+                my_cnt = min(cell_start[nc + 1] - my_nb, P.max_per_cell);
+            }
+        }
+        float ax = 0.f, ay = 0.f, az = 0.f;
+        double acc = 0.0;
+        for (int k = 0; k < STENCIL; k++) {                 // the stencil, in the reference's order
+            const int nb = __builtin_amdgcn_readlane(my_nb, k), n = __builtin_amdgcn_readlane(my_cnt, k);
+            const float *sx = snap_soa + nb;
+            if (FIELDS & PSAMD_PROBE_ACC) probe_acc_walk<MATH>(P, ctx, sx, sx + cap, sx + 2 * cap, sx + 3 * cap, n, eps2f, ax, ay, az);
+            if (FIELDS & PSAMD_PROBE_PHI) pot_walk<false>(ctx, sx, sx + cap, sx + 2 * cap, sx + 3 * cap, n, 0, eps2f, true, acc);
+        }
+        if (ALLP) {
+            // every other cell of the box in global index order (k_pot_pairs<true>'s walk); the cells of THIS cell's
+            // stencil are left out for this cell's turn
+            const size_t plane = (size_t)far.plane;
+            const int nblk = (P.num_cells_global + 63) >> 6, GG = P.G * P.G;
+            double fx = 0.0, fy = 0.0, fz = 0.0;
+            for (int blk = 0; blk < nblk; blk++) {
+                const int c2 = blk * 64 + lane;
+                int f_nb = 0, f_cnt = 0;
+                if (c2 < P.num_cells_global) {
+                    const int j3 = c2 / GG, rem = c2 - j3 * GG, j1 = rem / P.G, j2 = rem - j1 * P.G;
+                    f_nb = far.start[c2];
+                    f_cnt = far.n ? far.n[c2] : min(far.start[c2 + 1] - f_nb, P.max_per_cell);
+                    if (abs(j3 - i3) <= 1 && abs(j1 - i1) <= 1 && abs(j2 - i2) <= 1) f_cnt = 0;
+                }
+                for (unsigned long long ft = __ballot(f_cnt > 0); ft; ft &= ft - 1) {
+                    const int q = __builtin_amdgcn_readfirstlane(__ffsll((long long)ft) - 1);
+                    const int nb = __builtin_amdgcn_readlane(f_nb, q), n = __builtin_amdgcn_readlane(f_cnt, q);
+                    const float *sx = far.buf + nb;
+                    if (FIELDS & PSAMD_PROBE_ACC) {
+                        for (int j0 = 0; j0 < n; j0 += POT_CHAIN) {
+                            float cx = 0.f, cy = 0.f, cz = 0.f;
+                            probe_acc_walk<MATH>(P, ctx, sx + j0, sx + plane + j0, sx + 2 * plane + j0, sx + 3 * plane + j0,
+                                                 min(POT_CHAIN, n - j0), eps2f, cx, cy, cz);
+                            fx += (double)cx; fy += (double)cy; fz += (double)cz;
+                        }
+                    }
+                    if (FIELDS & PSAMD_PROBE_PHI)
+                        pot_walk<false>(ctx, sx, sx + plane, sx + 2 * plane, sx + 3 * plane, n, 0, eps2f, far.padded != 0, acc);
+                }
+            }
+            if (FIELDS & PSAMD_PROBE_ACC) {
+                ax = (float)((double)ax + fx); ay = (float)((double)ay + fy); az = (float)((double)az + fz);
+            }
+        }
+        if ((mine >> lane) & 1ull) {
+            const float phi = (FIELDS & PSAMD_PROBE_PHI) ? (float)(-acc) : 0.f;
+            out4[i] = make_float4(ax, ay, az, phi);          // (components not asked for were never touched: 0)
+            if (!(probe_finite(ax) && probe_finite(ay) && probe_finite(az) && probe_finite(phi))) nonfinite = 1;
+        }
+    }
+    const int cnt = __popcll(__ballot(nonfinite != 0));
+    if (lane == 0 && cnt) atomicAdd(&hdr[PH_NONFINITE], cnt);
+}
+
+__global__ void k_probe_finish(int64_t max_count, const int64_t *count_dev, const int *__restrict__ hdr,
+                               psamd_probe_result *own, psamd_probe_result *out)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    psamd_probe_result res;
+    res.done = entry_count(count_dev, max_count);
+    res.served = hdr[PH_SERVED]; res.outside = hdr[PH_OUTSIDE]; res.foreign = hdr[PH_FOREIGN]; res.nonfinite = hdr[PH_NONFINITE];
+    write_result(own, out, res);
+}
+
+template <int FIELDS, int MATH>
+static void launch_probe_pairs(hipStream_t st, const DevParams &P, const DeviceState &d, const ProbeArgs &a, const ProbeScratch &s,
+                               int *hdr, unsigned nwg)
+{
+    if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
+        if constexpr (MATH != 0) {     // (a context with all-pairs forces is created only with lean arithmetic; world 1: the own snapshot, cells by local == global index)
+            const PotFar far{d.snap_soa, d.cell_start, nullptr, (unsigned long long)P.sorted_cap, 1};
+            k_probe_pairs<FIELDS, MATH, true><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, far, a.out4);
+        }
+    } else
+        k_probe_pairs<FIELDS, MATH, false><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, PotFar{}, a.out4);
+}
+
+template <int FIELDS>
+static void launch_probe_fields(hipStream_t st, const DevParams &P, const DeviceState &d, const ProbeArgs &a, const ProbeScratch &s,
+                                int *hdr, unsigned nwg)
+{
+    if (!P.lean_math) launch_probe_pairs<FIELDS, 0>(st, P, d, a, s, hdr, nwg);
+    else if (P.flags & PSAMD_FLAG_FAST_MATH) launch_probe_pairs<FIELDS, 2>(st, P, d, a, s, hdr, nwg);
+    else launch_probe_pairs<FIELDS, 1>(st, P, d, a, s, hdr, nwg);
+}
+
+hipError_t launch_probe(hipStream_t st, const DevParams &P, const DeviceState &d, const ProbeArgs &a, const ProbeScratch &s)
+{
+    const int ncells = P.n_local_cells;
+    int *hdr = s.counts + ncells + 1;
+    {   const hipError_t e = hipMemsetAsync(s.counts, 0, (size_t)(ncells + 1 + PROBE_HDR_WORDS) * sizeof(int), st); if (e != hipSuccess) return e; }
+    const unsigned blocks = (unsigned)((a.max_count + PROBE_THREADS - 1) / PROBE_THREADS);
+    k_probe_locate<<<blocks, PROBE_THREADS, 0, st>>>(P, a.pos4, a.max_count, a.count_dev, s.code, s.counts, hdr, a.out4, a.outcome);
+    PS_LAUNCH_CHECK();
+    k_probe_scan<<<1, 1024, 0, st>>>(ncells, s.counts);
+    PS_LAUNCH_CHECK();
+    k_probe_scatter<<<blocks, PROBE_THREADS, 0, st>>>(a.max_count, a.count_dev, s.code, s.counts, s.order);
+    PS_LAUNCH_CHECK();
+    const unsigned nwg = (unsigned)((a.max_count + 255) / 256);
+    if (a.fields == PSAMD_PROBE_ACC) launch_probe_fields<PSAMD_PROBE_ACC>(st, P, d, a, s, hdr, nwg);
+    else if (a.fields == PSAMD_PROBE_PHI) launch_probe_fields<PSAMD_PROBE_PHI>(st, P, d, a, s, hdr, nwg);
+    else launch_probe_fields<PSAMD_PROBE_ACC | PSAMD_PROBE_PHI>(st, P, d, a, s, hdr, nwg);
+    PS_LAUNCH_CHECK();
+    k_probe_finish<<<1, 64, 0, st>>>(a.max_count, a.count_dev, hdr, s.own, a.result);
+    PS_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+}  // namespace psamd

@@ -1,5 +1,5 @@
 // services.hip -- the host side of the on-stream services: psamd_export_live (export.hip), psamd_inject (inject.hip),
-// psamd_remove (remove.hip), psamd_potential (potential.hip), their host-array forms and their result records.
+// psamd_remove (remove.hip), psamd_potential (potential.hip), psamd_probe (probe.hip), their host-array forms and their result records.
 // A service enqueues its launches on the context's stream and returns; nothing here enqueues a stage of the step.
 #include "context.hpp"
 
@@ -191,13 +191,20 @@ int psamd_remove(psamd_ctx *c, const psamd_remove_spec *spec)
 int psamd_remove_result_get(psamd_ctx *c, psamd_remove_result *out) { return read_own(c, out, c ? c->rem.own : nullptr, sizeof *out); }
 
 // ---- energy (potential.hip) ----
-// a frame is built, its particles have not moved, and -- a slab -- the halos are in and nothing of the plan is lent
-static int potential_ready(psamd_ctx *c)
+// a frame is built, its particles have not moved, and -- a slab -- the halos are in (potential and probe)
+static int frame_ready(psamd_ctx *c, const char *who)
 {
     if (c->wedged) return refuse_wedged(c);
     const bool ok = c->P.world > 1 ? c->slab_stage == 2 : (c->grid_built && c->slab_stage != 3);
-    if (!ok) return fail(c, PSAMD_ERR_STATE, c->P.world > 1 ? "potential belongs between slab_pairs and slab_apply"
-                                                             : "potential needs build_grid first, and a frame that has not been applied");
+    if (!ok) return fail(c, PSAMD_ERR_STATE, std::string(who) + (c->P.world > 1 ? " belongs between slab_pairs and slab_apply"
+                                                                                : " needs build_grid first, and a frame that has not been applied"));
+    return PSAMD_OK;
+}
+
+// ... and nothing of the plan is lent
+static int potential_ready(psamd_ctx *c)
+{
+    PS_TRY(frame_ready(c, "potential"));
     const SlabPlan &pl = c->plan;
     if (c->P.world > 1 && (pl.lentin_lo < pl.lentin_hi || pl.lentout_lo < pl.lentout_hi))
         return fail(c, PSAMD_ERR_UNSUPPORTED, "potential: this rank's plan lends cell layers (lentin / lentout not empty); only plans "
@@ -238,5 +245,42 @@ int psamd_download_potential(psamd_ctx *c, float *phi, int64_t capacity, psamd_p
     if (out) *out = got.result;
     return PSAMD_OK;
 }
+
+// ---- the field at chosen points (probe.hip) ----
+// the probes' scratch for max_count entries: grows only, and not under a capture (hipFree / hipMalloc cannot be recorded)
+static int grow_probe_scratch(psamd_ctx *c, ProbeScratch &s, int64_t max_count)
+{
+    if (max_count <= s.cap) return PSAMD_OK;
+    PS_TRY(refuse_capture(c, "probe", "max_count exceeds every earlier call's: the scratch would have to grow"));
+    for (void *p : {(void *)s.code, (void *)s.order}) if (p) PS_HIP(c, hipFree(p));
+    s.code = s.order = nullptr; s.cap = 0;
+    const int64_t room = (max_count + ENTRY_TILE - 1) / ENTRY_TILE * ENTRY_TILE;
+    PS_HIP(c, hipMalloc((void **)&s.code, (size_t)room * sizeof(int)));
+    PS_HIP(c, hipMalloc((void **)&s.order, (size_t)room * sizeof(int)));
+    s.cap = room;
+    return PSAMD_OK;
+}
+
+int psamd_probe(psamd_ctx *c, const psamd_probe_spec *spec)
+{
+    PS_TRY(service_args(c, spec));
+    if (spec->fields == 0 || (spec->fields & ~(PSAMD_PROBE_ACC | PSAMD_PROBE_PHI)) || spec->reserved != 0)
+        return fail(c, PSAMD_ERR_INVALID_ARG, "probe: fields 0 or with unknown bits, or reserved not 0");
+    if (spec->max_count < 0 || spec->max_count > INT32_MAX) return fail(c, PSAMD_ERR_INVALID_ARG, "probe: max_count outside [0, 2^31)");
+    if ((spec->max_count > 0 && (!spec->pos4 || !spec->out4)) || !aligned(spec->pos4, 16) || !aligned(spec->out4, 16) ||
+        !aligned(spec->outcome_dev, 4) || !aligned(spec->count_dev, 8) || !aligned(spec->result_dev, 8))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "probe: pos4 or out4 missing, or an array misaligned");
+    if ((c->P.flags & PSAMD_FLAG_ALL_PAIRS) && c->P.world > 1)
+        return fail(c, PSAMD_ERR_UNSUPPORTED, "probe: all-pairs contexts are served on one context only (world == 1)");
+    PS_TRY(frame_ready(c, "probe"));
+    psamd_probe_result *res = spec->result_dev ? spec->result_dev : c->prb.own;
+    if (spec->max_count == 0) return zero_result(c, c->prb.own, res, sizeof *res);
+    PS_TRY(grow_probe_scratch(c, c->prb, spec->max_count));
+    const ProbeArgs a{spec->fields, (const float4 *)spec->pos4, spec->max_count, spec->count_dev, (float4 *)spec->out4, spec->outcome_dev, res};
+    PS_HIP(c, launch_probe(c->stream, c->P, c->d, a, c->prb));
+    return PSAMD_OK;
+}
+
+int psamd_probe_result_get(psamd_ctx *c, psamd_probe_result *out) { return read_own(c, out, c ? c->prb.own : nullptr, sizeof *out); }
 
 }  // extern "C"

@@ -467,7 +467,8 @@ int psamd_slab_buffers_get(psamd_ctx *ctx, psamd_slab_buffers *out);
  * slab_finish of the step AFTER, on every rank alike; an error raised after a rank's
  * record was closed goes out with the next step's record and stops every rank there (or is reported by
  * psamd_synchronize).  All asynchronous on the context's stream.  With world == 1
- * the four calls are psamd_step(1) cut in four and no message exists. */
+ * the four calls are psamd_step(1) cut in four and no message exists; with world == 1 a frame is stepped by one
+ * family of calls -- these, or init_iframe / build_grid / calc_forces / step -- from its build to its end. */
 int psamd_slab_build(psamd_ctx *ctx);   /* init_iframe + build_grid of the own layers; packs halo_out   */
 int psamd_slab_pairs_interior(psamd_ctx *ctx);  /* optional, while the halo travels: the pair stage of the cells whose
                                                     stencil lies in the rank's own layers (needs the status records only) */

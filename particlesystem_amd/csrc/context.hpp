@@ -18,6 +18,7 @@
 
 #include "../../include/psamd.h"
 #include "device_types.h"
+#include "frame_stage.hpp"
 #include "geometry.hpp"
 #include "kernels.h"
 #include "partition.hpp"
@@ -33,6 +34,8 @@ struct SlabMsg {
 };
 // bytes of a transfer message with room for `recs` records
 inline size_t xfer_msg_bytes(size_t recs) { return ((size_t)MSG_HEADER_WORDS + recs * (sizeof(XferRec) / sizeof(int))) * sizeof(int); }
+// the kinds of stage sequence that are captured as hipGraphs (step.hip: run_segment)
+enum { SEG_BUILD = 0, SEG_PAIRS, SEG_APPLY, SEG_FINISH, SEG_STEP, NSEG };
 }  // namespace psamd
 
 using namespace psamd;      // (a private header: every host unit speaks these types)
@@ -41,7 +44,7 @@ struct psamd_ctx {
     Geometry geo;
     DevParams P{};
     DevParams P_int{}, P_rest{};      // the pair stage cut in two: interior own cells (no halo needed), the rest
-    bool have_interior = false, interior_done = false;
+    bool have_interior = false;
     SegLayout S{};
     DeviceState d;
     hipStream_t stream = nullptr;       // stream in use
@@ -51,13 +54,12 @@ struct psamd_ctx {
     int halo_out_c0[2] = {0, 0}, halo_out_cells[2] = {0, 0}, halo_in_cells[2] = {0, 0};
     std::map<int, int> cap_decisions; // slab: record number -> the transfer capacity all ranks agreed on in that step (adopted two steps on)
     int *pack_off[2] = {nullptr, nullptr}, *unpack_off[2] = {nullptr, nullptr};
-    int slab_stage = 0;               // 0 idle, 1 built, 2 pairs done, 3 applied
     size_t frame_ints = 0;            // ints zeroed by init_iframe
     std::vector<void *> allocs;
     std::string err;
     // host mirrors
     std::vector<CellInfo> celltab;
-    std::vector<QueueInfo> h_qinfo;   // valid while !queues_on_device_newer
+    std::vector<QueueInfo> h_qinfo;   // with h_queue the host's mirror of the queues, current while host_queues_valid
     std::vector<int32_t> h_queue;
     bool host_queues_valid = true;    // host mirror == device copy
     FrameScalars *h_fs = nullptr;     // pinned host copies of the per-frame scalars: TWO records, a step's number picks one
@@ -69,8 +71,7 @@ struct psamd_ctx {
     int snapshot_step = 0;
     void *staging = nullptr;          // device staging for AoS transfers
     size_t staging_bytes = 0;
-    // stage state machine
-    bool frame_reset = false, grid_built = false, pairs_done = false;
+    Stage stage = ST_IDLE;            // where the host stands in the frame in progress: moved by enter / leave alone (frame_stage.hpp)
     bool tdata_mirror = true;         // build_grid also writes the reference's T_DATA rows (psamd_set_tdata_mirror)
     bool frame_clean = true;          // the per-frame counts are zero: a finished step leaves them so (its last kernel is the next init_iframe)
     int step = 0;
@@ -117,7 +118,7 @@ struct psamd_ctx {
     // stage sequences as hipGraphs (psamd_set_graphs): per kind of sequence, the shapes captured so far
     struct GraphSlot { uint64_t key; hipGraphExec_t exec; uint64_t stamp; };
     bool graphs = false;
-    std::vector<GraphSlot> gcache[5];
+    std::vector<GraphSlot> gcache[NSEG];
     uint64_t gstamp = 0;
     int64_t graph_launches = 0, graph_captures = 0;
     std::string graph_refused;         // why the runtime would not capture (the context then runs without graphs)
@@ -170,7 +171,7 @@ int check_device_errors(psamd_ctx *c);              // step.hip: after a sync, t
 int drain_scalars(psamd_ctx *c, bool quiet = false);
 int refuse_wedged(psamd_ctx *c);
 int ensure_staging(psamd_ctx *c, size_t bytes);     // io.hip: the device staging buffer holds at least so many bytes
-void end_frame(psamd_ctx *c);                       // services.hip: the slots or queues changed under the host's frame
+void end_frame(psamd_ctx *c, Call why = CALL_CHANGED);  // services.hip: the slots or queues changed under the host's frame
 void drop_graphs(psamd_ctx *c);
 
 }  // namespace psamd

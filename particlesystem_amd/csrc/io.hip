@@ -98,8 +98,7 @@ int psamd_fill_particles(psamd_ctx *c, int64_t n, const float *xyz, const float 
     if (n_done) *n_done = 0;
     if (!c || n < 0 || (n > 0 && !xyz)) return PSAMD_ERR_INVALID_ARG;
     if (n == 0) return PSAMD_OK;
-    int rc = pull_queues(c);
-    if (rc != PSAMD_OK) return rc;
+    PS_TRY(pull_queues(c));
     const Geometry &g = c->geo;
     struct Rec { float4 p, v, a; int cell; };
     std::vector<int32_t> ids((size_t)n);
@@ -133,8 +132,7 @@ int psamd_fill_particles(psamd_ctx *c, int64_t n, const float *xyz, const float 
         std::vector<int> hc(m);
         for (size_t k = 0; k < m; k++) { hp[k] = recs[k].p; hv[k] = recs[k].v; ha[k] = recs[k].a; hc[k] = recs[k].cell; }
         const size_t bytes = m * (3 * sizeof(float4) + 2 * sizeof(int));
-        rc = ensure_staging(c, bytes);
-        if (rc != PSAMD_OK) return rc;
+        PS_TRY(ensure_staging(c, bytes));
         char *base = (char *)c->staging;
         float4 *dp = (float4 *)base, *dv = dp + m, *da = dv + m;
         int *dc = (int *)(da + m), *di = dc + m;
@@ -146,12 +144,11 @@ int psamd_fill_particles(psamd_ctx *c, int64_t n, const float *xyz, const float 
         PS_HIP(c, launch_place(c->stream, c->P, (int)done, di, dp, dv, da, dc, c->d));
         PS_HIP(c, hipStreamSynchronize(c->stream));
     }
-    rc = push_queues(c);
-    if (rc != PSAMD_OK) return rc;
+    PS_TRY(push_queues(c));
     if (ids_out) std::copy(ids.begin(), ids.begin() + done, ids_out);
     if (n_done) *n_done = done;
     if (c->live_bound >= 0) c->live_bound += placed;
-    c->grid_built = false; c->pairs_done = false; c->slab_stage = 0;
+    leave(c->stage, CALL_CHANGED);
     return status;
 }
 
@@ -159,14 +156,13 @@ int psamd_upload_particles(psamd_ctx *c, const void *p72, int64_t first, int64_t
 {
     if (!c || !p72 || first < 0 || count < 0 || first + count > c->geo.container) return PSAMD_ERR_INVALID_ARG;
     if (count == 0) return PSAMD_OK;
-    int rc = ensure_staging(c, (size_t)count * 72);
-    if (rc != PSAMD_OK) return rc;
+    PS_TRY(ensure_staging(c, (size_t)count * 72));
     PS_HIP(c, hipMemcpyAsync(c->staging, p72, (size_t)count * 72, hipMemcpyHostToDevice, c->stream));
     // odd grids are not centred (G/2 is an integer division): allow the longer half
     const float half_box = (float)((c->geo.G - c->geo.G / 2) * c->geo.cfg.cell_size);
     PS_HIP(c, launch_unpack_aos(c->stream, c->P, c->staging, (int)first, (int)count, half_box, c->d));
     PS_HIP(c, hipStreamSynchronize(c->stream));
-    c->grid_built = false; c->pairs_done = false; c->slab_stage = 0;
+    leave(c->stage, CALL_CHANGED);
     c->live_bound = -1;
     return check_device_errors(c);
 }
@@ -175,8 +171,7 @@ int psamd_download_particles(psamd_ctx *c, void *p72, int64_t first, int64_t cou
 {
     if (!c || !p72 || first < 0 || count < 0 || first + count > c->geo.container) return PSAMD_ERR_INVALID_ARG;
     if (count == 0) return PSAMD_OK;
-    int rc = ensure_staging(c, (size_t)count * 72);
-    if (rc != PSAMD_OK) return rc;
+    PS_TRY(ensure_staging(c, (size_t)count * 72));
     PS_HIP(c, launch_pack_aos(c->stream, c->P, c->staging, (int)first, (int)count, c->d));
     PS_HIP(c, hipMemcpyAsync(p72, c->staging, (size_t)count * 72, hipMemcpyDeviceToHost, c->stream));
     PS_HIP(c, hipStreamSynchronize(c->stream));
@@ -215,8 +210,7 @@ int psamd_upload_queues(psamd_ctx *c, const void *qi, const int32_t *queue)
 int psamd_download_queues(psamd_ctx *c, void *qi, int32_t *queue)
 {
     if (!c || !qi || !queue) return PSAMD_ERR_INVALID_ARG;
-    int rc = pull_queues(c);
-    if (rc != PSAMD_OK) return rc;
+    PS_TRY(pull_queues(c));
     std::memcpy(qi, c->h_qinfo.data(), c->h_qinfo.size() * sizeof(QueueInfo));
     std::memcpy(queue, c->h_queue.data(), c->h_queue.size() * sizeof(int32_t));
     return PSAMD_OK;
@@ -226,7 +220,7 @@ int psamd_download_queues(psamd_ctx *c, void *qi, int32_t *queue)
 // indexed by the own LOCAL cells (region 0); local cell lc is global cell lc + cell_off.
 static int fetch_sorted(psamd_ctx *c, std::vector<int> &start, std::vector<int> &ids)
 {
-    if (!c->grid_built) return fail(c, PSAMD_ERR_STATE, "grid lists requested before build_grid");
+    if (!built(c->stage)) return fail(c, PSAMD_ERR_STATE, "grid lists requested before build_grid");
     start.resize((size_t)c->P.n_own_cells + 1);
     PS_HIP(c, hipStreamSynchronize(c->stream));
     PS_HIP(c, hipMemcpy(start.data(), c->d.cell_start, start.size() * sizeof(int), hipMemcpyDeviceToHost));
@@ -239,8 +233,7 @@ int psamd_download_cellgrid(psamd_ctx *c, int32_t *out)
 {
     if (!c || !out) return PSAMD_ERR_INVALID_ARG;
     std::vector<int> start, ids;
-    int rc = fetch_sorted(c, start, ids);
-    if (rc != PSAMD_OK) return rc;
+    PS_TRY(fetch_sorted(c, start, ids));
     const Geometry &g = c->geo;
     const size_t stride = 1 + (size_t)g.max_per_cell;
     const int cell_off = c->P.reg_first[0] * g.G * g.G;
@@ -257,7 +250,7 @@ int psamd_download_cellgrid(psamd_ctx *c, int32_t *out)
 int psamd_download_force_counts(psamd_ctx *c, int32_t *out)
 {
     if (!c || !out) return PSAMD_ERR_INVALID_ARG;
-    if (!c->pairs_done) return fail(c, PSAMD_ERR_STATE, "force counts requested before the pair pass of this frame");
+    if (!pairs_done(c->stage)) return fail(c, PSAMD_ERR_STATE, "force counts requested before the pair pass of this frame");
     PS_HIP(c, hipStreamSynchronize(c->stream));
     const Geometry &g = c->geo;
     const DevParams &P = c->P;
@@ -278,8 +271,7 @@ int psamd_download_chunkgrid(psamd_ctx *c, int32_t *out)
 {
     if (!c || !out) return PSAMD_ERR_INVALID_ARG;
     std::vector<int> start, ids;
-    int rc = fetch_sorted(c, start, ids);
-    if (rc != PSAMD_OK) return rc;
+    PS_TRY(fetch_sorted(c, start, ids));
     const Geometry &g = c->geo;
     const size_t stride = 1 + (size_t)g.max_per_chunk;
     const int cell_off = c->P.reg_first[0] * g.G * g.G;
@@ -327,8 +319,8 @@ int psamd_get_gridmax(psamd_ctx *c, int32_t out2[2])
     // belongs to the next frame already and the step's scalars are in the host's copy (ps.cpp:1900 reads hostGridMax
     // between the stages; the reference's array keeps the build's values until the next init_iframe)
     const int rc = drain_scalars(c);
-    if (rc != PSAMD_OK && !c->grid_built) return rc;
-    if (c->grid_built) {
+    if (rc != PSAMD_OK && !built(c->stage)) return rc;
+    if (built(c->stage)) {
         FrameScalars fs{};
         PS_HIP(c, hipMemcpy(&fs, c->d.fs, sizeof fs, hipMemcpyDeviceToHost));
         out2[0] = fs.gridmax[0]; out2[1] = fs.gridmax[1];
@@ -423,8 +415,7 @@ int psamd_download_force4(psamd_ctx *c, void *out, int64_t first, int64_t count)
 {
     if (!c || !out || first < 0 || count < 0 || first + count > c->P.sorted_cap) return PSAMD_ERR_INVALID_ARG;
     if (count == 0) return PSAMD_OK;
-    int rc = ensure_staging(c, (size_t)count * sizeof(float4));
-    if (rc != PSAMD_OK) return rc;
+    PS_TRY(ensure_staging(c, (size_t)count * sizeof(float4)));
     PS_HIP(c, launch_force_gather(c->stream, c->P, c->d, c->staging, (int)first, (int)count));
     PS_HIP(c, hipMemcpyAsync(out, c->staging, (size_t)count * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     PS_HIP(c, hipStreamSynchronize(c->stream));
@@ -478,8 +469,7 @@ int psamd_snapshot_restore(psamd_ctx *c)
     if (!c->snapshot) return fail(c, PSAMD_ERR_STATE, "snapshot_restore without a saved snapshot");
     c->step = c->snapshot_step;
     c->live_bound = c->snapshot_live_bound;
-    end_frame(c);
-    c->frame_reset = false;
+    end_frame(c, CALL_RESTORE);
     return snapshot_copy(c, false);
 }
 

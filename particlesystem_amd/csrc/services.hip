@@ -40,10 +40,10 @@ static int read_own(psamd_ctx *c, void *out, const void *src, size_t bytes)
 }
 
 // The slots or the queues changed on the device: the host's frame in progress is over and its queue mirror is behind.
-void psamd::end_frame(psamd_ctx *c)
+void psamd::end_frame(psamd_ctx *c, Call why)
 {
     c->host_queues_valid = false;
-    c->grid_built = false; c->pairs_done = false; c->slab_stage = 0;
+    leave(c->stage, why);
 }
 
 // the entries' scratch for max_count entries: grows only (hipFree waits for the device; steady use never gets here)
@@ -195,8 +195,7 @@ int psamd_remove_result_get(psamd_ctx *c, psamd_remove_result *out) { return rea
 static int frame_ready(psamd_ctx *c, const char *who)
 {
     if (c->wedged) return refuse_wedged(c);
-    const bool ok = c->P.world > 1 ? c->slab_stage == 2 : (c->grid_built && c->slab_stage != 3);
-    if (!ok) return fail(c, PSAMD_ERR_STATE, std::string(who) + (c->P.world > 1 ? " belongs between slab_pairs and slab_apply"
+    if (!field_window(c->stage, c->P.world)) return fail(c, PSAMD_ERR_STATE, std::string(who) + (c->P.world > 1 ? " belongs between slab_pairs and slab_apply"
                                                                                 : " needs build_grid first, and a frame that has not been applied"));
     return PSAMD_OK;
 }

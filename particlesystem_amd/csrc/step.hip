@@ -11,7 +11,7 @@ int psamd::check_device_errors(psamd_ctx *c)
 {
     FrameScalars fs{};
     PS_HIP(c, hipMemcpy(&fs, c->d.fs, sizeof fs, hipMemcpyDeviceToHost));
-    if (!c->grid_built) for (int k = 0; k < 5; k++) fs.n_out[k] = c->last.n_out[k];      // (between steps the device's record is the next frame's, zeroed)
+    if (!built(c->stage)) for (int k = 0; k < 5; k++) fs.n_out[k] = c->last.n_out[k];      // (between steps the device's record is the next frame's, zeroed)
     if (fs.error & (ERR_BAD_ID | ERR_BAD_POS)) {
         // an upload error is reported once and then cleared: the rejected records stay in the
         // container, the caller is expected to upload valid ones over them
@@ -102,6 +102,18 @@ int psamd::refuse_wedged(psamd_ctx *c)
 {
     return fail(c, PSAMD_ERR_STATE, "the GPU stopped answering (a step's scalars did not arrive within " + std::to_string((int)c->wait_limit_s) +
                                     " s while its stream stayed busy): this context takes no further work; destroy it");
+}
+
+// The front of every stage call: a context, one that still answers, a call of the family a slab of several is stepped by,
+// and the order test (frame_stage.hpp).  A refused call has touched nothing.
+static int enter_stage(psamd_ctx *c, Call k)
+{
+    static const char *const plain[] = {"init_iframe", "build_grid", "calc_forces", "calc_forces", "step"};
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    if (k < CALL_SLAB_BUILD && c->P.world > 1) return slab_only(c, plain[k]);
+    const char *why = enter(c->stage, k);
+    return why ? fail(c, PSAMD_ERR_STATE, why) : (int)PSAMD_OK;
 }
 
 // which steps carry timing events is settled when the step begins (before anything is enqueued or replayed)
@@ -216,8 +228,6 @@ static int enq_lifecycle(psamd_ctx *c, int64_t bound)
 }
 
 // ---- hipGraph cache ----
-enum { SEG_BUILD = 0, SEG_PAIRS, SEG_APPLY, SEG_FINISH, SEG_STEP, NSEG };
-
 void psamd::drop_graphs(psamd_ctx *c)
 {
     for (auto &cache : c->gcache) {
@@ -378,7 +388,6 @@ static int finish_step(psamd_ctx *c)
     if (c->interior_ran) c->interior_steps.insert(seq);
     c->interior_ran = false;
     if (c->timing_now) { c->ev_level[c->tset] = c->timing_now; c->timed_steps++; }
-    c->grid_built = false; c->pairs_done = false;
     c->frame_clean = true;                       // (the step's last kernel zeroed the counts for the frame that follows)
     c->step++; c->steps_total++;
     // run-ahead: this step's record is read when the NEXT step has been enqueued (the record of the step before must be
@@ -400,73 +409,59 @@ extern "C" {
 
 int psamd_init_iframe(psamd_ctx *c)
 {
-    if (!c) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
-    if (c->P.world > 1) return slab_only(c, "init_iframe");
+    PS_TRY(enter_stage(c, CALL_INIT_IFRAME));
     begin_step(c);
-    if (c->grid_built) c->frame_clean = false;      // (a frame abandoned after its build: its counts are in the way)
-    const int rc = enq_init_iframe(c);
-    if (rc != PSAMD_OK) return rc;
+    if (built(c->stage)) c->frame_clean = false;      // (a frame abandoned after its build: its counts are in the way)
+    PS_TRY(enq_init_iframe(c));
     c->frame_clean = true;
-    c->frame_reset = true; c->grid_built = false; c->pairs_done = false;
+    leave(c->stage, CALL_INIT_IFRAME);
     return PSAMD_OK;
 }
 
 int psamd_build_grid(psamd_ctx *c)
 {
-    if (!c) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
-    if (c->P.world > 1) return slab_only(c, "build_grid");
-    if (!c->frame_reset) return fail(c, PSAMD_ERR_STATE, "build_grid needs init_iframe first");
-    const int rc = enq_build_grid(c);
-    if (rc != PSAMD_OK) return rc;
-    c->frame_reset = false; c->grid_built = true; c->pairs_done = false; c->frame_clean = false;
+    PS_TRY(enter_stage(c, CALL_BUILD_GRID));
+    PS_TRY(enq_build_grid(c));
+    c->frame_clean = false;
+    leave(c->stage, CALL_BUILD_GRID);
     return PSAMD_OK;
 }
 
 int psamd_calc_forces_pairs(psamd_ctx *c)
 {
-    if (!c) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
-    if (c->P.world > 1) return slab_only(c, "calc_forces");
-    if (!c->grid_built) return fail(c, PSAMD_ERR_STATE, "calc_forces needs build_grid first");
-    const int rc = enq_pairs(c, c->P, pairs_hint(c, c->P));
-    if (rc != PSAMD_OK) return rc;
-    c->pairs_done = true;
+    PS_TRY(enter_stage(c, CALL_PAIRS));
+    PS_TRY(enq_pairs(c, c->P, pairs_hint(c, c->P)));
+    leave(c->stage, CALL_PAIRS);
     return PSAMD_OK;
 }
 
 int psamd_calc_forces_apply(psamd_ctx *c)
 {
-    if (!c) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
-    if (c->P.world > 1) return slab_only(c, "calc_forces");
-    if (!c->grid_built || !c->pairs_done) return fail(c, PSAMD_ERR_STATE, "apply needs build_grid and the pair pass first");
+    PS_TRY(enter_stage(c, CALL_APPLY));
     const int64_t bound = live_bound_of(c);
     (void)pick_bucket_cap(c);
     int rc = enq_apply(c, bound);
     if (rc == PSAMD_OK) rc = enq_lifecycle(c, bound);
     if (rc != PSAMD_OK) { resync_scalars(c); return rc; }
+    leave(c->stage, CALL_APPLY);
     return finish_step(c);
 }
 
 int psamd_calc_forces(psamd_ctx *c)
 {
-    if (!c) return PSAMD_ERR_INVALID_ARG;
-    int rc = psamd_calc_forces_pairs(c);
-    if (rc != PSAMD_OK) return rc;
+    PS_TRY(psamd_calc_forces_pairs(c));
     return psamd_calc_forces_apply(c);
 }
 
 int psamd_step(psamd_ctx *c, int32_t nsteps)
 {
     if (!c || nsteps < 0) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
-    if (c->P.world > 1 && nsteps > 0) return slab_only(c, "step");
+    if (nsteps == 0) return c->wedged ? refuse_wedged(c) : (int)PSAMD_OK;
     for (int k = 0; k < nsteps; k++) {
         // init_iframe, build_grid, calc_forces: one sequence of launches (one graph)
+        PS_TRY(enter_stage(c, CALL_STEP));
         begin_step(c);
-        if (c->grid_built) c->frame_clean = false;
+        if (built(c->stage)) c->frame_clean = false;
         const int64_t hint = pairs_hint(c, c->P), bound = live_bound_of(c);
         const uint64_t key = launch_pairs_shape(c->P, hint) | ((uint64_t)bound << 24) | pick_bucket_cap(c) | (build_key(c) << 58);
         int rc = run_segment(c, SEG_STEP, key, [&]() {
@@ -479,9 +474,8 @@ int psamd_step(psamd_ctx *c, int32_t nsteps)
         });
         c->frame_clean = false;
         if (rc != PSAMD_OK) { resync_scalars(c); return rc; }
-        c->frame_reset = false; c->grid_built = true; c->pairs_done = true;
-        rc = finish_step(c);
-        if (rc != PSAMD_OK) return rc;
+        leave(c->stage, CALL_STEP);
+        PS_TRY(finish_step(c));
     }
     return PSAMD_OK;
 }
@@ -490,10 +484,9 @@ int psamd_step(psamd_ctx *c, int32_t nsteps)
 
 int psamd_slab_build(psamd_ctx *c)
 {
-    if (!c) return PSAMD_ERR_INVALID_ARG;
-    if (c->wedged) return refuse_wedged(c);
+    PS_TRY(enter_stage(c, CALL_SLAB_BUILD));
     begin_step(c);
-    if (c->grid_built) c->frame_clean = false;
+    if (built(c->stage)) c->frame_clean = false;
     {   // The transfer messages' capacity the ranks agreed on two steps ago (k_status_merge) takes effect now, on every rank
         // in this same step: the record of step s - 2 has been read by every host that starts step s, whatever its run-ahead.
         // A decision is an absolute number (grown, kept or shrunk: the rule is k_status_merge's), the same on every rank.
@@ -516,8 +509,8 @@ int psamd_slab_build(psamd_ctx *c)
         return (int)PSAMD_OK;
     });
     if (rc != PSAMD_OK) return rc;
-    c->frame_reset = false; c->grid_built = true; c->pairs_done = false; c->frame_clean = false;
-    c->slab_stage = 1;
+    c->frame_clean = false;
+    leave(c->stage, CALL_SLAB_BUILD);
     return PSAMD_OK;
 }
 
@@ -525,9 +518,8 @@ int psamd_slab_build(psamd_ctx *c)
 // stencil lies inside this rank's own layers
 int psamd_slab_pairs_interior(psamd_ctx *c)
 {
-    if (!c) return PSAMD_ERR_INVALID_ARG;
-    if (c->slab_stage != 1) return fail(c, PSAMD_ERR_STATE, "slab_pairs_interior belongs between slab_build and slab_pairs");
-    if (!c->have_interior || c->interior_done) return PSAMD_OK;
+    PS_TRY(enter_stage(c, CALL_SLAB_INTERIOR));
+    if (!c->have_interior || interior_passed(c->stage)) return PSAMD_OK;
     const int64_t hint = pairs_hint(c, c->P_int);
     const int rc = run_segment(c, SEG_PAIRS, launch_pairs_shape(c->P_int, hint) | (1ull << 40), [&]() {
         // (the status records have landed: the chunk lists' capacity rule over all ranks decides which particles the stage leaves alone)
@@ -535,17 +527,17 @@ int psamd_slab_pairs_interior(psamd_ctx *c)
         return enq_pairs(c, c->P_int, hint, false, true);
     });
     if (rc != PSAMD_OK) return rc;
-    c->interior_done = true; c->interior_ran = true;
+    c->interior_ran = true;
+    leave(c->stage, CALL_SLAB_INTERIOR);
     return PSAMD_OK;
 }
 
 int psamd_slab_pairs(psamd_ctx *c)
 {
-    if (!c) return PSAMD_ERR_INVALID_ARG;
-    if (c->slab_stage != 1) return fail(c, PSAMD_ERR_STATE, "slab_pairs needs slab_build (and the halo exchange) first");
+    PS_TRY(enter_stage(c, CALL_SLAB_PAIRS));
     const DevParams &P = c->P;
-    const DevParams &Pp = c->interior_done ? c->P_rest : c->P;
-    const bool second = c->interior_done;
+    const bool second = interior_passed(c->stage);
+    const DevParams &Pp = second ? c->P_rest : c->P;
     const int64_t hint = pairs_hint(c, Pp);
     // (the all-pairs far pass sizes its launch from the live bound on one GPU only -- a slab takes every entry of the
     // sorted order, see launch_pairs -- so the bound is no part of this key)
@@ -562,17 +554,13 @@ int psamd_slab_pairs(psamd_ctx *c)
         if (c->msg[MSG_FORCE_OUT].ptr) PS_HIP(c, launch_pack_force(c->stream, P, c->d, c->msg[MSG_FORCE_OUT].ptr, P.reg_layers[2] * GG * P.halo_cap_cell));
         return (int)PSAMD_OK;
     });
-    c->interior_done = false;
-    if (rc != PSAMD_OK) return rc;
-    c->pairs_done = true;
-    c->slab_stage = 2;
-    return PSAMD_OK;
+    leave(c->stage, CALL_SLAB_PAIRS, rc == PSAMD_OK);      // (the interior pass is spent either way)
+    return rc;
 }
 
 int psamd_slab_apply(psamd_ctx *c)
 {
-    if (!c) return PSAMD_ERR_INVALID_ARG;
-    if (c->slab_stage != 2) return fail(c, PSAMD_ERR_STATE, "slab_apply needs slab_pairs (and the force exchange) first");
+    PS_TRY(enter_stage(c, CALL_SLAB_APPLY));
     const int64_t bound = live_bound_of(c);
     const int rc = run_segment(c, SEG_APPLY, (uint64_t)bound | ((uint64_t)c->P.xfer_cap << 32), [&]() {
         // the status records of all ranks (all-gathered since slab_build): error bits, cell-overflow kills for the
@@ -584,15 +572,14 @@ int psamd_slab_apply(psamd_ctx *c)
     });
     if (rc != PSAMD_OK) return rc;
     c->slab_bound = bound;
-    c->slab_stage = 3;
+    leave(c->stage, CALL_SLAB_APPLY);
     return PSAMD_OK;
 }
 
 int psamd_slab_finish(psamd_ctx *c)
 {
-    if (!c) return PSAMD_ERR_INVALID_ARG;
-    if (c->slab_stage != 3) return fail(c, PSAMD_ERR_STATE, "slab_finish needs slab_apply (and the transfer exchange) first");
-    c->slab_stage = 0;
+    PS_TRY(enter_stage(c, CALL_SLAB_FINISH));
+    leave(c->stage, CALL_SLAB_FINISH);           // (the slab frame is over whatever becomes of the launches)
     const int64_t bound = c->slab_bound;
     const int rc = run_segment(c, SEG_FINISH, (uint64_t)bound | ((uint64_t)(c->P.xfer_cap & 0x1fffffff) << 32) | pick_bucket_cap(c), [&]() { return enq_lifecycle(c, bound); });
     if (rc != PSAMD_OK) { resync_scalars(c); return rc; }

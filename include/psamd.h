@@ -734,6 +734,12 @@ int psamd_device_view_get(psamd_ctx *ctx, psamd_device_view *out);
 /* Diagnostic builds (-DPSAMD_WAVE_TRACE) record per pair-kernel wave: start, end
  * (100 MHz real-time counter) and hardware id; 3 words per wave slot.  Zeros otherwise. */
 int psamd_debug_wave_trace(psamd_ctx *ctx, uint64_t *out, int64_t n_words);
+/* The packs of partly filled last slices of the frame's last pair stage (between psamd_calc_forces_pairs and the frame's
+ * end; the scalar walk of the two-pass stage has them, every other launch shape has none): *count packs, the first
+ * min(*count, capacity) of them as four cell numbers each in `cells` (-1: unused place), in pack order.  *shape (may be
+ * NULL): how that pair stage was launched -- wave slots / 32 in bits 0-9, bit 10 the tile walk (no packs), bit 11 the
+ * two-pass stage, from bit 12 the pack workgroups / 8.  Waits for the context's stream. */
+int psamd_debug_packs(psamd_ctx *ctx, int32_t *cells, int64_t capacity, int64_t *count, uint64_t *shape);
 
 /* Exhaustive check of the hand-written correctly rounded fp32 sqrt / reciprocal used by
  * the pair kernel against the compiler's forms, over every float with bit pattern in

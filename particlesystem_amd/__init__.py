@@ -320,6 +320,7 @@ ABI = [
     ("psamd_live_count", C.c_int, [_vp, C.POINTER(_i64)]),
     ("psamd_device_view_get", C.c_int, [_vp, C.POINTER(DeviceView)]),
     ("psamd_debug_wave_trace", C.c_int, [_vp, _vp, _i64]),
+    ("psamd_debug_packs", C.c_int, [_vp, _vp, _i64, C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]),
     ("psamd_selftest_math", C.c_int, [_vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     ("psamd_set_graphs", C.c_int, [_vp, C.c_int]),
     ("psamd_get_graph_stats", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
@@ -883,6 +884,15 @@ class ParticleSystem:
         out = np.zeros(n, np.uint64)
         self._ck(self.lib.psamd_debug_wave_trace(self.h, _ptr(out), n))
         return out.reshape(-1, 3)
+
+    def download_packs(self):
+        """psamd_debug_packs: (the last pair stage's packs as an (n, 4) array of cell numbers, -1 unused; its launch shape as a
+        dict: wave slots, tile walk, two-pass stage, pack workgroups)"""
+        n, shape = C.c_int64(), C.c_uint64()
+        out = np.full((self.sizes.num_cells, 4), -1, np.int32)
+        self._ck(self.lib.psamd_debug_packs(self.h, _ptr(out), len(out), C.byref(n), C.byref(shape)))
+        s = shape.value
+        return out[:n.value], dict(waves=32 * (s & 1023), tile=bool(s >> 10 & 1), two_pass=bool(s >> 11 & 1), pack_workgroups=8 * (s >> 12 & 0xfff))
 
     def selftest_math(self, lo_bits, hi_bits):
         out = (C.c_uint64 * 24)()

@@ -81,6 +81,7 @@ struct psamd_ctx {
     std::set<int> interior_steps;     // ... the numbers of such steps whose records have not been read yet
     int64_t tasks_last = 0;           // force tasks of the last step (all passes), sizes the next step's balanced pass
     int64_t packs_last = 0;           // ... of which packs of partly filled slices
+    uint64_t pairs_shape_last = 0;    // launch_pairs_shape of the last pair-stage launch (psamd_debug_packs)
     // upper bound of the live count at the next build_grid, kept on the host so that the
     // life-cycle kernels can be sized without a read-back (-1 = unknown)
     int64_t live_bound = 0, snapshot_live_bound = 0;

@@ -322,6 +322,10 @@ static int alloc_step_arrays(psamd_ctx *c)
     PS_HIP(c, hipMemsetAsync(c->prb.own, 0, sizeof(psamd_probe_result), c->stream));
     PS_HIP(c, dev_alloc(c, &d.trace, 3 * (LC * P.slices + 4)));
     PS_HIP(c, hipMemsetAsync(d.trace, 0, 3 * (LC * P.slices + 4) * sizeof(unsigned long long), c->stream));
+    // the packs of the leftovers by window (pack_fit.hpp); last, so that nothing older moves
+    PS_HIP(c, dev_alloc(c, &d.pack_stage, LC + 64));
+    PS_HIP(c, dev_alloc(c, &d.pack_count, LC / 64 + 1));
+    PS_HIP(c, dev_alloc(c, &d.pack_base, LC / 64 + 1));
     return PSAMD_OK;
 }
 

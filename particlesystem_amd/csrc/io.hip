@@ -482,6 +482,22 @@ int psamd_debug_wave_trace(psamd_ctx *c, uint64_t *out, int64_t n_words)
     return PSAMD_OK;
 }
 
+int psamd_debug_packs(psamd_ctx *c, int32_t *cells, int64_t capacity, int64_t *count, uint64_t *shape)
+{
+    if (!c || !count || capacity < 0 || (capacity > 0 && !cells)) return PSAMD_ERR_INVALID_ARG;
+    FrameScalars fs;
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    PS_HIP(c, hipMemcpy(&fs, c->d.fs, sizeof fs, hipMemcpyDeviceToHost));
+    // (only the two-pass stage runs the plan that writes n_merged: any other launch shape has no packs, whatever the word holds)
+    const bool planned = (c->pairs_shape_last >> 11 & 1) != 0;
+    const int64_t have = planned ? std::max<int64_t>(0, std::min<int64_t>(fs.n_merged, c->P.n_local_cells)) : 0;
+    *count = have;
+    if (shape) *shape = c->pairs_shape_last;
+    const int64_t n = std::min(have, capacity);
+    if (n > 0) PS_HIP(c, hipMemcpy(cells, c->d.merged_tasks, (size_t)n * sizeof(int4), hipMemcpyDeviceToHost));
+    return PSAMD_OK;
+}
+
 int psamd_selftest_math(psamd_ctx *c, uint32_t lo_bits, uint32_t hi_bits, uint64_t out24[24])
 {
     if (!c || !out24 || hi_bits < lo_bits) return PSAMD_ERR_INVALID_ARG;

@@ -155,6 +155,9 @@ struct DeviceState {
     long long *wave_pos = nullptr; // [waves + 1] where every wave slot of the balanced pass starts: task index << 32 | cost already walked inside the task
     int *task_ready = nullptr;    // [num_cells * slices] hand-off flags, zeroed with the frame
     int4 *merged_tasks = nullptr; // [num_cells] cells whose leftover slices share one wave (-1: unused)
+    int4 *pack_stage = nullptr;   // [num_cells, whole windows] the same, window by window as k_pack_windows leaves them (pack_fit.hpp)
+    int *pack_count = nullptr;    // [windows] packs of every window of 64 computed cells
+    int *pack_base = nullptr;     // [windows] the first pack of every window (k_plan_force, where its LDS does not hold them)
     // the merged tasks run beside k_pairs on a stream of their own (fork / join by events)
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;

@@ -1,7 +1,66 @@
 // plan.hip -- the plan of the balanced force pass: task list, packs, where every wave slot starts
 #include "balanced.hpp"
+#include "pack_fit.hpp"
 
 namespace psamd {
+
+// The largest of a wave's values (any ints), as a wave-uniform number: the row scan and the two
+// row broadcasts of the DPP network, the whole wave active.
+__device__ __forceinline__ int wave_max(int v)
+{
+#define PS_MAX_STEP(ctrl, rows) v = max(v, __builtin_amdgcn_update_dpp(v, v, ctrl, rows, 0xf, false))
+    PS_MAX_STEP(0x111, 0xf);      // row_shr:1, 2, 4, 8: lane 15 of every row of 16 holds its row's largest
+    PS_MAX_STEP(0x112, 0xf);
+    PS_MAX_STEP(0x114, 0xf);
+    PS_MAX_STEP(0x118, 0xf);
+    PS_MAX_STEP(0x142, 0xa);      // row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3: lane 63 holds the wave's
+    PS_MAX_STEP(0x143, 0xc);
+#undef PS_MAX_STEP
+    return __builtin_amdgcn_readlane(v, 63);
+}
+
+// The packs of the leftovers (pack_fit.hpp holds the rule and its reasons), a wave per window of PACK_WINDOW computed cells,
+// ahead of k_plan_force: best fit is a chain of dependent placements, about 55 instructions each (counted in the ISA), and 64
+// windows of up to 63 placements are by that count more than the plan's one workgroup could issue beside its own work;
+// side by side on CUs of their own a window is one chain: the kernel takes 13 us (profiles/pack_fit_ab.txt).  The lanes first hold the window's cells
+// (rank by decreasing leftover: 64 compares of distinct keys), then the sorted leftovers move to the lanes of their rank and
+// the lanes stand for the packs: a placement is one compare per pack, one wave_max over (used, lowest pack number first)
+// and the update of the pack that won.  Leftovers above half a wave cannot share one with anything placed before them:
+// they open packs rank by rank without the loop.  The window's packs go to pack_stage[64 w ..], their number to
+// pack_count[w]; k_plan_force numbers the windows' packs and moves them into merged_tasks.
+__global__ __launch_bounds__(PACK_WINDOW) void k_pack_windows(DevParams P, const int *__restrict__ active_count,
+                                                              int4 *__restrict__ pack_stage, int *__restrict__ pack_count)
+{
+    static_assert(PACK_WINDOW == 64 && PACK_LANES == 64 && PACK_GROUPS == 4, "a wave's lanes hold a window; a pack is an int4");
+    const int lane = threadIdx.x, w = blockIdx.x, j = w * PACK_WINDOW + lane;
+    const int cell = j < comp_count(P) ? comp_cell(P, j) : -1;
+    const int r = cell >= 0 ? (active_count[cell] & (PACK_LANES - 1)) : 0;
+    const int key = (r << 6) | (63 - lane);                  // decreasing leftover, ties in cell order
+    int rank = 0;
+#pragma unroll
+    for (int i = 0; i < 64; i++) rank += __builtin_amdgcn_readlane(key, i) > key ? 1 : 0;
+    const int sr = __builtin_amdgcn_ds_permute(rank << 2, r);          // lane k: the k-th leftover in that order, and its cell
+    const int sc = __builtin_amdgcn_ds_permute(rank << 2, cell);
+    const int nitems = __popcll(__ballot(r > 0)), nbig = __popcll(__ballot(r > PACK_LANES / 2));
+    constexpr int CLOSED = 1 << 20;                          // a pack not open yet, or with its four cells: nothing fits
+    int used = lane < nbig ? sr : CLOSED, ng = lane < nbig ? 1 : 0;    // lane b as pack b
+    int mypack = lane, myplace = 0;                          // lane k as the k-th leftover: where it went
+    int nopen = nbig;
+    for (int k = nbig; k < nitems; k++) {
+        const int rk = __builtin_amdgcn_readlane(sr, k);
+        const int best = wave_max(used <= PACK_LANES - rk ? ((used << 6) | (63 - lane)) : -1);
+        int b, nu, ngb = 0;
+        if (best < 0) { b = nopen++; nu = rk; }
+        else { b = 63 - (best & 63); nu = (best >> 6) + rk; ngb = __builtin_amdgcn_readlane(ng, b); }
+        if (ngb == PACK_GROUPS - 1) nu = CLOSED;
+        if (lane == b) { used = nu; ng = ngb + 1; }
+        if (lane == k) { mypack = b; myplace = ngb; }
+    }
+    int *out = reinterpret_cast<int *>(pack_stage + (size_t)w * PACK_WINDOW);
+    if (lane < nitems) out[PACK_GROUPS * mypack + myplace] = sc;
+    if (lane < nopen) for (int s = ng; s < PACK_GROUPS; s++) out[PACK_GROUPS * lane + s] = -1;
+    if (lane == 0) pack_count[w] = nopen;
+}
 
 // The plan of the balanced force pass, one launch of eight workgroups (one per XCD run of wave
 // slots).  Every workgroup works out, for itself, in LDS:
@@ -10,7 +69,7 @@ namespace psamd {
 //       (a task of cell c walks task_cost[c] bodies, the population of the cell's stencil);
 //       with `merge`, only full slices become ordinary tasks and the leftovers (a cell's last,
 //       partly filled slice: 20 of 64 lanes on average once the collided particles are gone) are
-//       packed, up to four cells to a wave, into merged tasks;
+//       packed, up to four cells to a wave, into merged tasks (k_pack_windows, just before this kernel);
 //   (2) where every wave slot of ITS run starts: the pass's work is the list of (task, stencil
 //       step) units -- task-major, 27 steps per task -- a unit costs the bodies of the neighbour
 //       cell it visits, and wave slot s takes the units from wave_pos[s] up to wave_pos[s + 1]:
@@ -27,6 +86,7 @@ __global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, bool m
                                                      const int *__restrict__ active_count, const int *__restrict__ task_cost,
                                                      int *__restrict__ task_list2, int *__restrict__ ctask_start_g,
                                                      long long *__restrict__ cost_start_g, int4 *__restrict__ merged_tasks,
+                                                     const int4 *__restrict__ pack_stage, const int *__restrict__ pack_count, int *__restrict__ pack_base_g,
                                                      long long *__restrict__ wave_pos, FrameScalars *fs, unsigned long long *trace,
                                                      StepState *st, int pass)
 {
@@ -42,11 +102,13 @@ __global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, bool m
     __shared__ long long wave_tot[16], wave_cost[16];
     __shared__ long long s_run[2];
     __shared__ long long s_runcost[2];
+    __shared__ int s_pbase[PLAN_LDS / PACK_WINDOW + 1];  // first pack of every window
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, x = blockIdx.x;
     const int ncomp = comp_count(P);
     const bool in_lds = ncomp + 1 <= PLAN_LDS && P.max_per_cell < (1 << 13);
     long long *cost_start = in_lds ? s_cost : cost_start_g;
     int *ctask_start = in_lds ? s_task : ctask_start_g;
+    int *pack_base = in_lds ? s_pbase : pack_base_g;
     if (in_lds) for (int j = tid; j < ncomp; j += 1024) { const int c = comp_cell(P, j), n = active_count[c]; s_ac[j] = n | ((n ? task_cost[c] : 0) << 13); }
     __syncthreads();
     PT(1);
@@ -56,38 +118,21 @@ __global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, bool m
     // ---- (1) prefixes, task list, packs ----
     const int per = (ncomp + 1023) / 1024;
     const int c0 = min(ncomp, tid * per), c1 = min(ncomp, c0 + per);
-    // the leftovers are packed greedily, in cell order, a run of cells per thread: six (two packs of
-    // three 20-lane leftovers) where there are threads enough -- each step of the greedy walk is a
-    // dependent LDS round trip, and this walk is done twice
-    const int pper = max(6, (ncomp + 1023) / 1024);
-    const int p0 = min(ncomp, tid * pper), p1 = min(ncomp, p0 + pper);
-    // out (may be null): the packs
-    auto pack = [&](int4 *out) -> int {
-        int npack = 0, used = 0, ng = 0;
-        int4 cur = make_int4(-1, -1, -1, -1);
-        auto flush = [&]() {
-            if (out) out[npack] = cur;
-            npack++;
-            cur = make_int4(-1, -1, -1, -1); used = 0; ng = 0;
-        };
-        for (int j = p0; j < p1; j++) {
-            const int r = act_of(j) & 63;
-            if (r == 0) continue;
-            const int c = comp_cell(P, j);
-            if (ng == 4 || used + r > 64) flush();
-            if (ng == 0) cur.x = c; else if (ng == 1) cur.y = c; else if (ng == 2) cur.z = c; else cur.w = c;
-            ng++; used += r;
-        }
-        if (ng) flush();
-        return npack;
-    };
+    // the packs of the leftovers: k_pack_windows listed every window's packs and counted them; here they are numbered,
+    // window by window (the counts ride in the high word of the tasks' prefix), and workgroup 0 moves them into place
+    const int nwin = (ncomp + PACK_WINDOW - 1) / PACK_WINDOW, wper = (nwin + 1023) / 1024;
+    const int w0 = min(nwin, tid * wper), w1 = min(nwin, w0 + wper);
     long long mine = 0, mycost = 0;   // tasks (low word) and packs (high word); bodies the tasks walk
     for (int j = c0; j < c1; j++) {
         const int n = act_of(j), nt = merge ? (n >> 6) : ((n + 63) >> 6);
         mine += nt;
         mycost += (long long)nt * cost_of(j);
     }
-    if (merge) mine |= (long long)pack(nullptr) << 32;
+    if (merge) {
+        int np = 0;
+        for (int w = w0; w < w1; w++) np += pack_count[w];
+        mine |= (long long)np << 32;
+    }
     long long incl = mine, cincl = mycost;
     for (int d = 1; d < 64; d <<= 1) {
         const long long o = __shfl_up(incl, d), oc = __shfl_up(cincl, d);
@@ -111,7 +156,10 @@ __global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, bool m
         run += n;
         crun += (long long)n * cost_of(j);
     }
-    if (merge && x == 0) pack(merged_tasks + (int)(run2 >> 32));
+    if (merge && x == 0) {
+        int first = (int)(run2 >> 32);
+        for (int w = w0; w < w1; w++) { pack_base[w] = first; first += pack_count[w]; }
+    }
     const int ntask = total;
     const long long T = ctotal;
     if (tid == 0) {
@@ -122,6 +170,11 @@ __global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, bool m
     if (!in_lds) __threadfence();                    // (every workgroup wrote the same values; this one reads its own)
     __syncthreads();
     PT(3);
+    if (merge && x == 0)
+        for (int i = tid; i < nwin * PACK_WINDOW; i += 1024) {
+            const int w = i / PACK_WINDOW, l = i - w * PACK_WINDOW;
+            if (l < pack_count[w]) merged_tasks[pack_base[w] + l] = pack_stage[i];
+        }
     if (nw <= 0) return;                             // (unbalanced pass: only the lists were wanted)
 
     // ---- (2) the wave slots of run x ----
@@ -176,8 +229,9 @@ __global__ __launch_bounds__(1024) void k_plan_force(DevParams P, int nw, bool m
 // nw: wave slots of the balanced pass (0: only the lists are wanted); merge: pack the partly filled last slices
 void launch_plan_force(hipStream_t st, const DevParams &P, const DeviceState &d, int nw, bool merge, int pass)
 {
+    if (merge) k_pack_windows<<<(comp_count(P) + PACK_WINDOW - 1) / PACK_WINDOW, PACK_WINDOW, 0, st>>>(P, d.active_count, d.pack_stage, d.pack_count);
     k_plan_force<<<8, 1024, 0, st>>>(P, nw, merge, d.cell_start, d.active_count, d.task_cost,
-                                     d.task_list2, d.ctask_start, d.cost_start, d.merged_tasks, d.wave_pos, d.fs, d.trace, d.st, pass);
+                                     d.task_list2, d.ctask_start, d.cost_start, d.merged_tasks, d.pack_stage, d.pack_count, d.pack_base, d.wave_pos, d.fs, d.trace, d.st, pass);
 }
 
 }  // namespace psamd

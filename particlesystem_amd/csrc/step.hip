@@ -179,6 +179,7 @@ static int64_t pairs_hint(const psamd_ctx *c, const DevParams &P)
 static int enq_pairs(psamd_ctx *c, const DevParams &P, int64_t tasks_hint, bool last = true, bool first = true)
 {
     if (first) tick(c, psamd_ctx::E_COLLIDE);
+    c->pairs_shape_last = launch_pairs_shape(P, tasks_hint);
     PS_HIP(c, launch_pairs(c->stream, P, c->d, (c->timing_now && first) ? c->ev[c->tset][psamd_ctx::E_FORCE] : nullptr, tasks_hint, first ? 0 : 1, live_bound_of(c)));
     if (last) tick(c, psamd_ctx::E_PAIRS_END);
     return PSAMD_OK;

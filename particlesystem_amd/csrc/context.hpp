@@ -11,8 +11,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -22,6 +20,7 @@
 #include "geometry.hpp"
 #include "kernels.h"
 #include "partition.hpp"
+#include "step_ledger.hpp"
 
 namespace psamd {
 // A slab message (device), by the ABI's `which` numbering (psamd_slab_msg_download in include/psamd.h); in a pair,
@@ -52,7 +51,6 @@ struct psamd_ctx {
     SlabPlan plan;
     SlabMsg msg[MSG_COUNT];
     int halo_out_c0[2] = {0, 0}, halo_out_cells[2] = {0, 0}, halo_in_cells[2] = {0, 0};
-    std::map<int, int> cap_decisions; // slab: record number -> the transfer capacity all ranks agreed on in that step (adopted two steps on)
     int *pack_off[2] = {nullptr, nullptr}, *unpack_off[2] = {nullptr, nullptr};
     size_t frame_ints = 0;            // ints zeroed by init_iframe
     std::vector<void *> allocs;
@@ -63,10 +61,7 @@ struct psamd_ctx {
     std::vector<int32_t> h_queue;
     bool host_queues_valid = true;    // host mirror == device copy
     FrameScalars *h_fs = nullptr;     // pinned host copies of the per-frame scalars: TWO records, a step's number picks one
-    FrameScalars last{};              // the record of the last step the host has read (consume_scalars)
-    int64_t processed_total = 0;      // sum over steps of the live particles at build_grid
-    int64_t max_bucket_seen = 0;
-    int bucket_cap0 = 2048;           // the longest operation list the step's replay instance sorts in LDS (2048 / 4096 / 8192, from the last lists seen)
+    StepLedger ledger;                // the steps enqueued, their records read and what follows from them (step_ledger.hpp)
     char *snapshot = nullptr;         // device image for snapshot_save / _restore
     int snapshot_step = 0;
     void *staging = nullptr;          // device staging for AoS transfers
@@ -76,18 +71,7 @@ struct psamd_ctx {
     bool frame_clean = true;          // the per-frame counts are zero: a finished step leaves them so (its last kernel is the next init_iframe)
     int step = 0;
     int64_t steps_total = 0;
-    int live_at_build = -1;           // host copy of fs->live (valid after a sync)
-    bool interior_ran = false;        // this step's pair stage ran in two passes (the scalars hold the second pass's task count)
-    std::set<int> interior_steps;     // ... the numbers of such steps whose records have not been read yet
-    int64_t tasks_last = 0;           // force tasks of the last step (all passes), sizes the next step's balanced pass
-    int64_t packs_last = 0;           // ... of which packs of partly filled slices
     uint64_t pairs_shape_last = 0;    // launch_pairs_shape of the last pair-stage launch (psamd_debug_packs)
-    // upper bound of the live count at the next build_grid, kept on the host so that the
-    // life-cycle kernels can be sized without a read-back (-1 = unknown)
-    int64_t live_bound = 0, snapshot_live_bound = 0;
-    // psamd_inject: max_count of the injects enqueued after step k (key k = scalars_seq at the call), until the record
-    // of step k + 1 -- the first that counts them -- has been read
-    std::map<int, int64_t> inject_tally;
     InjectScratch inj{};              // its scratch: inj.e grows with max_count, the rest is fixed
     RemoveScratch rem{};              // psamd_remove's scratch: rem.e grows with max_count, the rest is fixed
     ProbeScratch prb{};               // psamd_probe's scratch: code / order grow with max_count, the counters are fixed
@@ -96,14 +80,6 @@ struct psamd_ctx {
     int timing_period = 1;             // events are recorded on every timing_period-th step since set_timing
     int64_t timing_steps = 0;          // steps since set_timing
     int timing_now = 0;                // the level in force for the step being run (0 on the steps in between)
-    // The step's scalars: the device numbers the records it hands out (StepState.seq), the host counts the steps it has
-    // enqueued (scalars_seq) and the records it has read (scalars_seen).  run_ahead = 1: step k + 1 is enqueued once the
-    // record of step k - 1 has been read -- the host is never on a step's critical path; 0: every step's own record is
-    // waited for before the call returns.
-    int scalars_seq = 0, scalars_seen = 0;
-    int run_ahead = 1;
-    int pending_status = PSAMD_OK;     // the verdict of a step whose record was read by a call that does not report verdicts (kept for the next that does)
-    std::string pending_err;
     bool wedged = false;               // a step's scalars did not arrive within the wall-clock bound: the context refuses further work
     // Timing events: two sets, a timed step takes the one that was read longest ago; a set is read when it is taken again
     // or by psamd_get_timing -- never by the step that recorded it (the host runs ahead of the GPU).
@@ -131,6 +107,14 @@ struct psamd_ctx {
 namespace psamd {
 
 const char *status_text(int status);
+
+// what the ledger's rules read of the context
+inline LedgerParams ledger_params(const psamd_ctx *c)
+{
+    const DevParams &P = c->P;
+    return {P.slots_total, (P.flags & PSAMD_FLAG_EXPLOSIONS) != 0, P.world, P.xfer_cap, P.xfer2_cap, P.far_cap, P.xfer_cap0, P.xfer_cap_max,
+            comp_count(P), comp_count(c->P_int), comp_count(c->P_rest), P.world > 1 ? (int64_t)P.world * STATUS_KILL_CAP : 0, BUCKET_MAX};
+}
 
 inline int fail(psamd_ctx *c, int status, const std::string &what)
 {

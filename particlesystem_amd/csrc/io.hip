@@ -147,7 +147,7 @@ int psamd_fill_particles(psamd_ctx *c, int64_t n, const float *xyz, const float 
     PS_TRY(push_queues(c));
     if (ids_out) std::copy(ids.begin(), ids.begin() + done, ids_out);
     if (n_done) *n_done = done;
-    if (c->live_bound >= 0) c->live_bound += placed;
+    c->ledger.filled(placed);
     leave(c->stage, CALL_CHANGED);
     return status;
 }
@@ -163,7 +163,7 @@ int psamd_upload_particles(psamd_ctx *c, const void *p72, int64_t first, int64_t
     PS_HIP(c, launch_unpack_aos(c->stream, c->P, c->staging, (int)first, (int)count, half_box, c->d));
     PS_HIP(c, hipStreamSynchronize(c->stream));
     leave(c->stage, CALL_CHANGED);
-    c->live_bound = -1;
+    c->ledger.uploaded();
     return check_device_errors(c);
 }
 
@@ -324,8 +324,8 @@ int psamd_get_gridmax(psamd_ctx *c, int32_t out2[2])
         FrameScalars fs{};
         PS_HIP(c, hipMemcpy(&fs, c->d.fs, sizeof fs, hipMemcpyDeviceToHost));
         out2[0] = fs.gridmax[0]; out2[1] = fs.gridmax[1];
-        c->live_at_build = fs.live;
-    } else { out2[0] = c->last.gridmax[0]; out2[1] = c->last.gridmax[1]; }
+        c->ledger.frame_live(fs.live);
+    } else { out2[0] = c->ledger.last().gridmax[0]; out2[1] = c->ledger.last().gridmax[1]; }
     return PSAMD_OK;
 }
 
@@ -383,8 +383,8 @@ int psamd_get_counters(psamd_ctx *c, psamd_counters *o)
     o->births = (int64_t)d.births; o->births_failed = (int64_t)d.births_failed;
     o->cell_overflow_kills = (int64_t)d.cell_overflow_kills;
     o->steps = c->steps_total;
-    o->particles_processed = c->processed_total;
-    o->max_ops_one_queue = c->max_bucket_seen;
+    o->particles_processed = c->ledger.particles_processed();
+    o->max_ops_one_queue = c->ledger.longest_list();
     return PSAMD_OK;
 }
 
@@ -406,7 +406,7 @@ int psamd_device_view_get(psamd_ctx *c, psamd_device_view *o)
     o->pos4 = c->d.pos4; o->vel4 = c->d.vel4; o->acc4 = c->d.acc4; o->cell = c->d.cell; o->pflags = c->d.pflags;
     o->sorted_id = c->d.sorted_id; o->snap_soa = c->d.snap_soa; o->sorted_cap = c->P.sorted_cap; o->force4 = c->d.force4; o->cell_start = c->d.cell_start;
     o->container_size = c->P.slots_total; o->num_cells = c->P.n_own_cells;
-    o->live = c->live_at_build;
+    o->live = c->ledger.last_live();
     o->stream = (void *)c->stream;
     return PSAMD_OK;
 }
@@ -459,7 +459,7 @@ int psamd_snapshot_save(psamd_ctx *c)
     if (!c) return PSAMD_ERR_INVALID_ARG;
     if (!c->snapshot) PS_HIP(c, dev_alloc(c, &c->snapshot, snapshot_bytes(c)));
     c->snapshot_step = c->step;
-    c->snapshot_live_bound = c->live_bound;
+    c->ledger.snapshot_saved();
     return snapshot_copy(c, true);
 }
 
@@ -468,7 +468,7 @@ int psamd_snapshot_restore(psamd_ctx *c)
     if (!c) return PSAMD_ERR_INVALID_ARG;
     if (!c->snapshot) return fail(c, PSAMD_ERR_STATE, "snapshot_restore without a saved snapshot");
     c->step = c->snapshot_step;
-    c->live_bound = c->snapshot_live_bound;
+    c->ledger.snapshot_restored();
     end_frame(c, CALL_RESTORE);
     return snapshot_copy(c, false);
 }

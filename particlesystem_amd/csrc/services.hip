@@ -149,11 +149,9 @@ int psamd_inject(psamd_ctx *c, const psamd_inject_spec *spec)
     const InjectArgs a{(const float4 *)spec->pos4, (const float4 *)spec->vel4, spec->fert_age, spec->max_count, spec->count_dev,
                        spec->ids_dev, res};
     PS_HIP(c, launch_inject(c->stream, c->P, c->S, c->d, c->geo.queue_infos, a, c->inj));
-    // fill's transitions, and the device's queues are ahead of the host's mirror; every entry counts in the live bound,
-    // also when the record of a step enqueued before this call is read later (consume_scalars)
+    // fill's transitions, and the device's queues are ahead of the host's mirror; every entry counts in the live bound
     end_frame(c);
-    if (c->live_bound >= 0) c->live_bound = std::min<int64_t>(c->P.slots_total, c->live_bound + spec->max_count);
-    c->inject_tally[c->scalars_seq] += spec->max_count;
+    c->ledger.injected(ledger_params(c), spec->max_count);
     return PSAMD_OK;
 }
 

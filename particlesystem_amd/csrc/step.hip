@@ -11,7 +11,7 @@ int psamd::check_device_errors(psamd_ctx *c)
 {
     FrameScalars fs{};
     PS_HIP(c, hipMemcpy(&fs, c->d.fs, sizeof fs, hipMemcpyDeviceToHost));
-    if (!built(c->stage)) for (int k = 0; k < 5; k++) fs.n_out[k] = c->last.n_out[k];      // (between steps the device's record is the next frame's, zeroed)
+    if (!built(c->stage)) for (int k = 0; k < 5; k++) fs.n_out[k] = c->ledger.last().n_out[k];      // (between steps the device's record is the next frame's, zeroed)
     if (fs.error & (ERR_BAD_ID | ERR_BAD_POS)) {
         // an upload error is reported once and then cleared: the rejected records stay in the
         // container, the caller is expected to upload valid ones over them
@@ -88,9 +88,7 @@ static void tick(psamd_ctx *c, int e)        // a timing event on the context's 
 // from, rounded up to 64 Ki so that a free-running population does not mean a capture per step.  Steps
 // that carry timing events run eagerly (the events sit between the kernels).
 //
-// NOTHING in a step waits for the host: the step's tail decides everything on the device (lifecycle.hip), and the
-// one read-back of a step -- live count, sticky errors, list sizes: what the reference's driver fetches as
-// hostGridMax, ps.cpp:1878-1900 -- lands in a pinned record that the host reads a step late (consume_scalars).
+// Nothing in a step waits for the host; step_ledger.hpp has the pipeline of the scalar records, the hints and the verdicts.
 
 static int slab_only(psamd_ctx *c, const char *what)
 {
@@ -137,50 +135,23 @@ static int enq_init_iframe(psamd_ctx *c)
     return PSAMD_OK;
 }
 
-// is a cell with more than 1024 ids to be expected?  (the last frames the host has read; a wrong guess only costs time:
-// without the crowded cells' instance the ordinary one ranks such a cell through global memory)
-static bool big_cells_hint(const psamd_ctx *c) { return c->scalars_seen > 0 && c->last.max_cell_raw > 960; }
-static uint64_t build_key(const psamd_ctx *c) { return (c->frame_clean ? 0ull : 1ull) | (c->tdata_mirror ? 2ull : 0ull) | (big_cells_hint(c) ? 4ull : 0ull); }
+static uint64_t build_key(const psamd_ctx *c) { return (c->frame_clean ? 0ull : 1ull) | (c->tdata_mirror ? 2ull : 0ull) | (c->ledger.big_cells() ? 4ull : 0ull); }
 
 static int enq_build_grid(psamd_ctx *c)
 {
-    PS_HIP(c, launch_build_grid(c->stream, c->P, c->d, c->timing_now >= 2 ? &c->ev[c->tset][psamd_ctx::E_HIST] : nullptr, c->tdata_mirror, big_cells_hint(c)));
+    PS_HIP(c, launch_build_grid(c->stream, c->P, c->d, c->timing_now >= 2 ? &c->ev[c->tset][psamd_ctx::E_HIST] : nullptr, c->tdata_mirror, c->ledger.big_cells()));
     return PSAMD_OK;
 }
 
-// An upper bound of the particles alive at the NEXT build_grid, as far as the host can know it (< 0 inside: unknown --
-// state was uploaded -- every owned slot).  The host's figure comes from the scalars of the last step it has READ,
-// which with run-ahead is not the last step enqueued: every step in between may have added a child per particle
-// (explosions on) and a slab its arrivals.  Only the all-pairs far pass sizes a launch from this that must cover
-// every particle; everything else takes it as a hint.
-static int64_t live_bound_of(const psamd_ctx *c)
-{
-    int64_t b = c->live_bound >= 0 ? c->live_bound : (int64_t)c->P.slots_total;
-    for (int k = c->scalars_seen; k < c->scalars_seq && b < c->P.slots_total; k++) {
-        if (c->P.flags & PSAMD_FLAG_EXPLOSIONS) b *= 2;
-        b += 2 * (int64_t)c->P.xfer_cap + 2 * (int64_t)c->P.xfer2_cap + (int64_t)c->P.far_cap * c->P.world;
-    }
-    b = std::min<int64_t>(b, c->P.slots_total);
-    return c->graphs ? std::min<int64_t>((b + 65535) & ~(int64_t)65535, std::max<int64_t>(c->P.slots_total, 65536)) : b;
-}
-
-// size of the balanced force pass: the tasks of the last step whose scalars the host has read, else the bound of the
-// live count (a pass over part of the cells gets its share of the hint)
-static int64_t pairs_hint(const psamd_ctx *c, const DevParams &P)
-{
-    int64_t tasks_hint = (c->scalars_seen > 0 && c->tasks_last > 0) ? c->tasks_last
-                         : (c->live_bound >= 0 ? c->live_bound : (int64_t)c->P.slots_total) / 64 + comp_count(c->P);
-    // (high word: about how many packs of partly filled slices the pass will have -- their workgroups hold residency
-    // slots of the same launch; in steps of 64 so that the launch shape does not change with every step)
-    const int64_t packs = ((c->scalars_seen > 0 ? c->packs_last : 0) + 63) & ~(int64_t)63;
-    return (tasks_hint * comp_count(P) / std::max(1, comp_count(c->P))) | ((packs * comp_count(P) / std::max(1, comp_count(c->P))) << 32);
-}
+static int64_t alive_at_most(const psamd_ctx *c) { return c->ledger.alive_at_most(ledger_params(c), c->graphs); }
+static int64_t pairs_hint(const psamd_ctx *c, const DevParams &P) { return c->ledger.pairs_hint(ledger_params(c), comp_count(P)); }
+static uint64_t bucket_key(const psamd_ctx *c) { return c->ledger.bucket_key(ledger_params(c)); }
 
 static int enq_pairs(psamd_ctx *c, const DevParams &P, int64_t tasks_hint, bool last = true, bool first = true)
 {
     if (first) tick(c, psamd_ctx::E_COLLIDE);
     c->pairs_shape_last = launch_pairs_shape(P, tasks_hint);
-    PS_HIP(c, launch_pairs(c->stream, P, c->d, (c->timing_now && first) ? c->ev[c->tset][psamd_ctx::E_FORCE] : nullptr, tasks_hint, first ? 0 : 1, live_bound_of(c)));
+    PS_HIP(c, launch_pairs(c->stream, P, c->d, (c->timing_now && first) ? c->ev[c->tset][psamd_ctx::E_FORCE] : nullptr, tasks_hint, first ? 0 : 1, alive_at_most(c)));
     if (last) tick(c, psamd_ctx::E_PAIRS_END);
     return PSAMD_OK;
 }
@@ -197,22 +168,6 @@ static int enq_apply(psamd_ctx *c, int64_t bound)
     return PSAMD_OK;
 }
 
-// arrivals on top of the own particles: about what the op lists and move records of a step hold at most
-static int64_t lifecycle_bound(const psamd_ctx *c, int64_t bound)
-{
-    return bound + 2 * (int64_t)c->P.xfer_cap + 2 * (int64_t)c->P.xfer2_cap + (int64_t)c->P.far_cap * c->P.world
-           + (c->P.world > 1 ? (int64_t)c->P.world * STATUS_KILL_CAP : 0);
-}
-
-// Which instance replays the lists this step: the longest list of the last step the host has read is the hint (lists
-// longer than the instance sorts in LDS are sorted in global memory by the same workgroup: a wrong hint only costs time).
-static uint64_t pick_bucket_cap(psamd_ctx *c)
-{
-    const int last = c->scalars_seen > 0 ? c->last.max_bucket : 0;
-    c->bucket_cap0 = last > 4096 ? BUCKET_MAX : last > 2048 ? 4096 : 2048;
-    return c->bucket_cap0 > 4096 ? 2ull << 61 : c->bucket_cap0 > 2048 ? 1ull << 61 : 0ull;       // (part of a captured graph's key)
-}
-
 // free-slot queues and relocation (in slab mode: after the arrivals were merged in): census, bucketing -- the last
 // bucketing workgroup hands the step's scalars to the host's pinned record --, replay + commit; the last launch
 // is also the next frame's init_iframe
@@ -222,7 +177,7 @@ static int enq_lifecycle(psamd_ctx *c, int64_t bound)
     const SlabMsg *m = c->msg;
     const int *const in[5] = {m[MSG_XFER_IN].ptr, m[MSG_XFER_IN + 1].ptr, m[MSG_XFER2_IN].ptr, m[MSG_XFER2_IN + 1].ptr, m[MSG_FAR_IN].ptr};
     if (c->P.world > 1) PS_HIP(c, launch_inbox_merge(c->stream, c->P, c->d, in));
-    PS_HIP(c, launch_lifecycle(c->stream, c->P, c->d, c->geo.queue_infos, lifecycle_bound(c, bound), c->bucket_cap0,
+    PS_HIP(c, launch_lifecycle(c->stream, c->P, c->d, c->geo.queue_infos, StepLedger::lifecycle_bound(ledger_params(c), bound), c->ledger.bucket_cap(ledger_params(c)),
                                c->frame_ints, c->P.world > 1 ? 4 * c->geo.num_chunks : 0));
     tick(c, psamd_ctx::E_END);
     return PSAMD_OK;
@@ -287,7 +242,7 @@ static void resync_scalars(psamd_ctx *c)
     if (hipStreamSynchronize(c->stream) != hipSuccess) return;
     StepState st{};
     if (hipMemcpy(&st, c->d.st, sizeof st, hipMemcpyDeviceToHost) != hipSuccess) return;
-    c->scalars_seq = c->scalars_seen = st.seq;
+    c->ledger.resync(st.seq);
 }
 
 // Wait until the scalars of step `seq` are in the host's record: the publishing workgroup stores the record's
@@ -331,69 +286,35 @@ static int wait_scalars(psamd_ctx *c, int seq)
     return rc;
 }
 
-// Read the records of the steps up to number `upto` (waiting for them) and whatever has arrived beyond: the host's
-// bookkeeping of a step -- hints for the launches to come, the counters, and the step's verdict.
-// A slab fails COLLECTIVELY: only on error bits that were in a step's all-gathered status records,
-// which every rank sees alike (status_error) -- all ranks return the error from the same call.  An error this
-// rank raised after its status record was closed (a message that did not fit, an arrival for a queue it does not
-// hold) stays sticky, goes out with the next step's record and stops every rank there; returning it at once would
-// leave the ranks that have not heard of it waiting in the next exchange.  (psamd_synchronize reports whatever is pending.)
+// Read the records of the steps up to number `upto` (waiting for them) and whatever has arrived beyond; the first
+// verdict met is held for the call that reports it.
 static int consume_scalars(psamd_ctx *c, int upto)
 {
+    StepLedger &L = c->ledger;
     int verdict = PSAMD_OK;
-    while (c->scalars_seen < c->scalars_seq) {
-        const int s = c->scalars_seen + 1;
+    while (L.seen() < L.seq()) {
+        const int s = L.seen() + 1;
         if (s <= upto) { const int st = wait_scalars(c, s); if (st != PSAMD_OK) { if (!c->wedged) resync_scalars(c); return st; } }
         else if (*(volatile int32_t *)&c->h_fs[s & 1].seq != s) break;
         std::atomic_thread_fence(std::memory_order_acquire);
         const FrameScalars r = c->h_fs[s & 1];
-        c->scalars_seen = s;
-        c->last = r;
-        c->live_at_build = r.live;
-        const int64_t tasks_now = (int64_t)r.n_tasks2 + r.n_merged;       // ordinary tasks + packs of partial slices
-        // (a pair stage in two passes -- interior_ran is noted per step below -- reports the second pass's task count)
-        const bool two = c->interior_steps.count(s) != 0;
-        c->interior_steps.erase(s);
-        c->tasks_last = two ? tasks_now * comp_count(c->P) / std::max(1, comp_count(c->P_rest)) : tasks_now;
-        c->packs_last = two ? (int64_t)r.n_merged * comp_count(c->P) / std::max(1, comp_count(c->P_rest)) : r.n_merged;
-        c->live_bound = std::min<int64_t>(c->P.slots_total, (int64_t)r.live + r.n_moves);   // births and arrivals <= moves
-        // ... and what was injected after this step was enqueued (the record's live count does not include it)
-        for (auto it = c->inject_tally.begin(); it != c->inject_tally.end();) {
-            if (it->first < s) { it = c->inject_tally.erase(it); continue; }
-            c->live_bound = std::min<int64_t>(c->P.slots_total, c->live_bound + it->second);
-            ++it;
-        }
-        c->processed_total += r.live;
-        c->max_bucket_seen = std::max<int64_t>(c->max_bucket_seen, r.max_bucket);
-        if (c->P.world > 1 && r.xfer_cap_next > 0) c->cap_decisions[s] = r.xfer_cap_next;      // (every step's: an absolute number, the same on every rank)
-        if (verdict == PSAMD_OK && (c->P.world > 1 ? r.status_error != 0 : r.error != 0)) verdict = check_device_errors(c);
+        if (L.absorb(r, ledger_params(c), verdict != PSAMD_OK)) verdict = check_device_errors(c);
     }
-    if (verdict != PSAMD_OK && c->pending_status == PSAMD_OK) { c->pending_status = verdict; c->pending_err = c->err; }
+    L.hold_verdict(verdict, c->err);
     return PSAMD_OK;
 }
 
-static int take_verdict(psamd_ctx *c)
-{
-    if (c->pending_status == PSAMD_OK) return PSAMD_OK;
-    const int st = c->pending_status;
-    c->err = c->pending_err;
-    c->pending_status = PSAMD_OK;
-    return st;
-}
+static int take_verdict(psamd_ctx *c) { return c->ledger.take_verdict(c->err); }
 
 // the rest of the step, once enq_lifecycle is enqueued (or replayed): the host's bookkeeping
 static int finish_step(psamd_ctx *c)
 {
     c->host_queues_valid = false;
-    const int seq = ++c->scalars_seq;
-    if (c->interior_ran) c->interior_steps.insert(seq);
-    c->interior_ran = false;
+    c->ledger.enqueued();
     if (c->timing_now) { c->ev_level[c->tset] = c->timing_now; c->timed_steps++; }
     c->frame_clean = true;                       // (the step's last kernel zeroed the counts for the frame that follows)
     c->step++; c->steps_total++;
-    // run-ahead: this step's record is read when the NEXT step has been enqueued (the record of the step before must be
-    // out of the way by then: the two pinned records alternate); else now
-    const int rc = consume_scalars(c, c->run_ahead ? seq - 1 : seq);
+    const int rc = consume_scalars(c, c->ledger.due());
     return rc != PSAMD_OK ? rc : take_verdict(c);
 }
 
@@ -402,7 +323,7 @@ static int finish_step(psamd_ctx *c)
 int psamd::drain_scalars(psamd_ctx *c, bool quiet)
 {
     PS_HIP(c, hipStreamSynchronize(c->stream));
-    const int rc = consume_scalars(c, c->scalars_seq);
+    const int rc = consume_scalars(c, c->ledger.seq());
     return rc != PSAMD_OK ? rc : quiet ? (int)PSAMD_OK : take_verdict(c);
 }
 
@@ -439,8 +360,7 @@ int psamd_calc_forces_pairs(psamd_ctx *c)
 int psamd_calc_forces_apply(psamd_ctx *c)
 {
     PS_TRY(enter_stage(c, CALL_APPLY));
-    const int64_t bound = live_bound_of(c);
-    (void)pick_bucket_cap(c);
+    const int64_t bound = alive_at_most(c);
     int rc = enq_apply(c, bound);
     if (rc == PSAMD_OK) rc = enq_lifecycle(c, bound);
     if (rc != PSAMD_OK) { resync_scalars(c); return rc; }
@@ -463,8 +383,8 @@ int psamd_step(psamd_ctx *c, int32_t nsteps)
         PS_TRY(enter_stage(c, CALL_STEP));
         begin_step(c);
         if (built(c->stage)) c->frame_clean = false;
-        const int64_t hint = pairs_hint(c, c->P), bound = live_bound_of(c);
-        const uint64_t key = launch_pairs_shape(c->P, hint) | ((uint64_t)bound << 24) | pick_bucket_cap(c) | (build_key(c) << 58);
+        const int64_t hint = pairs_hint(c, c->P), bound = alive_at_most(c);
+        const uint64_t key = launch_pairs_shape(c->P, hint) | ((uint64_t)bound << 24) | bucket_key(c) | (build_key(c) << 58);
         int rc = run_segment(c, SEG_STEP, key, [&]() {
             int r = enq_init_iframe(c);
             if (r == PSAMD_OK) r = enq_build_grid(c);
@@ -488,17 +408,10 @@ int psamd_slab_build(psamd_ctx *c)
     PS_TRY(enter_stage(c, CALL_SLAB_BUILD));
     begin_step(c);
     if (built(c->stage)) c->frame_clean = false;
-    {   // The transfer messages' capacity the ranks agreed on two steps ago (k_status_merge) takes effect now, on every rank
-        // in this same step: the record of step s - 2 has been read by every host that starts step s, whatever its run-ahead.
-        // A decision is an absolute number (grown, kept or shrunk: the rule is k_status_merge's), the same on every rank.
-        const int s = c->scalars_seq + 1;
-        int cap = c->P.xfer_cap;
-        for (auto it = c->cap_decisions.begin(); it != c->cap_decisions.end() && it->first <= s - 2; it = c->cap_decisions.erase(it)) cap = it->second;
-        cap = std::max(c->P.xfer_cap0, std::min(cap, c->P.xfer_cap_max));
-        if (cap != c->P.xfer_cap) {
-            c->P.xfer_cap = c->P_int.xfer_cap = c->P_rest.xfer_cap = cap;
-            for (int k = MSG_XFER_OUT; k < MSG_XFER_IN + 2; k++) c->msg[k].bytes = xfer_msg_bytes((size_t)cap + 1);
-        }
+    // the transfer messages' capacity in force from this step on: both ends of every message change size in the same step
+    if (const int cap = c->ledger.adopt_cap(ledger_params(c)); cap != c->P.xfer_cap) {
+        c->P.xfer_cap = c->P_int.xfer_cap = c->P_rest.xfer_cap = cap;
+        for (int k = MSG_XFER_OUT; k < MSG_XFER_IN + 2; k++) c->msg[k].bytes = xfer_msg_bytes((size_t)cap + 1);
     }
     const int rc = run_segment(c, SEG_BUILD, build_key(c), [&]() {
         int r = enq_init_iframe(c);
@@ -528,7 +441,7 @@ int psamd_slab_pairs_interior(psamd_ctx *c)
         return enq_pairs(c, c->P_int, hint, false, true);
     });
     if (rc != PSAMD_OK) return rc;
-    c->interior_ran = true;
+    c->ledger.interior_pass_ran();
     leave(c->stage, CALL_SLAB_INTERIOR);
     return PSAMD_OK;
 }
@@ -562,7 +475,7 @@ int psamd_slab_pairs(psamd_ctx *c)
 int psamd_slab_apply(psamd_ctx *c)
 {
     PS_TRY(enter_stage(c, CALL_SLAB_APPLY));
-    const int64_t bound = live_bound_of(c);
+    const int64_t bound = alive_at_most(c);
     const int rc = run_segment(c, SEG_APPLY, (uint64_t)bound | ((uint64_t)c->P.xfer_cap << 32), [&]() {
         // the status records of all ranks (all-gathered since slab_build): error bits, cell-overflow kills for the
         // owner of queue record 0, the transfer messages' next capacity; in
@@ -582,7 +495,7 @@ int psamd_slab_finish(psamd_ctx *c)
     PS_TRY(enter_stage(c, CALL_SLAB_FINISH));
     leave(c->stage, CALL_SLAB_FINISH);           // (the slab frame is over whatever becomes of the launches)
     const int64_t bound = c->slab_bound;
-    const int rc = run_segment(c, SEG_FINISH, (uint64_t)bound | ((uint64_t)(c->P.xfer_cap & 0x1fffffff) << 32) | pick_bucket_cap(c), [&]() { return enq_lifecycle(c, bound); });
+    const int rc = run_segment(c, SEG_FINISH, (uint64_t)bound | ((uint64_t)(c->P.xfer_cap & 0x1fffffff) << 32) | bucket_key(c), [&]() { return enq_lifecycle(c, bound); });
     if (rc != PSAMD_OK) { resync_scalars(c); return rc; }
     return finish_step(c);
 }
@@ -646,7 +559,7 @@ int psamd_set_tdata_mirror(psamd_ctx *c, int enabled)
 int psamd_set_run_ahead(psamd_ctx *c, int steps)
 {
     if (!c || steps < 0 || steps > 1) return PSAMD_ERR_INVALID_ARG;
-    c->run_ahead = steps;
+    c->ledger.set_run_ahead(steps);
     return PSAMD_OK;
 }
 

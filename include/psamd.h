@@ -61,6 +61,10 @@ typedef enum psamd_status {
                                          x += v*dt + 0.5*a*dt*dt (ps.cpp:1274-1276); the velocity update is the same.
                                          dx is the fp32 product v*dt alone; the MAX_DX clamp, the wrap and the segment
                                          change act on it as they do on the reference's dx */
+#define PSAMD_FLAG_FAR_MONOPOLE 0x10u /* long-range gravity at a small multiple of the cutoff step's cost: the stencil first, in the
+                                         reference's order, then every OTHER cell of the box as one body -- its total mass at its
+                                         centre of mass.  See "long-range gravity" below.  Collisions stay short-range.  Not with
+                                         PSAMD_FLAG_ALL_PAIRS (PSAMD_ERR_INVALID_ARG); world == 1 only */
 
 /* Runtime form of the reference's compile-time configuration, common.h:12-70.
  * psamd_default_config() fills in the shipped values. */
@@ -726,6 +730,54 @@ int psamd_download_potential(psamd_ctx *ctx, float *phi, int64_t capacity, psamd
  * psamd_probe_result_get: the last probe's record, into host memory; waits for the context's stream. */
 int psamd_probe(psamd_ctx *ctx, const psamd_probe_spec *spec);
 int psamd_probe_result_get(psamd_ctx *ctx, psamd_probe_result *out);
+
+/* ---- long-range gravity (PSAMD_FLAG_FAR_MONOPOLE) ------------------------------ */
+/* The cutoff pass leaves most of a long-range force out; PSAMD_FLAG_ALL_PAIRS has all of it at O(N^2).  With this flag a
+ * particle's acceleration is the stencil's chain, exactly the cutoff pass's, plus ONE body per cell beyond its stencil.  Not
+ * in the reference; everything after the pair stage is untouched.
+ *
+ * Moments.  In the pair stage, from the snapshot psamd_build_grid left: cell c's moments come from the first
+ * min(count, MAX_PARTICLES_PER_CELL) entries of c in the sorted snapshot with the w_eff the force pass uses (0 for a kid,
+ * force_sign folded in).  In fp64, S = sum w_eff and Sx = sum w_eff*x, Sy, Sz likewise: the additions run in LIST ORDER,
+ * entry 0 first, one addition per entry, every sum started at +0; each product of two fp32 values is exact in fp64, so a
+ * fused multiply-add changes nothing.  M_c = (float)S, X_c = (float)(Sx / S), Y_c and Z_c likewise (fp64 division, one
+ * rounding to fp32).  If S == 0 -- an empty cell, or kids only -- M_c = X_c = Y_c = Z_c = 0.  A host that repeats these
+ * operations gets the same bits (tests/far_monopole_model.py does).
+ *
+ * Far acceleration.  For every particle the force pass serves (no kid, no collision this step), in cell c_i: the cells of
+ * the box are walked in global index order; a cell contributes the one body (X_c, Y_c, Z_c, M_c) through the context's own
+ * pair form -- the exact lean forms of the force pass, or the fast ones on a PSAMD_FLAG_FAST_MATH context.  A cell of c_i's own
+ * non-periodic 27-cell stencil contributes nothing (the cutoff pass has its bodies one by one), and neither does a cell with
+ * M_c == 0: they are left out or entered with mass 0, which gives the same bits -- a chain that starts at +0 never becomes -0.
+ *
+ * Association.  The cells go by blocks of 64 consecutive global indices (block b: cells 64 b .. 64 b + 63, the last one
+ * ragged).  A block's terms are ONE fp32 chain per component that starts at +0, in index order.  The blocks are dealt to 16
+ * parts -- part p holds the blocks [floor(nblk * p / 16), floor(nblk * (p + 1) / 16)) of nblk -- and a part's sum is the
+ * chain sums added in block order to +0.  The particle's record is (((stencil chain + part 0) + part 1) + ...) + part 15: the
+ * all-pairs far pass's scheme.  It depends on G and the global cell order alone -- not on the launch shape, the other
+ * particles, graphs on or off, run-ahead, or any max_count-like size: the same bytes from run to run.
+ *
+ * Consequences.  A cloud inside a 2x2x2 block of cells has no far cell: the force records and the whole step are the cutoff
+ * context's, byte for byte.  A frame with at most one adult per cell has X_c equal to that adult's position and M_c equal to
+ * its w_eff exactly, and the result is the all-pairs force up to association.
+ *
+ * Accuracy (an fp64 model of the method against an fp64 direct sum, 8192 bodies on 8^3 cells, uniform and clustered): the
+ * median particle's |a| is off by 0.2 %, the worst by 1-2 %; the cutoff alone leaves out 77-89 % for the median particle
+ * (tests/test_far_monopole_cpu.py).  The device follows the model to 1e-5 relative (tests/test_gpu_far_monopole.py).
+ *
+ * Refusals.  psamd_create: with PSAMD_FLAG_ALL_PAIRS PSAMD_ERR_INVALID_ARG; with world > 1, with a softening length outside
+ * the lean range, or without the two-pass pair stage (collision radius not small against the cell) PSAMD_ERR_UNSUPPORTED.
+ * psamd_potential, psamd_download_potential and psamd_probe return PSAMD_ERR_UNSUPPORTED on such a context, which stays
+ * usable: they promise exactly the bodies the force pass walks, and their monopole form is not built.  The flag combines
+ * freely with FAST_MATH, EULER, EXPLOSIONS, drag, force_sign, graphs, run-ahead and snapshot save / restore.
+ *
+ * Cost on an MI355X at N = 2^20, default constants (profiles/far_monopole_cost.txt): a step takes 6.43 ms with the flag, 2.17 ms without it (the cutoff step) and 285.9 ms with PSAMD_FLAG_ALL_PAIRS: 2.96 times the cutoff step, 44 times faster than all-pairs;
+ * 200 served particles against an fp64 direct sum over all 2^20 bodies: |a| off by 0.034 % for the median particle and 0.21 % for the worst, where the cutoff's records are off by 97.5 % (median).  The pair stage's own timer: 3.68 ms against 1.85 ms.
+ *
+ * psamd_download_cell_moments: float4[num_cells] = (X_c, Y_c, Z_c, M_c) of the frame, by global cell.  Valid from
+ * psamd_calc_forces_pairs until the frame ends (psamd_step cannot be interposed: use the stage calls); elsewhere
+ * PSAMD_ERR_STATE.  On a context without the flag PSAMD_ERR_UNSUPPORTED.  Waits for the context's stream. */
+int psamd_download_cell_moments(psamd_ctx *ctx, void *out_float4);
 
 /* ---- introspection -------------------------------------------------------- */
 int psamd_get_counters(psamd_ctx *ctx, psamd_counters *out);

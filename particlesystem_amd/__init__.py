@@ -32,6 +32,7 @@ FLAG_EXPLOSIONS = 0x1
 FLAG_FAST_MATH = 0x2
 FLAG_ALL_PAIRS = 0x4
 FLAG_EULER = 0x8
+FLAG_FAR_MONOPOLE = 0x10
 NUM_TIMERS = 9
 TIMER_NAMES = ("hist", "scan", "scatter", "sort_cells", "pairs", "apply", "lifecycle", "init_iframe", "collide")
 
@@ -291,6 +292,7 @@ ABI = [
     ("psamd_download_cellgrid", C.c_int, [_vp, _vp]),
     ("psamd_download_chunkgrid", C.c_int, [_vp, _vp]),
     ("psamd_download_force_counts", C.c_int, [_vp, _vp]),
+    ("psamd_download_cell_moments", C.c_int, [_vp, _vp]),
     ("psamd_get_pkgdistrib", C.c_int, [_vp, _vp]),
     ("psamd_get_cell_table", C.c_int, [_vp, _vp]),
     ("psamd_get_gridmax", C.c_int, [_vp, _ip]),
@@ -518,6 +520,12 @@ class ParticleSystem:
         """Per cell: particles the last pair pass computed a force for."""
         out = np.zeros(self.sizes.num_cells, np.int32)
         self._ck(self.lib.psamd_download_force_counts(self.h, _ptr(out)))
+        return out
+
+    def download_cell_moments(self):
+        """Per cell of the frame (far monopoles): (X, Y, Z, M), the centre of mass and the total w_eff, float32 [num_cells, 4]."""
+        out = np.zeros((self.sizes.num_cells, 4), np.float32)
+        self._ck(self.lib.psamd_download_cell_moments(self.h, _ptr(out)))
         return out
 
     def pkgdistrib(self):

@@ -171,12 +171,30 @@ __global__ void k_allpairs_combine(DevParams P, const int *__restrict__ act_star
     }
 }
 
+// The dense order of the pass (k_allp_prefix, k_allp_dense) and the sum of the parts (k_allpairs_combine) serve every far
+// field that goes by (dense task, part) waves: the all-pairs one below and the monopoles' (farfield.hip).
+// dense tasks: at most the particles alive (the host's bound; a slab also computes its neighbour's lent layers:
+// every entry of the sorted order).  The kernels go by the device's own count.
+int64_t far_dense_bound(const DevParams &P, const DeviceState &d, int64_t live_bound)
+{
+    return std::min<int64_t>(d.part_tasks, ((live_bound >= 0 && P.world == 1) ? live_bound : (int64_t)P.sorted_cap) / 64 + 2);
+}
+
+void launch_dense_order(hipStream_t st, const DevParams &P, const DeviceState &d)
+{
+    k_allp_prefix<<<1, 1024, 0, st>>>(P, d.active_count, d.act_start);
+    k_allp_dense<<<(comp_count(P) + 3) / 4, 256, 0, st>>>(P, d.cell_start, d.active_list, d.active_count, d.act_start, d.dense_gi, d.dense_cell);
+}
+
+void launch_far_combine(hipStream_t st, const DevParams &P, const DeviceState &d, const FarCells &far, int64_t dense_bound)
+{
+    k_allpairs_combine<<<(unsigned)((dense_bound * 64 + 255) / 256), 256, 0, st>>>(P, d.act_start, d.dense_gi, d.dense_cell, far, force_buf(d));
+}
+
 // What ran before is the stencil's chain (the two-pass pair stage: all-pairs contexts are created only with it, and only
 // with lean arithmetic); now every other cell (k_allp_far) and the sum.  fast: the tolerance mode's arithmetic.
 void launch_allpairs_far(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound)
 {
-    const int ncomp = comp_count(P);
-    const ForceBuf fbuf = force_buf(d);
     // where the far cells are found: the own snapshot (one GPU: local cell == global cell, lengths from consecutive starts) or the
     // all-gathered snapshot of all ranks with its index by global cell.
     FarCells far;
@@ -185,16 +203,13 @@ void launch_allpairs_far(hipStream_t st, const DevParams &P, const DeviceState &
     const int *far_start = gathered ? d.gstart : d.cell_start, *far_n = gathered ? d.gn : nullptr;
     far.plane = gathered ? (unsigned long long)P.allg_cap : (unsigned long long)P.sorted_cap;
     far.part_acc = d.part_acc; far.part_plane = (unsigned long long)d.part_tasks * 64;
-    // dense tasks: at most the particles alive (the host's bound; a slab also computes its neighbour's lent layers:
-    // every entry of the sorted order).  The kernels go by the device's own count.
-    const int64_t dense_bound = std::min<int64_t>(d.part_tasks, ((live_bound >= 0 && P.world == 1) ? live_bound : (int64_t)P.sorted_cap) / 64 + 2);
-    k_allp_prefix<<<1, 1024, 0, st>>>(P, d.active_count, d.act_start);
-    k_allp_dense<<<(ncomp + 3) / 4, 256, 0, st>>>(P, d.cell_start, d.active_list, d.active_count, d.act_start, d.dense_gi, d.dense_cell);
+    const int64_t dense_bound = far_dense_bound(P, d, live_bound);
+    launch_dense_order(st, P, d);
     const SnapSoa snap4{d.snap_soa, (size_t)P.sorted_cap};
     const unsigned far_wgs = (unsigned)((dense_bound * ALLP_PARTS + 3) / 4);
     if (fast) k_allp_far<2, 8><<<far_wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, far_buf, far_start, far_n);
     else k_allp_far<1, 8><<<far_wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, far_buf, far_start, far_n);
-    k_allpairs_combine<<<(unsigned)((dense_bound * 64 + 255) / 256), 256, 0, st>>>(P, d.act_start, d.dense_gi, d.dense_cell, far, fbuf);
+    launch_far_combine(st, P, d, far, dense_bound);
 }
 
 }  // namespace psamd

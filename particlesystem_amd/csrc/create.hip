@@ -191,6 +191,12 @@ static int derive_params(psamd_ctx *c, const psamd_config *cfg)
     if (P.key_bits > 63) return fail(c, PSAMD_ERR_UNSUPPORTED, "queue-op key does not fit 64 bits for this configuration");
     if ((cfg->flags & PSAMD_FLAG_ALL_PAIRS) && !P.lean_math) return fail(c, PSAMD_ERR_UNSUPPORTED, "all-pairs forces are built for the lean pair arithmetic only (EPS2 in its validated range)");
     if ((cfg->flags & PSAMD_FLAG_ALL_PAIRS) && !P.two_pass) return fail(c, PSAMD_ERR_UNSUPPORTED, "all-pairs forces need the two-pass pair stage (collision radius small against the cell)");
+    if (cfg->flags & PSAMD_FLAG_FAR_MONOPOLE) {
+        if (cfg->flags & PSAMD_FLAG_ALL_PAIRS) return fail(c, PSAMD_ERR_INVALID_ARG, "far monopoles and all-pairs forces are two force models: choose one");
+        if (cfg->world > 1) return fail(c, PSAMD_ERR_UNSUPPORTED, "far monopoles are served on one context only (world == 1)");
+        if (!P.lean_math) return fail(c, PSAMD_ERR_UNSUPPORTED, "far monopoles are built for the lean pair arithmetic only (EPS2 in its validated range)");
+        if (!P.two_pass) return fail(c, PSAMD_ERR_UNSUPPORTED, "far monopoles need the two-pass pair stage (collision radius small against the cell)");
+    }
     for (int k = 0; k < 5; k++) { c->S.seg_base[k] = g.seg_base[k]; c->S.info_base[k] = g.info_base[k]; }
     for (int k = 0; k < 4; k++) c->S.seg_size_t[k] = g.seg_size_t[k];
     P.eps2f = (float)cfg->eps2;
@@ -326,6 +332,21 @@ static int alloc_step_arrays(psamd_ctx *c)
     PS_HIP(c, dev_alloc(c, &d.pack_stage, LC + 64));
     PS_HIP(c, dev_alloc(c, &d.pack_count, LC / 64 + 1));
     PS_HIP(c, dev_alloc(c, &d.pack_base, LC / 64 + 1));
+    if (P.flags & PSAMD_FLAG_FAR_MONOPOLE) {
+        // far monopoles, behind everything a context without the flag allocates: the partial sums and the dense order
+        // of the all-pairs far pass (sized as there), and the cells' moments -- four planes and the packed coordinates,
+        // padded to whole blocks of 64 cells; the padding stays zero (k_cell_moments writes the cells of the box)
+        d.part_tasks = (int)(SC / 64 + 1);
+        PS_HIP(c, dev_alloc(c, &d.part_acc, (size_t)ALLP_PARTS * d.part_tasks * 64));
+        PS_HIP(c, dev_alloc(c, &d.act_start, LC + 1));
+        PS_HIP(c, dev_alloc(c, &d.dense_gi, SC));
+        PS_HIP(c, dev_alloc(c, &d.dense_cell, SC));
+        d.mom_cap = (g.num_cells + 63) / 64 * 64;
+        PS_HIP(c, dev_alloc(c, &d.cell_mom, 4 * (size_t)d.mom_cap + 64));     // + slack: scalar loads fetch whole groups
+        PS_HIP(c, dev_alloc(c, &d.cell_mom_j, (size_t)d.mom_cap));
+        PS_HIP(c, hipMemsetAsync(d.cell_mom, 0, (4 * (size_t)d.mom_cap + 64) * sizeof(float), c->stream));
+        PS_HIP(c, hipMemsetAsync(d.cell_mom_j, 0, (size_t)d.mom_cap * sizeof(int), c->stream));
+    }
     return PSAMD_OK;
 }
 

@@ -267,6 +267,21 @@ int psamd_download_force_counts(psamd_ctx *c, int32_t *out)
     return PSAMD_OK;
 }
 
+int psamd_download_cell_moments(psamd_ctx *c, void *out)
+{
+    if (!c || !out) return PSAMD_ERR_INVALID_ARG;
+    if (!(c->P.flags & PSAMD_FLAG_FAR_MONOPOLE)) return fail(c, PSAMD_ERR_UNSUPPORTED, "cell moments are formed on a context with far monopoles (PSAMD_FLAG_FAR_MONOPOLE) only");
+    if (!pairs_done(c->stage)) return fail(c, PSAMD_ERR_STATE, "cell moments requested before the pair pass of this frame");
+    const size_t n = (size_t)c->geo.num_cells, cap = (size_t)c->d.mom_cap;
+    std::vector<float> planes(4 * cap);
+    PS_HIP(c, hipMemcpyAsync(planes.data(), c->d.cell_mom, planes.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    float *o = static_cast<float *>(out);
+    for (size_t k = 0; k < n; k++)
+        for (size_t f = 0; f < 4; f++) o[4 * k + f] = planes[f * cap + k];
+    return PSAMD_OK;
+}
+
 int psamd_download_chunkgrid(psamd_ctx *c, int32_t *out)
 {
     if (!c || !out) return PSAMD_ERR_INVALID_ARG;

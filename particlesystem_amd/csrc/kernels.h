@@ -188,6 +188,11 @@ struct DeviceState {
     int *act_start = nullptr;     // all-pairs: [num_cells + 1] particles that need a force in the pass's cells before its j-th
     int *dense_gi = nullptr;      // all-pairs: [container] sorted index of the r-th particle that needs a force (cell order)
     int *dense_cell = nullptr;    // all-pairs: [container] its cell
+    // far monopoles (PSAMD_FLAG_FAR_MONOPOLE; part_acc .. dense_cell above are this pass's too): per cell of the box,
+    // padded with zeros to whole blocks of 64 cells, the planes X, Y, Z, M and the cell's packed grid coordinates
+    float *cell_mom = nullptr;    // [4][mom_cap]
+    int *cell_mom_j = nullptr;    // [mom_cap] (i3 << 20) | (i1 << 10) | i2
+    int mom_cap = 0;
     DevCounters *ctr = nullptr;
     // psamd_export_live: per tile of SLOT_TILE owned slots, the live count and the statistics' partials; the context's own result record
     int *exp_count = nullptr;
@@ -229,10 +234,18 @@ hipError_t launch_pairs(hipStream_t st, const DevParams &P, const DeviceState &d
 uint64_t launch_pairs_shape(const DevParams &P, int64_t tasks_hint);
 // launch_pairs' launches outside force.hip, in the order it makes them (their errors are launch_pairs' to collect):
 // the collision flags (collide.hip), the plan of the balanced force pass (plan.hip: nw wave slots, merge: with packs),
-// the far field of the all-pairs forces and its sum (allpairs.hip; fast: the tolerance mode's arithmetic)
+// the far field of the all-pairs forces and its sum (allpairs.hip; fast: the tolerance mode's arithmetic), or the far
+// monopoles and theirs (farfield.hip)
 void launch_collide(hipStream_t st, const DevParams &P, const DeviceState &d);
 void launch_plan_force(hipStream_t st, const DevParams &P, const DeviceState &d, int nw, bool merge, int pass);
 void launch_allpairs_far(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound);
+// ... and what allpairs.hip shares with the far monopoles: the host's bound of the dense tasks, the dense order of the
+// particles that need a force (act_start, dense_gi, dense_cell), the parts' sum onto the stencil's chain in part order
+int64_t far_dense_bound(const DevParams &P, const DeviceState &d, int64_t live_bound);
+void launch_dense_order(hipStream_t st, const DevParams &P, const DeviceState &d);
+void launch_far_combine(hipStream_t st, const DevParams &P, const DeviceState &d, const FarCells &far, int64_t dense_bound);
+// the far monopoles (farfield.hip): the cells' moments, then every cell beyond a particle's stencil as one body, and the sum
+void launch_far_monopole(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound);
 hipError_t launch_apply(hipStream_t st, const DevParams &P, const SegLayout &S, const DeviceState &d);
 hipError_t launch_frame_reset(hipStream_t st, const DeviceState &d, size_t frame_ints, int status_table);   // also clears the status record's header and census table
 // The step's tail behind k_apply: census of the queue operations (+ relocation phase 1), bucketing (the step's scalars go

@@ -198,9 +198,19 @@ static int frame_ready(psamd_ctx *c, const char *who)
     return PSAMD_OK;
 }
 
+// potential and probe promise exactly the bodies the force pass walks: with far monopoles a stencil-only answer would
+// break that silently, and their monopole form is not built
+static int refuse_far_monopole(psamd_ctx *c, const char *who)
+{
+    if (c->P.flags & PSAMD_FLAG_FAR_MONOPOLE)
+        return fail(c, PSAMD_ERR_UNSUPPORTED, std::string(who) + ": not served on a context with far monopoles (PSAMD_FLAG_FAR_MONOPOLE)");
+    return PSAMD_OK;
+}
+
 // ... and nothing of the plan is lent
 static int potential_ready(psamd_ctx *c)
 {
+    PS_TRY(refuse_far_monopole(c, "potential"));
     PS_TRY(frame_ready(c, "potential"));
     const SlabPlan &pl = c->plan;
     if (c->P.world > 1 && (pl.lentin_lo < pl.lentin_hi || pl.lentout_lo < pl.lentout_hi))
@@ -269,6 +279,7 @@ int psamd_probe(psamd_ctx *c, const psamd_probe_spec *spec)
         return fail(c, PSAMD_ERR_INVALID_ARG, "probe: pos4 or out4 missing, or an array misaligned");
     if ((c->P.flags & PSAMD_FLAG_ALL_PAIRS) && c->P.world > 1)
         return fail(c, PSAMD_ERR_UNSUPPORTED, "probe: all-pairs contexts are served on one context only (world == 1)");
+    PS_TRY(refuse_far_monopole(c, "probe"));
     PS_TRY(frame_ready(c, "probe"));
     psamd_probe_result *res = spec->result_dev ? spec->result_dev : c->prb.own;
     if (spec->max_count == 0) return zero_result(c, c->prb.own, res, sizeof *res);

@@ -65,6 +65,9 @@ typedef enum psamd_status {
                                          reference's order, then every OTHER cell of the box as one body -- its total mass at its
                                          centre of mass.  See "long-range gravity" below.  Collisions stay short-range.  Not with
                                          PSAMD_FLAG_ALL_PAIRS (PSAMD_ERR_INVALID_ARG); world == 1 only */
+#define PSAMD_FLAG_FAR_PYRAMID 0x20u  /* long-range gravity whose cost grows with log G instead of G^3: the stencil first, then coarser
+                                         cells for farther mass -- a pyramid of monopoles.  See "a pyramid of monopoles" below.  Not
+                                         with PSAMD_FLAG_ALL_PAIRS or PSAMD_FLAG_FAR_MONOPOLE (PSAMD_ERR_INVALID_ARG); world == 1 only */
 
 /* Runtime form of the reference's compile-time configuration, common.h:12-70.
  * psamd_default_config() fills in the shipped values. */
@@ -778,6 +781,67 @@ int psamd_probe_result_get(psamd_ctx *ctx, psamd_probe_result *out);
  * psamd_calc_forces_pairs until the frame ends (psamd_step cannot be interposed: use the stage calls); elsewhere
  * PSAMD_ERR_STATE.  On a context without the flag PSAMD_ERR_UNSUPPORTED.  Waits for the context's stream. */
 int psamd_download_cell_moments(psamd_ctx *ctx, void *out_float4);
+
+/* ---- a pyramid of monopoles (PSAMD_FLAG_FAR_PYRAMID) ---------------------------- */
+/* PSAMD_FLAG_FAR_MONOPOLE enters G^3 - 27 bodies per particle.  Most of them are distant and can be merged: with this flag
+ * farther mass comes in coarser cells, and a particle's far bodies grow with log G (about 300 on 16^3 cells, 500 on 40^3).  A force model of its
+ * own: contexts without the flag, PSAMD_FLAG_FAR_MONOPOLE contexts included, compute what they did.  Not in the reference.
+ *
+ * Levels.  Level 0 is the cell grid, G_0 = G.  Level l + 1 has G_{l+1} = ceil(G_l / 2) cells per axis.  The top level L is
+ * the first with G_L <= 4 (16 -> 8 -> 4: L = 2; 10 -> 5 -> 3: L = 2; G <= 4: L = 0).  The cell with coordinates (i1, i2, i3)
+ * lies in the level-l cell (i1 >> l, i2 >> l, i3 >> l); level-l cells are numbered (k3 * G_l + k1) * G_l + k2, like cells.
+ * (The packed cell coordinates are 10 bits each: G <= 1023, at most 9 levels.)
+ *
+ * Moments.  Level 0 is exactly PSAMD_FLAG_FAR_MONOPOLE's: the fp64 sums S, Sx, Sy, Sz over the first
+ * min(count, MAX_PARTICLES_PER_CELL) entries of the cell in list order, with the force pass's w_eff; the fp64 sums are kept.
+ * A level-(l+1) cell's four fp64 sums are its existing children's fp64 sums, added one at a time in ascending child index,
+ * each sum started at +0 (additions only: contraction cannot matter).  At every level M = (float)S, X = (float)(Sx / S), Y
+ * and Z likewise; S == 0 gives four zeros.  A host that repeats this gets the same bits (tests/far_pyramid_model.py does).
+ *
+ * Interaction set of a particle in cell i that the force pass serves (no kid, no collision this step):
+ *   at the top level, every level-L cell J with max-norm |J - (i >> L)| > 1;
+ *   at each level l < L, every level-l cell J whose parent is within 1 of i's parent, |(J >> 1) - (i >> (l + 1))| <= 1, and
+ *   which itself is not within 1 of i >> l.
+ * At level 0 "not within 1" is "not in the stencil": the cutoff pass has those bodies one by one.  Every cell of the box is
+ * thus covered exactly once: by the stencil, or by exactly one ancestor in the set.  A body of mass 0 contributes nothing.
+ * Each body goes through the context's own pair form (the exact lean form, or the fast one with PSAMD_FLAG_FAST_MATH).
+ *
+ * Association, fixed by G and the particle's cell alone.  Within a level the cells go in level index order by blocks of 64
+ * consecutive indices; a block is ONE fp32 chain per component started at +0; a level's sum is its block chains added in
+ * block order to +0.  The record is ((stencil chain + level L) + level L-1) + ... + level 0.  Cells outside the set are
+ * entered with mass 0 or skipped: the same bits, since a chain that starts at +0 never becomes -0.  Nothing depends on the
+ * launch shape, other particles, graphs, run-ahead or any bound: the same bytes from run to run.
+ *
+ * Consequences.  On a grid with G <= 4 the force records and whole steps are those of a PSAMD_FLAG_FAR_MONOPOLE context,
+ * byte for byte (one level, one block; the 15 empty parts there add +0).  A cloud inside a 2x2x2 block of cells gives the
+ * cutoff context's bytes: no ancestor of a stencil cell is ever in the set.
+ *
+ * Accuracy (an fp64 model of the method against an fp64 direct sum, 8192 bodies, uniform and clustered, 400 sampled;
+ * tests/test_far_pyramid_cpu.py): the median particle's |a| is off by 0.2-0.5 %, the worst
+ * by 2-4.4 % on 8^3 and 10^3 cells (the flat method on 8^3: 0.15-0.2 % and 1.6-3.5 %); the cutoff alone leaves out 77-91 % for the
+ * median particle.  A particle's far bodies: 153 of 491 on 8^3 cells, 295 of 4072 on 16^3 in the mean.  The device follows the
+ * model to 1e-5 relative (tests/test_gpu_far_pyramid.py).
+ *
+ * Refusals mirror PSAMD_FLAG_FAR_MONOPOLE's.  psamd_create: with PSAMD_FLAG_ALL_PAIRS or PSAMD_FLAG_FAR_MONOPOLE
+ * PSAMD_ERR_INVALID_ARG; with world > 1, a softening length outside the lean range, or without the two-pass pair stage
+ * PSAMD_ERR_UNSUPPORTED.  psamd_potential, psamd_download_potential and psamd_probe return PSAMD_ERR_UNSUPPORTED on such a
+ * context, which stays usable.  The flag combines freely with FAST_MATH, EULER, EXPLOSIONS, drag, force_sign, graphs,
+ * run-ahead and snapshot save / restore.
+ *
+ * Cost on an MI355X, default constants (profiles/far_pyramid_cost.txt): at N = 2^20 (16^3 cells) a step takes 6.19 ms with the flag, 6.43 ms with
+ * PSAMD_FLAG_FAR_MONOPOLE and 2.18 ms with neither (the pair stage's own timer: 3.46, 3.67 and 1.86 ms); at N = 2^22 (24^3 cells)
+ * 18.6, 27.9 and 9.3 ms (14.8, 24.4 and 8.5 ms).  200 served particles against an fp64 direct sum over all bodies: |a| off by
+ * 0.057 % for the median particle and 0.48 % for the worst at 2^20 (the flat method: 0.034 % and 0.21 %), 0.059 % and 0.21 % at 2^22
+ * (0.020 % and 0.13 %).  A fourteenth of the far bodies buys 4 % of the step at 16^3 and a third at 24^3: the walk is bound by
+ * scanning the blocks of its box, not by its pairs (by its structure; not profiled).
+ *
+ * psamd_far_levels: host only, no device.  *levels = L + 1, dims[0 .. L] = G_0 .. G_L, the rest of dims 0.
+ * psamd_download_level_moments: float4[G_level^3] = (X, Y, Z, M) of one level of the frame, by level cell index.  The validity
+ * window and error codes of psamd_download_cell_moments; a level outside [0, L] PSAMD_ERR_INVALID_ARG; on a context without
+ * PSAMD_FLAG_FAR_PYRAMID PSAMD_ERR_UNSUPPORTED.  Waits for the context's stream.  psamd_download_cell_moments also works on a
+ * pyramid context, where it returns level 0. */
+int psamd_far_levels(const psamd_config *cfg, int32_t *levels, int32_t dims[16]);
+int psamd_download_level_moments(psamd_ctx *ctx, int32_t level, void *out_float4);
 
 /* ---- introspection -------------------------------------------------------- */
 int psamd_get_counters(psamd_ctx *ctx, psamd_counters *out);

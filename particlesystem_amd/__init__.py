@@ -33,6 +33,7 @@ FLAG_FAST_MATH = 0x2
 FLAG_ALL_PAIRS = 0x4
 FLAG_EULER = 0x8
 FLAG_FAR_MONOPOLE = 0x10
+FLAG_FAR_PYRAMID = 0x20
 NUM_TIMERS = 9
 TIMER_NAMES = ("hist", "scan", "scatter", "sort_cells", "pairs", "apply", "lifecycle", "init_iframe", "collide")
 
@@ -293,6 +294,8 @@ ABI = [
     ("psamd_download_chunkgrid", C.c_int, [_vp, _vp]),
     ("psamd_download_force_counts", C.c_int, [_vp, _vp]),
     ("psamd_download_cell_moments", C.c_int, [_vp, _vp]),
+    ("psamd_download_level_moments", C.c_int, [_vp, C.c_int32, _vp]),
+    ("psamd_far_levels", C.c_int, [C.POINTER(Config), _ip, _ip]),
     ("psamd_get_pkgdistrib", C.c_int, [_vp, _vp]),
     ("psamd_get_cell_table", C.c_int, [_vp, _vp]),
     ("psamd_get_gridmax", C.c_int, [_vp, _ip]),
@@ -401,6 +404,17 @@ def slab_plan(cfg):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def far_levels(cfg):
+    """Host-only: the cells per axis of every level of the pyramid of monopoles, [G_0 .. G_L] (no GPU needed)."""
+    lib = load()
+    n = C.c_int32()
+    dims = (C.c_int32 * 16)()
+    st = lib.psamd_far_levels(C.byref(cfg), C.byref(n), dims)
+    if st != 0:
+        raise PsamdError(st, lib.psamd_status_string(st).decode())
+    return [int(dims[k]) for k in range(n.value)]
 
 
 def describe(cfg):
@@ -526,6 +540,15 @@ class ParticleSystem:
         """Per cell of the frame (far monopoles): (X, Y, Z, M), the centre of mass and the total w_eff, float32 [num_cells, 4]."""
         out = np.zeros((self.sizes.num_cells, 4), np.float32)
         self._ck(self.lib.psamd_download_cell_moments(self.h, _ptr(out)))
+        return out
+
+    def download_level_moments(self, level):
+        """Per cell of a level of the pyramid (PSAMD_FLAG_FAR_PYRAMID; level 0: the cells): (X, Y, Z, M), float32 [G_level^3, 4]."""
+        dims = far_levels(self.cfg)
+        if not 0 <= level < len(dims):
+            raise PsamdError(1, "no such level")
+        out = np.zeros((dims[level] ** 3, 4), np.float32)
+        self._ck(self.lib.psamd_download_level_moments(self.h, level, _ptr(out)))
         return out
 
     def pkgdistrib(self):

@@ -197,6 +197,12 @@ static int derive_params(psamd_ctx *c, const psamd_config *cfg)
         if (!P.lean_math) return fail(c, PSAMD_ERR_UNSUPPORTED, "far monopoles are built for the lean pair arithmetic only (EPS2 in its validated range)");
         if (!P.two_pass) return fail(c, PSAMD_ERR_UNSUPPORTED, "far monopoles need the two-pass pair stage (collision radius small against the cell)");
     }
+    if (cfg->flags & PSAMD_FLAG_FAR_PYRAMID) {
+        if (cfg->flags & (PSAMD_FLAG_ALL_PAIRS | PSAMD_FLAG_FAR_MONOPOLE)) return fail(c, PSAMD_ERR_INVALID_ARG, "the pyramid of monopoles, far monopoles and all-pairs forces are three force models: choose one");
+        if (cfg->world > 1) return fail(c, PSAMD_ERR_UNSUPPORTED, "the pyramid of monopoles is served on one context only (world == 1)");
+        if (!P.lean_math) return fail(c, PSAMD_ERR_UNSUPPORTED, "the pyramid of monopoles is built for the lean pair arithmetic only (EPS2 in its validated range)");
+        if (!P.two_pass) return fail(c, PSAMD_ERR_UNSUPPORTED, "the pyramid of monopoles needs the two-pass pair stage (collision radius small against the cell)");
+    }
     for (int k = 0; k < 5; k++) { c->S.seg_base[k] = g.seg_base[k]; c->S.info_base[k] = g.info_base[k]; }
     for (int k = 0; k < 4; k++) c->S.seg_size_t[k] = g.seg_size_t[k];
     P.eps2f = (float)cfg->eps2;
@@ -346,6 +352,26 @@ static int alloc_step_arrays(psamd_ctx *c)
         PS_HIP(c, dev_alloc(c, &d.cell_mom_j, (size_t)d.mom_cap));
         PS_HIP(c, hipMemsetAsync(d.cell_mom, 0, (4 * (size_t)d.mom_cap + 64) * sizeof(float), c->stream));
         PS_HIP(c, hipMemsetAsync(d.cell_mom_j, 0, (size_t)d.mom_cap * sizeof(int), c->stream));
+    }
+    if (P.flags & PSAMD_FLAG_FAR_PYRAMID) {
+        // the pyramid, likewise behind everything else and under its flag only: the same partial sums (a level is a part: at
+        // most FAR_MAX_LEVELS of the ALLP_PARTS planes are used) and dense order; the moment planes hold every level, each
+        // padded with zeros to whole blocks of 64 cells (the kernels write the cells of a level, never its padding), and
+        // the fp64 sums the levels are added up from
+        d.lev = far_levels_of(g.G);
+        static_assert(FAR_MAX_LEVELS <= ALLP_PARTS, "a level's sum goes into one of the partial-sum planes");
+        d.part_tasks = (int)(SC / 64 + 1);
+        PS_HIP(c, dev_alloc(c, &d.part_acc, (size_t)ALLP_PARTS * d.part_tasks * 64));
+        PS_HIP(c, dev_alloc(c, &d.act_start, LC + 1));
+        PS_HIP(c, dev_alloc(c, &d.dense_gi, SC));
+        PS_HIP(c, dev_alloc(c, &d.dense_cell, SC));
+        d.mom_cap = d.lev.off[d.lev.n];
+        PS_HIP(c, dev_alloc(c, &d.cell_mom, 4 * (size_t)d.mom_cap + 64));     // + slack: scalar loads fetch whole groups
+        PS_HIP(c, dev_alloc(c, &d.cell_mom_j, (size_t)d.mom_cap));
+        PS_HIP(c, dev_alloc(c, &d.lev_sum, 4 * (size_t)d.mom_cap));
+        PS_HIP(c, hipMemsetAsync(d.cell_mom, 0, (4 * (size_t)d.mom_cap + 64) * sizeof(float), c->stream));
+        PS_HIP(c, hipMemsetAsync(d.cell_mom_j, 0, (size_t)d.mom_cap * sizeof(int), c->stream));
+        PS_HIP(c, hipMemsetAsync(d.lev_sum, 0, 4 * (size_t)d.mom_cap * sizeof(double), c->stream));
     }
     return PSAMD_OK;
 }

@@ -102,6 +102,28 @@ struct FarCells {
 };
 constexpr int ALLP_PARTS = 16;
 
+// The pyramid of the far field (PSAMD_FLAG_FAR_PYRAMID): level 0 is the cell grid, level l + 1 has ceil(G_l / 2) cells per
+// axis, the top level is the first with at most 4.  A level's cells are numbered (k3 * G_l + k1) * G_l + k2 and live at
+// off[l] .. off[l] + G_l^3 of the moment planes; every off[l] is a multiple of 64 and the room up to off[l + 1] stays zero.
+// G <= 256 (16 M cells at the most): at most 7 levels, which fit the ALLP_PARTS partial sums.
+constexpr int FAR_MAX_LEVELS = 10;
+struct FarLevels {
+    int32_t n = 0;                      // L + 1
+    int32_t G[FAR_MAX_LEVELS] = {};
+    int32_t off[FAR_MAX_LEVELS + 1] = {};   // off[n]: the planes' length
+};
+inline FarLevels far_levels_of(int G)
+{
+    FarLevels v;
+    for (int g = G, o = 0;; g = (g + 1) / 2) {
+        v.G[v.n] = g; v.off[v.n] = o;
+        o += (g * g * g + 63) / 64 * 64;
+        v.off[++v.n] = o;
+        if (g <= 4 || v.n == FAR_MAX_LEVELS) break;
+    }
+    return v;
+}
+
 // Which cells / slots / records a rank holds.  All device code goes through these.
 #if defined(__HIPCC__)
 #define PS_HD __host__ __device__ __forceinline__

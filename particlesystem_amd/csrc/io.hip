@@ -267,19 +267,47 @@ int psamd_download_force_counts(psamd_ctx *c, int32_t *out)
     return PSAMD_OK;
 }
 
+// n cells from `first` of the four moment planes, as float4 = (X, Y, Z, M); waits for the stream
+static int download_moments(psamd_ctx *c, size_t first, size_t n, float *o)
+{
+    const size_t cap = (size_t)c->d.mom_cap;
+    std::vector<float> planes(4 * n);
+    for (size_t f = 0; f < 4; f++)
+        PS_HIP(c, hipMemcpyAsync(planes.data() + f * n, c->d.cell_mom + f * cap + first, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < n; k++)
+        for (size_t f = 0; f < 4; f++) o[4 * k + f] = planes[f * n + k];
+    return PSAMD_OK;
+}
+
 int psamd_download_cell_moments(psamd_ctx *c, void *out)
 {
     if (!c || !out) return PSAMD_ERR_INVALID_ARG;
-    if (!(c->P.flags & PSAMD_FLAG_FAR_MONOPOLE)) return fail(c, PSAMD_ERR_UNSUPPORTED, "cell moments are formed on a context with far monopoles (PSAMD_FLAG_FAR_MONOPOLE) only");
+    if (!(c->P.flags & (PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID))) return fail(c, PSAMD_ERR_UNSUPPORTED, "cell moments are formed on a context with far monopoles (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID) only");
     if (!pairs_done(c->stage)) return fail(c, PSAMD_ERR_STATE, "cell moments requested before the pair pass of this frame");
-    const size_t n = (size_t)c->geo.num_cells, cap = (size_t)c->d.mom_cap;
-    std::vector<float> planes(4 * cap);
-    PS_HIP(c, hipMemcpyAsync(planes.data(), c->d.cell_mom, planes.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    PS_HIP(c, hipStreamSynchronize(c->stream));
-    float *o = static_cast<float *>(out);
-    for (size_t k = 0; k < n; k++)
-        for (size_t f = 0; f < 4; f++) o[4 * k + f] = planes[f * cap + k];
+    return download_moments(c, 0, (size_t)c->geo.num_cells, static_cast<float *>(out));      // (a pyramid's level 0 starts the planes)
+}
+
+int psamd_far_levels(const psamd_config *cfg, int32_t *levels, int32_t dims[16])
+{
+    if (!cfg || !levels || !dims) return PSAMD_ERR_INVALID_ARG;
+    Geometry g;
+    if (!g.init(*cfg)) return PSAMD_ERR_INVALID_ARG;
+    const FarLevels lev = far_levels_of(g.G);
+    *levels = lev.n;
+    for (int k = 0; k < 16; k++) dims[k] = k < lev.n ? lev.G[k] : 0;
     return PSAMD_OK;
+}
+
+int psamd_download_level_moments(psamd_ctx *c, int32_t level, void *out)
+{
+    if (!c || !out) return PSAMD_ERR_INVALID_ARG;
+    if (!(c->P.flags & PSAMD_FLAG_FAR_PYRAMID)) return fail(c, PSAMD_ERR_UNSUPPORTED, "level moments are formed on a context with the pyramid of monopoles (PSAMD_FLAG_FAR_PYRAMID) only");
+    const FarLevels &lev = c->d.lev;
+    if (level < 0 || level >= lev.n) return fail(c, PSAMD_ERR_INVALID_ARG, "level moments: no such level");
+    if (!pairs_done(c->stage)) return fail(c, PSAMD_ERR_STATE, "level moments requested before the pair pass of this frame");
+    const size_t G = (size_t)lev.G[level];
+    return download_moments(c, (size_t)lev.off[level], G * G * G, static_cast<float *>(out));
 }
 
 int psamd_download_chunkgrid(psamd_ctx *c, int32_t *out)

@@ -16,7 +16,8 @@
 //                    for the packs: tile_walk.hpp), serial fp32 accumulation in the reference's order (fp32 VALU bound;
 //                    no MFMA: no contraction here, every pair needs its own rsqrt)
 //     allpairs.hip   the far field of the all-pairs forces, beyond the stencil
-//     farfield.hip   the far field as one monopole per cell (PSAMD_FLAG_FAR_MONOPOLE): the cells' moments, the walk
+//     farfield.hip   the far field as one monopole per cell (PSAMD_FLAG_FAR_MONOPOLE): the cells' moments, the walk; and
+//                    as a pyramid of them (PSAMD_FLAG_FAR_PYRAMID): the levels' moments, the walk by (task, level)
 //     selftest.hip   the short sqrt / reciprocal against the compiler's over whole float ranges
 //   apply.hip      k_apply: death / survive / integrate / wrap / re-hash in slot order (ps.cpp:1210-1333; streaming, HBM)
 //   lifecycle.hip  free-slot queues + relocation replayed in the reference's serial order (ps.cpp:1335-1374,

@@ -198,12 +198,12 @@ static int frame_ready(psamd_ctx *c, const char *who)
     return PSAMD_OK;
 }
 
-// potential and probe promise exactly the bodies the force pass walks: with far monopoles a stencil-only answer would
-// break that silently, and their monopole form is not built
+// potential and probe promise exactly the bodies the force pass walks: with far monopoles (flat or as a pyramid) a
+// stencil-only answer would break that silently, and their monopole form is not built
 static int refuse_far_monopole(psamd_ctx *c, const char *who)
 {
-    if (c->P.flags & PSAMD_FLAG_FAR_MONOPOLE)
-        return fail(c, PSAMD_ERR_UNSUPPORTED, std::string(who) + ": not served on a context with far monopoles (PSAMD_FLAG_FAR_MONOPOLE)");
+    if (c->P.flags & (PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID))
+        return fail(c, PSAMD_ERR_UNSUPPORTED, std::string(who) + ": not served on a context with far monopoles (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID)");
     return PSAMD_OK;
 }
 

@@ -254,9 +254,15 @@ typedef struct psamd_potential_result {
     double  phi_min, phi_max; /* over the finite ones; +inf / -inf if there is none                           */
 } psamd_potential_result;     /* 40 bytes */
 
+/* psamd_potential_spec.flags.  PSAMD_POTENTIAL_FAR: on a PSAMD_FLAG_FAR_MONOPOLE / PSAMD_FLAG_FAR_PYRAMID context, phi over
+ * the stencil AND the far bodies of the context's force model (see "energy" below).  The bit exists so that a caller
+ * written for "exactly the stencil's bodies" is never silently handed another quantity: without it such a context
+ * refuses, with it the caller has said which phi it wants.  An unknown bit on every other context. */
+#define PSAMD_POTENTIAL_FAR 0x1u
+
 /* What psamd_potential writes and where (device pointers). */
 typedef struct psamd_potential_spec {
-    uint32_t flags;           /* 0 (reserved for later)                                                       */
+    uint32_t flags;           /* 0, or PSAMD_POTENTIAL_FAR on a far-monopole context                          */
     int32_t  reserved;        /* 0                                                                            */
     float   *phi;             /* optional out, float[capacity], 4-byte aligned; required if capacity > 0      */
     int64_t  capacity;        /* entries phi holds                                                            */
@@ -266,6 +272,9 @@ typedef struct psamd_potential_spec {
 /* psamd_probe: which components of the field are wanted (see "the field at chosen points" below). */
 #define PSAMD_PROBE_ACC 0x1u   /* out4.xyz = acceleration at the point            */
 #define PSAMD_PROBE_PHI 0x2u   /* out4.w   = potential at the point               */
+#define PSAMD_PROBE_FAR 0x4u   /* a modifier beside ACC and / or PHI, on a PSAMD_FLAG_FAR_MONOPOLE / PSAMD_FLAG_FAR_PYRAMID
+                                  context: the field of the stencil AND the far bodies of the context's force model.  It
+                                  exists for PSAMD_POTENTIAL_FAR's reason; an unknown bit on every other context */
 
 /* What psamd_probe did. */
 typedef struct psamd_probe_result {
@@ -278,7 +287,7 @@ typedef struct psamd_probe_result {
 
 /* What psamd_probe reads and where it writes (device pointers). */
 typedef struct psamd_probe_spec {
-    uint32_t fields;          /* PSAMD_PROBE_ACC | PSAMD_PROBE_PHI, at least one                              */
+    uint32_t fields;          /* PSAMD_PROBE_ACC | PSAMD_PROBE_PHI, at least one; PSAMD_PROBE_FAR beside them  */
     int32_t  reserved;        /* 0                                                                            */
     const void *pos4;         /* float4[max_count] x, y, z (w ignored), 16-byte aligned: an export's pos4 can
                                  be passed as it is                                                           */
@@ -658,17 +667,51 @@ int psamd_remove_result_get(psamd_ctx *ctx, psamd_remove_result *out);
  * cuts; else PSAMD_ERR_UNSUPPORTED (the context stays usable): shipping phi of lent layers home would need a message of
  * its own.  The ranks' results combine like psamd_live_stats: counts and U add, the extrema take min and max.
  *
- * PSAMD_ERR_INVALID_ARG: a NULL context or spec, flags or reserved not 0, capacity < 0, phi not 4-byte aligned, phi NULL
- * with capacity > 0, result_dev not 8-byte aligned.
+ * Far-monopole contexts (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID; always world == 1).  Without PSAMD_POTENTIAL_FAR
+ * psamd_potential and psamd_download_potential return PSAMD_ERR_UNSUPPORTED: a stencil-only phi is not the potential of
+ * the field these contexts apply.  With PSAMD_POTENTIAL_FAR (host form: psamd_download_potential_far) a particle in cell c
+ * sees the stencil lists of c exactly as above and, behind them, the far bodies the force pass of this context enters for
+ * c, each as one body (X, Y, Z, M) of the moments: with PSAMD_FLAG_FAR_MONOPOLE every cell outside c's stencil, with
+ * PSAMD_FLAG_FAR_PYRAMID the interaction set of "a pyramid of monopoles" below, levels L down to 0.  A body with M == 0 or
+ * outside the set contributes no term.  The call forms the moments itself from the frame's snapshot with the pair stage's
+ * own kernels -- the same bits in the same buffers -- because this window opens before the pair stage has run; the window
+ * of psamd_download_cell_moments / psamd_download_level_moments is unchanged.  A far body's term is a listed body's: fp32
+ * differences, unfused r.r, + eps2, the hardware reciprocal square root, one multiply by M (the same on FAST_MATH
+ * contexts).  Association: within a level the cells go in level index order by blocks of 64 consecutive indices (the flat
+ * method is one level; the last block may be ragged); the terms of a block's members are ONE fp32 chain in index order
+ * started at +0, whose sum is carried into the fp64 accumulator; blocks in block order, levels top down, all behind the
+ * stencil's chains: stencil, level L, ..., level 0.  There is no 16-part split for the potential, so a pyramid context with
+ * G <= 4 gives the flat context's phi bit for bit, and a cloud inside a 2x2x2 block of cells gives the cutoff context's phi,
+ * U and record byte for byte.  A kid gets the field at its own position over its cell's set.  A cell whose moments are not
+ * numbers makes phi non-finite for those who take it (they count in `nonfinite`), as it does their force.  phi = (float)(-sum);
+ * U, the extrema and the counts as above.  The call still allocates nothing, waits for nothing, reads nothing back and may
+ * be captured; it disturbs neither the force records nor the step.  With at most one adult per cell the monopoles are exact
+ * and phi is the all-pairs phi up to association.
+ * Accuracy of the far phi (an fp64 model of the method against an fp64 direct sum over all bodies, 8192 bodies, uniform and
+ * clustered, on 8^3 and 10^3 cells; tests/test_far_potential_cpu.py): the median particle's far phi is off by
+ * 0.009-0.011 % flat and 0.02-0.11 % as a pyramid, the worst of 400 sampled by 0.04-0.07 % and 0.11-0.52 %; the stencil-only phi
+ * leaves out 78-91 % for the median particle.
+ * The device follows the model to 1e-5 relative (tests/test_gpu_far_potential.py).
+ * Cost on an MI355X at N = 2^20 on 16^3 cells (profiles/far_potential_cost.txt): on one built frame, host clock around the call
+ * + psamd_synchronize with the stream idle before it: 3.90 ms flat and 2.66 ms as a pyramid, beside 2.35 ms of psamd_potential
+ * on a cutoff context of the same cloud and 3.78, 3.57 and 1.97 ms of the three contexts' pair stage.  The flat form walks 4069 far
+ * bodies a (cell, slice) wave behind 27 lists of 256: 1.7 times the cutoff potential, nowhere near an all-pairs potential.
+ *
+ * PSAMD_ERR_INVALID_ARG: a NULL context or spec, flags with an unknown bit (PSAMD_POTENTIAL_FAR is one on a context with
+ * neither far flag) or reserved not 0, capacity < 0, phi not 4-byte aligned, phi NULL with capacity > 0, result_dev not
+ * 8-byte aligned.
  *
  * psamd_potential_result_get: the last call's record, into host memory; waits for the context's stream.
  * psamd_download_potential: the same pass into host memory (phi: `capacity` floats or NULL with capacity 0; out may be
  * NULL); only the min(count, capacity) entries cross PCIe and are written, count being the live count that
  * psamd_download_live reports at the same point (with no fields and capacity 0 it costs two small launches).  Waits for
- * the context's stream. */
+ * the context's stream.
+ * psamd_download_potential_far: the host form of a PSAMD_POTENTIAL_FAR call, otherwise psamd_download_potential; on a
+ * context with neither far flag PSAMD_ERR_UNSUPPORTED. */
 int psamd_potential(psamd_ctx *ctx, const psamd_potential_spec *spec);
 int psamd_potential_result_get(psamd_ctx *ctx, psamd_potential_result *out);
 int psamd_download_potential(psamd_ctx *ctx, float *phi, int64_t capacity, psamd_potential_result *out);
+int psamd_download_potential_far(psamd_ctx *ctx, float *phi, int64_t capacity, psamd_potential_result *out);
 
 /* ---- the field at chosen points ------------------------------------------------ */
 /* psamd_probe: the acceleration and the potential of the frame's field at points of the caller's choosing -- under a
@@ -709,6 +752,20 @@ int psamd_download_potential(psamd_ctx *ctx, float *phi, int64_t capacity, psamd
  * particle): equality with the force record is promised for cutoff contexts only.  With empty far cells the result is
  * the cutoff result bit for bit.  With world > 1 the call returns PSAMD_ERR_UNSUPPORTED; the context stays usable.
  *
+ * Far-monopole contexts (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID; world == 1).  Without PSAMD_PROBE_FAR the call
+ * returns PSAMD_ERR_UNSUPPORTED.  With it (beside ACC and / or PHI; alone it is PSAMD_ERR_INVALID_ARG) a served probe in cell
+ * c sees the stencil of c as above and then the far bodies the force pass enters for c, from moments the call forms itself
+ * (psamd_potential's far form, "energy" above).  phi: that far form's terms and association.  Acceleration: the force
+ * pass's association exactly -- every far body through the context's own pair form, chains per block of 64 from +0; flat:
+ * the block sums into the 16 parts by PSAMD_FLAG_FAR_MONOPOLE's rule, a = (((stencil + part 0) + ...) + part 15); pyramid: a
+ * level's sum is its block chains added in block order to +0, a = ((stencil + level L) + ...) + level 0.  Consequence: on an
+ * exact-path far context a PSAMD_PROBE_ACC | PSAMD_PROBE_FAR probe at the position of an adult the force pass serves returns
+ * that particle's force record BIT FOR BIT; a PHI probe at a listed kid's true position returns that kid's far phi bit for
+ * bit.  Outcomes, the NaN words, the determinism promise and count_dev are unchanged.
+ * Cost (profiles/far_potential_cost.txt): 65 536 far probes, ACC | PHI, at N = 2^20 (same protocol as the far potential): on
+ * particles' own positions 7.96 ms flat and 5.46 ms as a pyramid beside 4.69 ms of plain probes on a cutoff context; on a regular
+ * grid 4.66 and 3.24 ms beside 2.76 ms.
+ *
  * Determinism.  A probe's four words depend on its position and the frame alone: not on the other probes, their order,
  * max_count, graphs, or whether a slab or one context serves it.
  *
@@ -726,7 +783,8 @@ int psamd_download_potential(psamd_ctx *ctx, float *phi, int64_t capacity, psamd
  * positions, 0.89 ms for as many on a regular grid, beside 0.48 ms of psamd_potential and 0.39 ms of the force pass on
  * the same frames.  The cost follows the (wave, distinct cell) walks: 16 probes to a cell use a quarter of the lanes.
  *
- * PSAMD_ERR_INVALID_ARG: a NULL context or spec, fields 0 or with unknown bits, reserved != 0, max_count outside
+ * PSAMD_ERR_INVALID_ARG: a NULL context or spec, fields without ACC and PHI or with unknown bits (PSAMD_PROBE_FAR is one
+ * on a context with neither far flag), reserved != 0, max_count outside
  * [0, 2^31), pos4 or out4 NULL with max_count > 0 or not 16-byte aligned, outcome_dev not 4-byte aligned, count_dev or
  * result_dev not 8-byte aligned.  max_count == 0 writes a zero result and launches nothing else.
  *
@@ -770,8 +828,10 @@ int psamd_probe_result_get(psamd_ctx *ctx, psamd_probe_result *out);
  *
  * Refusals.  psamd_create: with PSAMD_FLAG_ALL_PAIRS PSAMD_ERR_INVALID_ARG; with world > 1, with a softening length outside
  * the lean range, or without the two-pass pair stage (collision radius not small against the cell) PSAMD_ERR_UNSUPPORTED.
- * psamd_potential, psamd_download_potential and psamd_probe return PSAMD_ERR_UNSUPPORTED on such a context, which stays
- * usable: they promise exactly the bodies the force pass walks, and their monopole form is not built.  The flag combines
+ * psamd_potential, psamd_download_potential and psamd_probe without PSAMD_POTENTIAL_FAR / PSAMD_PROBE_FAR return
+ * PSAMD_ERR_UNSUPPORTED on such a context, which stays usable: they promise exactly the stencil's bodies, and that is not this
+ * context's field.  With the bit (psamd_download_potential_far for the host form) they serve the stencil and then every cell
+ * beyond it as one body, formed from the frame's snapshot by the call itself ("energy", "the field at chosen points").  The flag combines
  * freely with FAST_MATH, EULER, EXPLOSIONS, drag, force_sign, graphs, run-ahead and snapshot save / restore.
  *
  * Cost on an MI355X at N = 2^20, default constants (profiles/far_monopole_cost.txt): a step takes 6.43 ms with the flag, 2.17 ms without it (the cutoff step) and 285.9 ms with PSAMD_FLAG_ALL_PAIRS: 2.96 times the cutoff step, 44 times faster than all-pairs;
@@ -824,8 +884,9 @@ int psamd_download_cell_moments(psamd_ctx *ctx, void *out_float4);
  *
  * Refusals mirror PSAMD_FLAG_FAR_MONOPOLE's.  psamd_create: with PSAMD_FLAG_ALL_PAIRS or PSAMD_FLAG_FAR_MONOPOLE
  * PSAMD_ERR_INVALID_ARG; with world > 1, a softening length outside the lean range, or without the two-pass pair stage
- * PSAMD_ERR_UNSUPPORTED.  psamd_potential, psamd_download_potential and psamd_probe return PSAMD_ERR_UNSUPPORTED on such a
- * context, which stays usable.  The flag combines freely with FAST_MATH, EULER, EXPLOSIONS, drag, force_sign, graphs,
+ * PSAMD_ERR_UNSUPPORTED.  psamd_potential, psamd_download_potential and psamd_probe without PSAMD_POTENTIAL_FAR /
+ * PSAMD_PROBE_FAR return PSAMD_ERR_UNSUPPORTED on such a context, which stays usable; with the bit they serve the stencil and
+ * then the interaction set above, levels L down to 0, from moments the call forms itself.  The flag combines freely with FAST_MATH, EULER, EXPLOSIONS, drag, force_sign, graphs,
  * run-ahead and snapshot save / restore.
  *
  * Cost on an MI355X, default constants (profiles/far_pyramid_cost.txt): at N = 2^20 (16^3 cells) a step takes 6.19 ms with the flag, 6.43 ms with

@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256, BALANCED_WAVES) void k_far_monopole(DevParams 
 // with lean arithmetic and only with world == 1); now the cells' moments, every cell beyond the stencil as one body, the sum.
 void launch_far_monopole(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound)
 {
-    k_cell_moments<<<(P.num_cells + 3) / 4, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.cell_mom, d.cell_mom_j, d.mom_cap, nullptr);
+    launch_far_moments(st, P, d);
     FarCells far;
     far.part_acc = d.part_acc; far.part_plane = (unsigned long long)d.part_tasks * 64;
     const int64_t dense_bound = far_dense_bound(P, d, live_bound);
@@ -197,6 +197,20 @@ __global__ __launch_bounds__(256) void k_level_moments(const FarLevels lev, int 
     mom[2 * cap + o] = none ? 0.f : (float)(Sz / S);
     mom[3 * cap + o] = none ? 0.f : (float)S;
     mom_j[o] = (k3 << 20) | (k1 << 10) | k2;
+}
+
+// The moments of the frame's snapshot, of the cells (far monopoles) or of every level (the pyramid, which keeps the fp64
+// sums): the pair stage forms them here, and so do psamd_potential and psamd_probe in their far form, whose window opens
+// before the pair stage has run -- the same kernels on the same snapshot, the same bits in the same buffers.
+void launch_far_moments(hipStream_t st, const DevParams &P, const DeviceState &d)
+{
+    const bool pyramid = (P.flags & PSAMD_FLAG_FAR_PYRAMID) != 0;
+    k_cell_moments<<<(P.num_cells + 3) / 4, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.cell_mom, d.cell_mom_j, d.mom_cap,
+                                                          pyramid ? d.lev_sum : nullptr);
+    if (!pyramid) return;
+    const FarLevels &lev = d.lev;
+    for (int l = 1; l < lev.n; l++)
+        k_level_moments<<<(lev.G[l] * lev.G[l] * lev.G[l] + 255) / 256, 256, 0, st>>>(lev, l, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap);
 }
 
 // (6 waves a SIMD, not k_far_monopole's 7: the second compare per body costs registers -- at 7 the compiler's report shows 68
@@ -326,9 +340,7 @@ __global__ void k_pyramid_combine(DevParams P, const int *__restrict__ act_start
 void launch_far_pyramid(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound)
 {
     const FarLevels &lev = d.lev;
-    k_cell_moments<<<(P.num_cells + 3) / 4, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.cell_mom, d.cell_mom_j, d.mom_cap, d.lev_sum);
-    for (int l = 1; l < lev.n; l++)
-        k_level_moments<<<(lev.G[l] * lev.G[l] * lev.G[l] + 255) / 256, 256, 0, st>>>(lev, l, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap);
+    launch_far_moments(st, P, d);
     FarCells far;
     far.part_acc = d.part_acc; far.part_plane = (unsigned long long)d.part_tasks * 64;
     const int64_t dense_bound = far_dense_bound(P, d, live_bound);

@@ -248,6 +248,9 @@ void launch_allpairs_far(hipStream_t st, const DevParams &P, const DeviceState &
 int64_t far_dense_bound(const DevParams &P, const DeviceState &d, int64_t live_bound);
 void launch_dense_order(hipStream_t st, const DevParams &P, const DeviceState &d);
 void launch_far_combine(hipStream_t st, const DevParams &P, const DeviceState &d, const FarCells &far, int64_t dense_bound);
+// the moments of a far-monopole context's frame, of the cells or of every level of the pyramid (farfield.hip): the pair
+// stage's, and the far forms of psamd_potential and psamd_probe, which may run before it
+void launch_far_moments(hipStream_t st, const DevParams &P, const DeviceState &d);
 // the far monopoles (farfield.hip): the cells' moments, then every cell beyond a particle's stencil as one body, and the sum
 void launch_far_monopole(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound);
 // the pyramid of monopoles (farfield.hip): the moments of every level, then per level the cells under the neighbours of a
@@ -284,9 +287,10 @@ hipError_t launch_export_live(hipStream_t st, const DevParams &P, const DeviceSt
                               int64_t capacity, int64_t *count_out, psamd_live_stats *stats_out);
 
 // psamd_potential: phi of every particle in the own cells' lists (k_pot_pairs), U and the extrema in a fixed tree, phi of the
-// first `capacity` live particles in slot order (phi null or capacity 0: the result alone); result_dev may be null
+// first `capacity` live particles in slot order (phi null or capacity 0: the result alone); result_dev may be null.
+// far_set (PSAMD_POTENTIAL_FAR, far-monopole contexts only): the moments first, then the cell's far set behind the stencil
 hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceState &d, float *phi, int64_t capacity,
-                            psamd_potential_result *result_dev);
+                            psamd_potential_result *result_dev, bool far_set);
 
 // psamd_probe (max_count > 0): locate + count, the cells' prefix, the cell-major order, the pair pass (one probe to a lane), the
 // result record

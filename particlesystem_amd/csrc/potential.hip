@@ -9,7 +9,8 @@
 // in three launches that nothing in between has to wait for:
 //   k_pot_pairs   one wave per (own cell, 64-particle slice), one lane per particle: the 27-cell stencil in the
 //                 reference's order, the bodies as wave-uniform (scalar) loads of the four planes, eight to a group in
-//                 pair_math.hpp's packed forms; all-pairs contexts go on over every other cell in global order.  The
+//                 pair_math.hpp's packed forms; all-pairs contexts go on over every other cell in global order, far-
+//                 monopole contexts asked with PSAMD_POTENTIAL_FAR over the cell's far set (pot_walk.hpp).  The
 //                 lane's own entry is left out BY SORTED INDEX: two particles at one point see each other.
 //                 phi by sorted index.
 //   k_pot_reduce  per tile of POT_TILE sorted entries: phi scattered to slot order through sorted_id; U, the extrema and
@@ -24,6 +25,14 @@
 // nothing but the cell order and the cells' list lengths: the same bits from run to run, with graphs or without, on one
 // context and on the slab that holds the particle.  Against an fp64 direct sum: 1.5e-7 relative for phi, 1e-8 for U
 // (tests/test_gpu_potential.py prints the largest error of every case).
+//
+// PSAMD_POTENTIAL_FAR (far-monopole contexts): the moments are formed first, by the pair stage's own kernels from the
+// same snapshot (launch_far_moments: the same bits in the same buffers, whether the pair stage has run or not); behind
+// the stencil's chains come the levels top down, of each level the blocks of 64 cells in index order, a block's members
+// one chain from +0.  The set is a function of the wave's one cell: members and masks are scalar.
+//
+// VGPRs / waves per SIMD of k_pot_pairs as the compiler reports them for gfx950, no instance with scratch:
+//   cutoff 40 / 8      all-pairs 44 / 8      far monopoles 42 / 8
 #include "pot_walk.hpp"
 #include "slot_walk.hpp"
 
@@ -35,13 +44,13 @@ static_assert(POT_ITEMS == SLOT_ITEMS, "a wave walks POT_ITEMS batches of 64 sor
 
 __device__ __forceinline__ bool pot_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
-template <bool ALLP>
+template <int FAR>      // 0: the stencil alone; 1: all-pairs; 2: far monopoles, flat or as a pyramid
 __global__ __launch_bounds__(POT_THREADS) void k_pot_pairs(DevParams P, const int *__restrict__ cell_start,
                                                            const float *__restrict__ snap_soa,
                                                            const float *__restrict__ snap_age,
                                                            const int *__restrict__ sorted_id,
                                                            const float4 *__restrict__ pos4, const PotFar far,
-                                                           float *__restrict__ phi_sorted)
+                                                           const PotMono mono, float *__restrict__ phi_sorted)
 {
     // (cell, slice) tasks of every own cell, cell-major; four independent waves per workgroup, an XCD's workgroups a
     // contiguous run of cells (force.hip, k_pairs).  Slices past a cell's count end at once.
@@ -85,7 +94,8 @@ __global__ __launch_bounds__(POT_THREADS) void k_pot_pairs(DevParams P, const in
         const float *sx = snap_soa + nb;
         pot_walk<false>(ctx, sx, sx + cap, sx + 2 * cap, sx + 3 * cap, n, 0, eps2f, true, acc);
     }
-    if (ALLP) {
+    if (FAR == 2) pot_far_walk(ctx, mono, i1, i2, i3, lane, eps2f, acc);      // (world == 1: local cell == global cell)
+    if (FAR == 1) {
         // every other cell of the box in global index order, 64 cell ranges to a vector load (allpairs.hip); the wave's
         // particles share one cell, so the cells of its stencil are left out for the whole wave
         const size_t plane = (size_t)far.plane;
@@ -248,7 +258,7 @@ __global__ __launch_bounds__(POT_THREADS) void k_pot_finish(DevParams P, int nti
 }
 
 hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceState &d, float *phi, int64_t capacity,
-                            psamd_potential_result *result_dev)
+                            psamd_potential_result *result_dev, bool far_set)
 {
     const int ntiles = slot_tiles(P.slots_total);
     const bool want_phi = phi && capacity > 0 && ntiles > 0;
@@ -256,15 +266,19 @@ hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceStat
     if (want_phi) { const hipError_t e = launch_fill_int(st, reinterpret_cast<int *>(d.pot_slot), 0x7fc00000, (size_t)P.slots_total); if (e != hipSuccess) return e; }
     const int ntask = P.n_own_cells * P.slices;
     if (ntask > 0) {
-        if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
+        if (far_set) {
+            launch_far_moments(st, P, d);
+            PS_LAUNCH_CHECK();
+            k_pot_pairs<2><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, PotFar{}, pot_mono(P, d), d.pot_sorted);
+        } else if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
             // the own snapshot (cells by local == global index) or the gathered one with its index by global cell
             const bool gathered = P.world > 1;
             const PotFar far{gathered ? reinterpret_cast<const float *>(d.allg_in) : d.snap_soa, gathered ? d.gstart : d.cell_start,
                              gathered ? d.gn : nullptr, gathered ? (unsigned long long)P.allg_cap : (unsigned long long)P.sorted_cap,
                              gathered ? 0 : 1};
-            k_pot_pairs<true><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, far, d.pot_sorted);
+            k_pot_pairs<1><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, far, PotMono{}, d.pot_sorted);
         } else
-            k_pot_pairs<false><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, PotFar{}, d.pot_sorted);
+            k_pot_pairs<0><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, PotFar{}, PotMono{}, d.pot_sorted);
         PS_LAUNCH_CHECK();
     }
     if (ntiles > 0) {

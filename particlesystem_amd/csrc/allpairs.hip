@@ -155,15 +155,18 @@ __global__ __launch_bounds__(256, BALANCED_WAVES) void k_allp_far(DevParams P, c
 
 // All-pairs: a particle's acceleration = (((stencil chain + part 0) + part 1) + ...) + part 15, the same
 // association on one GPU and on any number of ranks.  One thread per particle that needs a force, in the dense order.
+// NPARTS: the parts that were written, ALLP_PARTS of them unrolled, or 0: nparts of them (the pyramid's levels).
+template <int NPARTS>
 __global__ void k_allpairs_combine(DevParams P, const int *__restrict__ act_start, const int *__restrict__ dense_gi,
-                                   const int *__restrict__ dense_cell, const FarCells far, const ForceBuf force4)
+                                   const int *__restrict__ dense_cell, const FarCells far, int nparts, const ForceBuf force4)
 {
+    if (NPARTS) nparts = NPARTS;
     const int n = min(act_start[comp_count(P)], (int)far.part_plane);
     for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
         const int gi = dense_gi[r], lc = dense_cell[r];
         float4 a = force4.get(P, lc, gi);                   // (flag 0, not a kid: it is on the active list)
 #pragma unroll
-        for (int p = 0; p < ALLP_PARTS; p++) {
+        for (int p = 0; p < nparts; p++) {
             const float4 b = far.part_acc[(size_t)p * far.part_plane + (size_t)r];
             a.x += b.x; a.y += b.y; a.z += b.z;
         }
@@ -172,7 +175,7 @@ __global__ void k_allpairs_combine(DevParams P, const int *__restrict__ act_star
 }
 
 // The dense order of the pass (k_allp_prefix, k_allp_dense) and the sum of the parts (k_allpairs_combine) serve every far
-// field that goes by (dense task, part) waves: the all-pairs one below and the monopoles' (farfield.hip).
+// field that goes by (dense task, part) waves: the all-pairs one below and the monopoles' (farfield.hip), flat or as a pyramid.
 // dense tasks: at most the particles alive (the host's bound; a slab also computes its neighbour's lent layers:
 // every entry of the sorted order).  The kernels go by the device's own count.
 int64_t far_dense_bound(const DevParams &P, const DeviceState &d, int64_t live_bound)
@@ -186,9 +189,11 @@ void launch_dense_order(hipStream_t st, const DevParams &P, const DeviceState &d
     k_allp_dense<<<(comp_count(P) + 3) / 4, 256, 0, st>>>(P, d.cell_start, d.active_list, d.active_count, d.act_start, d.dense_gi, d.dense_cell);
 }
 
-void launch_far_combine(hipStream_t st, const DevParams &P, const DeviceState &d, const FarCells &far, int64_t dense_bound)
+void launch_far_combine(hipStream_t st, const DevParams &P, const DeviceState &d, const FarCells &far, int nparts, int64_t dense_bound)
 {
-    k_allpairs_combine<<<(unsigned)((dense_bound * 64 + 255) / 256), 256, 0, st>>>(P, d.act_start, d.dense_gi, d.dense_cell, far, force_buf(d));
+    const unsigned wgs = (unsigned)((dense_bound * 64 + 255) / 256);
+    if (nparts == ALLP_PARTS) k_allpairs_combine<ALLP_PARTS><<<wgs, 256, 0, st>>>(P, d.act_start, d.dense_gi, d.dense_cell, far, nparts, force_buf(d));
+    else k_allpairs_combine<0><<<wgs, 256, 0, st>>>(P, d.act_start, d.dense_gi, d.dense_cell, far, nparts, force_buf(d));
 }
 
 // What ran before is the stencil's chain (the two-pass pair stage: all-pairs contexts are created only with it, and only
@@ -209,7 +214,7 @@ void launch_allpairs_far(hipStream_t st, const DevParams &P, const DeviceState &
     const unsigned far_wgs = (unsigned)((dense_bound * ALLP_PARTS + 3) / 4);
     if (fast) k_allp_far<2, 8><<<far_wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, far_buf, far_start, far_n);
     else k_allp_far<1, 8><<<far_wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, far_buf, far_start, far_n);
-    launch_far_combine(st, P, d, far, dense_bound);
+    launch_far_combine(st, P, d, far, ALLP_PARTS, dense_bound);
 }
 
 }  // namespace psamd

@@ -191,17 +191,17 @@ static int derive_params(psamd_ctx *c, const psamd_config *cfg)
     if (P.key_bits > 63) return fail(c, PSAMD_ERR_UNSUPPORTED, "queue-op key does not fit 64 bits for this configuration");
     if ((cfg->flags & PSAMD_FLAG_ALL_PAIRS) && !P.lean_math) return fail(c, PSAMD_ERR_UNSUPPORTED, "all-pairs forces are built for the lean pair arithmetic only (EPS2 in its validated range)");
     if ((cfg->flags & PSAMD_FLAG_ALL_PAIRS) && !P.two_pass) return fail(c, PSAMD_ERR_UNSUPPORTED, "all-pairs forces need the two-pass pair stage (collision radius small against the cell)");
-    if (cfg->flags & PSAMD_FLAG_FAR_MONOPOLE) {
-        if (cfg->flags & PSAMD_FLAG_ALL_PAIRS) return fail(c, PSAMD_ERR_INVALID_ARG, "far monopoles and all-pairs forces are two force models: choose one");
-        if (cfg->world > 1) return fail(c, PSAMD_ERR_UNSUPPORTED, "far monopoles are served on one context only (world == 1)");
-        if (!P.lean_math) return fail(c, PSAMD_ERR_UNSUPPORTED, "far monopoles are built for the lean pair arithmetic only (EPS2 in its validated range)");
-        if (!P.two_pass) return fail(c, PSAMD_ERR_UNSUPPORTED, "far monopoles need the two-pass pair stage (collision radius small against the cell)");
-    }
-    if (cfg->flags & PSAMD_FLAG_FAR_PYRAMID) {
-        if (cfg->flags & (PSAMD_FLAG_ALL_PAIRS | PSAMD_FLAG_FAR_MONOPOLE)) return fail(c, PSAMD_ERR_INVALID_ARG, "the pyramid of monopoles, far monopoles and all-pairs forces are three force models: choose one");
-        if (cfg->world > 1) return fail(c, PSAMD_ERR_UNSUPPORTED, "the pyramid of monopoles is served on one context only (world == 1)");
-        if (!P.lean_math) return fail(c, PSAMD_ERR_UNSUPPORTED, "the pyramid of monopoles is built for the lean pair arithmetic only (EPS2 in its validated range)");
-        if (!P.two_pass) return fail(c, PSAMD_ERR_UNSUPPORTED, "the pyramid of monopoles needs the two-pass pair stage (collision radius small against the cell)");
+    if (cfg->flags & (PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID)) {
+        // (both flags: what the flat method refuses comes first, then the choice between the two)
+        const bool mono = (cfg->flags & PSAMD_FLAG_FAR_MONOPOLE) != 0, pyr = (cfg->flags & PSAMD_FLAG_FAR_PYRAMID) != 0;
+        const std::string who = mono ? "far monopoles" : "the pyramid of monopoles", is = mono ? " are " : " is ";
+        const char *two = "far monopoles and all-pairs forces are two force models: choose one";
+        const char *three = "the pyramid of monopoles, far monopoles and all-pairs forces are three force models: choose one";
+        if (cfg->flags & PSAMD_FLAG_ALL_PAIRS) return fail(c, PSAMD_ERR_INVALID_ARG, mono ? two : three);
+        if (cfg->world > 1) return fail(c, PSAMD_ERR_UNSUPPORTED, who + is + "served on one context only (world == 1)");
+        if (!P.lean_math) return fail(c, PSAMD_ERR_UNSUPPORTED, who + is + "built for the lean pair arithmetic only (EPS2 in its validated range)");
+        if (!P.two_pass) return fail(c, PSAMD_ERR_UNSUPPORTED, who + (mono ? " need" : " needs") + " the two-pass pair stage (collision radius small against the cell)");
+        if (mono && pyr) return fail(c, PSAMD_ERR_INVALID_ARG, three);
     }
     for (int k = 0; k < 5; k++) { c->S.seg_base[k] = g.seg_base[k]; c->S.info_base[k] = g.info_base[k]; }
     for (int k = 0; k < 4; k++) c->S.seg_size_t[k] = g.seg_size_t[k];
@@ -212,6 +212,19 @@ static int derive_params(psamd_ctx *c, const psamd_config *cfg)
 
 // room of a neighbour transfer message, in records: the most a step can ask for (also sizes the op and move lists)
 static size_t xfer_room(const DevParams &P) { return (size_t)P.xfer_cap_max + (size_t)P.xfer2_cap + (size_t)P.far_cap * (size_t)std::max(1, P.world) / 2 + 1; }
+
+// What a far pass by (dense task, part) waves needs, the all-pairs one and the monopoles': the partial sums -- one float4 per
+// (part, particle that needs a force), dense, 64 to a task; every entry of the sorted order could be one -- and the dense order.
+static int alloc_dense_parts(psamd_ctx *c, size_t SC, size_t LC)
+{
+    DeviceState &d = c->d;
+    d.part_tasks = (int)(SC / 64 + 1);
+    PS_HIP(c, dev_alloc(c, &d.part_acc, (size_t)ALLP_PARTS * d.part_tasks * 64));
+    PS_HIP(c, dev_alloc(c, &d.act_start, LC + 1));
+    PS_HIP(c, dev_alloc(c, &d.dense_gi, SC));
+    PS_HIP(c, dev_alloc(c, &d.dense_cell, SC));
+    return PSAMD_OK;
+}
 
 // The step's device arrays.  The SEQUENCE of the HIP calls here is load-bearing, the copies and fills between the
 // allocations included (the runtime allocates on their first use): with the three fills and the chunk_segs copy moved
@@ -269,15 +282,7 @@ static int alloc_step_arrays(psamd_ctx *c)
     PS_HIP(c, dev_alloc(c, &d.snap_age, SC));
     PS_HIP(c, dev_alloc(c, &d.force4, SC));
     PS_HIP(c, dev_alloc(c, &d.celltab, (size_t)g.num_cells));
-    if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
-        // partial sums of the all-pairs far pass: one float4 per (part, particle that needs a force) -- dense, 64 to a task;
-        // every entry of the sorted order could be one
-        d.part_tasks = (int)(SC / 64 + 1);
-        PS_HIP(c, dev_alloc(c, &d.part_acc, (size_t)ALLP_PARTS * d.part_tasks * 64));
-        PS_HIP(c, dev_alloc(c, &d.act_start, LC + 1));
-        PS_HIP(c, dev_alloc(c, &d.dense_gi, SC));
-        PS_HIP(c, dev_alloc(c, &d.dense_cell, SC));
-    }
+    if (P.flags & PSAMD_FLAG_ALL_PAIRS) PS_TRY(alloc_dense_parts(c, SC, LC));
     PS_HIP(c, dev_alloc(c, &d.chunk_skip, C));               // the chunk lists' capacity rule (chunk_cap_block)
     PS_HIP(c, dev_alloc(c, &d.chunk_segs, (size_t)g.num_chunks * 27));
     {
@@ -338,40 +343,23 @@ static int alloc_step_arrays(psamd_ctx *c)
     PS_HIP(c, dev_alloc(c, &d.pack_stage, LC + 64));
     PS_HIP(c, dev_alloc(c, &d.pack_count, LC / 64 + 1));
     PS_HIP(c, dev_alloc(c, &d.pack_base, LC / 64 + 1));
-    if (P.flags & PSAMD_FLAG_FAR_MONOPOLE) {
-        // far monopoles, behind everything a context without the flag allocates: the partial sums and the dense order
-        // of the all-pairs far pass (sized as there), and the cells' moments -- four planes and the packed coordinates,
-        // padded to whole blocks of 64 cells; the padding stays zero (k_cell_moments writes the cells of the box)
-        d.part_tasks = (int)(SC / 64 + 1);
-        PS_HIP(c, dev_alloc(c, &d.part_acc, (size_t)ALLP_PARTS * d.part_tasks * 64));
-        PS_HIP(c, dev_alloc(c, &d.act_start, LC + 1));
-        PS_HIP(c, dev_alloc(c, &d.dense_gi, SC));
-        PS_HIP(c, dev_alloc(c, &d.dense_cell, SC));
-        d.mom_cap = (g.num_cells + 63) / 64 * 64;
-        PS_HIP(c, dev_alloc(c, &d.cell_mom, 4 * (size_t)d.mom_cap + 64));     // + slack: scalar loads fetch whole groups
-        PS_HIP(c, dev_alloc(c, &d.cell_mom_j, (size_t)d.mom_cap));
-        PS_HIP(c, hipMemsetAsync(d.cell_mom, 0, (4 * (size_t)d.mom_cap + 64) * sizeof(float), c->stream));
-        PS_HIP(c, hipMemsetAsync(d.cell_mom_j, 0, (size_t)d.mom_cap * sizeof(int), c->stream));
-    }
-    if (P.flags & PSAMD_FLAG_FAR_PYRAMID) {
-        // the pyramid, likewise behind everything else and under its flag only: the same partial sums (a level is a part: at
-        // most FAR_MAX_LEVELS of the ALLP_PARTS planes are used) and dense order; the moment planes hold every level, each
-        // padded with zeros to whole blocks of 64 cells (the kernels write the cells of a level, never its padding), and
+    if (P.flags & (PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID)) {
+        // the far field of monopoles, behind everything a context without the flags allocates: the partial sums and the dense
+        // order (a pyramid's level is a part: at most FAR_MAX_LEVELS of the ALLP_PARTS planes are used), and the moments --
+        // four planes and the packed coordinates of every level (flat: the cell grid alone), each level padded to whole
+        // blocks of 64 cells; the padding stays zero (the kernels write the cells of a level); under the pyramid's flag only,
         // the fp64 sums the levels are added up from
-        d.lev = far_levels_of(g.G);
+        const bool pyramid = (P.flags & PSAMD_FLAG_FAR_PYRAMID) != 0;
+        d.lev = pyramid ? far_levels_of(g.G) : far_one_level(g.G);
         static_assert(FAR_MAX_LEVELS <= ALLP_PARTS, "a level's sum goes into one of the partial-sum planes");
-        d.part_tasks = (int)(SC / 64 + 1);
-        PS_HIP(c, dev_alloc(c, &d.part_acc, (size_t)ALLP_PARTS * d.part_tasks * 64));
-        PS_HIP(c, dev_alloc(c, &d.act_start, LC + 1));
-        PS_HIP(c, dev_alloc(c, &d.dense_gi, SC));
-        PS_HIP(c, dev_alloc(c, &d.dense_cell, SC));
+        PS_TRY(alloc_dense_parts(c, SC, LC));
         d.mom_cap = d.lev.off[d.lev.n];
         PS_HIP(c, dev_alloc(c, &d.cell_mom, 4 * (size_t)d.mom_cap + 64));     // + slack: scalar loads fetch whole groups
         PS_HIP(c, dev_alloc(c, &d.cell_mom_j, (size_t)d.mom_cap));
-        PS_HIP(c, dev_alloc(c, &d.lev_sum, 4 * (size_t)d.mom_cap));
+        if (pyramid) PS_HIP(c, dev_alloc(c, &d.lev_sum, 4 * (size_t)d.mom_cap));
         PS_HIP(c, hipMemsetAsync(d.cell_mom, 0, (4 * (size_t)d.mom_cap + 64) * sizeof(float), c->stream));
         PS_HIP(c, hipMemsetAsync(d.cell_mom_j, 0, (size_t)d.mom_cap * sizeof(int), c->stream));
-        PS_HIP(c, hipMemsetAsync(d.lev_sum, 0, 4 * (size_t)d.mom_cap * sizeof(double), c->stream));
+        if (pyramid) PS_HIP(c, hipMemsetAsync(d.lev_sum, 0, 4 * (size_t)d.mom_cap * sizeof(double), c->stream));
     }
     return PSAMD_OK;
 }

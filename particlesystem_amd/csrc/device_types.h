@@ -123,6 +123,13 @@ inline FarLevels far_levels_of(int G)
     }
     return v;
 }
+// the flat method (PSAMD_FLAG_FAR_MONOPOLE): the cell grid alone
+inline FarLevels far_one_level(int G)
+{
+    FarLevels v;
+    v.n = 1; v.G[0] = G; v.off[1] = (G * G * G + 63) / 64 * 64;
+    return v;
+}
 
 // Which cells / slots / records a rank holds.  All device code goes through these.
 #if defined(__HIPCC__)

@@ -1,0 +1,148 @@
+// far_walk.hpp -- what every walk over a far-field context's moments shares (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID):
+// where the moments are, a level's place and size, the cells of a level that concern a range of grid cells, and the force
+// pass's chain over one block of 64 level cells.  The force pass (farfield.hip, k_far_walk), psamd_potential's far form
+// (potential.hip, k_pot_pairs<2>) and psamd_probe's (probe.hip, k_probe_pairs<.., 2>) are written on these; device-inline only.
+//
+// The flat method is a pyramid of one level: its set is the top level's rule at level 0.  Cell i's set is, at the top level
+// L, every cell that holds mass and is not adjacent to i >> L, and at a level l below it every such cell whose parent is
+// adjacent to i's parent and which is not itself adjacent to i >> l (psamd.h, "a pyramid of monopoles").
+#pragma once
+
+#include "pair_math.hpp"
+
+namespace psamd {
+
+// Where a far-field context finds the moments the pair stage's own kernels form (farfield.hip): four planes X, Y, Z, M of
+// mom_cap and the packed coordinates (i3 << 20) | (i1 << 10) | i2, every level padded with zeros to whole blocks of 64.
+// nparts: the partial sums the force pass deals a level's blocks to (16 flat, 1 pyramid) -- the probe's acceleration
+// repeats them.  A level's size and place follow from nlev and G (far_level): a few scalar operations.
+struct FarMoments {
+    const float *mom;
+    const int *mom_j;
+    int mom_cap, nparts;
+    int nlev, G;            // L + 1 and G_0
+};
+
+inline FarMoments far_moments_of(const DevParams &P, const DeviceState &d)
+{
+    return FarMoments{d.cell_mom, d.cell_mom_j, d.mom_cap, (P.flags & PSAMD_FLAG_FAR_PYRAMID) ? 1 : ALLP_PARTS, d.lev.n, P.G};
+}
+
+// Level l (wave-uniform): G_l cells an axis at off .. off + G_l^3 of the planes, nblk blocks of 64 (far_levels_of's rule).
+struct FarLevel {
+    int G, off, nblk;
+    bool top;
+};
+
+__device__ __forceinline__ FarLevel far_level(const FarMoments &m, int l)
+{
+    FarLevel v;
+    v.G = m.G; v.off = 0;
+    for (int k = 0; k < l; k++) { v.off += (v.G * v.G * v.G + 63) / 64 * 64; v.G = (v.G + 1) / 2; }
+    v.nblk = (v.G * v.G * v.G + 63) >> 6;
+    v.top = l == m.nlev - 1;
+    return v;
+}
+
+// A box of cells, of the grid or of a level: lo .. hi on each axis (1 ~ i1, 2 ~ i2, 3 ~ i3).
+struct FarBox {
+    int lo1, hi1, lo2, hi2, lo3, hi3;
+};
+
+// Particles whose grid cells lie in `cells`: the cells of level l any of them may have to leave out or to take -- at the top
+// level the neighbours of their level cells, below it the children of the neighbours of their parents -- clamped to the level.
+__device__ __forceinline__ FarBox far_box(const FarLevel &v, int l, const FarBox &cells)
+{
+    FarBox b;
+    if (v.top) {
+        b.lo1 = (cells.lo1 >> l) - 1; b.lo2 = (cells.lo2 >> l) - 1; b.lo3 = (cells.lo3 >> l) - 1;
+        b.hi1 = (cells.hi1 >> l) + 1; b.hi2 = (cells.hi2 >> l) + 1; b.hi3 = (cells.hi3 >> l) + 1;
+    } else {
+        b.lo1 = 2 * ((cells.lo1 >> (l + 1)) - 1); b.lo2 = 2 * ((cells.lo2 >> (l + 1)) - 1); b.lo3 = 2 * ((cells.lo3 >> (l + 1)) - 1);
+        b.hi1 = 2 * ((cells.hi1 >> (l + 1)) + 1) + 1; b.hi2 = 2 * ((cells.hi2 >> (l + 1)) + 1) + 1; b.hi3 = 2 * ((cells.hi3 >> (l + 1)) + 1) + 1;
+    }
+    b.lo1 = max(b.lo1, 0); b.lo2 = max(b.lo2, 0); b.lo3 = max(b.lo3, 0);
+    b.hi1 = min(b.hi1, v.G - 1); b.hi2 = min(b.hi2, v.G - 1); b.hi3 = min(b.hi3, v.G - 1);
+    return b;
+}
+
+// The blocks [blk_lo, blk_hi) of the level that can hold a member of a set: all of the top level, below it those with a
+// cell of the box (every cell of the box has its index between the box's corners').
+__device__ __forceinline__ void far_blocks(const FarLevel &v, const FarBox &b, int &blk_lo, int &blk_hi)
+{
+    blk_lo = v.top ? 0 : ((b.lo3 * v.G + b.lo1) * v.G + b.lo2) >> 6;
+    blk_hi = v.top ? v.nblk : (((b.hi3 * v.G + b.hi1) * v.G + b.hi2) >> 6) + 1;
+}
+
+// must a particle whose cell of the level is (a1, a2, a3) leave out the level cell with packed coordinates j?  It is adjacent
+// to the particle's own (a finer level or the stencil has its mass) or -- below the top -- its parent is not adjacent to the
+// particle's parent (a coarser level has it).
+__device__ __forceinline__ bool far_leaves_out(bool top, int j, int a1, int a2, int a3)
+{
+    const int J3 = j >> 20, J1 = (j >> 10) & 1023, J2 = j & 1023;
+    const bool adj = abs(J3 - a3) <= 1 && abs(J1 - a1) <= 1 && abs(J2 - a2) <= 1;
+    const bool par = top || (abs((J3 >> 1) - (a3 >> 1)) <= 1 && abs((J1 >> 1) - (a1 >> 1)) <= 1 && abs((J2 >> 1) - (a2 >> 1)) <= 1);
+    return adj || !par;
+}
+
+// Level l as the ONE cell (i1, i2, i3) sees it (potential and probe: all lanes of a wave walk one cell's set): the level, the
+// cell's cell of the level and the blocks that can hold a member.  Wave-uniform: scalar arithmetic.
+struct FarLevelView {
+    FarLevel lev;
+    int a1, a2, a3, blk_lo, blk_hi;
+};
+
+__device__ __forceinline__ FarLevelView far_level_view(const FarMoments &m, int l, int i1, int i2, int i3)
+{
+    FarLevelView v;
+    v.lev = far_level(m, l);
+    v.a1 = i1 >> l; v.a2 = i2 >> l; v.a3 = i3 >> l;
+    far_blocks(v.lev, far_box(v.lev, l, FarBox{i1, i1, i2, i2, i3, i3}), v.blk_lo, v.blk_hi);
+    return v;
+}
+
+// lane = cell of block blk of the level: the members of the cell's set, as a wave-uniform mask.  A member holds mass (M != 0:
+// a moment that is no number counts) and is not left out.
+__device__ __forceinline__ unsigned long long far_members(const FarMoments &m, const FarLevelView &v, int blk, int lane)
+{
+    const int at = v.lev.off + blk * 64 + lane;
+    const bool nz = m.mom[3 * (size_t)m.mom_cap + at] != 0.f;
+    return __ballot(nz && !far_leaves_out(v.lev.top, m.mom_j[at], v.a1, v.a2, v.a3));
+}
+
+// One block of 64 level cells (wave-uniform pointers to its moments: scalar loads) as ONE fp32 chain per component from +0,
+// in index order, through the context's pair form (MATH 1: pairsN_exact_lean, 2: pairsN_fast), eight cells to a call.  A
+// group of eight with no bit in evalm holds nothing any lane evaluates -- eight zeros -- and is skipped; leave(g, qw) zeroes
+// the masses of the group's cells that are not the lane's: such a body adds +-0 to a chain that started at +0, the same bits
+// as skipping it.  This is the force pass's association; the probe's acceleration repeats it with a wave-uniform mask.
+template <int MATH, class Leave>
+__device__ __forceinline__ void far_block_chain(const DevParams &P, const PairCtx &ctx, const float *__restrict__ sx,
+                                                const float *__restrict__ sy, const float *__restrict__ sz,
+                                                const float *__restrict__ sw, unsigned long long evalm, float eps2f,
+                                                Leave leave, float &ax, float &ay, float &az)
+{
+    ax = 0.f; ay = 0.f; az = 0.f;
+    int flag = 0;
+    for (int g = 0; g < 64; g += 8) {
+        if (((evalm >> g) & 0xffull) == 0ull) continue;
+        v2f qx[4], qy[4], qz[4], qw[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            qx[i] = v2f{sx[g + 2 * i], sx[g + 2 * i + 1]};
+            qy[i] = v2f{sy[g + 2 * i], sy[g + 2 * i + 1]};
+            qz[i] = v2f{sz[g + 2 * i], sz[g + 2 * i + 1]};
+            qw[i] = v2f{sw[g + 2 * i], sw[g + 2 * i + 1]};
+        }
+        leave(g, qw);
+        if (MATH == 1) pairsN_exact_lean<8>(P, ctx, qx, qy, qz, qw, 0, nullptr, nullptr, ax, ay, az, flag);
+        else (void)pairsN_fast<8>(ctx, qx, qy, qz, qw, eps2f, ax, ay, az);
+    }
+}
+
+// body k of a group of eight out of the chain: its mass becomes 0
+__device__ __forceinline__ void far_drop(v2f (&qw)[4], int k, bool drop)
+{
+    if (k & 1) qw[k >> 1].y = drop ? 0.f : qw[k >> 1].y; else qw[k >> 1].x = drop ? 0.f : qw[k >> 1].x;
+}
+
+}  // namespace psamd

@@ -1,21 +1,29 @@
-// farfield.hip -- far-field gravity from one monopole per cell (PSAMD_FLAG_FAR_MONOPOLE) or from a pyramid of them
-// (PSAMD_FLAG_FAR_PYRAMID); neither is in the reference
-#include "pair_math.hpp"
+// farfield.hip -- far-field gravity from monopoles: one per cell of the box (PSAMD_FLAG_FAR_MONOPOLE, the flat method) or a
+// pyramid of them (PSAMD_FLAG_FAR_PYRAMID); neither is in the reference.  The moments' kernels, ONE force walk for both
+// methods (k_far_walk) and its launch.
+//
+// A particle's acceleration = the stencil's chain, exactly force.hip's cutoff pass (the reference's order), plus its far set
+// (far_walk.hpp): flat, every other cell of the box as ONE body -- the cell's total w_eff at its centre of mass
+// (k_cell_moments); as a pyramid, farther mass in coarser cells -- level 0 is the cell grid, a level-(l+1) cell sums the fp64
+// sums of its (at most 8) children in index order, and every cell of the box beyond the stencil is under exactly one member
+// of the set.  The flat method's cost grows with the number of cells, G^3 - 27 bodies a particle; the pyramid's with log G.
+//
+// The walk goes by allpairs.hip's dense tasks -- the particles that need a force, in cell order, 64 to a wave whatever their
+// cells -- and (task, part) items, one wave each; part p of the partial sums is
+//   flat      the p-th sixteenth of level 0's blocks of 64 cells (level 0 is the top level: the top level's rule),
+//   pyramid   level L - p, of which a wave walks the blocks that hold a cell of its box,
+// so that k_allpairs_combine's sum in part order is ((stencil + part 0) + part 1) + ..., the pyramid's top level first.
+// Within a part: blocks in index order, a block ONE chain of at most 64 additions from +0 (far_block_chain), the chains'
+// sums added in block order to +0.  All 64 lanes walk the same cells, so the moments are wave-uniform loads, 8 to a call of
+// the context's pair form.  What differs from lane to lane is which cells a lane must leave out (far_leaves_out: the cutoff
+// pass, a finer or a coarser level has their mass): there the lane enters the cell with mass 0, which adds +-0 to a chain
+// that started at +0 -- the same bits as skipping it.  A wave's particles come from a short run of cells, so nearly every
+// group of 8 cells lies outside the box around everything any lane leaves out (far_box) and is walked with no per-lane
+// work at all; the test for that is scalar.  Below the top level nothing outside that box is in any lane's set: such blocks
+// and groups add zeros only and are skipped.  The association depends on nothing but G and the global cell order.
+#include "far_walk.hpp"
 
 namespace psamd {
-
-// ------------------------------------------------------------------ far monopoles (PSAMD_FLAG_FAR_MONOPOLE, not in the reference)
-// A particle's acceleration = the stencil's chain, exactly force.hip's cutoff pass (the reference's order), plus every
-// other cell of the box in GLOBAL index order as ONE body: the cell's total w_eff at its centre of mass (k_cell_moments).
-// The pass goes by allpairs.hip's dense tasks -- the particles that need a force, in cell order, 64 to a wave whatever
-// their cells -- and its 16 parts: a wave (dense task, part) walks the 64-cell blocks of its part; a block's monopoles
-// are ONE chain of at most 64 additions started at +0, the chain's sum is added to the part's, k_allpairs_combine adds
-// the parts to the stencil's chain in part order.  All 64 lanes walk the same cells, so the monopoles are wave-uniform
-// loads, 8 to a call of the context's pair form.  What differs from lane to lane is the 27 cells a lane must leave out
-// (the cutoff pass has their bodies one by one): there the lane enters the cell with mass 0, which adds +-0 to a chain
-// that started at +0 -- the same bits as skipping it.  A wave's particles come from a short run of cells, so nearly every
-// group of 8 cells lies outside the box around all their stencils and is walked with no per-lane work at all; the
-// test for that is scalar.  The association depends on nothing but G and the global cell order.
 
 // a double from another lane (k wave-uniform)
 __device__ __forceinline__ double lane_f64(double v, int k)
@@ -64,115 +72,6 @@ __device__ __forceinline__ int wave_max_i(int v)
     return v;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256, BALANCED_WAVES) void k_far_monopole(DevParams P, const SnapSoa snap4, const int *__restrict__ act_start,
-                                                                            const int *__restrict__ dense_gi, const int *__restrict__ dense_cell,
-                                                                            const FarCells far, const float *__restrict__ mom,
-                                                                            const int *__restrict__ mom_j, int mom_cap)
-{
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int n_act = act_start[comp_count(P)];
-    const int ntask = min((n_act + 63) >> 6, (int)(far.part_plane >> 6));      // (the partial sums' room: never short, see create.hip)
-    const int nitem = ntask * ALLP_PARTS, nwg = (nitem + 3) >> 2;
-    // (the launch is sized from the host's bound of the live count, the items from the device's own count, as in k_allp_far)
-    for (int b = blockIdx.x; b < nwg; b += gridDim.x) {
-    // part-major, as in k_allp_far: an XCD's run of items reads one eighth of the monopoles
-    const int slot = __builtin_amdgcn_readfirstlane(xcd_contiguous(b, nwg) * 4 + wave);
-    if (slot >= nitem) continue;
-    const int part = slot / ntask, T = slot - part * ntask;
-    const int r = T * 64 + lane;
-    const bool valid = r < n_act;
-    const int rr = valid ? r : T * 64;                      // (a lane past the end rides along on the task's first particle; nothing of it is stored)
-    const int gi = dense_gi[rr], c = dense_cell[rr];
-    const float4 me = snap4[gi];
-    const int GG = P.G * P.G;
-    const int i3 = c / GG, irem = c - i3 * GG, i1 = irem / P.G, i2 = irem - i1 * P.G;      // (world == 1: local cell == global cell)
-    const PairCtx ctx = {me.x, me.y, me.z, 0.f, 0, gi, false};
-    const float eps2f = (float)P.eps2;
-    // The box around the stencils of the wave's particles, from the lowest and the highest of their cells: every cell
-    // whose index lies between the two has its coordinates in it.  Scalar arithmetic.
-    int lo1 = 0, hi1 = P.G - 1, lo2 = 0, hi2 = P.G - 1, lo3, hi3;
-    {
-        const int c_hi = __builtin_amdgcn_readfirstlane(wave_max_i(c)), c_lo = __builtin_amdgcn_readfirstlane(-wave_max_i(-c));
-        const int a3 = c_lo / GG, b3 = c_hi / GG;
-        lo3 = a3; hi3 = b3;
-        if (a3 == b3) {
-            const int ra = c_lo - a3 * GG, rb = c_hi - b3 * GG, a1 = ra / P.G, b1 = rb / P.G;
-            lo1 = a1; hi1 = b1;
-            if (a1 == b1) { lo2 = ra - a1 * P.G; hi2 = rb - b1 * P.G; }
-        }
-        lo1--; lo2--; lo3--; hi1++; hi2++; hi3++;
-    }
-    const int nblk = (P.num_cells_global + 63) >> 6;        // (mom_cap == nblk * 64: the planes are padded with zeros)
-    const int blk_lo = nblk * part / ALLP_PARTS, blk_hi = nblk * (part + 1) / ALLP_PARTS;
-    float px = 0.f, py = 0.f, pz = 0.f;                     // the part's sum
-    for (int blk = blk_lo; blk < blk_hi; blk++) {
-        // lane = cell: which of the block's 64 cells hold mass at all, and which of those lie in the box
-        const int jp = mom_j[blk * 64 + lane];
-        const bool nz = mom[3 * (size_t)mom_cap + blk * 64 + lane] != 0.f;
-        const int j3 = jp >> 20, j1 = (jp >> 10) & 1023, j2 = jp & 1023;
-        const unsigned long long nzm = __ballot(nz);
-        const unsigned long long nearm = __ballot(nz && j3 >= lo3 && j3 <= hi3 && j1 >= lo1 && j1 <= hi1 && j2 >= lo2 && j2 <= hi2);
-        if (nzm == 0ull) continue;                          // (a chain of nothing is +0, and the part's sum never is -0)
-        const float *sx = mom + (size_t)blk * 64, *sy = sx + mom_cap, *sz = sy + mom_cap, *sw = sz + mom_cap;
-        float ax = 0.f, ay = 0.f, az = 0.f;                 // the block's chain
-        int flag = 0;
-        for (int g = 0; g < 64; g += 8) {
-            if (((nzm >> g) & 0xffull) == 0ull) continue;   // (eight cells of mass 0 add eight zeros)
-            v2f qx[4], qy[4], qz[4], qw[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                qx[i] = v2f{sx[g + 2 * i], sx[g + 2 * i + 1]};
-                qy[i] = v2f{sy[g + 2 * i], sy[g + 2 * i + 1]};
-                qz[i] = v2f{sz[g + 2 * i], sz[g + 2 * i + 1]};
-                qw[i] = v2f{sw[g + 2 * i], sw[g + 2 * i + 1]};
-            }
-            if (((nearm >> g) & 0xffull) != 0ull) {
-                // some lane may have one of these cells in its own stencil: the cutoff pass has its bodies
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int j = __builtin_amdgcn_readlane(jp, g + k);
-                    const bool hit = abs((j >> 20) - i3) <= 1 && abs(((j >> 10) & 1023) - i1) <= 1 && abs((j & 1023) - i2) <= 1;
-                    if (k & 1) qw[k >> 1].y = hit ? 0.f : qw[k >> 1].y; else qw[k >> 1].x = hit ? 0.f : qw[k >> 1].x;
-                }
-            }
-            if (MODE == 1) pairsN_exact_lean<8>(P, ctx, qx, qy, qz, qw, 0, nullptr, nullptr, ax, ay, az, flag);
-            else (void)pairsN_fast<8>(ctx, qx, qy, qz, qw, eps2f, ax, ay, az);
-        }
-        px += ax; py += ay; pz += az;
-    }
-    if (valid) far.part_acc[(size_t)part * far.part_plane + (size_t)r] = make_float4(px, py, pz, 0.f);
-    }
-}
-
-// What ran before is the stencil's chain (the two-pass pair stage: contexts with the flag are created only with it, only
-// with lean arithmetic and only with world == 1); now the cells' moments, every cell beyond the stencil as one body, the sum.
-void launch_far_monopole(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound)
-{
-    launch_far_moments(st, P, d);
-    FarCells far;
-    far.part_acc = d.part_acc; far.part_plane = (unsigned long long)d.part_tasks * 64;
-    const int64_t dense_bound = far_dense_bound(P, d, live_bound);
-    launch_dense_order(st, P, d);
-    const SnapSoa snap4{d.snap_soa, (size_t)P.sorted_cap};
-    const unsigned far_wgs = (unsigned)((dense_bound * ALLP_PARTS + 3) / 4);
-    if (fast) k_far_monopole<2><<<far_wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, d.cell_mom, d.cell_mom_j, d.mom_cap);
-    else k_far_monopole<1><<<far_wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, d.cell_mom, d.cell_mom_j, d.mom_cap);
-    launch_far_combine(st, P, d, far, dense_bound);
-}
-
-// ------------------------------------------------------------------ a pyramid of monopoles (PSAMD_FLAG_FAR_PYRAMID, not in the reference)
-// The far monopoles' cost grows with the number of cells: G^3 - 27 bodies a particle.  Here farther mass comes in coarser
-// cells.  Level 0 is the cell grid with k_cell_moments' moments, a level-(l+1) cell sums the fp64 sums of its (at most 8)
-// children in index order; cell i's set is, at the top level, every cell not adjacent to i >> L, and at every level below,
-// every cell whose parent is adjacent to i's parent and which is not itself adjacent to i >> l: every cell of the box
-// beyond the stencil is under exactly one member.  The walk keeps k_far_monopole's shape -- dense tasks, wave-uniform
-// moments as scalar operands, a body that is not the lane's entered with mass 0 -- with (task, level) items: part p of the
-// partial sums is level L - p, so that the parts' sum in part order is ((stencil + level L) + level L-1) + ... + level 0.
-// Within a level: blocks of 64 cells in index order, a block one chain from +0, the chain sums added in block order to +0.
-// A block or a group of 8 in which no lane of the wave has a body adds zeros only and is skipped: below the top level that
-// is everything outside the box of the children of the neighbours of the wave's parents, a few blocks of the level.
-
 // One thread per cell of level l >= 1: the fp64 sums of its children in ascending child index, each started at +0.
 __global__ __launch_bounds__(256) void k_level_moments(const FarLevels lev, int l, float *__restrict__ mom, int *__restrict__ mom_j,
                                                        double *__restrict__ sums, int mom_cap)
@@ -213,29 +112,39 @@ void launch_far_moments(hipStream_t st, const DevParams &P, const DeviceState &d
         k_level_moments<<<(lev.G[l] * lev.G[l] * lev.G[l] + 255) / 256, 256, 0, st>>>(lev, l, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap);
 }
 
-// (6 waves a SIMD, not k_far_monopole's 7: the second compare per body costs registers -- at 7 the compiler's report shows 68
-// bytes of scratch a lane in the exact instance, at 6 it shows 8 (80 VGPRs); by that report, not by a timing)
+// (the pyramid's instances at 6 waves a SIMD, not the flat ones' 7: the parent compare per body costs registers -- at 7 the
+// compiler's report shows 68 bytes of scratch a lane in the exact instance, at 6 it shows 8 (80 VGPRs); by that report, not
+// by a timing)
 constexpr int PYRAMID_WAVES = 6;
 
-template <int MODE>
-__global__ __launch_bounds__(256, PYRAMID_WAVES) void k_far_pyramid(DevParams P, const SnapSoa snap4, const int *__restrict__ act_start,
-                                                                           const int *__restrict__ dense_gi, const int *__restrict__ dense_cell,
-                                                                           const FarCells far, const FarLevels lev, const float *__restrict__ mom,
-                                                                           const int *__restrict__ mom_j, int mom_cap)
+// The force walk of both methods.  PYRAMID is a compile-time parameter: the flat instances have l = 0 and top = true as
+// constants and carry neither the level arithmetic nor the parent compare.  mom, mom_j: at.mom and at.mom_j once more, as
+// __restrict__ kernel arguments -- what tells the compiler that the store of the partial sums does not touch the moments, so
+// that they stay scalar loads (a pointer inside a struct cannot say it).
+template <int MODE, bool PYRAMID>
+__global__ __launch_bounds__(256, PYRAMID ? PYRAMID_WAVES : BALANCED_WAVES) void k_far_walk(DevParams P, const SnapSoa snap4,
+                                                                                             const int *__restrict__ act_start,
+                                                                                             const int *__restrict__ dense_gi,
+                                                                                             const int *__restrict__ dense_cell,
+                                                                                             const FarCells far, const FarMoments at,
+                                                                                             const float *__restrict__ mom,
+                                                                                             const int *__restrict__ mom_j)
 {
+    const FarMoments m = {mom, mom_j, at.mom_cap, at.nparts, at.nlev, P.G};      // (P.G is at.G: one scalar fewer alive across the walk)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n_act = act_start[comp_count(P)];
     const int ntask = min((n_act + 63) >> 6, (int)(far.part_plane >> 6));      // (the partial sums' room: never short, see create.hip)
-    const int nitem = ntask * lev.n, nwg = (nitem + 3) >> 2;
+    const int nitem = ntask * (PYRAMID ? m.nlev : ALLP_PARTS), nwg = (nitem + 3) >> 2;
+    // (the launch is sized from the host's bound of the live count, the items from the device's own count, as in k_allp_far)
     for (int b = blockIdx.x; b < nwg; b += gridDim.x) {
-    // level-major: the top level's items first
+    // part-major, as in k_allp_far: an XCD's run of items reads one share of the moments (the pyramid's top level comes first)
     const int slot = __builtin_amdgcn_readfirstlane(xcd_contiguous(b, nwg) * 4 + wave);
     if (slot >= nitem) continue;
-    const int part = slot / ntask, T = slot - part * ntask, l = lev.n - 1 - part;
-    const bool top = part == 0;
-    int Gl = 0, off = 0;
-#pragma unroll
-    for (int k = 0; k < FAR_MAX_LEVELS; k++) if (k == l) { Gl = lev.G[k]; off = lev.off[k]; }
+    const int part = slot / ntask, T = slot - part * ntask;
+    const int l = PYRAMID ? m.nlev - 1 - part : 0;
+    FarLevel lev = far_level(m, l);
+    if (!PYRAMID) lev.top = true;                           // (one level: a constant for the compiler)
+    const bool top = lev.top;
     const int r = T * 64 + lane;
     const bool valid = r < n_act;
     const int rr = valid ? r : T * 64;                      // (a lane past the end rides along on the task's first particle; nothing of it is stored)
@@ -243,113 +152,74 @@ __global__ __launch_bounds__(256, PYRAMID_WAVES) void k_far_pyramid(DevParams P,
     const float4 me = snap4[gi];
     const int GG = P.G * P.G;
     const int i3 = c / GG, irem = c - i3 * GG, i1 = irem / P.G, i2 = irem - i1 * P.G;      // (world == 1: local cell == global cell)
-    const int a1 = i1 >> l, a2 = i2 >> l, a3 = i3 >> l;     // the lane's cell of this level, and its parent
-    const int p1 = a1 >> 1, p2 = a2 >> 1, p3 = a3 >> 1;
+    const int a1 = i1 >> l, a2 = i2 >> l, a3 = i3 >> l;     // the lane's cell of this level
     const PairCtx ctx = {me.x, me.y, me.z, 0.f, 0, gi, false};
     const float eps2f = (float)P.eps2;
-    // The cells of the wave's particles lie in a box given by the lowest and the highest of them (k_far_monopole).  Shifted
-    // by the level it bounds the lanes' level cells; the bodies any lane may have to mask or to take are, at the top level,
-    // the neighbours of those, and below it the children of the neighbours of their parents.  Scalar arithmetic.
-    int lo1 = 0, hi1 = P.G - 1, lo2 = 0, hi2 = P.G - 1, lo3, hi3;
+    // The cells of the wave's particles lie in a box given by the lowest and the highest of them: every cell whose index
+    // lies between the two has its coordinates in it.  far_box makes of it the level cells any lane may have to leave out
+    // or to take.  Scalar arithmetic.
+    FarBox box = {0, P.G - 1, 0, P.G - 1, 0, 0};
     {
         const int c_hi = __builtin_amdgcn_readfirstlane(wave_max_i(c)), c_lo = __builtin_amdgcn_readfirstlane(-wave_max_i(-c));
-        const int b3lo = c_lo / GG, b3hi = c_hi / GG;
-        lo3 = b3lo; hi3 = b3hi;
-        if (b3lo == b3hi) {
-            const int ra = c_lo - b3lo * GG, rb = c_hi - b3hi * GG, b1lo = ra / P.G, b1hi = rb / P.G;
-            lo1 = b1lo; hi1 = b1hi;
-            if (b1lo == b1hi) { lo2 = ra - b1lo * P.G; hi2 = rb - b1hi * P.G; }
+        box.lo3 = c_lo / GG; box.hi3 = c_hi / GG;
+        if (box.lo3 == box.hi3) {
+            const int ra = c_lo - box.lo3 * GG, rb = c_hi - box.hi3 * GG;
+            box.lo1 = ra / P.G; box.hi1 = rb / P.G;
+            if (box.lo1 == box.hi1) { box.lo2 = ra - box.lo1 * P.G; box.hi2 = rb - box.hi1 * P.G; }
         }
-        if (top) {
-            lo1 = (lo1 >> l) - 1; lo2 = (lo2 >> l) - 1; lo3 = (lo3 >> l) - 1;
-            hi1 = (hi1 >> l) + 1; hi2 = (hi2 >> l) + 1; hi3 = (hi3 >> l) + 1;
-        } else {
-            lo1 = 2 * ((lo1 >> (l + 1)) - 1); lo2 = 2 * ((lo2 >> (l + 1)) - 1); lo3 = 2 * ((lo3 >> (l + 1)) - 1);
-            hi1 = 2 * ((hi1 >> (l + 1)) + 1) + 1; hi2 = 2 * ((hi2 >> (l + 1)) + 1) + 1; hi3 = 2 * ((hi3 >> (l + 1)) + 1) + 1;
-        }
-        lo1 = max(lo1, 0); lo2 = max(lo2, 0); lo3 = max(lo3, 0);
-        hi1 = min(hi1, Gl - 1); hi2 = min(hi2, Gl - 1); hi3 = min(hi3, Gl - 1);
+        box = far_box(lev, l, box);
     }
-    // the top level takes every block; a level below only those that hold a cell of the box: every cell of the box has
-    // its index between the box's corners'
-    const int blk_lo = top ? 0 : ((lo3 * Gl + lo1) * Gl + lo2) >> 6;
-    const int blk_hi = top ? (Gl * Gl * Gl + 63) >> 6 : (((hi3 * Gl + hi1) * Gl + hi2) >> 6) + 1;
-    float px = 0.f, py = 0.f, pz = 0.f;                     // the level's sum
+    int blk_lo, blk_hi;
+    if (PYRAMID) far_blocks(lev, box, blk_lo, blk_hi);
+    else { blk_lo = lev.nblk * part / ALLP_PARTS; blk_hi = lev.nblk * (part + 1) / ALLP_PARTS; }
+    float px = 0.f, py = 0.f, pz = 0.f;                     // the part's sum
     for (int blk = blk_lo; blk < blk_hi; blk++) {
         // lane = cell: which of the block's 64 cells hold mass at all, and which of those lie in the box
-        const int base = off + blk * 64;
-        const int jp = mom_j[base + lane];
-        const bool nz = mom[3 * (size_t)mom_cap + base + lane] != 0.f;
+        const int base = lev.off + blk * 64;
+        const int jp = m.mom_j[base + lane];
+        const bool nz = m.mom[3 * (size_t)m.mom_cap + base + lane] != 0.f;
         const int j3 = jp >> 20, j1 = (jp >> 10) & 1023, j2 = jp & 1023;
-        const unsigned long long nearm = __ballot(nz && j3 >= lo3 && j3 <= hi3 && j1 >= lo1 && j1 <= hi1 && j2 >= lo2 && j2 <= hi2);
+        const unsigned long long nearm = __ballot(nz && j3 >= box.lo3 && j3 <= box.hi3 && j1 >= box.lo1 && j1 <= box.hi1 && j2 >= box.lo2 && j2 <= box.hi2);
         const unsigned long long evalm = top ? __ballot(nz) : nearm;      // (below the top level no lane has a body outside the box)
-        if (evalm == 0ull) continue;                        // (a chain of nothing is +0, and the level's sum never is -0)
-        const float *sx = mom + base, *sy = sx + mom_cap, *sz = sy + mom_cap, *sw = sz + mom_cap;
-        float ax = 0.f, ay = 0.f, az = 0.f;                 // the block's chain
-        int flag = 0;
-        for (int g = 0; g < 64; g += 8) {
-            if (((evalm >> g) & 0xffull) == 0ull) continue; // (eight bodies of mass 0, or in no lane's set, add eight zeros)
-            v2f qx[4], qy[4], qz[4], qw[4];
+        if (evalm == 0ull) continue;                        // (a chain of nothing is +0, and the part's sum never is -0)
+        const float *sx = m.mom + base, *sy = sx + m.mom_cap, *sz = sy + m.mom_cap, *sw = sz + m.mom_cap;
+        float ax, ay, az;                                   // the block's chain
+        far_block_chain<MODE>(P, ctx, sx, sy, sz, sw, evalm, eps2f, [&](int g, v2f (&qw)[4]) {
+            // outside the box no lane leaves anything out; inside it every lane asks for its own cell
+            if (((nearm >> g) & 0xffull) == 0ull) return;
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                qx[i] = v2f{sx[g + 2 * i], sx[g + 2 * i + 1]};
-                qy[i] = v2f{sy[g + 2 * i], sy[g + 2 * i + 1]};
-                qz[i] = v2f{sz[g + 2 * i], sz[g + 2 * i + 1]};
-                qw[i] = v2f{sw[g + 2 * i], sw[g + 2 * i + 1]};
-            }
-            if (((nearm >> g) & 0xffull) != 0ull) {
-                // some lane may have to leave one of these out: it is adjacent to the lane's cell of this level (a finer
-                // level or the stencil has its mass), or -- below the top -- its parent is not adjacent to the lane's parent
-                // (a coarser level has it)
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int j = __builtin_amdgcn_readlane(jp, g + k);
-                    const int J3 = j >> 20, J1 = (j >> 10) & 1023, J2 = j & 1023;
-                    const bool adj = abs(J3 - a3) <= 1 && abs(J1 - a1) <= 1 && abs(J2 - a2) <= 1;
-                    const bool par = top || (abs((J3 >> 1) - p3) <= 1 && abs((J1 >> 1) - p1) <= 1 && abs((J2 >> 1) - p2) <= 1);
-                    const bool hit = adj || !par;
-                    if (k & 1) qw[k >> 1].y = hit ? 0.f : qw[k >> 1].y; else qw[k >> 1].x = hit ? 0.f : qw[k >> 1].x;
-                }
-            }
-            if (MODE == 1) pairsN_exact_lean<8>(P, ctx, qx, qy, qz, qw, 0, nullptr, nullptr, ax, ay, az, flag);
-            else (void)pairsN_fast<8>(ctx, qx, qy, qz, qw, eps2f, ax, ay, az);
-        }
+            for (int k = 0; k < 8; k++) far_drop(qw, k, far_leaves_out(top, __builtin_amdgcn_readlane(jp, g + k), a1, a2, a3));
+        }, ax, ay, az);
         px += ax; py += ay; pz += az;
     }
     if (valid) far.part_acc[(size_t)part * far.part_plane + (size_t)r] = make_float4(px, py, pz, 0.f);
     }
 }
 
-// ((stencil chain + level L) + level L-1) + ... + level 0: k_allpairs_combine over the nparts parts that were written
-__global__ void k_pyramid_combine(DevParams P, const int *__restrict__ act_start, const int *__restrict__ dense_gi,
-                                  const int *__restrict__ dense_cell, const FarCells far, int nparts, const ForceBuf force4)
+template <bool PYRAMID>
+static void launch_far_walk(hipStream_t st, unsigned wgs, const DevParams &P, const DeviceState &d, bool fast, const FarCells &far)
 {
-    const int n = min(act_start[comp_count(P)], (int)far.part_plane);
-    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
-        const int gi = dense_gi[r], lc = dense_cell[r];
-        float4 a = force4.get(P, lc, gi);                   // (flag 0, not a kid: it is on the active list)
-        for (int p = 0; p < nparts; p++) {
-            const float4 b = far.part_acc[(size_t)p * far.part_plane + (size_t)r];
-            a.x += b.x; a.y += b.y; a.z += b.z;
-        }
-        force4.put(P, lc, gi, a);
-    }
+    const SnapSoa snap4{d.snap_soa, (size_t)P.sorted_cap};
+    const FarMoments m = far_moments_of(P, d);
+    if (fast) k_far_walk<2, PYRAMID><<<wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, m, m.mom, m.mom_j);
+    else k_far_walk<1, PYRAMID><<<wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, m, m.mom, m.mom_j);
 }
 
-// What ran before is the stencil's chain, as for launch_far_monopole; now the moments of every level, the walk, the sum.
-void launch_far_pyramid(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound)
+// What ran before is the stencil's chain (the two-pass pair stage: contexts with either flag are created only with it, only
+// with lean arithmetic and only with world == 1); now the moments, the walk by (dense task, part) items, the parts' sum.
+void launch_far_field(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound)
 {
-    const FarLevels &lev = d.lev;
+    const bool pyramid = (P.flags & PSAMD_FLAG_FAR_PYRAMID) != 0;
+    const int parts = pyramid ? d.lev.n : ALLP_PARTS;
     launch_far_moments(st, P, d);
     FarCells far;
     far.part_acc = d.part_acc; far.part_plane = (unsigned long long)d.part_tasks * 64;
     const int64_t dense_bound = far_dense_bound(P, d, live_bound);
     launch_dense_order(st, P, d);
-    const SnapSoa snap4{d.snap_soa, (size_t)P.sorted_cap};
-    const unsigned far_wgs = (unsigned)((dense_bound * lev.n + 3) / 4);
-    if (fast) k_far_pyramid<2><<<far_wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, lev, d.cell_mom, d.cell_mom_j, d.mom_cap);
-    else k_far_pyramid<1><<<far_wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, lev, d.cell_mom, d.cell_mom_j, d.mom_cap);
-    k_pyramid_combine<<<(unsigned)((dense_bound * 64 + 255) / 256), 256, 0, st>>>(P, d.act_start, d.dense_gi, d.dense_cell, far, lev.n, force_buf(d));
+    const unsigned far_wgs = (unsigned)((dense_bound * parts + 3) / 4);
+    if (pyramid) launch_far_walk<true>(st, far_wgs, P, d, fast, far);
+    else launch_far_walk<false>(st, far_wgs, P, d, fast, far);
+    launch_far_combine(st, P, d, far, parts, dense_bound);
 }
 
 }  // namespace psamd

@@ -473,8 +473,7 @@ static hipError_t launch_pairs_mode(hipStream_t st, const DevParams &P, const De
             if (shape.tile) PS_BALANCED(1, 16); else PS_BALANCED(0, NQ);
 #undef PS_BALANCED
             if (P.flags & PSAMD_FLAG_ALL_PAIRS) launch_allpairs_far(st, P, d, MODE == 2, live_bound);
-            else if (P.flags & PSAMD_FLAG_FAR_MONOPOLE) launch_far_monopole(st, P, d, MODE == 2, live_bound);
-            else if (P.flags & PSAMD_FLAG_FAR_PYRAMID) launch_far_pyramid(st, P, d, MODE == 2, live_bound);
+            else if (P.flags & (PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID)) launch_far_field(st, P, d, MODE == 2, live_bound);
             return hipGetLastError();
         }
     }

@@ -193,10 +193,11 @@ struct DeviceState {
     float *cell_mom = nullptr;    // [4][mom_cap]
     int *cell_mom_j = nullptr;    // [mom_cap] (i3 << 20) | (i1 << 10) | i2
     int mom_cap = 0;
-    // the pyramid (PSAMD_FLAG_FAR_PYRAMID): cell_mom / cell_mom_j hold every level (mom_cap == lev.off[lev.n], level 0
-    // first, so the cells' moments are where the far monopoles have them), and the fp64 sums S, Sx, Sy, Sz the levels add up
-    double *lev_sum = nullptr;    // [4][mom_cap]
+    // the levels of those planes (mom_cap == lev.off[lev.n]): one, the cell grid, on a flat context; on the pyramid
+    // (PSAMD_FLAG_FAR_PYRAMID) every level, level 0 first, so the cells' moments are where the far monopoles have them, and
+    // the fp64 sums S, Sx, Sy, Sz the levels add up
     FarLevels lev;
+    double *lev_sum = nullptr;    // [4][mom_cap]
     DevCounters *ctr = nullptr;
     // psamd_export_live: per tile of SLOT_TILE owned slots, the live count and the statistics' partials; the context's own result record
     int *exp_count = nullptr;
@@ -244,18 +245,18 @@ void launch_collide(hipStream_t st, const DevParams &P, const DeviceState &d);
 void launch_plan_force(hipStream_t st, const DevParams &P, const DeviceState &d, int nw, bool merge, int pass);
 void launch_allpairs_far(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound);
 // ... and what allpairs.hip shares with the far monopoles: the host's bound of the dense tasks, the dense order of the
-// particles that need a force (act_start, dense_gi, dense_cell), the parts' sum onto the stencil's chain in part order
+// particles that need a force (act_start, dense_gi, dense_cell), the sum of the nparts parts that were written onto the
+// stencil's chain in part order
 int64_t far_dense_bound(const DevParams &P, const DeviceState &d, int64_t live_bound);
 void launch_dense_order(hipStream_t st, const DevParams &P, const DeviceState &d);
-void launch_far_combine(hipStream_t st, const DevParams &P, const DeviceState &d, const FarCells &far, int64_t dense_bound);
+void launch_far_combine(hipStream_t st, const DevParams &P, const DeviceState &d, const FarCells &far, int nparts, int64_t dense_bound);
 // the moments of a far-monopole context's frame, of the cells or of every level of the pyramid (farfield.hip): the pair
 // stage's, and the far forms of psamd_potential and psamd_probe, which may run before it
 void launch_far_moments(hipStream_t st, const DevParams &P, const DeviceState &d);
-// the far monopoles (farfield.hip): the cells' moments, then every cell beyond a particle's stencil as one body, and the sum
-void launch_far_monopole(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound);
-// the pyramid of monopoles (farfield.hip): the moments of every level, then per level the cells under the neighbours of a
-// particle's parent that are not its own cell's neighbours (the top level: all that are not), and the sum, top level first
-void launch_far_pyramid(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound);
+// the far field of a far-monopole context, flat or as a pyramid (farfield.hip): the moments, then a particle's far set -- every
+// cell beyond its stencil as one body, or per level the cells under the neighbours of its parent that are not its own cell's
+// neighbours (the top level: all that are not) -- and the parts' sum, the pyramid's top level first
+void launch_far_field(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound);
 hipError_t launch_apply(hipStream_t st, const DevParams &P, const SegLayout &S, const DeviceState &d);
 hipError_t launch_frame_reset(hipStream_t st, const DeviceState &d, size_t frame_ints, int status_table);   // also clears the status record's header and census table
 // The step's tail behind k_apply: census of the queue operations (+ relocation phase 1), bucketing (the step's scalars go

@@ -16,8 +16,11 @@
 //                    for the packs: tile_walk.hpp), serial fp32 accumulation in the reference's order (fp32 VALU bound;
 //                    no MFMA: no contraction here, every pair needs its own rsqrt)
 //     allpairs.hip   the far field of the all-pairs forces, beyond the stencil
-//     farfield.hip   the far field as one monopole per cell (PSAMD_FLAG_FAR_MONOPOLE): the cells' moments, the walk; and
-//                    as a pyramid of them (PSAMD_FLAG_FAR_PYRAMID): the levels' moments, the walk by (task, level)
+//     farfield.hip   the far field as one monopole per cell (PSAMD_FLAG_FAR_MONOPOLE) or as a pyramid of them
+//                    (PSAMD_FLAG_FAR_PYRAMID): the moments of the cells and of the levels, one walk by (task, part) items --
+//                    a part is a sixteenth of the cell grid's blocks, or a level
+//     far_walk.hpp   what that walk shares with the far forms of potential.hip and probe.hip: where the moments are, a
+//                    level's place, the members of a far set, the chain over a block of 64 level cells (device-inline only)
 //     selftest.hip   the short sqrt / reciprocal against the compiler's over whole float ranges
 //   apply.hip      k_apply: death / survive / integrate / wrap / re-hash in slot order (ps.cpp:1210-1333; streaming, HBM)
 //   lifecycle.hip  free-slot queues + relocation replayed in the reference's serial order (ps.cpp:1335-1374,

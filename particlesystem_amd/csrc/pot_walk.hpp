@@ -90,66 +90,7 @@ struct PotFar {
     int padded;
 };
 
-// ------------------------------------------------------------------ far monopoles (PSAMD_POTENTIAL_FAR, PSAMD_PROBE_FAR)
-// Where a far-monopole context (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID) finds the moments the pair stage's own
-// kernels form (farfield.hip: four planes of mom_cap and the packed coordinates, every level padded with zeros to whole
-// blocks of 64).  The flat method is a pyramid of one level: its set is the top level's rule at level 0.  nparts: the
-// partial sums the force pass deals a level's blocks to (16 flat, 1 pyramid) -- the probe's acceleration repeats them.
-struct PotMono {
-    const float *mom;
-    const int *mom_j;
-    int mom_cap, nparts;
-    int nlev, G;            // L + 1 and G_0: a level's size and place follow from them (far_levels_of), a few scalar operations
-};
-
-inline PotMono pot_mono(const DevParams &P, const DeviceState &d)
-{
-    const bool pyramid = (P.flags & PSAMD_FLAG_FAR_PYRAMID) != 0;
-    return PotMono{d.cell_mom, d.cell_mom_j, d.mom_cap, pyramid ? 1 : ALLP_PARTS, pyramid ? d.lev.n : 1, P.G};
-}
-
-// Level l as cell (i1, i2, i3) sees it: its cell of the level, that cell's parent, and the blocks [blk_lo, blk_hi) that can
-// hold a member of its set -- all of the top level, below it those with a child of a neighbour of the parent (every cell of
-// that box has its index between the box's corners').  Wave-uniform: scalar arithmetic.
-struct FarLevelView {
-    int off, a1, a2, a3, p1, p2, p3, blk_lo, blk_hi, nblk;
-    bool top;
-};
-
-__device__ __forceinline__ FarLevelView far_level_view(const PotMono &m, int l, int i1, int i2, int i3)
-{
-    FarLevelView v;
-    int Gl = m.G;
-    v.off = 0;
-    for (int k = 0; k < l; k++) { v.off += (Gl * Gl * Gl + 63) / 64 * 64; Gl = (Gl + 1) / 2; }      // (far_levels_of)
-    v.top = l == m.nlev - 1;
-    v.a1 = i1 >> l; v.a2 = i2 >> l; v.a3 = i3 >> l;
-    v.p1 = v.a1 >> 1; v.p2 = v.a2 >> 1; v.p3 = v.a3 >> 1;
-    v.nblk = (Gl * Gl * Gl + 63) >> 6;
-    v.blk_lo = 0; v.blk_hi = v.nblk;
-    if (!v.top) {
-        const int lo1 = max(2 * (v.p1 - 1), 0), lo2 = max(2 * (v.p2 - 1), 0), lo3 = max(2 * (v.p3 - 1), 0);
-        const int hi1 = min(2 * (v.p1 + 1) + 1, Gl - 1), hi2 = min(2 * (v.p2 + 1) + 1, Gl - 1), hi3 = min(2 * (v.p3 + 1) + 1, Gl - 1);
-        v.blk_lo = ((lo3 * Gl + lo1) * Gl + lo2) >> 6;
-        v.blk_hi = (((hi3 * Gl + hi1) * Gl + hi2) >> 6) + 1;
-    }
-    return v;
-}
-
-// lane = cell of block blk of the level: the members of the set, as a wave-uniform mask.  A member holds mass (M != 0: a
-// moment that is no number counts), is not within 1 of the cell's own cell of the level and -- below the top -- has its
-// parent within 1 of the cell's parent (psamd.h, "a pyramid of monopoles").
-__device__ __forceinline__ unsigned long long far_members(const PotMono &m, const FarLevelView &v, int blk, int lane)
-{
-    const int at = v.off + blk * 64 + lane;
-    const int jp = m.mom_j[at];
-    const bool nz = m.mom[3 * (size_t)m.mom_cap + at] != 0.f;
-    const int J3 = jp >> 20, J1 = (jp >> 10) & 1023, J2 = jp & 1023;
-    const bool adj = abs(J3 - v.a3) <= 1 && abs(J1 - v.a1) <= 1 && abs(J2 - v.a2) <= 1;
-    const bool par = v.top || (abs((J3 >> 1) - v.p3) <= 1 && abs((J1 >> 1) - v.p1) <= 1 && abs((J2 >> 1) - v.p2) <= 1);
-    return __ballot(nz && !adj && par);
-}
-
+// Far-field contexts (PSAMD_POTENTIAL_FAR, PSAMD_PROBE_FAR; far_walk.hpp says where the moments are and which are members).
 // One block of 64 level cells (wave-uniform pointers to its moments: scalar loads): the members' terms -- pot_group's, on
 // FAST_MATH contexts too -- are ONE fp32 chain in index order started at +0, its sum carried on in acc.  A group of eight
 // without a member adds eight zeros and is skipped: a chain that starts at +0 never becomes -0.
@@ -164,21 +105,6 @@ __device__ __forceinline__ void pot_far_block(const PairCtx &ctx, const float *_
         pot_group<false, false, true>(ctx, sx, sy, sz, sw, g, 8, 0, eps2f, a, keep);
     }
     acc += (double)a;
-}
-
-// The far part of phi for the cell (i1, i2, i3) all lanes of the wave walk: levels top down, blocks in index order.
-__device__ __forceinline__ void pot_far_walk(const PairCtx &ctx, const PotMono &m, int i1, int i2, int i3, int lane,
-                                             float eps2f, double &acc)
-{
-    for (int l = m.nlev - 1; l >= 0; l--) {
-        const FarLevelView v = far_level_view(m, l, i1, i2, i3);
-        for (int blk = v.blk_lo; blk < v.blk_hi; blk++) {
-            const unsigned long long take = far_members(m, v, blk, lane);
-            if (take == 0ull) continue;
-            const float *sx = m.mom + v.off + blk * 64, *sy = sx + m.mom_cap, *sz = sy + m.mom_cap, *sw = sz + m.mom_cap;
-            pot_far_block(ctx, sx, sy, sz, sw, take, eps2f, acc);
-        }
-    }
 }
 
 }  // namespace psamd

@@ -10,7 +10,7 @@
 //   k_pot_pairs   one wave per (own cell, 64-particle slice), one lane per particle: the 27-cell stencil in the
 //                 reference's order, the bodies as wave-uniform (scalar) loads of the four planes, eight to a group in
 //                 pair_math.hpp's packed forms; all-pairs contexts go on over every other cell in global order, far-
-//                 monopole contexts asked with PSAMD_POTENTIAL_FAR over the cell's far set (pot_walk.hpp).  The
+//                 field contexts asked with PSAMD_POTENTIAL_FAR over the cell's far set (far_walk.hpp).  The
 //                 lane's own entry is left out BY SORTED INDEX: two particles at one point see each other.
 //                 phi by sorted index.
 //   k_pot_reduce  per tile of POT_TILE sorted entries: phi scattered to slot order through sorted_id; U, the extrema and
@@ -26,13 +26,15 @@
 // context and on the slab that holds the particle.  Against an fp64 direct sum: 1.5e-7 relative for phi, 1e-8 for U
 // (tests/test_gpu_potential.py prints the largest error of every case).
 //
-// PSAMD_POTENTIAL_FAR (far-monopole contexts): the moments are formed first, by the pair stage's own kernels from the
-// same snapshot (launch_far_moments: the same bits in the same buffers, whether the pair stage has run or not); behind
-// the stencil's chains come the levels top down, of each level the blocks of 64 cells in index order, a block's members
-// one chain from +0.  The set is a function of the wave's one cell: members and masks are scalar.
+// PSAMD_POTENTIAL_FAR (far-field contexts, flat or as a pyramid): the moments are formed first, by the pair stage's own
+// kernels from the same snapshot (launch_far_moments: the same bits in the same buffers, whether the pair stage has run or
+// not); behind the stencil's chains come the levels top down (flat: the one level), of each level the blocks of 64 cells in
+// index order, a block's members one chain from +0 (pot_far_walk).  Levels, blocks and members are far_walk.hpp's, the ones
+// the force pass walks; the set is a function of the wave's one cell: members and masks are scalar.
 //
 // VGPRs / waves per SIMD of k_pot_pairs as the compiler reports them for gfx950, no instance with scratch:
 //   cutoff 40 / 8      all-pairs 44 / 8      far monopoles 42 / 8
+#include "far_walk.hpp"
 #include "pot_walk.hpp"
 #include "slot_walk.hpp"
 
@@ -44,13 +46,28 @@ static_assert(POT_ITEMS == SLOT_ITEMS, "a wave walks POT_ITEMS batches of 64 sor
 
 __device__ __forceinline__ bool pot_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
+// The far part of phi for the cell (i1, i2, i3) all lanes of the wave walk: levels top down, blocks in index order.
+__device__ __forceinline__ void pot_far_walk(const PairCtx &ctx, const FarMoments &m, int i1, int i2, int i3, int lane,
+                                             float eps2f, double &acc)
+{
+    for (int l = m.nlev - 1; l >= 0; l--) {
+        const FarLevelView v = far_level_view(m, l, i1, i2, i3);
+        for (int blk = v.blk_lo; blk < v.blk_hi; blk++) {
+            const unsigned long long take = far_members(m, v, blk, lane);
+            if (take == 0ull) continue;
+            const float *sx = m.mom + v.lev.off + blk * 64, *sy = sx + m.mom_cap, *sz = sy + m.mom_cap, *sw = sz + m.mom_cap;
+            pot_far_block(ctx, sx, sy, sz, sw, take, eps2f, acc);
+        }
+    }
+}
+
 template <int FAR>      // 0: the stencil alone; 1: all-pairs; 2: far monopoles, flat or as a pyramid
 __global__ __launch_bounds__(POT_THREADS) void k_pot_pairs(DevParams P, const int *__restrict__ cell_start,
                                                            const float *__restrict__ snap_soa,
                                                            const float *__restrict__ snap_age,
                                                            const int *__restrict__ sorted_id,
                                                            const float4 *__restrict__ pos4, const PotFar far,
-                                                           const PotMono mono, float *__restrict__ phi_sorted)
+                                                           const FarMoments mono, float *__restrict__ phi_sorted)
 {
     // (cell, slice) tasks of every own cell, cell-major; four independent waves per workgroup, an XCD's workgroups a
     // contiguous run of cells (force.hip, k_pairs).  Slices past a cell's count end at once.
@@ -269,16 +286,16 @@ hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceStat
         if (far_set) {
             launch_far_moments(st, P, d);
             PS_LAUNCH_CHECK();
-            k_pot_pairs<2><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, PotFar{}, pot_mono(P, d), d.pot_sorted);
+            k_pot_pairs<2><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, PotFar{}, far_moments_of(P, d), d.pot_sorted);
         } else if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
             // the own snapshot (cells by local == global index) or the gathered one with its index by global cell
             const bool gathered = P.world > 1;
             const PotFar far{gathered ? reinterpret_cast<const float *>(d.allg_in) : d.snap_soa, gathered ? d.gstart : d.cell_start,
                              gathered ? d.gn : nullptr, gathered ? (unsigned long long)P.allg_cap : (unsigned long long)P.sorted_cap,
                              gathered ? 0 : 1};
-            k_pot_pairs<1><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, far, PotMono{}, d.pot_sorted);
+            k_pot_pairs<1><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, far, FarMoments{}, d.pot_sorted);
         } else
-            k_pot_pairs<0><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, PotFar{}, PotMono{}, d.pot_sorted);
+            k_pot_pairs<0><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, PotFar{}, FarMoments{}, d.pot_sorted);
         PS_LAUNCH_CHECK();
     }
     if (ntiles > 0) {

@@ -27,16 +27,18 @@
 // far) -- NOT the force pass's far-field association (allpairs.hip: 16 partial sums), so equality with the force record
 // is promised for cutoff contexts only; with empty far cells the result is the cutoff result bit for bit.
 //
-// PSAMD_PROBE_FAR (far-monopole contexts, flat or as a pyramid): the moments are formed first, by the pair stage's own
-// kernels (launch_far_moments); behind the stencil a cell's turn goes on over its far set -- a function of the one cell
-// being walked, so members and masks are scalar.  The acceleration repeats the FORCE PASS's association (farfield.hip):
-// every member through the context's pair form, eight level cells to a call with the others entered at mass 0, a block
-// of 64 one chain from +0, the block sums into the level's sum (flat: into the 16 parts) from +0, those added to the
+// PSAMD_PROBE_FAR (far-field contexts, flat or as a pyramid): the moments are formed first, by the pair stage's own
+// kernels (launch_far_moments); behind the stencil a cell's turn goes on over its far set (far_walk.hpp: levels, blocks and
+// members are the force pass's) -- a function of the one cell being walked, so members and masks are scalar.  The
+// acceleration IS the force pass's association (farfield.hip): a block of 64 level cells goes through the same
+// far_block_chain -- every member through the context's pair form, eight level cells to a call with the others entered at
+// mass 0, one chain from +0 -- the block sums into the level's sum (flat: into the 16 parts) from +0, those added to the
 // stencil's chain top level first (part 0 first): on the exact path a probe on a served adult returns its force record
-// bit for bit.  phi: pot_walk.hpp's far walk, psamd_potential's.
+// bit for bit.  phi: pot_far_block over the same blocks, psamd_potential's.
 //
 // The kernel is templated on acc / phi / both, generic exact / lean exact / fast, cutoff / all-pairs / far monopoles; the
 // registers and waves per SIMD of every instance are in the table at k_probe_pairs.
+#include "far_walk.hpp"
 #include "multisplit.hpp"
 #include "pot_walk.hpp"
 
@@ -157,47 +159,21 @@ __device__ __forceinline__ void probe_acc_walk(const DevParams &P, const PairCtx
     }
 }
 
-// One block of 64 level cells of a far set (wave-uniform pointers to its moments, `take` its members): the force pass's
-// chain for the block -- k_far_monopole's and k_far_pyramid's inner loop with a scalar mask.  A group of eight without a
-// member is skipped, a cell of a group that is none is entered with mass 0: both add zeros to a chain that started at +0.
-template <int MATH>
-__device__ __forceinline__ void probe_far_block(const DevParams &P, const PairCtx &ctx, const float *__restrict__ sx,
-                                                const float *__restrict__ sy, const float *__restrict__ sz,
-                                                const float *__restrict__ sw, unsigned long long take, float eps2f,
-                                                float &ax, float &ay, float &az)
-{
-    int flag = 0;
-    for (int g = 0; g < 64; g += 8) {
-        const unsigned keep = (unsigned)(take >> g) & 0xffu;
-        if (keep == 0u) continue;
-        v2f qx[4], qy[4], qz[4], qw[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            qx[i] = v2f{sx[g + 2 * i], sx[g + 2 * i + 1]};
-            qy[i] = v2f{sy[g + 2 * i], sy[g + 2 * i + 1]};
-            qz[i] = v2f{sz[g + 2 * i], sz[g + 2 * i + 1]};
-            qw[i] = v2f{(keep >> (2 * i)) & 1u ? sw[g + 2 * i] : 0.f, (keep >> (2 * i + 1)) & 1u ? sw[g + 2 * i + 1] : 0.f};
-        }
-        if (MATH == 1) pairsN_exact_lean<8>(P, ctx, qx, qy, qz, qw, 0, nullptr, nullptr, ax, ay, az, flag);
-        else (void)pairsN_fast<8>(ctx, qx, qy, qz, qw, eps2f, ax, ay, az);
-    }
-}
-
 __device__ __forceinline__ bool probe_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // VGPRs / waves per SIMD as the compiler reports them for gfx950, no instance with scratch (cutoff | all-pairs | far
 // monopoles; the generic exact form has neither an all-pairs nor a far-monopole instance):
 //                 generic exact      lean exact            fast
-//   acc           28 / 8             66 / 7 | 83 / 5 | 79 / 6       58 / 8 | 75 / 6 | 73 / 6
+//   acc           28 / 8             66 / 7 | 83 / 5 | 79 / 6       58 / 8 | 75 / 6 | 71 / 7
 //   phi           40 / 7             40 / 7 | 41 / 7 | 41 / 7       40 / 7 | 41 / 7 | 41 / 7
-//   acc and phi   44 / 7             72 / 7 | 87 / 5 | 83 / 5       62 / 7 | 77 / 6 | 75 / 6
+//   acc and phi   44 / 7             72 / 7 | 87 / 5 | 83 / 5       62 / 7 | 77 / 6 | 73 / 6
 // (acc and phi walk a cell's list once each: the two passes share no registers, and their loads hit the scalar cache.)
 template <int FIELDS, int MATH, int FAR>      // FAR 0: the stencil alone; 1: all-pairs; 2: far monopoles, flat or as a pyramid
 __global__ __launch_bounds__(PROBE_THREADS) void k_probe_pairs(DevParams P, const int *__restrict__ cell_start,
                                                                const float *__restrict__ snap_soa,
                                                                const float4 *__restrict__ pos4, const int *__restrict__ code,
                                                                const int *__restrict__ order, int *__restrict__ hdr,
-                                                               const PotFar far, const PotMono mono, float4 *__restrict__ out4)
+                                                               const PotFar far, const FarMoments mono, float4 *__restrict__ out4)
 {
     // waves of 64 consecutive served entries, four independent waves per workgroup, an XCD's workgroups a contiguous run
     // of the cell-major order (force.hip, k_pairs).  The launch is sized by max_count, the work by the served count.
@@ -246,15 +222,19 @@ __global__ __launch_bounds__(PROBE_THREADS) void k_probe_pairs(DevParams P, cons
             for (int l = mono.nlev - 1; l >= 0; l--) {
                 const FarLevelView v = far_level_view(mono, l, i1, i2, i3);
                 for (int part = 0; part < mono.nparts; part++) {
-                    const int b_lo = max(v.blk_lo, v.nblk * part / mono.nparts), b_hi = min(v.blk_hi, v.nblk * (part + 1) / mono.nparts);
+                    const int b_lo = max(v.blk_lo, v.lev.nblk * part / mono.nparts), b_hi = min(v.blk_hi, v.lev.nblk * (part + 1) / mono.nparts);
                     float px = 0.f, py = 0.f, pz = 0.f;     // the part's sum
                     for (int blk = b_lo; blk < b_hi; blk++) {
                         const unsigned long long take = far_members(mono, v, blk, lane);
                         if (take == 0ull) continue;         // (a chain of nothing is +0, and neither sum ever is -0)
-                        const float *sx = mono.mom + v.off + blk * 64, *sy = sx + mono.mom_cap, *sz = sy + mono.mom_cap, *sw = sz + mono.mom_cap;
+                        const float *sx = mono.mom + v.lev.off + blk * 64, *sy = sx + mono.mom_cap, *sz = sy + mono.mom_cap, *sw = sz + mono.mom_cap;
                         if (FIELDS & PSAMD_PROBE_ACC) {
-                            float cx = 0.f, cy = 0.f, cz = 0.f;
-                            probe_far_block<MATH>(P, ctx, sx, sy, sz, sw, take, eps2f, cx, cy, cz);
+                            // the force pass's chain for the block; what a cell of a group is left out by is a scalar mask here
+                            float cx, cy, cz;
+                            far_block_chain<MATH>(P, ctx, sx, sy, sz, sw, take, eps2f, [&](int g, v2f (&qw)[4]) {
+#pragma unroll
+                                for (int k = 0; k < 8; k++) far_drop(qw, k, !((take >> (g + k)) & 1ull));
+                            }, cx, cy, cz);
                             px += cx; py += cy; pz += cz;
                         }
                         if (FIELDS & PSAMD_PROBE_PHI) pot_far_block(ctx, sx, sy, sz, sw, take, eps2f, acc);
@@ -324,14 +304,14 @@ static void launch_probe_pairs(hipStream_t st, const DevParams &P, const DeviceS
 {
     if (a.fields & PSAMD_PROBE_FAR) {
         if constexpr (MATH != 0)       // (far-monopole contexts are created only with lean arithmetic and world 1)
-            k_probe_pairs<FIELDS, MATH, 2><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, PotFar{}, pot_mono(P, d), a.out4);
+            k_probe_pairs<FIELDS, MATH, 2><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, PotFar{}, far_moments_of(P, d), a.out4);
     } else if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
         if constexpr (MATH != 0) {     // (a context with all-pairs forces is created only with lean arithmetic; world 1: the own snapshot, cells by local == global index)
             const PotFar far{d.snap_soa, d.cell_start, nullptr, (unsigned long long)P.sorted_cap, 1};
-            k_probe_pairs<FIELDS, MATH, 1><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, far, PotMono{}, a.out4);
+            k_probe_pairs<FIELDS, MATH, 1><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, far, FarMoments{}, a.out4);
         }
     } else
-        k_probe_pairs<FIELDS, MATH, 0><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, PotFar{}, PotMono{}, a.out4);
+        k_probe_pairs<FIELDS, MATH, 0><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, PotFar{}, FarMoments{}, a.out4);
 }
 
 template <int FIELDS>

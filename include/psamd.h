@@ -68,6 +68,9 @@ typedef enum psamd_status {
 #define PSAMD_FLAG_FAR_PYRAMID 0x20u  /* long-range gravity whose cost grows with log G instead of G^3: the stencil first, then coarser
                                          cells for farther mass -- a pyramid of monopoles.  See "a pyramid of monopoles" below.  Not
                                          with PSAMD_FLAG_ALL_PAIRS or PSAMD_FLAG_FAR_MONOPOLE (PSAMD_ERR_INVALID_ARG); world == 1 only */
+#define PSAMD_FLAG_FAR_QUADRUPOLE 0x40u /* a modifier of PSAMD_FLAG_FAR_PYRAMID (alone: PSAMD_ERR_INVALID_ARG): every cell of the
+                                         pyramid also carries its second moments, and every far body adds its quadrupole term.  See
+                                         "quadrupoles on the pyramid" below */
 
 /* Runtime form of the reference's compile-time configuration, common.h:12-70.
  * psamd_default_config() fills in the shipped values. */
@@ -903,6 +906,68 @@ int psamd_download_cell_moments(psamd_ctx *ctx, void *out_float4);
  * pyramid context, where it returns level 0. */
 int psamd_far_levels(const psamd_config *cfg, int32_t *levels, int32_t dims[16]);
 int psamd_download_level_moments(psamd_ctx *ctx, int32_t level, void *out_float4);
+
+/* ---- quadrupoles on the pyramid (PSAMD_FLAG_FAR_QUADRUPOLE) ---------------------- */
+/* The pyramid enters a level-l cell as a point mass at distances of only two of its own edges, and that is what its error
+ * is made of.  With this flag, a modifier of PSAMD_FLAG_FAR_PYRAMID, every cell of every level also carries its second moments
+ * and every far body adds its quadrupole term.  The interaction set, the members, the blocks, the levels and every monopole
+ * term are the pyramid's; contexts without the flag compute what they did, in the same bytes.
+ *
+ * Moments.  Ten fp64 sums per cell of every level: S, Sx, Sy, Sz as on the pyramid (the same bits) and six raw second
+ * moments S_ab in the plane order (a, b) = xx, yy, zz, xy, xz, yz.  Level 0: over the first min(count,
+ * MAX_PARTICLES_PER_CELL) entries in list order, every sum started at +0, one addition per entry; the term of entry j is
+ * RN(RN(w_eff * x_a) * x_b) -- the inner product is exact in fp64, the outer one is ONE fp64 rounding; no operation is fused.
+ * Level l + 1: the children's sums added in ascending child index to +0 (raw moments about the origin need no shift).
+ * At every level, in fp64 and unfused, C_ab = (float)(S_ab - RN(RN(S_a / S) * S_b)), a the first index of the plane's name;
+ * S == 0 gives six zeros.  A cell with one adult gives six exact zeros (both products round the same real number).  M, X, Y,
+ * Z are the pyramid context's bit for bit.  A host that repeats this gets the same bits (tests/far_quadrupole_model.py does).
+ *
+ * The quadrupole term of a member (X, Y, Z, M != 0, C) on a particle at x: the second-order Taylor term of the softened
+ * kernel about the centre of mass (the first-order term vanishes there),
+ *     a_q = -3 (C d) u^5 + 7.5 (d.C.d) u^7 d - 1.5 T u^5 d,    d = (X, Y, Z) - x,  u = (d.d + eps2)^(-1/2),  T = Cxx + Cyy + Czz.
+ * In fp32, the same operations on exact and PSAMD_FLAG_FAST_MATH contexts, every product and sum rounded once unless it is
+ * written fma (one rounding for a * b + c):
+ *     dx = X - x,  dy = Y - y,  dz = Z - z
+ *     r2 = (dx*dx + dy*dy) + dz*dz                      u  = rsq(r2 + eps2)      (the hardware reciprocal square root, 1 ulp)
+ *     u2 = u*u,  u3 = u2*u,  u5 = u3*u2,  u7 = u5*u2
+ *     gx = fma(Cxz, dz, fma(Cxy, dy, Cxx*dx))           gy = fma(Cyz, dz, fma(Cyy, dy, Cxy*dx))
+ *     gz = fma(Czz, dz, fma(Cyz, dy, Cxz*dx))           q  = fma(gz, dz, fma(gy, dy, gx*dx))
+ *     T  = (Cxx + Cyy) + Czz                            s  = fma(7.5*u7, q, (-1.5*T)*u5)       m3 = -3*u5
+ *     a_q = (fma(m3, gx, s*dx), fma(m3, gy, s*dy), fma(m3, gz, s*dz))
+ * A later far potential and far probe on such a context will have to repeat this sequence.
+ *
+ * Association.  Within a block of 64 level cells the quadrupole terms form their OWN fp32 chain per component: from +0, in
+ * index order, over the members of the monopole chain.  A level's quadrupole sum is its blocks' quadrupole chains added in
+ * block order to +0; the level's part is RN(monopole sum + quadrupole sum) per component, and the record is
+ * ((stencil + part L) + ...) + part 0 as on the pyramid.  A cell outside a particle's set is skipped or adds +0: the same
+ * bits.  Nothing depends on the launch shape, other particles, graphs or run-ahead.
+ *
+ * Consequences.  A cloud inside a 2x2x2 block of cells gives the cutoff context's bytes.  On G <= 4 with at most one adult per
+ * cell (kids anywhere) every C is an exact zero and every quadrupole chain is +0: records and whole steps are the
+ * PSAMD_FLAG_FAR_PYRAMID context's, byte for byte.
+ *
+ * Accuracy (an fp64 model of the method against an fp64 direct sum, the clouds of tests/test_far_pyramid_cpu.py;
+ * tests/test_far_quadrupole_cpu.py): the median particle's |a| is off by 0.07-0.11 %, the worst by 0.5-1.7 % on 8^3 and
+ * 10^3 cells, where the pyramid of monopoles is off by 0.2-0.5 % and 1.9-4.4 %: the median falls to 0.21-0.35 of the pyramid's.
+ * The device follows the model to 1e-5 relative (tests/test_gpu_far_quadrupole.py).
+ *
+ * Refusals.  psamd_create: the flag without PSAMD_FLAG_FAR_PYRAMID PSAMD_ERR_INVALID_ARG; everything else as the pyramid
+ * refuses it.  psamd_potential, psamd_download_potential, psamd_download_potential_far and psamd_probe return
+ * PSAMD_ERR_UNSUPPORTED on such a context even with PSAMD_POTENTIAL_FAR / PSAMD_PROBE_FAR, and the context stays usable:
+ * their far forms are monopoles only, which is not this context's field.  The flag combines with FAST_MATH, EULER,
+ * EXPLOSIONS, drag, force_sign, graphs, run-ahead and snapshot save / restore as the pyramid does.
+ *
+ * Cost on an MI355X (profiles/far_quadrupole_cost.txt): at N = 2^20 (16^3 cells) a step takes 7.27 ms with the flag against 6.22 ms
+ * for the pyramid of monopoles in the same run and 2.18 ms for the cutoff step (the pair stage's own timer: 4.59, 3.49 and
+ * 1.88 ms): 1.17 times the pyramid step.  At N = 2^22 (24^3 cells) 23.6 ms against 18.7 ms and 9.4 ms (19.7, 15.0 and 8.5 ms):
+ * 1.26 times.  200 served particles against an fp64 direct sum over all bodies: |a| off by 0.037 % for the median particle and
+ * 0.14 % for the worst at 2^20 (the pyramid: 0.057 % and 0.48 %), 0.047 % and 0.11 % at 2^22 (0.059 % and 0.21 %).  The far
+ * work grows 1.7 times: with the quadrupole term the pairs weigh as much as the scan of the blocks (not profiled).
+ *
+ * psamd_download_level_quadrupoles: float[G_level^3][6] = (Cxx, Cyy, Czz, Cxy, Cxz, Cyz) of one level of the frame, by level
+ * cell index.  The validity window and error codes of psamd_download_level_moments; NULL arguments or a level outside [0, L]
+ * PSAMD_ERR_INVALID_ARG; on a context without the flag PSAMD_ERR_UNSUPPORTED.  Waits for the context's stream. */
+int psamd_download_level_quadrupoles(psamd_ctx *ctx, int32_t level, void *out_float6);
 
 /* ---- introspection -------------------------------------------------------- */
 int psamd_get_counters(psamd_ctx *ctx, psamd_counters *out);

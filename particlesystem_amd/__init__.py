@@ -34,6 +34,7 @@ FLAG_ALL_PAIRS = 0x4
 FLAG_EULER = 0x8
 FLAG_FAR_MONOPOLE = 0x10
 FLAG_FAR_PYRAMID = 0x20
+FLAG_FAR_QUADRUPOLE = 0x40
 NUM_TIMERS = 9
 TIMER_NAMES = ("hist", "scan", "scatter", "sort_cells", "pairs", "apply", "lifecycle", "init_iframe", "collide")
 
@@ -299,6 +300,7 @@ ABI = [
     ("psamd_download_force_counts", C.c_int, [_vp, _vp]),
     ("psamd_download_cell_moments", C.c_int, [_vp, _vp]),
     ("psamd_download_level_moments", C.c_int, [_vp, C.c_int32, _vp]),
+    ("psamd_download_level_quadrupoles", C.c_int, [_vp, C.c_int32, _vp]),
     ("psamd_far_levels", C.c_int, [C.POINTER(Config), _ip, _ip]),
     ("psamd_get_pkgdistrib", C.c_int, [_vp, _vp]),
     ("psamd_get_cell_table", C.c_int, [_vp, _vp]),
@@ -554,6 +556,16 @@ class ParticleSystem:
             raise PsamdError(1, "no such level")
         out = np.zeros((dims[level] ** 3, 4), np.float32)
         self._ck(self.lib.psamd_download_level_moments(self.h, level, _ptr(out)))
+        return out
+
+    def download_level_quadrupoles(self, level):
+        """Per cell of a level of a quadrupole context (PSAMD_FLAG_FAR_QUADRUPOLE): the central second moments
+        (Cxx, Cyy, Czz, Cxy, Cxz, Cyz), float32 [G_level^3, 6]."""
+        dims = far_levels(self.cfg)
+        if not 0 <= level < len(dims):
+            raise PsamdError(1, "no such level")
+        out = np.zeros((dims[level] ** 3, 6), np.float32)
+        self._ck(self.lib.psamd_download_level_quadrupoles(self.h, level, _ptr(out)))
         return out
 
     def pkgdistrib(self):

@@ -191,6 +191,8 @@ static int derive_params(psamd_ctx *c, const psamd_config *cfg)
     if (P.key_bits > 63) return fail(c, PSAMD_ERR_UNSUPPORTED, "queue-op key does not fit 64 bits for this configuration");
     if ((cfg->flags & PSAMD_FLAG_ALL_PAIRS) && !P.lean_math) return fail(c, PSAMD_ERR_UNSUPPORTED, "all-pairs forces are built for the lean pair arithmetic only (EPS2 in its validated range)");
     if ((cfg->flags & PSAMD_FLAG_ALL_PAIRS) && !P.two_pass) return fail(c, PSAMD_ERR_UNSUPPORTED, "all-pairs forces need the two-pass pair stage (collision radius small against the cell)");
+    if ((cfg->flags & PSAMD_FLAG_FAR_QUADRUPOLE) && !(cfg->flags & PSAMD_FLAG_FAR_PYRAMID))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "quadrupoles (PSAMD_FLAG_FAR_QUADRUPOLE) belong to the pyramid of monopoles: set PSAMD_FLAG_FAR_PYRAMID too");
     if (cfg->flags & (PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID)) {
         // (both flags: what the flat method refuses comes first, then the choice between the two)
         const bool mono = (cfg->flags & PSAMD_FLAG_FAR_MONOPOLE) != 0, pyr = (cfg->flags & PSAMD_FLAG_FAR_PYRAMID) != 0;
@@ -348,18 +350,20 @@ static int alloc_step_arrays(psamd_ctx *c)
         // order (a pyramid's level is a part: at most FAR_MAX_LEVELS of the ALLP_PARTS planes are used), and the moments --
         // four planes and the packed coordinates of every level (flat: the cell grid alone), each level padded to whole
         // blocks of 64 cells; the padding stays zero (the kernels write the cells of a level); under the pyramid's flag only,
-        // the fp64 sums the levels are added up from
+        // the fp64 sums the levels are added up from.  With quadrupoles (PSAMD_FLAG_FAR_QUADRUPOLE) six planes more of each:
+        // the central second moments behind X, Y, Z, M and the raw ones behind S, Sx, Sy, Sz
         const bool pyramid = (P.flags & PSAMD_FLAG_FAR_PYRAMID) != 0;
+        const size_t planes = (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) ? 10 : 4;
         d.lev = pyramid ? far_levels_of(g.G) : far_one_level(g.G);
         static_assert(FAR_MAX_LEVELS <= ALLP_PARTS, "a level's sum goes into one of the partial-sum planes");
         PS_TRY(alloc_dense_parts(c, SC, LC));
         d.mom_cap = d.lev.off[d.lev.n];
-        PS_HIP(c, dev_alloc(c, &d.cell_mom, 4 * (size_t)d.mom_cap + 64));     // + slack: scalar loads fetch whole groups
+        PS_HIP(c, dev_alloc(c, &d.cell_mom, planes * (size_t)d.mom_cap + 64));     // + slack: scalar loads fetch whole groups
         PS_HIP(c, dev_alloc(c, &d.cell_mom_j, (size_t)d.mom_cap));
-        if (pyramid) PS_HIP(c, dev_alloc(c, &d.lev_sum, 4 * (size_t)d.mom_cap));
-        PS_HIP(c, hipMemsetAsync(d.cell_mom, 0, (4 * (size_t)d.mom_cap + 64) * sizeof(float), c->stream));
+        if (pyramid) PS_HIP(c, dev_alloc(c, &d.lev_sum, planes * (size_t)d.mom_cap));
+        PS_HIP(c, hipMemsetAsync(d.cell_mom, 0, (planes * (size_t)d.mom_cap + 64) * sizeof(float), c->stream));
         PS_HIP(c, hipMemsetAsync(d.cell_mom_j, 0, (size_t)d.mom_cap * sizeof(int), c->stream));
-        if (pyramid) PS_HIP(c, hipMemsetAsync(d.lev_sum, 0, 4 * (size_t)d.mom_cap * sizeof(double), c->stream));
+        if (pyramid) PS_HIP(c, hipMemsetAsync(d.lev_sum, 0, planes * (size_t)d.mom_cap * sizeof(double), c->stream));
     }
     return PSAMD_OK;
 }

@@ -1,6 +1,6 @@
 // far_walk.hpp -- what every walk over a far-field context's moments shares (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID):
 // where the moments are, a level's place and size, the cells of a level that concern a range of grid cells, and the force
-// pass's chain over one block of 64 level cells.  The force pass (farfield.hip, k_far_walk), psamd_potential's far form
+// pass's chain over one block of 64 level cells, the quadrupole term of a far body (PSAMD_FLAG_FAR_QUADRUPOLE).  The force pass (farfield.hip, k_far_walk), psamd_potential's far form
 // (potential.hip, k_pot_pairs<2>) and psamd_probe's (probe.hip, k_probe_pairs<.., 2>) are written on these; device-inline only.
 //
 // The flat method is a pyramid of one level: its set is the top level's rule at level 0.  Cell i's set is, at the top level
@@ -115,11 +115,12 @@ __device__ __forceinline__ unsigned long long far_members(const FarMoments &m, c
 // group of eight with no bit in evalm holds nothing any lane evaluates -- eight zeros -- and is skipped; leave(g, qw) zeroes
 // the masses of the group's cells that are not the lane's: such a body adds +-0 to a chain that started at +0, the same bits
 // as skipping it.  This is the force pass's association; the probe's acceleration repeats it with a wave-uniform mask.
-template <int MATH, class Leave>
+// after(g, qx, qy, qz, qw): what else a walk does with the group's eight bodies, behind their pair terms (the quadrupole chain)
+template <int MATH, class Leave, class After>
 __device__ __forceinline__ void far_block_chain(const DevParams &P, const PairCtx &ctx, const float *__restrict__ sx,
                                                 const float *__restrict__ sy, const float *__restrict__ sz,
                                                 const float *__restrict__ sw, unsigned long long evalm, float eps2f,
-                                                Leave leave, float &ax, float &ay, float &az)
+                                                Leave leave, After after, float &ax, float &ay, float &az)
 {
     ax = 0.f; ay = 0.f; az = 0.f;
     int flag = 0;
@@ -136,13 +137,70 @@ __device__ __forceinline__ void far_block_chain(const DevParams &P, const PairCt
         leave(g, qw);
         if (MATH == 1) pairsN_exact_lean<8>(P, ctx, qx, qy, qz, qw, 0, nullptr, nullptr, ax, ay, az, flag);
         else (void)pairsN_fast<8>(ctx, qx, qy, qz, qw, eps2f, ax, ay, az);
+        after(g, qx, qy, qz, qw);
     }
+}
+
+template <int MATH, class Leave>
+__device__ __forceinline__ void far_block_chain(const DevParams &P, const PairCtx &ctx, const float *__restrict__ sx,
+                                                const float *__restrict__ sy, const float *__restrict__ sz,
+                                                const float *__restrict__ sw, unsigned long long evalm, float eps2f,
+                                                Leave leave, float &ax, float &ay, float &az)
+{
+    far_block_chain<MATH>(P, ctx, sx, sy, sz, sw, evalm, eps2f, leave, [](int, v2f (&)[4], v2f (&)[4], v2f (&)[4], v2f (&)[4]) {}, ax, ay, az);
 }
 
 // body k of a group of eight out of the chain: its mass becomes 0
 __device__ __forceinline__ void far_drop(v2f (&qw)[4], int k, bool drop)
 {
     if (k & 1) qw[k >> 1].y = drop ? 0.f : qw[k >> 1].y; else qw[k >> 1].x = drop ? 0.f : qw[k >> 1].x;
+}
+
+// ---- quadrupoles on the pyramid (PSAMD_FLAG_FAR_QUADRUPOLE) ----
+// The quadrupole term of ONE far body at (X, Y, Z) with the central second moments C = (Cxx, Cyy, Czz, Cxy, Cxz, Cyz) on the
+// particle at (xi, yi, zi): the second-order Taylor term of the softened kernel about the body's centre of mass,
+//   a_q = -3 (C d) u^5 + 7.5 (d.C.d) u^7 d - 1.5 T u^5 d,   d = (X, Y, Z) - x,  u = (d.d + eps2)^(-1/2),  T = Cxx + Cyy + Czz.
+// The ONE form of every context, exact and PSAMD_FLAG_FAST_MATH alike, and of every kernel that inlines it: each
+// multiply-add is an explicit fmaf or explicitly unfused (__fmul_rn, __fadd_rn), so the bits do not depend on the
+// compiler's contraction setting or on the code around the call.  The operation sequence is psamd.h's ("quadrupoles on the
+// pyramid"), line for line.
+__device__ __forceinline__ void far_quad_term(float xi, float yi, float zi, float X, float Y, float Z, float cxx, float cyy,
+                                              float czz, float cxy, float cxz, float cyz, float eps2f, float &tx, float &ty,
+                                              float &tz)
+{
+    const float dx = X - xi, dy = Y - yi, dz = Z - zi;                  // as the pair forms form it
+    const float r2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+    const float u = __builtin_amdgcn_rsqf(__fadd_rn(r2, eps2f));
+    const float u2 = __fmul_rn(u, u), u3 = __fmul_rn(u2, u), u5 = __fmul_rn(u3, u2), u7 = __fmul_rn(u5, u2);
+    const float gx = fmaf(cxz, dz, fmaf(cxy, dy, __fmul_rn(cxx, dx)));  // C d
+    const float gy = fmaf(cyz, dz, fmaf(cyy, dy, __fmul_rn(cxy, dx)));
+    const float gz = fmaf(czz, dz, fmaf(cyz, dy, __fmul_rn(cxz, dx)));
+    const float q = fmaf(gz, dz, fmaf(gy, dy, __fmul_rn(gx, dx)));      // d.C.d
+    const float T = __fadd_rn(__fadd_rn(cxx, cyy), czz);
+    const float s = fmaf(__fmul_rn(7.5f, u7), q, __fmul_rn(__fmul_rn(-1.5f, T), u5));      // what multiplies d
+    const float m3 = __fmul_rn(-3.0f, u5);
+    tx = fmaf(m3, gx, __fmul_rn(s, dx)); ty = fmaf(m3, gy, __fmul_rn(s, dy)); tz = fmaf(m3, gz, __fmul_rn(s, dz));
+}
+
+// The quadrupole terms of a group of eight level cells, added in index order to the block's quadrupole chain (bx, by, bz).
+// c6: the block's Cxx plane at the group (wave-uniform: scalar loads), the five other planes mom_cap apart.  qw: the group's
+// masses AFTER the lane's leave-outs -- a body whose mass is 0 there is no member of the lane's set: +0 is added in its
+// place, which leaves every bit of the chain as it is.
+__device__ __forceinline__ void far_quad_group(const PairCtx &ctx, const v2f (&qx)[4], const v2f (&qy)[4], const v2f (&qz)[4],
+                                               const v2f (&qw)[4], const float *__restrict__ c6, int mom_cap, float eps2f,
+                                               float &bx, float &by, float &bz)
+{
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const bool odd = (k & 1) != 0;
+        const float X = odd ? qx[k >> 1].y : qx[k >> 1].x, Y = odd ? qy[k >> 1].y : qy[k >> 1].x, Z = odd ? qz[k >> 1].y : qz[k >> 1].x;
+        const bool in = (odd ? qw[k >> 1].y : qw[k >> 1].x) != 0.f;
+        const float *c = c6 + k;
+        float tx, ty, tz;
+        far_quad_term(ctx.xi, ctx.yi, ctx.zi, X, Y, Z, c[0], c[mom_cap], c[2 * (size_t)mom_cap], c[3 * (size_t)mom_cap],
+                      c[4 * (size_t)mom_cap], c[5 * (size_t)mom_cap], eps2f, tx, ty, tz);
+        bx = __fadd_rn(bx, in ? tx : 0.f); by = __fadd_rn(by, in ? ty : 0.f); bz = __fadd_rn(bz, in ? tz : 0.f);
+    }
 }
 
 }  // namespace psamd

@@ -31,10 +31,23 @@ __device__ __forceinline__ double lane_f64(double v, int k)
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), k), __builtin_amdgcn_readlane(__double2loint(v), k));
 }
 
+// Quadrupole contexts (PSAMD_FLAG_FAR_QUADRUPOLE) carry six sums more per cell of every level, the raw second moments
+// S_ab = sum RN(RN(w_eff x_a) x_b) in the plane order xx, yy, zz, xy, xz, yz (the inner product is exact in fp64, the outer
+// one rounding; every operation explicitly unfused), and six float planes of central moments behind X, Y, Z, M:
+// C_ab = (float)(S_ab - RN(RN(S_a / S) S_b)), a the first index of the plane's name.  QUAD is a compile-time parameter of
+// the moments' kernels and of the walk: the instances without it are what they were, instruction for instruction.
+constexpr int QUAD_A[6] = {0, 1, 2, 0, 0, 1}, QUAD_B[6] = {0, 1, 2, 1, 2, 2};      // plane -> (a, b), 0 ~ x
+
+__device__ __forceinline__ float far_central(double Sab, double Sa, double Sb, double S)
+{
+    return (float)__dsub_rn(Sab, __dmul_rn(__ddiv_rn(Sa, S), Sb));
+}
+
 // One wave per cell of the box (world == 1: local cell == global cell).  The cell's list is the first
 // min(count, MAX_PARTICLES_PER_CELL) entries of the sorted snapshot; S, Sx, Sy, Sz are fp64 sums over it IN LIST ORDER
 // (entry 0 first, one addition per entry: the lanes fetch 64 entries at a time and every lane adds them one by one).  A
 // product of two fp32 values is exact in fp64, so nothing here depends on contraction.
+template <bool QUAD>
 __global__ __launch_bounds__(256) void k_cell_moments(DevParams P, const int *__restrict__ cell_start, const float *__restrict__ snap,
                                                       float *__restrict__ mom, int *__restrict__ mom_j, int mom_cap,
                                                       double *__restrict__ sums)      // (the pyramid keeps the fp64 sums; else null)
@@ -44,15 +57,28 @@ __global__ __launch_bounds__(256) void k_cell_moments(DevParams P, const int *__
     const int b = cell_start[c], n = min(cell_start[c + 1] - b, P.max_per_cell);
     const size_t cap = (size_t)P.sorted_cap;
     double S = 0.0, Sx = 0.0, Sy = 0.0, Sz = 0.0;
+    double Q[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int j0 = 0; j0 < n; j0 += 64) {
         const int j = j0 + lane;
         double w = 0.0, wx = 0.0, wy = 0.0, wz = 0.0;
+        double q[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         if (j < n) {
             w = (double)snap[3 * cap + b + j];
             wx = w * (double)snap[b + j]; wy = w * (double)snap[cap + b + j]; wz = w * (double)snap[2 * cap + b + j];
+            if (QUAD) {
+                const double wa[3] = {wx, wy, wz}, xb[3] = {(double)snap[b + j], (double)snap[cap + b + j], (double)snap[2 * cap + b + j]};
+#pragma unroll
+                for (int f = 0; f < 6; f++) q[f] = __dmul_rn(wa[QUAD_A[f]], xb[QUAD_B[f]]);
+            }
         }
         const int m = min(64, n - j0);
-        for (int k = 0; k < m; k++) { S += lane_f64(w, k); Sx += lane_f64(wx, k); Sy += lane_f64(wy, k); Sz += lane_f64(wz, k); }
+        for (int k = 0; k < m; k++) {
+            S += lane_f64(w, k); Sx += lane_f64(wx, k); Sy += lane_f64(wy, k); Sz += lane_f64(wz, k);
+            if (QUAD) {
+#pragma unroll
+                for (int f = 0; f < 6; f++) Q[f] = __dadd_rn(Q[f], lane_f64(q[f], k));
+            }
+        }
     }
     if (lane == 0) {
         const bool none = S == 0.0;          // an empty cell, or kids only
@@ -63,6 +89,14 @@ __global__ __launch_bounds__(256) void k_cell_moments(DevParams P, const int *__
         const int GG = P.G * P.G, i3 = c / GG, rem = c - i3 * GG, i1 = rem / P.G;
         mom_j[c] = (i3 << 20) | (i1 << 10) | (rem - i1 * P.G);
         if (sums) { sums[c] = S; sums[mom_cap + c] = Sx; sums[2 * (size_t)mom_cap + c] = Sy; sums[3 * (size_t)mom_cap + c] = Sz; }
+        if (QUAD) {
+            const double Sa[3] = {Sx, Sy, Sz};
+#pragma unroll
+            for (int f = 0; f < 6; f++) {
+                mom[(4 + f) * (size_t)mom_cap + c] = none ? 0.f : far_central(Q[f], Sa[QUAD_A[f]], Sa[QUAD_B[f]], S);
+                sums[(4 + f) * (size_t)mom_cap + c] = Q[f];
+            }
+        }
     }
 }
 
@@ -73,6 +107,7 @@ __device__ __forceinline__ int wave_max_i(int v)
 }
 
 // One thread per cell of level l >= 1: the fp64 sums of its children in ascending child index, each started at +0.
+template <bool QUAD>
 __global__ __launch_bounds__(256) void k_level_moments(const FarLevels lev, int l, float *__restrict__ mom, int *__restrict__ mom_j,
                                                        double *__restrict__ sums, int mom_cap)
 {
@@ -82,11 +117,16 @@ __global__ __launch_bounds__(256) void k_level_moments(const FarLevels lev, int 
     const size_t cap = (size_t)mom_cap;
     const double *cs = sums + lev.off[l - 1];
     double S = 0.0, Sx = 0.0, Sy = 0.0, Sz = 0.0;
+    double Q[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int c3 = 2 * k3; c3 <= min(2 * k3 + 1, Gc - 1); c3++)
         for (int c1 = 2 * k1; c1 <= min(2 * k1 + 1, Gc - 1); c1++)
             for (int c2 = 2 * k2; c2 <= min(2 * k2 + 1, Gc - 1); c2++) {
                 const int ci = (c3 * Gc + c1) * Gc + c2;
                 S += cs[ci]; Sx += cs[cap + ci]; Sy += cs[2 * cap + ci]; Sz += cs[3 * cap + ci];
+                if (QUAD) {
+#pragma unroll
+                    for (int f = 0; f < 6; f++) Q[f] = __dadd_rn(Q[f], cs[(4 + f) * cap + ci]);
+                }
             }
     const int o = lev.off[l] + k;
     const bool none = S == 0.0;
@@ -96,6 +136,14 @@ __global__ __launch_bounds__(256) void k_level_moments(const FarLevels lev, int 
     mom[2 * cap + o] = none ? 0.f : (float)(Sz / S);
     mom[3 * cap + o] = none ? 0.f : (float)S;
     mom_j[o] = (k3 << 20) | (k1 << 10) | k2;
+    if (QUAD) {
+        const double Sa[3] = {Sx, Sy, Sz};
+#pragma unroll
+        for (int f = 0; f < 6; f++) {
+            sums[(4 + f) * cap + o] = Q[f];
+            mom[(4 + f) * cap + o] = none ? 0.f : far_central(Q[f], Sa[QUAD_A[f]], Sa[QUAD_B[f]], S);
+        }
+    }
 }
 
 // The moments of the frame's snapshot, of the cells (far monopoles) or of every level (the pyramid, which keeps the fp64
@@ -103,26 +151,40 @@ __global__ __launch_bounds__(256) void k_level_moments(const FarLevels lev, int 
 // before the pair stage has run -- the same kernels on the same snapshot, the same bits in the same buffers.
 void launch_far_moments(hipStream_t st, const DevParams &P, const DeviceState &d)
 {
-    const bool pyramid = (P.flags & PSAMD_FLAG_FAR_PYRAMID) != 0;
-    k_cell_moments<<<(P.num_cells + 3) / 4, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.cell_mom, d.cell_mom_j, d.mom_cap,
-                                                          pyramid ? d.lev_sum : nullptr);
+    const bool pyramid = (P.flags & PSAMD_FLAG_FAR_PYRAMID) != 0, quad = (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) != 0;
+    const unsigned cell_wgs = (unsigned)((P.num_cells + 3) / 4);
+    if (quad) k_cell_moments<true><<<cell_wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.cell_mom, d.cell_mom_j, d.mom_cap, d.lev_sum);
+    else k_cell_moments<false><<<cell_wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.cell_mom, d.cell_mom_j, d.mom_cap,
+                                                         pyramid ? d.lev_sum : nullptr);
     if (!pyramid) return;
     const FarLevels &lev = d.lev;
-    for (int l = 1; l < lev.n; l++)
-        k_level_moments<<<(lev.G[l] * lev.G[l] * lev.G[l] + 255) / 256, 256, 0, st>>>(lev, l, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap);
+    for (int l = 1; l < lev.n; l++) {
+        const unsigned wgs = (unsigned)((lev.G[l] * lev.G[l] * lev.G[l] + 255) / 256);
+        if (quad) k_level_moments<true><<<wgs, 256, 0, st>>>(lev, l, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap);
+        else k_level_moments<false><<<wgs, 256, 0, st>>>(lev, l, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap);
+    }
 }
 
 // (the pyramid's instances at 6 waves a SIMD, not the flat ones' 7: the parent compare per body costs registers -- at 7 the
 // compiler's report shows 68 bytes of scratch a lane in the exact instance, at 6 it shows 8 (80 VGPRs); by that report, not
 // by a timing)
 constexpr int PYRAMID_WAVES = 6;
+// (the quadrupole instances at 5: by the compiler's report, at 6 they spill 48 (fast) and 104 (exact) bytes of scratch a lane
+// in 80 VGPRs; at 5 the fast one takes 93 VGPRs and none, the exact one 96 and 8; at 4 the exact one takes 103 and none, which
+// does not pay for a wave)
+constexpr int QUAD_WAVES = 5;
 
 // The force walk of both methods.  PYRAMID is a compile-time parameter: the flat instances have l = 0 and top = true as
 // constants and carry neither the level arithmetic nor the parent compare.  mom, mom_j: at.mom and at.mom_j once more, as
 // __restrict__ kernel arguments -- what tells the compiler that the store of the partial sums does not touch the moments, so
 // that they stay scalar loads (a pointer inside a struct cannot say it).
-template <int MODE, bool PYRAMID>
-__global__ __launch_bounds__(256, PYRAMID ? PYRAMID_WAVES : BALANCED_WAVES) void k_far_walk(DevParams P, const SnapSoa snap4,
+//
+// QUAD (PSAMD_FLAG_FAR_QUADRUPOLE, the pyramid only): every member adds its quadrupole term (far_walk.hpp, far_quad_term)
+// to a chain of its own per block -- from +0, in index order, behind the group's pair terms -- whose sums add up in block
+// order to +0 like the monopoles'; the part is RN(monopole sum + quadrupole sum).  The six C planes lie behind the four of
+// mom, so they come through the same __restrict__ argument as wave-uniform loads.
+template <int MODE, bool PYRAMID, bool QUAD>
+__global__ __launch_bounds__(256, QUAD ? QUAD_WAVES : PYRAMID ? PYRAMID_WAVES : BALANCED_WAVES) void k_far_walk(DevParams P, const SnapSoa snap4,
                                                                                              const int *__restrict__ act_start,
                                                                                              const int *__restrict__ dense_gi,
                                                                                              const int *__restrict__ dense_cell,
@@ -173,6 +235,7 @@ __global__ __launch_bounds__(256, PYRAMID ? PYRAMID_WAVES : BALANCED_WAVES) void
     if (PYRAMID) far_blocks(lev, box, blk_lo, blk_hi);
     else { blk_lo = lev.nblk * part / ALLP_PARTS; blk_hi = lev.nblk * (part + 1) / ALLP_PARTS; }
     float px = 0.f, py = 0.f, pz = 0.f;                     // the part's sum
+    float ux = 0.f, uy = 0.f, uz = 0.f;                     // ... and its quadrupole sum
     for (int blk = blk_lo; blk < blk_hi; blk++) {
         // lane = cell: which of the block's 64 cells hold mass at all, and which of those lie in the box
         const int base = lev.off + blk * 64;
@@ -184,25 +247,34 @@ __global__ __launch_bounds__(256, PYRAMID ? PYRAMID_WAVES : BALANCED_WAVES) void
         if (evalm == 0ull) continue;                        // (a chain of nothing is +0, and the part's sum never is -0)
         const float *sx = m.mom + base, *sy = sx + m.mom_cap, *sz = sy + m.mom_cap, *sw = sz + m.mom_cap;
         float ax, ay, az;                                   // the block's chain
-        far_block_chain<MODE>(P, ctx, sx, sy, sz, sw, evalm, eps2f, [&](int g, v2f (&qw)[4]) {
+        float bx = 0.f, by = 0.f, bz = 0.f;                 // the block's quadrupole chain
+        const auto leave = [&](int g, v2f (&qw)[4]) {
             // outside the box no lane leaves anything out; inside it every lane asks for its own cell
             if (((nearm >> g) & 0xffull) == 0ull) return;
 #pragma unroll
             for (int k = 0; k < 8; k++) far_drop(qw, k, far_leaves_out(top, __builtin_amdgcn_readlane(jp, g + k), a1, a2, a3));
-        }, ax, ay, az);
+        };
+        if (QUAD) {
+            const float *sc = sw + m.mom_cap;
+            far_block_chain<MODE>(P, ctx, sx, sy, sz, sw, evalm, eps2f, leave, [&](int g, v2f (&qx)[4], v2f (&qy)[4], v2f (&qz)[4], v2f (&qw)[4]) {
+                far_quad_group(ctx, qx, qy, qz, qw, sc + g, m.mom_cap, eps2f, bx, by, bz);
+            }, ax, ay, az);
+            ux = __fadd_rn(ux, bx); uy = __fadd_rn(uy, by); uz = __fadd_rn(uz, bz);
+        } else far_block_chain<MODE>(P, ctx, sx, sy, sz, sw, evalm, eps2f, leave, ax, ay, az);
         px += ax; py += ay; pz += az;
     }
+    if (QUAD) { px = __fadd_rn(px, ux); py = __fadd_rn(py, uy); pz = __fadd_rn(pz, uz); }
     if (valid) far.part_acc[(size_t)part * far.part_plane + (size_t)r] = make_float4(px, py, pz, 0.f);
     }
 }
 
-template <bool PYRAMID>
+template <bool PYRAMID, bool QUAD>
 static void launch_far_walk(hipStream_t st, unsigned wgs, const DevParams &P, const DeviceState &d, bool fast, const FarCells &far)
 {
     const SnapSoa snap4{d.snap_soa, (size_t)P.sorted_cap};
     const FarMoments m = far_moments_of(P, d);
-    if (fast) k_far_walk<2, PYRAMID><<<wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, m, m.mom, m.mom_j);
-    else k_far_walk<1, PYRAMID><<<wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, m, m.mom, m.mom_j);
+    if (fast) k_far_walk<2, PYRAMID, QUAD><<<wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, m, m.mom, m.mom_j);
+    else k_far_walk<1, PYRAMID, QUAD><<<wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, m, m.mom, m.mom_j);
 }
 
 // What ran before is the stencil's chain (the two-pass pair stage: contexts with either flag are created only with it, only
@@ -217,8 +289,9 @@ void launch_far_field(hipStream_t st, const DevParams &P, const DeviceState &d, 
     const int64_t dense_bound = far_dense_bound(P, d, live_bound);
     launch_dense_order(st, P, d);
     const unsigned far_wgs = (unsigned)((dense_bound * parts + 3) / 4);
-    if (pyramid) launch_far_walk<true>(st, far_wgs, P, d, fast, far);
-    else launch_far_walk<false>(st, far_wgs, P, d, fast, far);
+    if (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) launch_far_walk<true, true>(st, far_wgs, P, d, fast, far);
+    else if (pyramid) launch_far_walk<true, false>(st, far_wgs, P, d, fast, far);
+    else launch_far_walk<false, false>(st, far_wgs, P, d, fast, far);
     launch_far_combine(st, P, d, far, parts, dense_bound);
 }
 

@@ -267,16 +267,17 @@ int psamd_download_force_counts(psamd_ctx *c, int32_t *out)
     return PSAMD_OK;
 }
 
-// n cells from `first` of the four moment planes, as float4 = (X, Y, Z, M); waits for the stream
-static int download_moments(psamd_ctx *c, size_t first, size_t n, float *o)
+// n cells from `first` of `count` moment planes from plane `plane0` on, cell by cell: float4 = (X, Y, Z, M) of the four
+// first planes, float[6] = (Cxx, Cyy, Czz, Cxy, Cxz, Cyz) of the six behind them; waits for the stream
+static int download_moments(psamd_ctx *c, size_t first, size_t n, float *o, size_t plane0 = 0, size_t count = 4)
 {
     const size_t cap = (size_t)c->d.mom_cap;
-    std::vector<float> planes(4 * n);
-    for (size_t f = 0; f < 4; f++)
-        PS_HIP(c, hipMemcpyAsync(planes.data() + f * n, c->d.cell_mom + f * cap + first, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    std::vector<float> planes(count * n);
+    for (size_t f = 0; f < count; f++)
+        PS_HIP(c, hipMemcpyAsync(planes.data() + f * n, c->d.cell_mom + (plane0 + f) * cap + first, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     PS_HIP(c, hipStreamSynchronize(c->stream));
     for (size_t k = 0; k < n; k++)
-        for (size_t f = 0; f < 4; f++) o[4 * k + f] = planes[f * n + k];
+        for (size_t f = 0; f < count; f++) o[count * k + f] = planes[f * n + k];
     return PSAMD_OK;
 }
 
@@ -308,6 +309,17 @@ int psamd_download_level_moments(psamd_ctx *c, int32_t level, void *out)
     if (!pairs_done(c->stage)) return fail(c, PSAMD_ERR_STATE, "level moments requested before the pair pass of this frame");
     const size_t G = (size_t)lev.G[level];
     return download_moments(c, (size_t)lev.off[level], G * G * G, static_cast<float *>(out));
+}
+
+int psamd_download_level_quadrupoles(psamd_ctx *c, int32_t level, void *out)
+{
+    if (!c || !out) return PSAMD_ERR_INVALID_ARG;
+    if (!(c->P.flags & PSAMD_FLAG_FAR_QUADRUPOLE)) return fail(c, PSAMD_ERR_UNSUPPORTED, "level quadrupoles are formed on a context with quadrupoles on the pyramid (PSAMD_FLAG_FAR_QUADRUPOLE) only");
+    const FarLevels &lev = c->d.lev;
+    if (level < 0 || level >= lev.n) return fail(c, PSAMD_ERR_INVALID_ARG, "level quadrupoles: no such level");
+    if (!pairs_done(c->stage)) return fail(c, PSAMD_ERR_STATE, "level quadrupoles requested before the pair pass of this frame");
+    const size_t G = (size_t)lev.G[level];
+    return download_moments(c, (size_t)lev.off[level], G * G * G, static_cast<float *>(out), 4, 6);
 }
 
 int psamd_download_chunkgrid(psamd_ctx *c, int32_t *out)

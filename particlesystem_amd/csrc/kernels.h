@@ -190,14 +190,14 @@ struct DeviceState {
     int *dense_cell = nullptr;    // all-pairs: [container] its cell
     // far monopoles (PSAMD_FLAG_FAR_MONOPOLE; part_acc .. dense_cell above are this pass's too): per cell of the box,
     // padded with zeros to whole blocks of 64 cells, the planes X, Y, Z, M and the cell's packed grid coordinates
-    float *cell_mom = nullptr;    // [4][mom_cap]
+    float *cell_mom = nullptr;    // [4][mom_cap]; with quadrupoles (PSAMD_FLAG_FAR_QUADRUPOLE) [10][mom_cap]: Cxx, Cyy, Czz, Cxy, Cxz, Cyz behind
     int *cell_mom_j = nullptr;    // [mom_cap] (i3 << 20) | (i1 << 10) | i2
     int mom_cap = 0;
     // the levels of those planes (mom_cap == lev.off[lev.n]): one, the cell grid, on a flat context; on the pyramid
     // (PSAMD_FLAG_FAR_PYRAMID) every level, level 0 first, so the cells' moments are where the far monopoles have them, and
     // the fp64 sums S, Sx, Sy, Sz the levels add up
     FarLevels lev;
-    double *lev_sum = nullptr;    // [4][mom_cap]
+    double *lev_sum = nullptr;    // [4][mom_cap]; with quadrupoles [10][mom_cap]: the raw Sxx, Syy, Szz, Sxy, Sxz, Syz behind
     DevCounters *ctr = nullptr;
     // psamd_export_live: per tile of SLOT_TILE owned slots, the live count and the statistics' partials; the context's own result record
     int *exp_count = nullptr;

@@ -203,8 +203,12 @@ static bool far_context(const psamd_ctx *c) { return (c->P.flags & (PSAMD_FLAG_F
 // potential and probe promise exactly the bodies the force pass walks: with far monopoles (flat or as a pyramid) a
 // stencil-only answer would break that silently, and a caller written for the stencil's bodies is never handed another
 // quantity -- the monopole form is served only where it is asked for (PSAMD_POTENTIAL_FAR, PSAMD_PROBE_FAR)
+// ... and on a quadrupole context (PSAMD_FLAG_FAR_QUADRUPOLE) the far form is monopoles only: not that context's field either
 static int refuse_far_monopole(psamd_ctx *c, const char *who, bool far_asked)
 {
+    if (c->P.flags & PSAMD_FLAG_FAR_QUADRUPOLE)
+        return fail(c, PSAMD_ERR_UNSUPPORTED, std::string(who) + ": the far form is monopoles only; a context with quadrupoles on the pyramid "
+                                              "(PSAMD_FLAG_FAR_QUADRUPOLE) is not served");
     if (far_context(c) && !far_asked)
         return fail(c, PSAMD_ERR_UNSUPPORTED, std::string(who) + ": on a context with far monopoles (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID) "
                                               "only the far form is served (PSAMD_POTENTIAL_FAR, psamd_download_potential_far, PSAMD_PROBE_FAR)");

@@ -253,11 +253,17 @@ __device__ __forceinline__ void commit_move(const DevParams &P, const StepState 
     }
 }
 
+// what a replayed operation needs to drop its particle; what a thread has counted for the step's counters
+struct CommitCtx {
+    const DevParams &P; const StepState *__restrict__ stp; MoveRec *moves; const ParticleArrays &A; const float4 *__restrict__ stage;
+    __device__ __forceinline__ void commit(int m, int dst) const { commit_move(P, stp, moves, m, dst, A, stage); }
+};
+struct ReplayTally { unsigned long long lost = 0, reloc = 0, births = 0, births_failed = 0; };
+
 // q_insert / q_remove exactly as the reference's (app_common.cu:305-376), one at a time: what the lists are walked
 // with when a queue is about to run empty or to fill up.  The queue's slots are read and written through `at`.
-struct SerialTally { unsigned long long lost = 0, reloc = 0, births = 0, births_failed = 0; };
 template <typename At>
-__device__ __forceinline__ void serial_op(QueueInfo &q, int sub, int arg, At at, MoveRec *moves, SerialTally &t)
+__device__ __forceinline__ void serial_op(QueueInfo &q, int sub, int arg, At at, MoveRec *moves, ReplayTally &t)
 {
     if (sub == 2) {                                // q_insert(arg), app_common.cu:346-376
         if (q.count == q.seg_size) return;
@@ -324,25 +330,102 @@ struct ReplayLds {
     uint64_t *kbuf; int *abuf; int *window; unsigned char *sub; int *wave_tot; int *flag;
 };
 
-// A list of at most CAP operations: rank them by key in LDS, then replay.  When the queue provably neither runs
-// empty nor fills up during the step (prefix sums of +1/-1 over the sorted operations), every operation's effect on
-// the circular FIFO has a closed form -- the k-th remove takes logical element k, the
-// k-th insert becomes logical element count0 + k -- and all of them are applied at once;
-// otherwise one lane walks the list exactly as q_insert / q_remove do.
-template <int CAP>
-__device__ __forceinline__ void replay_short(const DevParams &P, const int rec, const int start, const int n,
-                                             const uint64_t *__restrict__ keys, const int *__restrict__ args,
-                                             QueueInfo *qinfo, int *queue, MoveRec *moves, DevCounters *ctr,
-                                             const StepState *__restrict__ stp, const ParticleArrays &A, const float4 *__restrict__ stage,
-                                             const ReplayLds<CAP> &L)
+// ------------------------------------------------------------------ the replay of a sorted list: the pieces both roads call
+// When the queue provably neither runs empty nor fills up during the step (prefix sums of +1/-1 over the sorted
+// operations), every operation's effect on the circular FIFO has a closed form -- the k-th remove takes logical
+// element k, the k-th insert becomes logical element count0 + k -- applied at once on the queue in global memory (only
+// the R + I touched entries move); otherwise one lane walks the list exactly as q_insert / q_remove do.  A road owns its
+// sort and the loops in which a thread meets its operations with their (insert, remove) prefixes.
+// Every function below that contains barriers is reached by all REPLAY_THREADS threads of the workgroup or by none.
+// the key bits below the record bits: (chunk, id, sub)
+__device__ __forceinline__ uint64_t key_low_mask(const DevParams &P) { return P.key_rec_shift >= 64 ? ~0ull : ((1ull << P.key_rec_shift) - 1ull); }
+
+// one queue record's step; ins_arg: the list's insert arguments in list order (short road: LDS, long: the ping-pong's dead side)
+struct ClosedForm {
+    int *seg, *ins_arg; int count0, size, F;           // F: offset of logical element 0
+    // would this operation meet an empty or a full queue?
+    __device__ __forceinline__ bool meets_end(int sub, int ins_b, int rem_b) const
+    {
+        const int c = count0 + ins_b - rem_b;
+        return sub == 2 ? !(c < size) : !(c >= 2);
+    }
+    // the rem_b-th remove takes an element the queue had, or one of this step's inserts
+    __device__ __forceinline__ void remove(const CommitCtx &C, int sub, int arg, int rem_b, ReplayTally &t) const
+    {
+        const int item = (rem_b < count0) ? seg[(F + rem_b) % size] : ins_arg[rem_b - count0];
+        C.moves[arg].dst = item;
+        C.commit(arg, item);
+        if (sub == 1) t.reloc++; else t.births++;
+    }
+    // the queue after I inserts and R removes (barriers; the first one stands behind the last remove(), which reads what is cleared here)
+    __device__ __forceinline__ void finish(QueueInfo &q, int I, int R) const
+    {
+        constexpr int NT = REPLAY_THREADS;
+        const int tid = threadIdx.x;
+        __syncthreads();
+        for (int r = tid; r < R; r += NT) seg[(F + r) % size] = -1;             // every removed element
+        __syncthreads();
+        for (int k = tid; k < I; k += NT)                                        // inserts that stayed
+            if (count0 + k >= R) seg[(F + count0 + k) % size] = ins_arg[k];
+        if (tid == 0) {
+            q.count = count0 + I - R;
+            q.front = q.rloc + (F + R) % size;
+            q.rear = q.rloc + (F + count0 + I - 1) % size;
+        }
+    }
+};
+
+// Rare (a queue about to run empty or fill up): lane 0 walks the list exactly as q_insert / q_remove do, on a copy of
+// the segment in the LDS window when it fits, and every thread commits the removes from what the walk left in
+// moves[].dst (barriers; none between copying the window out and committing: they touch different arrays).
+template <typename Sub, typename Arg>
+__device__ __forceinline__ ReplayTally serial_walk(const CommitCtx &C, QueueInfo &q, int *queue, int *window, bool in_lds, int n, Sub sub, Arg arg)
 {
     constexpr int NT = REPLAY_THREADS;
+    const int tid = threadIdx.x;
+    ReplayTally t;
+    if (in_lds) for (int e = tid; e < q.seg_size; e += NT) window[e] = queue[q.rloc + e];
+    __syncthreads();
+    if (tid == 0) {
+        if (in_lds) for (int e = 0; e < n; e++) serial_op(q, sub(e), arg(e), [&](int pos) -> int & { return window[pos - q.rloc]; }, C.moves, t);
+        else for (int e = 0; e < n; e++) serial_op(q, sub(e), arg(e), [&](int pos) -> int & { return queue[pos]; }, C.moves, t);
+    }
+    __syncthreads();                                   // (the walk's moves[].dst, for every thread of the workgroup)
+    if (in_lds) for (int e = tid; e < q.seg_size; e += NT) queue[q.rloc + e] = window[e];
+    for (int e = tid; e < n; e += NT)
+        if (sub(e) != 2) C.commit(arg(e), C.moves[arg(e)].dst);
+    return t;
+}
+
+// the way out of both roads: the queue record, the counters as a wave's sums and one lane's atomics (every lane gets here)
+__device__ __forceinline__ void replay_done(QueueInfo *qinfo, int rec, const QueueInfo &q, DevCounters *ctr, const ReplayTally &t)
+{
+    if (threadIdx.x == 0) qinfo[rec] = q;
+    DevCounters *mine = ctr + (blockIdx.x % COUNTER_COPIES);
+    const unsigned long long reloc = (unsigned long long)wave_incl_scan((int)t.reloc), births = (unsigned long long)wave_incl_scan((int)t.births),
+                             lost = (unsigned long long)wave_incl_scan((int)t.lost), births_failed = (unsigned long long)wave_incl_scan((int)t.births_failed);
+    if ((threadIdx.x & 63) == 63) {
+        if (reloc) atomicAdd(&mine->relocations, reloc);
+        if (births) atomicAdd(&mine->births, births);
+        if (lost) atomicAdd(&mine->relocations_lost, lost);
+        if (births_failed) atomicAdd(&mine->births_failed, births_failed);
+    }
+}
+
+// A list of at most CAP operations.  This road owns the sort -- the operations ranked by key in LDS -- and the
+// enumeration: consecutive operations per thread, their prefixes from one packed scan.  The rest is the shared replay.
+template <int CAP>
+__device__ __forceinline__ void replay_short(const CommitCtx &C, const int rec, const int start, const int n,
+                                             const uint64_t *__restrict__ keys, const int *__restrict__ args,
+                                             QueueInfo *qinfo, int *queue, DevCounters *ctr, const ReplayLds<CAP> &L)
+{
+    constexpr int NT = REPLAY_THREADS;
+    const DevParams &P = C.P;
     uint64_t *kbuf = L.kbuf;
-    int *abuf = L.abuf, *window = L.window, *wave_tot = L.wave_tot;
+    int *abuf = L.abuf, *wave_tot = L.wave_tot;
     unsigned char *s_sub = L.sub;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     QueueInfo q = qinfo[rec];
-    const bool in_lds = q.seg_size <= ReplayLds<CAP>::WINDOW_SLOTS;
     queue += slot_index(P, q.rloc) - q.rloc;           // owned segments only, back to back
     // Inside one bucket the record bits of the keys are all the same: what is sorted is (chunk, id, sub) with the
     // operation's place in the bucket packed in below it -- one 8-byte word per operation, its argument fetched
@@ -351,7 +434,7 @@ __device__ __forceinline__ void replay_short(const DevParams &P, const int rec, 
     constexpr int IDX_BITS = CAP == 2048 ? 11 : CAP == 4096 ? 12 : 13;
     static_assert((1 << IDX_BITS) >= CAP, "an operation's place in the bucket must fit");
     const bool packed_keys = P.key_rec_shift + IDX_BITS <= 64;              // (else, a geometry with > 2^51 (chunk, id) pairs: keys and arguments side by side)
-    const uint64_t low_mask = P.key_rec_shift >= 64 ? ~0ull : ((1ull << P.key_rec_shift) - 1ull);
+    const uint64_t low_mask = key_low_mask(P);
     for (int e = tid; e < n; e += NT) {
         const uint64_t k = keys[start + e];
         kbuf[e] = packed_keys ? (((k & low_mask) << IDX_BITS) | (uint64_t)e) : k;
@@ -384,9 +467,6 @@ __device__ __forceinline__ void replay_short(const DevParams &P, const int rec, 
         for (int e = tid; e < n; e += NT) s_sub[e] = (unsigned char)(kbuf[e] & 3ull);
     }
     __syncthreads();
-    const int *s_arg = abuf;
-    int *ins_arg = (int *)kbuf;                        // keys no longer needed
-
     // prefix counts of inserts / removes before each of my (up to CAP / NT consecutive) operations
     const int per = (n + NT - 1) / NT, e0 = tid * per, e1 = min(n, e0 + per);
     int my_ins = 0, my_rem = 0;
@@ -398,87 +478,40 @@ __device__ __forceinline__ void replay_short(const DevParams &P, const int rec, 
     int off = 0, total = 0;
     for (int k = 0; k < NT / 64; k++) { if (k < wv) off += wave_tot[k]; total += wave_tot[k]; }
     const int excl = off + incl - packed;
-    int ins_b = excl & 0xffff, rem_b = excl >> 16;
-    const int I = total & 0xffff, R = total >> 16;
-    const int count0 = q.count, size = q.seg_size;
-    {   // would any operation meet an empty or a full queue?
-        int ib = ins_b, rb = rem_b;
-        bool bad = (count0 <= 0);
-        for (int e = e0; e < e1; e++) {
-            const int c = count0 + ib - rb;
-            if (s_sub[e] == 2) { bad |= !(c < size); ib++; } else { bad |= !(c >= 2); rb++; }
-        }
-        if (bad) *L.flag = 1;
-    }
+    const int ins_b = excl & 0xffff, rem_b = excl >> 16, I = total & 0xffff, R = total >> 16;
+    const int *s_arg = abuf;
+    int *ins_arg = (int *)kbuf;                        // keys no longer needed
+    const ClosedForm cf{queue + q.rloc, ins_arg, q.count, q.seg_size, q.front - q.rloc};
+    bool bad = q.count <= 0;
+    for (int e = e0, ib = ins_b, rb = rem_b; e < e1; e++) { bad |= cf.meets_end(s_sub[e], ib, rb); if (s_sub[e] == 2) ib++; else rb++; }
+    if (bad) *L.flag = 1;
     __syncthreads();
-    unsigned long long lost = 0, reloc = 0, births = 0, births_failed = 0;
-    if (*L.flag) {
-        // rare (a queue about to run empty or fill up): one lane walks the list exactly as
-        // q_insert / q_remove do, on a copy of the segment in LDS when it fits
-        if (in_lds) { for (int e = tid; e < q.seg_size; e += NT) window[e] = queue[q.rloc + e]; __syncthreads(); }
-        if (tid == 0) {
-            SerialTally t;
-            if (in_lds) for (int e = 0; e < n; e++) serial_op(q, s_sub[e], s_arg[e], [&](int pos) -> int & { return window[pos - q.rloc]; }, moves, t);
-            else for (int e = 0; e < n; e++) serial_op(q, s_sub[e], s_arg[e], [&](int pos) -> int & { return queue[pos]; }, moves, t);
-            lost = t.lost; reloc = t.reloc; births = t.births; births_failed = t.births_failed;
-        }
-        __syncthreads();                               // (the walk's moves[].dst, for every thread of the workgroup)
-        if (in_lds) for (int e = tid; e < q.seg_size; e += NT) queue[q.rloc + e] = window[e];
-        for (int e = tid; e < n; e += NT)
-            if (s_sub[e] != 2) commit_move(P, stp, moves, s_arg[e], moves[s_arg[e]].dst, A, stage);
-    } else {
-        // closed form, straight on the queue in global memory: only the R + I touched entries move
-        int *seg = queue + q.rloc;
-        const int F = q.front - q.rloc;                // offset of logical element 0
+    ReplayTally t;
+    if (*L.flag)
+        t = serial_walk(C, q, queue, L.window, q.seg_size <= ReplayLds<CAP>::WINDOW_SLOTS, n, [=](int e) { return (int)s_sub[e]; }, [=](int e) { return s_arg[e]; });
+    else {
         for (int e = e0, ib = ins_b; e < e1; e++) if (s_sub[e] == 2) ins_arg[ib++] = s_arg[e];
         __syncthreads();
-        for (int e = e0, rb = rem_b; e < e1; e++)
-            if (s_sub[e] != 2) {
-                const int item = (rb < count0) ? seg[(F + rb) % size] : ins_arg[rb - count0];
-                moves[s_arg[e]].dst = item;
-                commit_move(P, stp, moves, s_arg[e], item, A, stage);
-                if (s_sub[e] == 1) reloc++; else births++;
-                rb++;
-            }
-        __syncthreads();
-        for (int r = tid; r < R; r += NT) seg[(F + r) % size] = -1;             // every removed element
-        __syncthreads();
-        for (int k = tid; k < I; k += NT)                                        // inserts that stayed
-            if (count0 + k >= R) seg[(F + count0 + k) % size] = ins_arg[k];
-        if (tid == 0) {
-            q.count = count0 + I - R;
-            q.front = q.rloc + (F + R) % size;
-            q.rear = q.rloc + (F + count0 + I - 1) % size;
-        }
+        for (int e = e0, rb = rem_b; e < e1; e++) if (s_sub[e] != 2) cf.remove(C, s_sub[e], s_arg[e], rb++, t);
+        cf.finish(q, I, R);
     }
-    __syncthreads();
-    if (tid == 0) qinfo[rec] = q;
-    DevCounters *mine = ctr + (blockIdx.x % COUNTER_COPIES);
-    reloc = (unsigned long long)wave_incl_scan((int)reloc); births = (unsigned long long)wave_incl_scan((int)births);
-    lost = (unsigned long long)wave_incl_scan((int)lost); births_failed = (unsigned long long)wave_incl_scan((int)births_failed);
-    if (lane == 63) {
-        if (reloc) atomicAdd(&mine->relocations, reloc);
-        if (births) atomicAdd(&mine->births, births);
-        if (lost) atomicAdd(&mine->relocations_lost, lost);
-        if (births_failed) atomicAdd(&mine->births_failed, births_failed);
-    }
+    replay_done(qinfo, rec, q, ctr, t);
 }
 
 // A list LONGER than the instance sorts in LDS (a collapsing cloud; 1024 particles per cell; queue record 0, where the
-// reference frees overflow-killed slots, ps.cpp:1523-1526; or simply a step whose lists outgrew the host's hint):
-// the same workgroup sorts it in global memory -- its bucket [start, start + n) of the sorted arrays, with the same
-// range of the unsorted arrays (dead once bucketed) as the other side of a ping-pong -- by most-significant-digit
-// radix partition, 8 bits a level below the keys' common prefix, down to ranges the LDS network takes; then streams
-// the sorted list through the closed form in chunks of one operation per thread (three passes: count and check,
-// removes, queue update), or walks it with one lane when the queue would run empty or fill up.  Keys are distinct
-// (record | chunk | slot | sub-step), so the order is the reference's serial order whatever the partitions did.
+// reference frees overflow-killed slots, ps.cpp:1523-1526; or simply a step whose lists outgrew the host's hint).
+// This road owns the sort -- the same workgroup sorts the list in global memory: its bucket [start, start + n) of the
+// sorted arrays, with the same range of the unsorted arrays (dead once bucketed) as the other side of a ping-pong, by
+// most-significant-digit radix partition, 8 bits a level below the keys' common prefix, down to ranges the LDS
+// network takes -- and the enumeration: the sorted list streamed in chunks of one operation per thread, the prefixes
+// carried from chunk to chunk.  The rest is the shared replay, the insert list on the dead side of the ping-pong.  Keys are
+// distinct (record | chunk | slot | sub-step), so the order is the reference's serial order whatever the partitions did.
 // (Until round 5 this was the HOST's business: it read the step's scalars, saw a list beyond the replay's reach and
 // launched a radix sort of all keys plus a streamed replay -- which kept the host on every step's critical path.)
 template <int CAP>
-__device__ void replay_long(const DevParams &P, const int rec, const int start, const int n,
+__device__ void replay_long(const CommitCtx &C, const int rec, const int start, const int n,
                             uint64_t *keys, int *args, uint64_t *keys2, int *args2,
-                            QueueInfo *qinfo, int *queue, MoveRec *moves, DevCounters *ctr,
-                            const StepState *__restrict__ stp, const ParticleArrays &A, const float4 *__restrict__ stage,
+                            QueueInfo *qinfo, int *queue, DevCounters *ctr,
                             const ReplayLds<CAP> &L, int (*s_cnt)[256], int *s_cur, int *s_misc)
 {
     constexpr int NT = REPLAY_THREADS;
@@ -495,7 +528,7 @@ __device__ void replay_long(const DevParams &P, const int rec, const int start, 
     __syncthreads();
     for (int k = 0; k < NT / 64; k++) { k_or |= red[2 * k]; k_and &= red[2 * k + 1]; }
     __syncthreads();
-    const uint64_t diff = (k_or ^ k_and) & (P.key_rec_shift >= 64 ? ~0ull : ((1ull << P.key_rec_shift) - 1ull));
+    const uint64_t diff = (k_or ^ k_and) & key_low_mask(C.P);
     const int top = diff ? 64 - __builtin_clzll(diff) : 0;     // bits [0, top) distinguish the keys
 
     // tile: range [lo, lo + len), len <= CAP, living on side `side` -> sorted, on side 0
@@ -599,13 +632,12 @@ __device__ void replay_long(const DevParams &P, const int rec, const int start, 
     }
     __syncthreads();
 
-    // ---- the sorted list, streamed: keys / args = side 0, scratch for the insert arguments = side 1's args
+    // ---- the sorted list, streamed: keys / args = side 0, the insert arguments on side 1's args
     const uint64_t *skeys = K[0];
     const int *sargs = Ar[0];
-    int *scratch = Ar[1];
     QueueInfo q = qinfo[rec];
-    queue += slot_index(P, q.rloc) - q.rloc;                // the queue array is stored like the slots: only the owned segments, back to back
-    const int count0 = q.count, size = q.seg_size;
+    queue += slot_index(C.P, q.rloc) - q.rloc;              // the queue array is stored like the slots: only the owned segments, back to back
+    const ClosedForm cf{queue + q.rloc, Ar[1], q.count, q.seg_size, q.front - q.rloc};
     int *s_carry = L.flag + 1, *s_bad = L.flag;
     // prefix of (inserts, removes) over one chunk of NT operations, carried from chunk to chunk
     auto chunk_scan = [&](int c0, int &sub, int &arg, int &ins_b, int &rem_b) {
@@ -623,69 +655,33 @@ __device__ void replay_long(const DevParams &P, const int rec, const int start, 
         if (tid == NT - 1) { s_carry[0] = oi + ii; s_carry[1] = orr + ir; }
         __syncthreads();
     };
-    if (tid == 0) { s_carry[0] = 0; s_carry[1] = 0; *s_bad = count0 <= 0 ? 1 : 0; }
+    if (tid == 0) { s_carry[0] = 0; s_carry[1] = 0; *s_bad = q.count <= 0 ? 1 : 0; }
     __syncthreads();
     for (int c0 = 0; c0 < n; c0 += NT) {
         int sub, arg, ins_b, rem_b;
         chunk_scan(c0, sub, arg, ins_b, rem_b);
         if (sub >= 0) {
-            const int c = count0 + ins_b - rem_b;
-            if (sub == 2) { if (!(c < size)) *s_bad = 1; scratch[ins_b] = arg; }
-            else if (!(c >= 2)) *s_bad = 1;
+            if (cf.meets_end(sub, ins_b, rem_b)) *s_bad = 1;
+            if (sub == 2) cf.ins_arg[ins_b] = arg;
         }
     }
     __syncthreads();
     const int I = s_carry[0], R = s_carry[1];
-    unsigned long long lost = 0, reloc = 0, births = 0, births_failed = 0;
-    if (!*s_bad) {
-        int *seg = queue + q.rloc;
-        const int F = q.front - q.rloc;                // offset of logical element 0
+    ReplayTally t;
+    if (*s_bad)
+        t = serial_walk(C, q, queue, L.window, q.seg_size <= ReplayLds<CAP>::WINDOW_SLOTS, n, [=](int e) { return (int)(skeys[e] & 3ull); }, [=](int e) { return sargs[e]; });
+    else {
         __syncthreads();
         if (tid == 0) { s_carry[0] = 0; s_carry[1] = 0; }
         __syncthreads();
         for (int c0 = 0; c0 < n; c0 += NT) {
             int sub, arg, ins_b, rem_b;
             chunk_scan(c0, sub, arg, ins_b, rem_b);
-            if (sub >= 0 && sub != 2) {
-                const int item = (rem_b < count0) ? seg[(F + rem_b) % size] : scratch[rem_b - count0];
-                moves[arg].dst = item;
-                commit_move(P, stp, moves, arg, item, A, stage);
-                if (sub == 1) reloc++; else births++;
-            }
+            if (sub >= 0 && sub != 2) cf.remove(C, sub, arg, rem_b, t);
         }
-        __syncthreads();
-        for (int r = tid; r < R; r += NT) seg[(F + r) % size] = -1;             // every removed element
-        __syncthreads();
-        for (int k = tid; k < I; k += NT)                                        // inserts that stayed
-            if (count0 + k >= R) seg[(F + count0 + k) % size] = scratch[k];
-        if (tid == 0) {
-            q.count = count0 + I - R;
-            q.front = q.rloc + (F + R) % size;
-            q.rear = q.rloc + (F + count0 + I - 1) % size;
-            qinfo[rec] = q;
-        }
-    } else {
-        const bool in_lds = q.seg_size <= ReplayLds<CAP>::WINDOW_SLOTS;
-        int *window = L.window;
-        if (in_lds) { for (int e = tid; e < q.seg_size; e += NT) window[e] = queue[q.rloc + e]; }
-        __syncthreads();
-        if (tid == 0) {
-            SerialTally t;
-            if (in_lds) for (int e = 0; e < n; e++) serial_op(q, (int)(skeys[e] & 3ull), sargs[e], [&](int pos) -> int & { return window[pos - q.rloc]; }, moves, t);
-            else for (int e = 0; e < n; e++) serial_op(q, (int)(skeys[e] & 3ull), sargs[e], [&](int pos) -> int & { return queue[pos]; }, moves, t);
-            lost = t.lost; reloc = t.reloc; births = t.births; births_failed = t.births_failed;
-            qinfo[rec] = q;
-        }
-        __syncthreads();
-        if (in_lds) for (int e = tid; e < q.seg_size; e += NT) queue[q.rloc + e] = window[e];
-        for (int e = tid; e < n; e += NT)
-            if ((skeys[e] & 3ull) != 2ull) commit_move(P, stp, moves, sargs[e], moves[sargs[e]].dst, A, stage);
+        cf.finish(q, I, R);
     }
-    DevCounters *mine = ctr + (blockIdx.x % COUNTER_COPIES);
-    if (reloc) atomicAdd(&mine->relocations, reloc);
-    if (lost) atomicAdd(&mine->relocations_lost, lost);
-    if (births) atomicAdd(&mine->births, births);
-    if (births_failed) atomicAdd(&mine->births_failed, births_failed);
+    replay_done(qinfo, rec, q, ctr, t);
 }
 
 // CAP: the longest list the instance sorts in LDS; one workgroup per queue record.  CAP = 2048: 27 KB of LDS, five
@@ -733,8 +729,9 @@ __global__ __launch_bounds__(REPLAY_THREADS) void k_replay_commit(DevParams P, i
     if (n <= 0) return;
     ReplayLds<CAP> L{reinterpret_cast<uint64_t *>(raw), reinterpret_cast<int *>(raw + ReplayLds<CAP>::KEY_BYTES), reinterpret_cast<int *>(raw),
                      s_sub, wave_tot, s_flag};
-    if (n <= CAP) replay_short<CAP>(P, rec, start, n, keys, args, qinfo, queue, moves, ctr, stp, A, stage, L);
-    else replay_long<CAP>(P, rec, start, n, keys, args, keys2, args2, qinfo, queue, moves, ctr, stp, A, stage, L, s_cnt, s_cur, s_misc);
+    const CommitCtx C{P, stp, moves, A, stage};
+    if (n <= CAP) replay_short<CAP>(C, rec, start, n, keys, args, qinfo, queue, ctr, L);
+    else replay_long<CAP>(C, rec, start, n, keys, args, keys2, args2, qinfo, queue, ctr, L, s_cnt, s_cur, s_misc);
 }
 
 // Relocation phase 1a on a slab, right after apply: the state of the departing particles goes into the outboxes

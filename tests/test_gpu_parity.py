@@ -391,15 +391,102 @@ def test_big_segments_replay_in_global_memory():
     assert g.counters["relocations"] > 1000
 
 
+BIG_SEGMENT = {"chunk_factor": 2, "chunk_dim": 8, "max_particles_num": 38 * 4096}      # 78 slots a cell, interior segments of 216 x 78
+
+
+def fill_cells(rng, ix, iy, iz, per=78):
+    """`per` particles in the middle of every cell of the box of cell indices ix x iy x iz (16^3 cells of 5.0 from -40)"""
+    ijk = np.stack(np.meshgrid(ix, iy, iz, indexing="ij"), -1).reshape(-1, 3)
+    lo = (-40.0 + 5.0 * ijk).astype(np.float32)
+    return (np.repeat(lo, per, axis=0) + rng.uniform(1.0, 4.0, (len(lo) * per, 3))).astype(np.float32)
+
+
+def big_segment_pair(xyz, v):
+    """particles at rest but for v (weight 1e-3: nothing pulls them out of their cells) around an interior segment of
+    16 848 slots, more than the LDS window of any replay instance (16 512 for the largest): (gpu, oracle, interior records)"""
+    g, o = make_pair(xyz, age=3.0, fert=1e6, w=np.float32(1e-3), vxyz=v, collision_radius=0.0, **BIG_SEGMENT)
+    assert g.sizes.seg_size_t[0] == 216 * 78 and 216 * 78 > (8192 + 64) * 2              # ReplayLds<8192>::WINDOW_SLOTS
+    return g, o, g.sizes.seg_count[0]
+
+
+def test_queue_runs_empty_on_a_segment_in_global_memory():
+    """The serial walk on a segment that fits no LDS window, reached from a SHORT list.  The interior segment of one
+    chunk, cells 1..6 along every axis, is filled to 48 free slots; 160 fast particles in the face layer x < -35 hop into
+    it in the first step while 40 of its own hop out: the queue runs empty in mid-list, 72 relocations are lost.  A
+    second group hops from beyond the opposite face into that face layer and drifts in at max_v during the following
+    steps: removes on a queue that is empty from the start.  Every step has far fewer than 2048 operations in all, so
+    each list is sorted in LDS whatever the instance."""
+    rng = np.random.default_rng(141)
+    free, n_in, n_out = 48, 160, 40
+    r6 = np.arange(1, 7)
+    inner = fill_cells(rng, r6, r6, r6)[:216 * 78 - free]
+
+    def yz():
+        return rng.uniform(-34.5, -5.5, (n_in, 2))
+    first = np.concatenate([rng.uniform(-39.5, -35.5, (n_in, 1)), yz()], axis=1).astype(np.float32)
+    second = np.concatenate([rng.uniform(0.5, 4.5, (n_in, 1)), yz()], axis=1).astype(np.float32)
+    xyz = np.concatenate([inner, first, second])
+    v = np.zeros_like(xyz)
+    v[len(inner):len(inner) + n_in, 0] = 300.0                        # clamped to one cell per step, then to max_v
+    v[len(inner) + n_in:, 0] = -300.0
+    v[np.nonzero(inner[:, 0] < -30.0)[0][:n_out], 0] = -300.0
+    g, o, n_interior = big_segment_pair(xyz, v)
+    assert o.queue_info["count"][:n_interior].min() == free
+    ran_empty = 0
+    for k in range(4):
+        before = dict(o.counters)
+        g.step(1); o.step(1)
+        compare_all(g, o, "empty queue, big segment, step %d" % (k + 1))
+        d = {n: c - before[n] for n, c in o.counters.items()}
+        # every operation of the step, all queues together: a relocation is a remove and an insert
+        ops = 2 * (d["relocations"] + d["relocations_lost"]) + d["births"] + d["births_failed"] + d["deaths_age"] \
+            + d["deaths_collision"] + d["cell_overflow_kills"]
+        assert ops < 2048 and g.counters["max_ops_one_queue"] < 2048, (k, ops, g.counters["max_ops_one_queue"])
+        if d["relocations_lost"] + d["births_failed"] > 0 and o.queue_info["count"][:n_interior].min() == 0:
+            ran_empty += 1
+    assert ran_empty >= 2 and o.counters["relocations_lost"] > 72, (ran_empty, o.counters)
+
+
+def test_long_list_runs_a_queue_empty_on_a_segment_in_global_memory():
+    """The same segment, filled to 48 free slots, reached from a LONG list: the three face layers below it (x, y and
+    z index 0), 78 to a cell, hop into it in the first step, 8424 removes, and 400 of its own leave through the far
+    x face -- every moved particle is one operation on the segment's record, more than any instance sorts in LDS
+    (replay_long whatever the hint), the queue runs empty, and its serial walk works on the segment in global memory."""
+    rng = np.random.default_rng(142)
+    free, n_out = 48, 400
+    r6 = np.arange(1, 7)
+    inner = fill_cells(rng, r6, r6, r6)[:216 * 78 - free]
+    faces = [fill_cells(rng, [0], r6, r6), fill_cells(rng, r6, [0], r6), fill_cells(rng, r6, r6, [0])]
+    xyz = np.concatenate([inner] + faces)
+    v = np.zeros_like(xyz)
+    first = len(inner)
+    for axis, f in enumerate(faces):
+        v[first:first + len(f), axis] = 300.0                         # clamped to one cell per step
+        first += len(f)
+    v[np.nonzero(inner[:, 0] > -10.0)[0][:n_out], 0] = 300.0
+    g, o, n_interior = big_segment_pair(xyz, v)
+    assert o.queue_info["count"][:n_interior].min() == free
+    for k in range(2):
+        before = dict(o.counters)
+        g.step(1); o.step(1)
+        compare_all(g, o, "long list, empty queue, big segment, step %d" % (k + 1))
+        if k == 0:
+            d = {n: c - before[n] for n, c in o.counters.items()}
+            assert d["relocations"] + d["relocations_lost"] > 8192 and d["relocations_lost"] > 0, d
+            assert o.queue_info["count"][:n_interior].min() == 0
+            assert g.counters["max_ops_one_queue"] > 8192
+
+
 @pytest.mark.parametrize("size", ["mid", "small", "big"])
 def test_long_operation_lists(size):
     """Fast particles fill the corner segment at the box centre (its 8 cells are [-5,5)^3) and move
     one cell along every axis: 7/8 of them leave it in one step, while more, one cell further out,
     move INTO it.  Small: 3600 + 2000 particles, more queue operations on one record than a
     workgroup used to sort in LDS (4096; now 8192).  Big (twice the container, 8208-slot corner
-    segments): 7200 + 4000, more than the in-LDS replay holds at all -- the radix sort of all keys and
-    the streamed closed-form replay (k_replay) run; and with the queue nearly empty (third step) its
-    serial walk.  Mid: 2000 + 1400, a list between 2048 and 4096 operations -- the long-list instance in the
+    segments): 7200 + 4000, more than the in-LDS replay holds at all -- k_replay_commit's replay_long runs:
+    the workgroup's radix partition of its list in global memory and the closed-form replay streamed in
+    chunks; and with the queue nearly empty (third step) the serial walk.  Mid: 2000 + 1400, a list between
+    2048 and 4096 operations -- the long-list instance in the
     first step, and in the next, on that step's hint, the 4096-operation instance for every queue."""
     big = size == "big"
     rng = np.random.default_rng(121)

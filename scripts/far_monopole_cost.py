@@ -24,7 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: F401, E402  (before the library: one HIP runtime)
 
-import far_monopole_model as M  # noqa: E402
+import far_model as F  # noqa: E402
 import particlesystem_amd as ps  # noqa: E402
 
 N = 1 << 20
@@ -90,11 +90,11 @@ def main():
     served = np.nonzero(f[:, 3].view(np.int32) == 0)[0]
     pick = rng.choice(served, 200, replace=False)
     idx = where[order[pick]]
-    want = M.direct(xyz, np.full(N, 60.0, np.float32), 0.2, idx, chunk=8)
+    want = F.direct(xyz, np.full(N, 60.0, np.float32), 0.2, idx, chunk=8)
     for name in ("far_monopole", "cutoff"):
         o, ff = dev[name]
         assert np.array_equal(o, order)
-        rel = M.rel_dev(ff[pick, :3].astype(np.float64), want)
+        rel = F.rel_dev(ff[pick, :3].astype(np.float64), want)
         res[name]["deviation_from_direct_sum"] = {"median": float(np.median(rel)), "max": float(rel.max()), "sampled": 200}
     far, cut, allp = (res[k]["ms_per_step"] for k in ("far_monopole", "cutoff", "all_pairs"))
     res["far_over_cutoff"] = far / cut

@@ -23,7 +23,7 @@ sys.path.insert(0, os.path.join(ROOT, "scripts"))
 import numpy as np  # noqa: E402
 import torch  # noqa: F401, E402  (before the library: one HIP runtime)
 
-import far_monopole_model as M  # noqa: E402
+import far_model as F  # noqa: E402
 import particlesystem_amd as ps  # noqa: E402
 from far_monopole_cost import records, timed  # noqa: E402
 
@@ -51,11 +51,11 @@ def measure(n, over, steps, sampled=200):
     order, f = dev["far_pyramid"]
     served = np.nonzero(f[:, 3].view(np.int32) == 0)[0]
     pick = rng.choice(served, sampled, replace=False)
-    want = M.direct(xyz, np.full(n, 60.0, np.float32), 0.2, where[order[pick]], chunk=8 if n <= 1 << 20 else 2)
+    want = F.direct(xyz, np.full(n, 60.0, np.float32), 0.2, where[order[pick]], chunk=8 if n <= 1 << 20 else 2)
     for _, key, _ in MODELS:
         o, ff = dev[key]
         assert np.array_equal(o, order)
-        rel = M.rel_dev(ff[pick, :3].astype(np.float64), want)
+        rel = F.rel_dev(ff[pick, :3].astype(np.float64), want)
         res[key]["deviation_from_direct_sum"] = {"median": float(np.median(rel)), "max": float(rel.max()), "sampled": sampled}
     res["pyramid_over_far_monopole"] = res["far_pyramid"]["ms_per_step"] / res["far_monopole"]["ms_per_step"]
     res["pyramid_over_cutoff"] = res["far_pyramid"]["ms_per_step"] / res["cutoff"]["ms_per_step"]

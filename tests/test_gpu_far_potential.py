@@ -1,10 +1,10 @@
 """PSAMD_POTENTIAL_FAR and PSAMD_PROBE_FAR on the device (include/psamd.h, "energy" and "the field at chosen points", far-
-monopole contexts): phi and U against the numpy model (far_potential_model.py; 1e-5 relative, psamd_potential's bar), the
+monopole contexts): phi and U against the numpy model (far_model.py; 1e-5 relative, psamd_potential's bar), the
 exact limits (a confined cloud: the cutoff context's bytes; G = 4: the flat context's), one adult per cell against an
 all-pairs context, a list of two slices, the probe's acceleration against the force records BIT FOR BIT, the probe's phi,
 the same bytes however the call is made, the refusals.
 
-Contexts hold max_particles_num=16384 (test_gpu_far_pyramid.py's GRID): 4^3 (one level), 8^3 (8, 4), 10^3 (10, 5, 3: ragged)
+Contexts hold max_particles_num=16384 (far_harness.py's GRID): 4^3 (one level), 8^3 (8, 4), 10^3 (10, 5, 3: ragged)
 and 16^3 (16, 8, 4: levels of several blocks)."""
 import ctypes as C
 import functools
@@ -13,18 +13,16 @@ import numpy as np
 import pytest
 import torch
 
-import far_monopole_model as M
-import far_potential_model as F
+import far_model as F
 import particlesystem_amd as ps
-from test_gpu_far_pyramid import GRID, box_cloud, index_of, low_corner
-from test_gpu_potential import hip_runtime
+from far_harness import GRID, INVALID_ARG, STATE, UNSUPPORTED, box_cloud, fill_lists, hip_runtime, low_corner, open_frame
 from util import assert_same_particles
 
 pytestmark = pytest.mark.gpu
 
 PYR, MONO = ps.FLAG_FAR_PYRAMID, ps.FLAG_FAR_MONOPOLE
+METHOD = {MONO: "flat", PYR: "pyramid"}                               # (far_model.py's names)
 REL = 1e-5
-INVALID_ARG, STATE, UNSUPPORTED = 1, 8, 9
 EPS2 = 0.2
 DEV = torch.device("cuda", 0)
 BOTH = pytest.mark.parametrize("flag", [MONO, PYR], ids=["flat", "pyramid"])
@@ -41,10 +39,6 @@ def make(G, flags, **over):
     return g
 
 
-def frame(g):
-    g.init_iframe(); g.build_grid()
-
-
 def body_cloud(n, seed, G, kids=True):
     rng = np.random.default_rng(seed)
     age = rng.uniform(15 / 7, 7.5, n).astype(np.float32)
@@ -58,13 +52,6 @@ def by_fill(ids, phi):
     out = np.empty(len(ids), np.float32)
     out[np.argsort(ids)] = np.asarray(phi.cpu().numpy() if isinstance(phi, torch.Tensor) else phi)
     return out
-
-
-def lists_of(g, ids):
-    """(the lists as indices into the fill, the sorted order as indices into the fill)"""
-    where = index_of(g, ids)
-    lists = [where[row[1:1 + row[0]]] for row in g.download_cellgrid()]
-    return lists, np.concatenate(lists)
 
 
 def pos4_of(xyz):
@@ -89,9 +76,9 @@ def _scene(G, flag, sign):
     c = body_cloud(n, 40 + G, G)
     g = make(G, flag, force_sign=sign)
     ids = g.fill_particles(**c)
-    frame(g)
+    open_frame(g)
     res = g.download_potential(far=True)
-    lists, order = lists_of(g, ids)
+    lists, order = fill_lists(g, ids)
     assert len(order) == n and g.counters["cell_overflow_kills"] == 0
     g.calc_forces_pairs()
     f = g.download_force4(0, n)
@@ -99,11 +86,11 @@ def _scene(G, flag, sign):
     g.close()
     kid = c["age"] < 1.5
     w_eff = np.where(kid, np.float32(0.0), np.float32(sign) * c["w"]).astype(np.float32)
-    cell = M.cells_of(c["xyz"], G)
-    levmom = F.level_moments(lists, c["xyz"], w_eff, G, flag == PYR)
-    want = F.phi64(lists, c["xyz"], w_eff, G, EPS2, c["xyz"], cell, np.arange(n), levmom, flag == PYR)
+    cell = F.cells_of(c["xyz"], G)
+    moments = F.level_moments(lists, c["xyz"], w_eff, G, METHOD[flag])
+    want = F.phi64(lists, c["xyz"], w_eff, G, EPS2, c["xyz"], cell, np.arange(n), METHOD[flag], moments)
     return dict(c=c, ids=ids, res=res, phi=by_fill(ids, res["phi"]), lists=lists, order=order, f=f, kid=kid, w_eff=w_eff, cell=cell,
-                levmom=levmom, want=want)
+                moments=moments, want=want)
 
 
 # ---- 1. against the model -----------------------------------------------------------------------------------------------
@@ -115,8 +102,8 @@ def test_phi_and_U_follow_the_model(G, sign, flag):
     s = scene(G, flag, sign)
     rel = np.abs(s["phi"].astype(np.float64) - s["want"]) / np.abs(s["want"])
     U = F.energy(s["w_eff"], s["want"])
-    near = F.phi64(s["lists"], s["c"]["xyz"], s["w_eff"], G, EPS2, s["c"]["xyz"][:200], s["cell"][:200], np.arange(200), far=False)
-    faith = F.phi32(s["lists"], s["c"]["xyz"], s["w_eff"], G, EPS2, s["c"]["xyz"][:400], s["cell"][:400], np.arange(400), s["levmom"], flag == PYR)
+    near = F.phi64(s["lists"], s["c"]["xyz"], s["w_eff"], G, EPS2, s["c"]["xyz"][:200], s["cell"][:200], np.arange(200), METHOD[flag], far=False)
+    faith = F.phi32(s["lists"], s["c"]["xyz"], s["w_eff"], G, EPS2, s["c"]["xyz"][:400], s["cell"][:400], np.arange(400), METHOD[flag], s["moments"])
     rel32 = np.abs(s["phi"][:400].astype(np.float64) - faith) / np.abs(faith)
     print("far phi, %d bodies on %d^3 cells, flags %#x, sign %+.0f: max relative deviation from the model %.3g, U %.3g; from the "
           "model's fp32 association %.3g; the stencil alone is %.3g of phi (median)"
@@ -142,7 +129,7 @@ def test_confined_cloud_is_the_cutoff_result_byte_for_byte():
     for flags in (0, MONO, PYR):
         g = ps.ParticleSystem(ps.default_config(flags=flags))
         g.fill_particles(xyz, age=age, fert_age=np.float32(1e6))
-        frame(g)
+        open_frame(g)
         got.append(g.potential(phi=True, far=flags != 0))
         got.append(g.download_potential(far=flags != 0))
         g.calc_forces()
@@ -158,7 +145,7 @@ def test_one_level_is_the_flat_context_byte_for_byte():
     for flag in (PYR, MONO):
         g = make(4, flag)
         g.fill_particles(**c)
-        frame(g)
+        open_frame(g)
         got.append(g.potential(phi=True, far=True))
         near = g.probe(pos4_of(c["xyz"]), far=True)
         got.append(near["out4"])
@@ -189,7 +176,7 @@ def test_one_adult_per_cell_is_the_all_pairs_phi():
     for flags in (flag, ps.FLAG_ALL_PAIRS):
         g = make(G, flags)
         g.fill_particles(xyz, age=age, w=w, fert_age=np.float32(1e6))
-        frame(g)
+        open_frame(g)
         got.append(g.download_potential(far=flags == flag))
         g.calc_forces()
         g.close()
@@ -213,15 +200,15 @@ def test_both_slices_of_a_long_list_carry_the_far_part(flag):
     rng = np.random.default_rng(96)
     crowd = (low_corner(4, 2, 3, G) + rng.uniform(0.05, 4.95, (many, 3))).astype(np.float32)
     full = (3 * G + 4) * G + 2
-    keep = M.cells_of(c["xyz"], G) != full
+    keep = F.cells_of(c["xyz"], G) != full
     xyz = np.concatenate([c["xyz"][keep], crowd])
     age = np.concatenate([c["age"][keep], np.full(many, 3.0, np.float32)])
     w = np.concatenate([c["w"][keep], np.full(many, 60.0, np.float32)])
     ids = g.fill_particles(xyz, age=age, w=w, fert_age=np.float32(1e6))
-    frame(g)
+    open_frame(g)
     res = g.potential(phi=True, far=True)
     ex = g.export_live(ps.EXPORT_ID | ps.EXPORT_POS)
-    lists, _ = lists_of(g, ids)
+    lists, _ = fill_lists(g, ids)
     g.calc_forces()
     kills = g.counters["cell_overflow_kills"]
     g.close()
@@ -234,8 +221,8 @@ def test_both_slices_of_a_long_list_carry_the_far_part(flag):
     w_eff = np.where(age < 1.5, np.float32(0), w).astype(np.float32)
     crowd_idx = lists[full]
     cell = np.full(many, full)
-    want = F.phi64(lists, xyz, w_eff, G, EPS2, xyz[crowd_idx], cell, crowd_idx, pyramid=flag == PYR)
-    near = F.phi64(lists, xyz, w_eff, G, EPS2, xyz[crowd_idx], cell, crowd_idx, far=False)
+    want = F.phi64(lists, xyz, w_eff, G, EPS2, xyz[crowd_idx], cell, crowd_idx, METHOD[flag])
+    near = F.phi64(lists, xyz, w_eff, G, EPS2, xyz[crowd_idx], cell, crowd_idx, METHOD[flag], far=False)
     rel = np.abs(phi[crowd_idx] - want) / np.abs(want)
     print("a list of %d, flags %#x: max relative deviation %.3g (first slice %.3g, second %.3g); far part %.3g of phi"
           % (many, flag, rel.max(), rel[:64].max(), rel[64:].max(), np.median(1 - near / want)))
@@ -251,7 +238,7 @@ def test_an_acc_probe_on_a_served_adult_is_its_force_record_bit_for_bit(G, flag)
     s = scene(G, flag)
     g = make(G, flag)
     g.fill_particles(**s["c"])
-    frame(g)
+    open_frame(g)
     adults = s["order"][~s["kid"][s["order"]]]
     out = g.probe(pos4_of(s["c"]["xyz"][adults]), phi=False, far=True)
     g.calc_forces()
@@ -277,13 +264,13 @@ def test_fast_math_probes_give_the_same_bytes_twice_and_follow_the_model(flag):
     for _ in range(2):
         g = make(G, flag | ps.FLAG_FAST_MATH)
         g.fill_particles(**s["c"])
-        frame(g)
+        open_frame(g)
         outs.append(g.probe(pos4_of(s["c"]["xyz"][adults]), far=True)["out4"].cpu().numpy())
         g.calc_forces()
         g.close()
     assert outs[0].tobytes() == outs[1].tobytes()
-    want = F.accel64(s["lists"], s["c"]["xyz"], s["w_eff"], G, EPS2, s["c"]["xyz"][adults], s["cell"][adults], s["levmom"], flag == PYR)
-    rel = M.rel_dev(outs[0][:, :3].astype(np.float64), want)
+    want = F.accel64(s["lists"], s["c"]["xyz"], s["w_eff"], G, EPS2, s["c"]["xyz"][adults], s["cell"][adults], METHOD[flag], s["moments"])
+    rel = F.rel_dev(outs[0][:, :3].astype(np.float64), want)
     print("fast-math far probes, flags %#x: max relative deviation of a from the model %.3g" % (flag, rel.max()))
     assert rel.max() < REL
 
@@ -297,7 +284,7 @@ def test_probe_phi(G, flag):
     c, n = s["c"], len(s["ids"])
     g = make(G, flag)
     g.fill_particles(**c)
-    frame(g)
+    open_frame(g)
     on = g.probe(pos4_of(c["xyz"]), acc=False, far=True)["out4"].cpu().numpy()[:, 3]
     # a regular grid of points, two of them outside the box and one not a number
     k = np.arange(12)
@@ -314,12 +301,12 @@ def test_probe_phi(G, flag):
     out4, code = res["out4"].cpu().numpy(), res["outcome"].cpu().numpy()
     assert code[-3:].tolist() == [ps.PROBE_OUTSIDE] * 3 and (bits(out4[-3:]) == 0x7fc00000).all() and (code[:-3] == ps.PROBE_SERVED).all()
     assert res["served"] == 12 ** 3 and res["outside"] == 3 and res["nonfinite"] == 0
-    cell = M.cells_of(grid[:-3], G)
+    cell = F.cells_of(grid[:-3], G)
     minus = np.full(len(cell), -1)
-    want = F.phi64(s["lists"], c["xyz"], s["w_eff"], G, EPS2, grid[:-3], cell, minus, s["levmom"], flag == PYR)
-    wacc = F.accel64(s["lists"], c["xyz"], s["w_eff"], G, EPS2, grid[:-3], cell, s["levmom"], flag == PYR)
+    want = F.phi64(s["lists"], c["xyz"], s["w_eff"], G, EPS2, grid[:-3], cell, minus, METHOD[flag], s["moments"])
+    wacc = F.accel64(s["lists"], c["xyz"], s["w_eff"], G, EPS2, grid[:-3], cell, METHOD[flag], s["moments"])
     rphi = np.abs(out4[:-3, 3] - want) / np.abs(want)
-    racc = M.rel_dev(out4[:-3, :3].astype(np.float64), wacc)
+    racc = F.rel_dev(out4[:-3, :3].astype(np.float64), wacc)
     print("far probes on %d^3 cells, flags %#x: on adults, phi + own term to %.3g; on a grid phi to %.3g, a to %.3g"
           % (G, flag, rel.max(), rphi.max(), racc.max()))
     assert rel.max() < 4 * 2.0 ** -24                                     # two roundings to fp32 and the sum's: "to rounding"
@@ -336,7 +323,7 @@ def test_the_same_bytes_before_and_after_the_pair_stage_and_nothing_else_moves(f
     b = make(G, flag)                                                     # never makes a far call
     for x in (g, b):
         x.fill_particles(**s["c"])
-        frame(x)
+        open_frame(x)
     pts = pos4_of(s["c"]["xyz"][:1000])
     first = g.potential(phi=True, far=True)
     again = g.potential(phi=True, far=True)
@@ -365,7 +352,7 @@ def test_the_far_call_is_captured_into_a_graph_and_replays_on_a_later_frame(flag
     c = body_cloud(6000, 48, G)
     g.fill_particles(**c, vxyz=box_cloud(6000, 49, 2.0))
     g.step(1)
-    frame(g)
+    open_frame(g)
     cap = g.owned_slots()
     phi = torch.zeros(cap, dtype=torch.float32, device=DEV)
     rec = torch.zeros(C.sizeof(ps.PotentialResult), dtype=torch.uint8, device=DEV)
@@ -380,7 +367,7 @@ def test_the_far_call_is_captured_into_a_graph_and_replays_on_a_later_frame(flag
     assert hip.hipGraphInstantiate(C.byref(exe), graph, None, None, 0) == 0
     g.calc_forces()
     g.step(2)
-    frame(g)                                                              # another frame: the graph holds nothing of the one it was captured in
+    open_frame(g)                                                         # another frame: the graph holds nothing of the one it was captured in
     assert hip.hipGraphLaunch(exe, stream) == 0
     assert hip.hipStreamSynchronize(stream) == 0
     replayed = ps.PotentialResult.from_buffer_copy(rec.cpu().numpy().tobytes()).to_dict()
@@ -403,7 +390,7 @@ def test_refusals_and_arguments():
     for flags in (0, ps.FLAG_ALL_PAIRS):                                  # the bits are unknown bits there
         g = make(8, flags)
         g.fill_particles(**c)
-        frame(g)
+        open_frame(g)
         assert g.lib.psamd_potential(g.h, C.byref(far_spec)) == INVALID_ARG
         assert g.lib.psamd_probe(g.h, C.byref(probe(ps.PROBE_ACC | ps.PROBE_FAR))) == INVALID_ARG
         assert g.lib.psamd_download_potential_far(g.h, None, 0, None) == UNSUPPORTED
@@ -416,7 +403,7 @@ def test_refusals_and_arguments():
         assert g.lib.psamd_potential(g.h, C.byref(far_spec)) == STATE    # outside the window
         assert g.lib.psamd_download_potential_far(g.h, None, 0, None) == STATE
         assert g.lib.psamd_probe(g.h, C.byref(probe(ps.PROBE_PHI | ps.PROBE_FAR))) == STATE
-        frame(g)
+        open_frame(g)
         assert g.lib.psamd_potential(g.h, C.byref(ps.Potential())) == UNSUPPORTED      # without the bit: as before
         assert g.lib.psamd_download_potential(g.h, None, 0, None) == UNSUPPORTED
         assert g.lib.psamd_probe(g.h, C.byref(probe(ps.PROBE_ACC | ps.PROBE_PHI))) == UNSUPPORTED

@@ -21,7 +21,7 @@ import torch
 
 import particlesystem_amd as ps
 from particlesystem_amd import slab
-from util import SENTINEL, capacities, cloud, ragged
+from util import SENTINEL, capacities, cloud, hip_runtime, ragged
 
 pytestmark = pytest.mark.gpu
 
@@ -281,23 +281,6 @@ def test_same_bits_twice_with_graphs_and_after_the_pair_stage():
     assert h.graph_stats()[0] > 0
     assert np.array_equal(bits(a["phi"]), bits(d["phi"])) and plain == {k: d[k] for k in d if k != "phi"}
     g.close(); h.close()
-
-
-def hip_runtime():
-    """the HIP runtime torch loaded (the library is bound to the same copy)"""
-    for line in open("/proc/self/maps"):
-        if "libamdhip64.so" in line:
-            hip = C.CDLL(line.split()[-1])
-            break
-    else:
-        raise RuntimeError("no HIP runtime in this process")
-    vp = C.c_void_p
-    for name, args in (("hipStreamBeginCapture", [vp, C.c_int]), ("hipStreamEndCapture", [vp, C.POINTER(vp)]),
-                       ("hipGraphInstantiate", [C.POINTER(vp), vp, vp, vp, C.c_size_t]), ("hipGraphLaunch", [vp, vp]),
-                       ("hipStreamSynchronize", [vp]), ("hipGraphExecDestroy", [vp]), ("hipGraphDestroy", [vp])):
-        getattr(hip, name).restype = C.c_int
-        getattr(hip, name).argtypes = args
-    return hip
 
 
 def test_the_call_is_captured_into_a_graph_and_replays_on_a_later_frame():

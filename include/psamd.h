@@ -262,10 +262,16 @@ typedef struct psamd_potential_result {
  * written for "exactly the stencil's bodies" is never silently handed another quantity: without it such a context
  * refuses, with it the caller has said which phi it wants.  An unknown bit on every other context. */
 #define PSAMD_POTENTIAL_FAR 0x1u
+/* A modifier of PSAMD_POTENTIAL_FAR on a PSAMD_FLAG_FAR_QUADRUPOLE context: every far body also adds its quadrupole term, so
+ * that phi is the potential of the field that context applies.  PSAMD_POTENTIAL_FAR alone was documented as "each far body as
+ * one body (X, Y, Z, M)" and stays that promise: the quadrupole form is asked for by name, and without this bit such a context
+ * refuses.  An unknown bit on every other context; without PSAMD_POTENTIAL_FAR PSAMD_ERR_INVALID_ARG. */
+#define PSAMD_POTENTIAL_QUADRUPOLE 0x2u
 
 /* What psamd_potential writes and where (device pointers). */
 typedef struct psamd_potential_spec {
-    uint32_t flags;           /* 0, or PSAMD_POTENTIAL_FAR on a far-monopole context                          */
+    uint32_t flags;           /* 0, or PSAMD_POTENTIAL_FAR on a far-monopole context (| PSAMD_POTENTIAL_QUADRUPOLE
+                                 on a quadrupole context)                                                     */
     int32_t  reserved;        /* 0                                                                            */
     float   *phi;             /* optional out, float[capacity], 4-byte aligned; required if capacity > 0      */
     int64_t  capacity;        /* entries phi holds                                                            */
@@ -278,6 +284,9 @@ typedef struct psamd_potential_spec {
 #define PSAMD_PROBE_FAR 0x4u   /* a modifier beside ACC and / or PHI, on a PSAMD_FLAG_FAR_MONOPOLE / PSAMD_FLAG_FAR_PYRAMID
                                   context: the field of the stencil AND the far bodies of the context's force model.  It
                                   exists for PSAMD_POTENTIAL_FAR's reason; an unknown bit on every other context */
+#define PSAMD_PROBE_QUADRUPOLE 0x8u   /* a modifier of PSAMD_PROBE_FAR on a PSAMD_FLAG_FAR_QUADRUPOLE context: the far bodies'
+                                  quadrupole terms too (PSAMD_POTENTIAL_QUADRUPOLE's rule); an unknown bit on every other
+                                  context, PSAMD_ERR_INVALID_ARG without PSAMD_PROBE_FAR */
 
 /* What psamd_probe did. */
 typedef struct psamd_probe_result {
@@ -290,7 +299,8 @@ typedef struct psamd_probe_result {
 
 /* What psamd_probe reads and where it writes (device pointers). */
 typedef struct psamd_probe_spec {
-    uint32_t fields;          /* PSAMD_PROBE_ACC | PSAMD_PROBE_PHI, at least one; PSAMD_PROBE_FAR beside them  */
+    uint32_t fields;          /* PSAMD_PROBE_ACC | PSAMD_PROBE_PHI, at least one; PSAMD_PROBE_FAR (and
+                                 PSAMD_PROBE_QUADRUPOLE) beside them                                          */
     int32_t  reserved;        /* 0                                                                            */
     const void *pos4;         /* float4[max_count] x, y, z (w ignored), 16-byte aligned: an export's pos4 can
                                  be passed as it is                                                           */
@@ -700,8 +710,31 @@ int psamd_remove_result_get(psamd_ctx *ctx, psamd_remove_result *out);
  * on a cutoff context of the same cloud and 3.78, 3.57 and 1.97 ms of the three contexts' pair stage.  The flat form walks 4069 far
  * bodies a (cell, slice) wave behind 27 lists of 256: 1.7 times the cutoff potential, nowhere near an all-pairs potential.
  *
+ * Quadrupole contexts (PSAMD_FLAG_FAR_QUADRUPOLE; they are pyramid contexts).  PSAMD_POTENTIAL_FAR alone promises each far body
+ * as one body (X, Y, Z, M), which is not the field such a context applies: without a bit and with PSAMD_POTENTIAL_FAR alone
+ * psamd_potential, psamd_download_potential and psamd_download_potential_far return PSAMD_ERR_UNSUPPORTED (the context stays
+ * usable).  With PSAMD_POTENTIAL_FAR | PSAMD_POTENTIAL_QUADRUPOLE (host form: psamd_download_potential_flags) every member of the
+ * interaction set adds, beside its monopole term, the quadrupole term of "quadrupoles on the pyramid" below -- in the
+ * convention of these sums (sum of w u, phi = (float)(-sum)) t_q = 1.5 (d.C.d) u^5 - 0.5 T u^3, the term whose gradient is that
+ * section's a_q -- from the ten planes the call forms itself.  Association: the stencil's chains and every block's monopole
+ * chain are PSAMD_POTENTIAL_FAR's on a pyramid context, bit for bit; behind a block's monopole chain comes that block's
+ * quadrupole chain -- ONE fp32 chain from +0, in index order, over the members of the monopole chain -- and each of the two is
+ * carried into the fp64 accumulator by an addition of its own (acc += monopole chain; acc += quadrupole chain); blocks in
+ * block order, levels top down.  Consequences: with every C an exact zero (G <= 4, at most one adult a cell, kids anywhere)
+ * every quadrupole chain is +0, and phi, U and the record are those a PSAMD_FLAG_FAR_PYRAMID context returns under
+ * PSAMD_POTENTIAL_FAR, byte for byte; a cloud inside a 2x2x2 block of cells gives the cutoff context's phi, U and record byte
+ * for byte.  Window, PSAMD_ERR_STATE, alignment, capacity and "allocates nothing, waits for nothing, may be captured" are
+ * unchanged.
+ * Accuracy of the quadrupole far phi (the fp64 model against an fp64 direct sum, the clouds above;
+ * tests/test_far_quad_potential_cpu.py): the median particle's phi is off by 0.006-0.011 %, the worst of 400 sampled by
+ * 0.029-0.042 %, where the pyramid of monopoles is off by 0.02-0.11 % and 0.11-0.52 %: the median falls to 0.06-0.41 of the
+ * pyramid's.  The device follows the model to 1e-5 relative (tests/test_gpu_far_quad_potential.py).
+ * Cost on an MI355X at N = 2^20 on 16^3 cells (profiles/far_quad_potential_cost.txt; the far potential's protocol, both contexts in
+ * one run): 3.59 ms on the quadrupole context beside 2.67 ms of the far potential on a pyramid context, 1.35 times.
+ *
  * PSAMD_ERR_INVALID_ARG: a NULL context or spec, flags with an unknown bit (PSAMD_POTENTIAL_FAR is one on a context with
- * neither far flag) or reserved not 0, capacity < 0, phi not 4-byte aligned, phi NULL with capacity > 0, result_dev not
+ * neither far flag, PSAMD_POTENTIAL_QUADRUPOLE on a context without PSAMD_FLAG_FAR_QUADRUPOLE), PSAMD_POTENTIAL_QUADRUPOLE without
+ * PSAMD_POTENTIAL_FAR, or reserved not 0, capacity < 0, phi not 4-byte aligned, phi NULL with capacity > 0, result_dev not
  * 8-byte aligned.
  *
  * psamd_potential_result_get: the last call's record, into host memory; waits for the context's stream.
@@ -710,11 +743,16 @@ int psamd_remove_result_get(psamd_ctx *ctx, psamd_remove_result *out);
  * psamd_download_live reports at the same point (with no fields and capacity 0 it costs two small launches).  Waits for
  * the context's stream.
  * psamd_download_potential_far: the host form of a PSAMD_POTENTIAL_FAR call, otherwise psamd_download_potential; on a
- * context with neither far flag PSAMD_ERR_UNSUPPORTED. */
+ * context with neither far flag PSAMD_ERR_UNSUPPORTED.
+ * psamd_download_potential_flags: the host form of a psamd_potential call with these spec flags, the same body as the two
+ * above; `flags` is validated as psamd_potential validates it, ahead of the other arguments (so PSAMD_POTENTIAL_FAR on a
+ * context with neither far flag is PSAMD_ERR_INVALID_ARG here).  The host form of every later bit: no further _xxx form will
+ * be added. */
 int psamd_potential(psamd_ctx *ctx, const psamd_potential_spec *spec);
 int psamd_potential_result_get(psamd_ctx *ctx, psamd_potential_result *out);
 int psamd_download_potential(psamd_ctx *ctx, float *phi, int64_t capacity, psamd_potential_result *out);
 int psamd_download_potential_far(psamd_ctx *ctx, float *phi, int64_t capacity, psamd_potential_result *out);
+int psamd_download_potential_flags(psamd_ctx *ctx, uint32_t flags, float *phi, int64_t capacity, psamd_potential_result *out);
 
 /* ---- the field at chosen points ------------------------------------------------ */
 /* psamd_probe: the acceleration and the potential of the frame's field at points of the caller's choosing -- under a
@@ -765,6 +803,23 @@ int psamd_download_potential_far(psamd_ctx *ctx, float *phi, int64_t capacity, p
  * exact-path far context a PSAMD_PROBE_ACC | PSAMD_PROBE_FAR probe at the position of an adult the force pass serves returns
  * that particle's force record BIT FOR BIT; a PHI probe at a listed kid's true position returns that kid's far phi bit for
  * bit.  Outcomes, the NaN words, the determinism promise and count_dev are unchanged.
+ *
+ * Quadrupole contexts (PSAMD_FLAG_FAR_QUADRUPOLE).  Without a modifier and with PSAMD_PROBE_FAR alone the call returns
+ * PSAMD_ERR_UNSUPPORTED (monopoles only are not that context's field).  With PSAMD_PROBE_FAR | PSAMD_PROBE_QUADRUPOLE beside ACC
+ * and / or PHI every far body adds its quadrupole term too.  phi: psamd_potential's quadrupole form ("energy" above), terms and
+ * association.  Acceleration: the force pass's association exactly -- per block the monopole chain and, behind each group's
+ * pair terms, the block's quadrupole chain from +0; per level the monopole sum and the quadrupole sum add up in block order to
+ * +0, the level's part is RN(monopole sum + quadrupole sum), and a = ((stencil + part L) + ...) + part 0.  Consequences: on an
+ * exact or PSAMD_FLAG_FAST_MATH quadrupole context an ACC | FAR | QUADRUPOLE probe at the position of an adult the force pass
+ * serves returns that adult's force record BIT FOR BIT; a PHI | FAR | QUADRUPOLE probe at a listed kid's true position returns
+ * that kid's phi from psamd_potential (FAR | QUADRUPOLE) bit for bit; with every C an exact zero the words are those a
+ * PSAMD_FLAG_FAR_PYRAMID context returns under PSAMD_PROBE_FAR, and for a cloud inside a 2x2x2 block of cells the cutoff
+ * context's, byte for byte.  A probe's words depend on its position and the frame alone, also on whether ACC and PHI are asked
+ * for together or one by one.
+ * Cost (profiles/far_quad_potential_cost.txt): 65 536 probes, ACC | PHI, at N = 2^20, beside far probes on a pyramid context in
+ * the same run: on particles' own positions 6.13 ms beside 5.37 ms (1.14 times), on a regular grid 3.62 ms beside 3.21 ms
+ * (1.13 times).
+ *
  * Cost (profiles/far_potential_cost.txt): 65 536 far probes, ACC | PHI, at N = 2^20 (same protocol as the far potential): on
  * particles' own positions 7.96 ms flat and 5.46 ms as a pyramid beside 4.69 ms of plain probes on a cutoff context; on a regular
  * grid 4.66 and 3.24 ms beside 2.76 ms.
@@ -787,7 +842,8 @@ int psamd_download_potential_far(psamd_ctx *ctx, float *phi, int64_t capacity, p
  * the same frames.  The cost follows the (wave, distinct cell) walks: 16 probes to a cell use a quarter of the lanes.
  *
  * PSAMD_ERR_INVALID_ARG: a NULL context or spec, fields without ACC and PHI or with unknown bits (PSAMD_PROBE_FAR is one
- * on a context with neither far flag), reserved != 0, max_count outside
+ * on a context with neither far flag, PSAMD_PROBE_QUADRUPOLE on a context without PSAMD_FLAG_FAR_QUADRUPOLE),
+ * PSAMD_PROBE_QUADRUPOLE without PSAMD_PROBE_FAR, reserved != 0, max_count outside
  * [0, 2^31), pos4 or out4 NULL with max_count > 0 or not 16-byte aligned, outcome_dev not 4-byte aligned, count_dev or
  * result_dev not 8-byte aligned.  max_count == 0 writes a zero result and launches nothing else.
  *
@@ -934,7 +990,11 @@ int psamd_download_level_moments(psamd_ctx *ctx, int32_t level, void *out_float4
  *     gz = fma(Czz, dz, fma(Cyz, dy, Cxz*dx))           q  = fma(gz, dz, fma(gy, dy, gx*dx))
  *     T  = (Cxx + Cyy) + Czz                            s  = fma(7.5*u7, q, (-1.5*T)*u5)       m3 = -3*u5
  *     a_q = (fma(m3, gx, s*dx), fma(m3, gy, s*dy), fma(m3, gz, s*dz))
- * A later far potential and far probe on such a context will have to repeat this sequence.
+ * The far potential and the far probes of such a context (PSAMD_POTENTIAL_QUADRUPOLE, PSAMD_PROBE_QUADRUPOLE) repeat this
+ * sequence up to q and T -- u7 apart -- and form the potential's term from it, in the convention of the potential's sums (sum of
+ * w u, phi = -sum):
+ *     t_q = fma(1.5*u5, q, (-0.5*T)*u3)                                    (= 1.5 (d.C.d) u^5 - 0.5 T u^3; its gradient is a_q)
+ * A probe's acceleration term is a_q above, operation for operation.
  *
  * Association.  Within a block of 64 level cells the quadrupole terms form their OWN fp32 chain per component: from +0, in
  * index order, over the members of the monopole chain.  A level's quadrupole sum is its blocks' quadrupole chains added in
@@ -953,8 +1013,11 @@ int psamd_download_level_moments(psamd_ctx *ctx, int32_t level, void *out_float4
  *
  * Refusals.  psamd_create: the flag without PSAMD_FLAG_FAR_PYRAMID PSAMD_ERR_INVALID_ARG; everything else as the pyramid
  * refuses it.  psamd_potential, psamd_download_potential, psamd_download_potential_far and psamd_probe return
- * PSAMD_ERR_UNSUPPORTED on such a context even with PSAMD_POTENTIAL_FAR / PSAMD_PROBE_FAR, and the context stays usable:
- * their far forms are monopoles only, which is not this context's field.  The flag combines with FAST_MATH, EULER,
+ * PSAMD_ERR_UNSUPPORTED on such a context without a modifier and with PSAMD_POTENTIAL_FAR / PSAMD_PROBE_FAR alone, and the
+ * context stays usable: those far forms are monopoles only, which is not this context's field.  Its own field is served where
+ * it is asked for by name: PSAMD_POTENTIAL_FAR | PSAMD_POTENTIAL_QUADRUPOLE (host form: psamd_download_potential_flags) and
+ * PSAMD_PROBE_FAR | PSAMD_PROBE_QUADRUPOLE ("energy", "the field at chosen points"); either quadrupole bit without its FAR bit is
+ * PSAMD_ERR_INVALID_ARG, and on a context without the flag both are unknown bits.  The flag combines with FAST_MATH, EULER,
  * EXPLOSIONS, drag, force_sign, graphs, run-ahead and snapshot save / restore as the pyramid does.
  *
  * Cost on an MI355X (profiles/far_quadrupole_cost.txt): at N = 2^20 (16^3 cells) a step takes 7.27 ms with the flag against 6.22 ms

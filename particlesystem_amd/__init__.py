@@ -191,6 +191,7 @@ class PotentialResult(_Record):
 
 
 POTENTIAL_FAR = 0x1     # psamd_potential_spec.flags: the stencil and the far bodies of a far-monopole context's force model
+POTENTIAL_QUADRUPOLE = 0x2      # a modifier of POTENTIAL_FAR on a quadrupole context: the far bodies' quadrupole terms too
 
 
 class Potential(C.Structure):
@@ -211,6 +212,7 @@ def merge_potential(results):
 # psamd_probe: the field bits, and the outcome codes of the entries
 PROBE_ACC, PROBE_PHI = 0x1, 0x2
 PROBE_FAR = 0x4         # a modifier beside ACC / PHI on a far-monopole context: the far bodies of its force model too
+PROBE_QUADRUPOLE = 0x8  # a modifier of PROBE_FAR on a quadrupole context: the far bodies' quadrupole terms too
 PROBE_SERVED, PROBE_OUTSIDE, PROBE_FOREIGN = 0, 1, 2
 
 
@@ -353,6 +355,7 @@ ABI = [
     ("psamd_potential_result_get", C.c_int, [_vp, C.POINTER(PotentialResult)]),
     ("psamd_download_potential", C.c_int, [_vp, _vp, _i64, C.POINTER(PotentialResult)]),
     ("psamd_download_potential_far", C.c_int, [_vp, _vp, _i64, C.POINTER(PotentialResult)]),
+    ("psamd_download_potential_flags", C.c_int, [_vp, C.c_uint32, _vp, _i64, C.POINTER(PotentialResult)]),
     ("psamd_probe", C.c_int, [_vp, C.POINTER(ProbeSpec)]),
     ("psamd_probe_result_get", C.c_int, [_vp, C.POINTER(ProbeResult)]),
 ]
@@ -835,15 +838,16 @@ class ParticleSystem:
         return r.to_dict()
 
     # ---- energy (include/psamd.h) -----------------------------------------------
-    def potential(self, phi=False, capacity=None, far=False):
+    def potential(self, phi=False, capacity=None, far=False, *, quadrupole=False):
         """psamd_potential: {"listed", "nonfinite", "potential", "phi_min", "phi_max"} of the frame that is built (after
         build_grid; a slab: between slab_pairs and slab_apply) and, with phi=True, "phi": a float32 torch device tensor of
         min(live count, capacity) entries that pairs, entry for entry, with export_live() at the same point of the stream.
-        far=True: PSAMD_POTENTIAL_FAR -- on a far-monopole context, the far bodies of its force model behind the stencil.
+        far=True: PSAMD_POTENTIAL_FAR -- on a far-monopole context, the far bodies of its force model behind the stencil;
+        quadrupole=True beside it: PSAMD_POTENTIAL_QUADRUPOLE -- on a quadrupole context, their quadrupole terms too.
         Waits for the context's stream.  torch must have been imported before the library was loaded."""
         import torch
         dev = torch.device("cuda", int(self.cfg.device))
-        spec = Potential(flags=POTENTIAL_FAR if far else 0)
+        spec = Potential(flags=(POTENTIAL_FAR if far else 0) | (POTENTIAL_QUADRUPOLE if quadrupole else 0))
         result = torch.zeros(C.sizeof(PotentialResult), dtype=torch.uint8, device=dev)
         spec.result_dev = result.data_ptr()
         out = count = None
@@ -867,11 +871,15 @@ class ParticleSystem:
         self._ck(self.lib.psamd_potential_result_get(self.h, C.byref(r)))
         return r.to_dict()
 
-    def download_potential(self, phi=True, capacity=None, far=False):
-        """psamd_download_potential (far=True: psamd_download_potential_far), the numpy form of potential(): "phi" is a
-        float32 array of min(live count, capacity)"""
+    def download_potential(self, phi=True, capacity=None, far=False, *, quadrupole=False):
+        """psamd_download_potential (far=True: psamd_download_potential_far; quadrupole=True: psamd_download_potential_flags
+        with PSAMD_POTENTIAL_QUADRUPOLE beside what `far` gives), the numpy form of potential(): "phi" is a float32 array of
+        min(live count, capacity)"""
         r = PotentialResult()
         call = self.lib.psamd_download_potential_far if far else self.lib.psamd_download_potential
+        if quadrupole:
+            flags = (POTENTIAL_FAR if far else 0) | POTENTIAL_QUADRUPOLE
+            call = lambda h, out, cap, res: self.lib.psamd_download_potential_flags(h, flags, out, cap, res)
         if not phi:
             self._ck(call(self.h, None, 0, C.byref(r)))
             return r.to_dict()
@@ -884,28 +892,31 @@ class ParticleSystem:
         res["phi"] = out[:min(n.value, capacity)]
         return res
 
-    def energy(self, far=False):
+    def energy(self, far=False, *, quadrupole=False):
         """{"kinetic", "potential", "total"} of the frame that is built: one potential() and one live_stats() at the same
         point of the stream (kinetic: psamd_live_stats.kinetic, sum 0.5 w |v|^2 over the live particles); far=True: the
-        potential of a far-monopole context's own field (PSAMD_POTENTIAL_FAR)"""
-        u = self.potential(far=far)["potential"]
+        potential of a far-monopole context's own field (PSAMD_POTENTIAL_FAR), with quadrupole=True beside it of a
+        quadrupole context's (PSAMD_POTENTIAL_QUADRUPOLE)"""
+        u = self.potential(far=far, quadrupole=quadrupole)["potential"]
         k = float(self.live_stats()["kinetic"])
         return {"kinetic": k, "potential": u, "total": k + u}
 
     # ---- the field at chosen points (include/psamd.h) ---------------------------
-    def probe(self, pos4, count=None, acc=True, phi=True, outcome=False, far=False):
+    def probe(self, pos4, count=None, acc=True, phi=True, outcome=False, far=False, *, quadrupole=False):
         """psamd_probe from a torch device tensor: pos4 float32 [m, 4] (x, y, z; w ignored -- an export's "pos4" as it is);
         count: None (all m entries) or a 1-element int64 device tensor that work on torch's current stream may write just
         before.  Returns {"out4": float32 [m, 4] device tensor (acceleration in xyz, potential in w; quiet NaNs where the
         entry was not served), "done", "served", "outside", "foreign", "nonfinite"} and, with outcome=True, "outcome": an
         int32 device tensor of m entries (PROBE_SERVED, PROBE_OUTSIDE, PROBE_FOREIGN).  Entries at or past the count keep
         the zeros (out4) and -1 (outcome) they were allocated with.  far=True: PSAMD_PROBE_FAR beside the components -- on a
-        far-monopole context, the far bodies of its force model too.  Waits for the context's stream."""
+        far-monopole context, the far bodies of its force model too; quadrupole=True beside it: PSAMD_PROBE_QUADRUPOLE -- on a
+        quadrupole context, their quadrupole terms too.  Waits for the context's stream."""
         import torch
         dev = pos4.device
         m = int(pos4.shape[0])
         assert pos4.dtype == torch.float32 and tuple(pos4.shape) == (m, 4) and pos4.is_contiguous() and pos4.is_cuda, "probe: bad pos4 tensor"
-        spec = ProbeSpec(fields=(PROBE_ACC if acc else 0) | (PROBE_PHI if phi else 0) | (PROBE_FAR if far else 0), max_count=m)
+        spec = ProbeSpec(fields=(PROBE_ACC if acc else 0) | (PROBE_PHI if phi else 0) | (PROBE_FAR if far else 0) |
+                         (PROBE_QUADRUPOLE if quadrupole else 0), max_count=m)
         out4 = torch.zeros((max(m, 1), 4), dtype=torch.float32, device=dev)
         spec.pos4, spec.out4 = (pos4.data_ptr(), out4.data_ptr()) if m > 0 else (None, None)
         if count is not None:

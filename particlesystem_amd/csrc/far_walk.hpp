@@ -1,7 +1,8 @@
 // far_walk.hpp -- what every walk over a far-field context's moments shares (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID):
 // where the moments are, a level's place and size, the cells of a level that concern a range of grid cells, and the force
-// pass's chain over one block of 64 level cells, the quadrupole term of a far body (PSAMD_FLAG_FAR_QUADRUPOLE).  The force pass (farfield.hip, k_far_walk), psamd_potential's far form
-// (potential.hip, k_pot_pairs<2>) and psamd_probe's (probe.hip, k_probe_pairs<.., 2>) are written on these; device-inline only.
+// pass's chain over one block of 64 level cells, the quadrupole terms of a far body -- acceleration and potential, on one shared
+// front -- (PSAMD_FLAG_FAR_QUADRUPOLE).  The force pass (farfield.hip, k_far_walk), psamd_potential's far forms (potential.hip,
+// k_pot_pairs<2> and <3>) and psamd_probe's (probe.hip, k_probe_pairs<.., 2> and <.., 3>) are written on these; device-inline only.
 //
 // The flat method is a pyramid of one level: its set is the top level's rule at level 0.  Cell i's set is, at the top level
 // L, every cell that holds mass and is not adjacent to i >> L, and at a level l below it every such cell whose parent is
@@ -157,38 +158,65 @@ __device__ __forceinline__ void far_drop(v2f (&qw)[4], int k, bool drop)
 }
 
 // ---- quadrupoles on the pyramid (PSAMD_FLAG_FAR_QUADRUPOLE) ----
-// The quadrupole term of ONE far body at (X, Y, Z) with the central second moments C = (Cxx, Cyy, Czz, Cxy, Cxz, Cyz) on the
-// particle at (xi, yi, zi): the second-order Taylor term of the softened kernel about the body's centre of mass,
-//   a_q = -3 (C d) u^5 + 7.5 (d.C.d) u^7 d - 1.5 T u^5 d,   d = (X, Y, Z) - x,  u = (d.d + eps2)^(-1/2),  T = Cxx + Cyy + Czz.
-// The ONE form of every context, exact and PSAMD_FLAG_FAST_MATH alike, and of every kernel that inlines it: each
-// multiply-add is an explicit fmaf or explicitly unfused (__fmul_rn, __fadd_rn), so the bits do not depend on the
-// compiler's contraction setting or on the code around the call.  The operation sequence is psamd.h's ("quadrupoles on the
-// pyramid"), line for line.
+// ONE far body at (X, Y, Z) with the central second moments C = (Cxx, Cyy, Czz, Cxy, Cxz, Cyz) seen from (xi, yi, zi): what
+// its quadrupole acceleration and its quadrupole potential share -- d = (X, Y, Z) - x, the powers of u = (d.d + eps2)^(-1/2),
+// g = C d, q = d.C.d, T = Cxx + Cyy + Czz.  The ONE form of every context, exact and PSAMD_FLAG_FAST_MATH alike, and of every
+// kernel that inlines it: each multiply-add is an explicit fmaf or explicitly unfused (__fmul_rn, __fadd_rn), so the bits do
+// not depend on the compiler's contraction setting or on the code around the call.  The operation sequence is psamd.h's
+// ("quadrupoles on the pyramid"), line for line.
+struct FarQuadFront {
+    float dx, dy, dz, u3, u5, u7, gx, gy, gz, q, T;      // (u7: the acceleration's alone -- dead code where only phi is formed)
+};
+
+__device__ __forceinline__ FarQuadFront far_quad_front(float xi, float yi, float zi, float X, float Y, float Z, float cxx,
+                                                       float cyy, float czz, float cxy, float cxz, float cyz, float eps2f)
+{
+    FarQuadFront f;
+    f.dx = X - xi; f.dy = Y - yi; f.dz = Z - zi;                        // as the pair forms form it
+    const float r2 = __fadd_rn(__fadd_rn(__fmul_rn(f.dx, f.dx), __fmul_rn(f.dy, f.dy)), __fmul_rn(f.dz, f.dz));
+    const float u = __builtin_amdgcn_rsqf(__fadd_rn(r2, eps2f));
+    const float u2 = __fmul_rn(u, u);
+    f.u3 = __fmul_rn(u2, u); f.u5 = __fmul_rn(f.u3, u2); f.u7 = __fmul_rn(f.u5, u2);
+    f.gx = fmaf(cxz, f.dz, fmaf(cxy, f.dy, __fmul_rn(cxx, f.dx)));      // C d
+    f.gy = fmaf(cyz, f.dz, fmaf(cyy, f.dy, __fmul_rn(cxy, f.dx)));
+    f.gz = fmaf(czz, f.dz, fmaf(cyz, f.dy, __fmul_rn(cxz, f.dx)));
+    f.q = fmaf(f.gz, f.dz, fmaf(f.gy, f.dy, __fmul_rn(f.gx, f.dx)));    // d.C.d
+    f.T = __fadd_rn(__fadd_rn(cxx, cyy), czz);
+    return f;
+}
+
+// The quadrupole acceleration, the second-order Taylor term of the softened kernel about the body's centre of mass:
+//   a_q = -3 (C d) u^5 + 7.5 (d.C.d) u^7 d - 1.5 T u^5 d
+__device__ __forceinline__ void far_quad_acc(const FarQuadFront &f, float &tx, float &ty, float &tz)
+{
+    const float s = fmaf(__fmul_rn(7.5f, f.u7), f.q, __fmul_rn(__fmul_rn(-1.5f, f.T), f.u5));      // what multiplies d
+    const float m3 = __fmul_rn(-3.0f, f.u5);
+    tx = fmaf(m3, f.gx, __fmul_rn(s, f.dx)); ty = fmaf(m3, f.gy, __fmul_rn(s, f.dy)); tz = fmaf(m3, f.gz, __fmul_rn(s, f.dz));
+}
+
+// The quadrupole potential in the convention of the potential's sums (sum of w u, phi = -sum): the term whose gradient is a_q,
+//   t_q = 1.5 (d.C.d) u^5 - 0.5 T u^3
+__device__ __forceinline__ float far_quad_phi(const FarQuadFront &f)
+{
+    return fmaf(__fmul_rn(1.5f, f.u5), f.q, __fmul_rn(__fmul_rn(-0.5f, f.T), f.u3));
+}
+
 __device__ __forceinline__ void far_quad_term(float xi, float yi, float zi, float X, float Y, float Z, float cxx, float cyy,
                                               float czz, float cxy, float cxz, float cyz, float eps2f, float &tx, float &ty,
                                               float &tz)
 {
-    const float dx = X - xi, dy = Y - yi, dz = Z - zi;                  // as the pair forms form it
-    const float r2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-    const float u = __builtin_amdgcn_rsqf(__fadd_rn(r2, eps2f));
-    const float u2 = __fmul_rn(u, u), u3 = __fmul_rn(u2, u), u5 = __fmul_rn(u3, u2), u7 = __fmul_rn(u5, u2);
-    const float gx = fmaf(cxz, dz, fmaf(cxy, dy, __fmul_rn(cxx, dx)));  // C d
-    const float gy = fmaf(cyz, dz, fmaf(cyy, dy, __fmul_rn(cxy, dx)));
-    const float gz = fmaf(czz, dz, fmaf(cyz, dy, __fmul_rn(cxz, dx)));
-    const float q = fmaf(gz, dz, fmaf(gy, dy, __fmul_rn(gx, dx)));      // d.C.d
-    const float T = __fadd_rn(__fadd_rn(cxx, cyy), czz);
-    const float s = fmaf(__fmul_rn(7.5f, u7), q, __fmul_rn(__fmul_rn(-1.5f, T), u5));      // what multiplies d
-    const float m3 = __fmul_rn(-3.0f, u5);
-    tx = fmaf(m3, gx, __fmul_rn(s, dx)); ty = fmaf(m3, gy, __fmul_rn(s, dy)); tz = fmaf(m3, gz, __fmul_rn(s, dz));
+    far_quad_acc(far_quad_front(xi, yi, zi, X, Y, Z, cxx, cyy, czz, cxy, cxz, cyz, eps2f), tx, ty, tz);
 }
 
-// The quadrupole terms of a group of eight level cells, added in index order to the block's quadrupole chain (bx, by, bz).
+// The quadrupole terms of a group of eight level cells, added in index order to the block's quadrupole chains: (bx, by, bz)
+// of the acceleration (ACC) and bp of the potential (PHI); a body's front is formed once for both.
 // c6: the block's Cxx plane at the group (wave-uniform: scalar loads), the five other planes mom_cap apart.  qw: the group's
 // masses AFTER the lane's leave-outs -- a body whose mass is 0 there is no member of the lane's set: +0 is added in its
 // place, which leaves every bit of the chain as it is.
+template <bool ACC, bool PHI>
 __device__ __forceinline__ void far_quad_group(const PairCtx &ctx, const v2f (&qx)[4], const v2f (&qy)[4], const v2f (&qz)[4],
                                                const v2f (&qw)[4], const float *__restrict__ c6, int mom_cap, float eps2f,
-                                               float &bx, float &by, float &bz)
+                                               float &bx, float &by, float &bz, float &bp)
 {
 #pragma unroll
     for (int k = 0; k < 8; k++) {
@@ -196,11 +224,48 @@ __device__ __forceinline__ void far_quad_group(const PairCtx &ctx, const v2f (&q
         const float X = odd ? qx[k >> 1].y : qx[k >> 1].x, Y = odd ? qy[k >> 1].y : qy[k >> 1].x, Z = odd ? qz[k >> 1].y : qz[k >> 1].x;
         const bool in = (odd ? qw[k >> 1].y : qw[k >> 1].x) != 0.f;
         const float *c = c6 + k;
-        float tx, ty, tz;
-        far_quad_term(ctx.xi, ctx.yi, ctx.zi, X, Y, Z, c[0], c[mom_cap], c[2 * (size_t)mom_cap], c[3 * (size_t)mom_cap],
-                      c[4 * (size_t)mom_cap], c[5 * (size_t)mom_cap], eps2f, tx, ty, tz);
-        bx = __fadd_rn(bx, in ? tx : 0.f); by = __fadd_rn(by, in ? ty : 0.f); bz = __fadd_rn(bz, in ? tz : 0.f);
+        const FarQuadFront f = far_quad_front(ctx.xi, ctx.yi, ctx.zi, X, Y, Z, c[0], c[mom_cap], c[2 * (size_t)mom_cap],
+                                              c[3 * (size_t)mom_cap], c[4 * (size_t)mom_cap], c[5 * (size_t)mom_cap], eps2f);
+        if (ACC) {
+            float tx, ty, tz;
+            far_quad_acc(f, tx, ty, tz);
+            bx = __fadd_rn(bx, in ? tx : 0.f); by = __fadd_rn(by, in ? ty : 0.f); bz = __fadd_rn(bz, in ? tz : 0.f);
+        }
+        if (PHI) bp = __fadd_rn(bp, in ? far_quad_phi(f) : 0.f);
     }
+}
+
+// (the force pass's: the acceleration alone)
+__device__ __forceinline__ void far_quad_group(const PairCtx &ctx, const v2f (&qx)[4], const v2f (&qy)[4], const v2f (&qz)[4],
+                                               const v2f (&qw)[4], const float *__restrict__ c6, int mom_cap, float eps2f,
+                                               float &bx, float &by, float &bz)
+{
+    float none = 0.f;
+    far_quad_group<true, false>(ctx, qx, qy, qz, qw, c6, mom_cap, eps2f, bx, by, bz, none);
+}
+
+// The quadrupole chain of the potential for one block of 64 level cells (wave-uniform pointers to its X, Y, Z planes and its
+// Cxx plane: scalar loads), behind the block's monopole chain (pot_walk.hpp, pot_far_block): ONE fp32 chain from +0, in index
+// order, over the members `take` (wave-uniform) of the monopole chain, its sum carried on in acc by an addition of its own.
+// A group of eight without a member adds eight zeros and is skipped.
+__device__ __forceinline__ void far_quad_phi_block(const PairCtx &ctx, const float *__restrict__ sx, const float *__restrict__ sy,
+                                                   const float *__restrict__ sz, const float *__restrict__ sc, int mom_cap,
+                                                   unsigned long long take, float eps2f, double &acc)
+{
+    float a = 0.f;
+    for (int g = 0; g < 64; g += 8) {
+        const unsigned keep = (unsigned)(take >> g) & 0xffu;
+        if (keep == 0u) continue;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const float *c = sc + g + k;
+            const FarQuadFront f = far_quad_front(ctx.xi, ctx.yi, ctx.zi, sx[g + k], sy[g + k], sz[g + k], c[0], c[mom_cap],
+                                                  c[2 * (size_t)mom_cap], c[3 * (size_t)mom_cap], c[4 * (size_t)mom_cap],
+                                                  c[5 * (size_t)mom_cap], eps2f);
+            a = __fadd_rn(a, ((keep >> k) & 1u) ? far_quad_phi(f) : 0.f);
+        }
+    }
+    acc += (double)a;
 }
 
 }  // namespace psamd

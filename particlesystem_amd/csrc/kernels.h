@@ -289,9 +289,10 @@ hipError_t launch_export_live(hipStream_t st, const DevParams &P, const DeviceSt
 
 // psamd_potential: phi of every particle in the own cells' lists (k_pot_pairs), U and the extrema in a fixed tree, phi of the
 // first `capacity` live particles in slot order (phi null or capacity 0: the result alone); result_dev may be null.
-// far_set (PSAMD_POTENTIAL_FAR, far-monopole contexts only): the moments first, then the cell's far set behind the stencil
+// flags: the spec's, validated.  PSAMD_POTENTIAL_FAR (far-monopole contexts only): the moments first, then the cell's far set
+// behind the stencil; with PSAMD_POTENTIAL_QUADRUPOLE (quadrupole contexts only) every member's quadrupole term too
 hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceState &d, float *phi, int64_t capacity,
-                            psamd_potential_result *result_dev, bool far_set);
+                            psamd_potential_result *result_dev, uint32_t flags);
 
 // psamd_probe (max_count > 0): locate + count, the cells' prefix, the cell-major order, the pair pass (one probe to a lane), the
 // result record

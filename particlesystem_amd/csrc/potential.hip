@@ -32,8 +32,15 @@
 // index order, a block's members one chain from +0 (pot_far_walk).  Levels, blocks and members are far_walk.hpp's, the ones
 // the force pass walks; the set is a function of the wave's one cell: members and masks are scalar.
 //
+// PSAMD_POTENTIAL_FAR | PSAMD_POTENTIAL_QUADRUPOLE (quadrupole contexts): all of the above bit for bit, and behind every
+// block's monopole chain that block's quadrupole chain -- the members' terms t_q = 1.5 (d.C.d) u^5 - 0.5 T u^3 (far_walk.hpp,
+// far_quad_phi: the force term's front), one fp32 chain from +0 in index order, carried into the fp64 sum by an addition of
+// its own.
+//
 // VGPRs / waves per SIMD of k_pot_pairs as the compiler reports them for gfx950, no instance with scratch:
-//   cutoff 40 / 8      all-pairs 44 / 8      far monopoles 42 / 8
+//   cutoff 40 / 8      all-pairs 44 / 8      far monopoles 42 / 8      quadrupoles 43 / 7
+// (the quadrupole instance holds a group's X, Y, Z and six C planes in scalar registers: the report shows 32 of them kept in
+// vector lanes and no scratch, so it keeps the launch bound of the others -- by that report, not by a timing)
 #include "far_walk.hpp"
 #include "pot_walk.hpp"
 #include "slot_walk.hpp"
@@ -46,7 +53,10 @@ static_assert(POT_ITEMS == SLOT_ITEMS, "a wave walks POT_ITEMS batches of 64 sor
 
 __device__ __forceinline__ bool pot_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
-// The far part of phi for the cell (i1, i2, i3) all lanes of the wave walk: levels top down, blocks in index order.
+// The far part of phi for the cell (i1, i2, i3) all lanes of the wave walk: levels top down, blocks in index order.  QUAD:
+// behind a block's monopole chain that block's quadrupole chain, over the same members (the six C planes lie behind the
+// four of mom, mom_cap apart: wave-uniform loads like the moments).
+template <bool QUAD>
 __device__ __forceinline__ void pot_far_walk(const PairCtx &ctx, const FarMoments &m, int i1, int i2, int i3, int lane,
                                              float eps2f, double &acc)
 {
@@ -57,11 +67,12 @@ __device__ __forceinline__ void pot_far_walk(const PairCtx &ctx, const FarMoment
             if (take == 0ull) continue;
             const float *sx = m.mom + v.lev.off + blk * 64, *sy = sx + m.mom_cap, *sz = sy + m.mom_cap, *sw = sz + m.mom_cap;
             pot_far_block(ctx, sx, sy, sz, sw, take, eps2f, acc);
+            if (QUAD) far_quad_phi_block(ctx, sx, sy, sz, sw + m.mom_cap, m.mom_cap, take, eps2f, acc);
         }
     }
 }
 
-template <int FAR>      // 0: the stencil alone; 1: all-pairs; 2: far monopoles, flat or as a pyramid
+template <int FAR>      // 0: the stencil alone; 1: all-pairs; 2: far monopoles, flat or as a pyramid; 3: ... and their quadrupole terms
 __global__ __launch_bounds__(POT_THREADS) void k_pot_pairs(DevParams P, const int *__restrict__ cell_start,
                                                            const float *__restrict__ snap_soa,
                                                            const float *__restrict__ snap_age,
@@ -111,7 +122,7 @@ __global__ __launch_bounds__(POT_THREADS) void k_pot_pairs(DevParams P, const in
         const float *sx = snap_soa + nb;
         pot_walk<false>(ctx, sx, sx + cap, sx + 2 * cap, sx + 3 * cap, n, 0, eps2f, true, acc);
     }
-    if (FAR == 2) pot_far_walk(ctx, mono, i1, i2, i3, lane, eps2f, acc);      // (world == 1: local cell == global cell)
+    if (FAR >= 2) pot_far_walk<FAR == 3>(ctx, mono, i1, i2, i3, lane, eps2f, acc);      // (world == 1: local cell == global cell)
     if (FAR == 1) {
         // every other cell of the box in global index order, 64 cell ranges to a vector load (allpairs.hip); the wave's
         // particles share one cell, so the cells of its stencil are left out for the whole wave
@@ -275,7 +286,7 @@ __global__ __launch_bounds__(POT_THREADS) void k_pot_finish(DevParams P, int nti
 }
 
 hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceState &d, float *phi, int64_t capacity,
-                            psamd_potential_result *result_dev, bool far_set)
+                            psamd_potential_result *result_dev, uint32_t flags)
 {
     const int ntiles = slot_tiles(P.slots_total);
     const bool want_phi = phi && capacity > 0 && ntiles > 0;
@@ -283,7 +294,11 @@ hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceStat
     if (want_phi) { const hipError_t e = launch_fill_int(st, reinterpret_cast<int *>(d.pot_slot), 0x7fc00000, (size_t)P.slots_total); if (e != hipSuccess) return e; }
     const int ntask = P.n_own_cells * P.slices;
     if (ntask > 0) {
-        if (far_set) {
+        if (flags & PSAMD_POTENTIAL_QUADRUPOLE) {
+            launch_far_moments(st, P, d);
+            PS_LAUNCH_CHECK();
+            k_pot_pairs<3><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, PotFar{}, far_moments_of(P, d), d.pot_sorted);
+        } else if (flags & PSAMD_POTENTIAL_FAR) {
             launch_far_moments(st, P, d);
             PS_LAUNCH_CHECK();
             k_pot_pairs<2><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, PotFar{}, far_moments_of(P, d), d.pot_sorted);

@@ -36,7 +36,14 @@
 // stencil's chain top level first (part 0 first): on the exact path a probe on a served adult returns its force record
 // bit for bit.  phi: pot_far_block over the same blocks, psamd_potential's.
 //
-// The kernel is templated on acc / phi / both, generic exact / lean exact / fast, cutoff / all-pairs / far monopoles; the
+// PSAMD_PROBE_FAR | PSAMD_PROBE_QUADRUPOLE (quadrupole contexts): the acceleration is k_far_walk<.., true, true>'s association
+// -- far_quad_group as far_block_chain's `after` hook: a block's quadrupole chain from +0 behind each group's pair terms, the
+// blocks' quadrupole chains added in block order to +0, the level's part RN(monopole sum + quadrupole sum) -- and phi is
+// psamd_potential's quadrupole form: behind a block's monopole chain its quadrupole chain, each carried into the fp64 sum by
+// its own addition.  Where both are asked for, a body's front (far_walk.hpp, far_quad_front) is formed once, in the
+// acceleration's walk, and phi's chain rides along: the same terms in the same order as the walk of its own.
+//
+// The kernel is templated on acc / phi / both, generic exact / lean exact / fast, cutoff / all-pairs / far monopoles / quadrupoles; the
 // registers and waves per SIMD of every instance are in the table at k_probe_pairs.
 #include "far_walk.hpp"
 #include "multisplit.hpp"
@@ -162,13 +169,15 @@ __device__ __forceinline__ void probe_acc_walk(const DevParams &P, const PairCtx
 __device__ __forceinline__ bool probe_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // VGPRs / waves per SIMD as the compiler reports them for gfx950, no instance with scratch (cutoff | all-pairs | far
-// monopoles; the generic exact form has neither an all-pairs nor a far-monopole instance):
-//                 generic exact      lean exact            fast
-//   acc           28 / 8             66 / 7 | 83 / 5 | 79 / 6       58 / 8 | 75 / 6 | 71 / 7
-//   phi           40 / 7             40 / 7 | 41 / 7 | 41 / 7       40 / 7 | 41 / 7 | 41 / 7
-//   acc and phi   44 / 7             72 / 7 | 87 / 5 | 83 / 5       62 / 7 | 77 / 6 | 73 / 6
-// (acc and phi walk a cell's list once each: the two passes share no registers, and their loads hit the scalar cache.)
-template <int FIELDS, int MATH, int FAR>      // FAR 0: the stencil alone; 1: all-pairs; 2: far monopoles, flat or as a pyramid
+// monopoles | quadrupoles; the generic exact form has no all-pairs, far-monopole or quadrupole instance):
+//                 generic exact      lean exact                      fast
+//   acc           28 / 8             66 / 7 | 83 / 5 | 79 / 6 | 134 / 3      58 / 8 | 75 / 6 | 71 / 7 | 114 / 4
+//   phi           40 / 7             40 / 7 | 41 / 7 | 41 / 7 | 47 / 7       40 / 7 | 41 / 7 | 41 / 7 | 47 / 7
+//   acc and phi   44 / 7             72 / 7 | 87 / 5 | 83 / 5 | 135 / 3      62 / 7 | 77 / 6 | 73 / 6 | 115 / 4
+// (acc and phi walk a cell's list once each: the two passes share no registers, and their loads hit the scalar cache.  The
+// quadrupole instances with acc carry a group's pair rows and its ten planes at once; the report shows 55-83 scalar registers
+// kept in vector lanes and no scratch, so they keep the others' launch bound -- by that report, not by a timing.)
+template <int FIELDS, int MATH, int FAR>      // FAR 0: the stencil alone; 1: all-pairs; 2: far monopoles, flat or as a pyramid; 3: ... and their quadrupole terms
 __global__ __launch_bounds__(PROBE_THREADS) void k_probe_pairs(DevParams P, const int *__restrict__ cell_start,
                                                                const float *__restrict__ snap_soa,
                                                                const float4 *__restrict__ pos4, const int *__restrict__ code,
@@ -216,30 +225,48 @@ __global__ __launch_bounds__(PROBE_THREADS) void k_probe_pairs(DevParams P, cons
             if (FIELDS & PSAMD_PROBE_ACC) probe_acc_walk<MATH>(P, ctx, sx, sx + cap, sx + 2 * cap, sx + 3 * cap, n, eps2f, ax, ay, az);
             if (FIELDS & PSAMD_PROBE_PHI) pot_walk<false>(ctx, sx, sx + cap, sx + 2 * cap, sx + 3 * cap, n, 0, eps2f, true, acc);
         }
-        if (FAR == 2) {
+        if (FAR >= 2) {
             // the far set of THIS cell (world == 1: local cell == global cell), levels top down; a level's blocks in index
             // order, dealt to the force pass's parts (one part a level on a pyramid)
+            constexpr bool QUAD = FAR == 3, ACC = (FIELDS & PSAMD_PROBE_ACC) != 0, PHI = (FIELDS & PSAMD_PROBE_PHI) != 0;
             for (int l = mono.nlev - 1; l >= 0; l--) {
                 const FarLevelView v = far_level_view(mono, l, i1, i2, i3);
                 for (int part = 0; part < mono.nparts; part++) {
                     const int b_lo = max(v.blk_lo, v.lev.nblk * part / mono.nparts), b_hi = min(v.blk_hi, v.lev.nblk * (part + 1) / mono.nparts);
                     float px = 0.f, py = 0.f, pz = 0.f;     // the part's sum
+                    float ux = 0.f, uy = 0.f, uz = 0.f;     // ... and its quadrupole sum (QUAD)
                     for (int blk = b_lo; blk < b_hi; blk++) {
                         const unsigned long long take = far_members(mono, v, blk, lane);
                         if (take == 0ull) continue;         // (a chain of nothing is +0, and neither sum ever is -0)
                         const float *sx = mono.mom + v.lev.off + blk * 64, *sy = sx + mono.mom_cap, *sz = sy + mono.mom_cap, *sw = sz + mono.mom_cap;
-                        if (FIELDS & PSAMD_PROBE_ACC) {
+                        float bp = 0.f;                     // the block's quadrupole chain of phi, where the acceleration's walk forms it
+                        if (ACC) {
                             // the force pass's chain for the block; what a cell of a group is left out by is a scalar mask here
                             float cx, cy, cz;
-                            far_block_chain<MATH>(P, ctx, sx, sy, sz, sw, take, eps2f, [&](int g, v2f (&qw)[4]) {
+                            const auto leave = [&](int g, v2f (&qw)[4]) {
 #pragma unroll
                                 for (int k = 0; k < 8; k++) far_drop(qw, k, !((take >> (g + k)) & 1ull));
-                            }, cx, cy, cz);
+                            };
+                            if (QUAD) {
+                                // ... and the force pass's quadrupole chain behind each group's pair terms; with PHI the
+                                // potential's quadrupole chain from the same front of every body
+                                float bx = 0.f, by = 0.f, bz = 0.f;
+                                const float *sc = sw + mono.mom_cap;
+                                far_block_chain<MATH>(P, ctx, sx, sy, sz, sw, take, eps2f, leave, [&](int g, v2f (&qx)[4], v2f (&qy)[4], v2f (&qz)[4], v2f (&qw)[4]) {
+                                    far_quad_group<true, PHI>(ctx, qx, qy, qz, qw, sc + g, mono.mom_cap, eps2f, bx, by, bz, bp);
+                                }, cx, cy, cz);
+                                ux = __fadd_rn(ux, bx); uy = __fadd_rn(uy, by); uz = __fadd_rn(uz, bz);
+                            } else far_block_chain<MATH>(P, ctx, sx, sy, sz, sw, take, eps2f, leave, cx, cy, cz);
                             px += cx; py += cy; pz += cz;
                         }
-                        if (FIELDS & PSAMD_PROBE_PHI) pot_far_block(ctx, sx, sy, sz, sw, take, eps2f, acc);
+                        if (PHI) {
+                            pot_far_block(ctx, sx, sy, sz, sw, take, eps2f, acc);
+                            if (QUAD && ACC) acc += (double)bp;
+                            else if (QUAD) far_quad_phi_block(ctx, sx, sy, sz, sw + mono.mom_cap, mono.mom_cap, take, eps2f, acc);
+                        }
                     }
-                    if (FIELDS & PSAMD_PROBE_ACC) { ax += px; ay += py; az += pz; }
+                    if (ACC && QUAD) { px = __fadd_rn(px, ux); py = __fadd_rn(py, uy); pz = __fadd_rn(pz, uz); }
+                    if (ACC) { ax += px; ay += py; az += pz; }
                 }
             }
         }
@@ -302,7 +329,10 @@ template <int FIELDS, int MATH>
 static void launch_probe_pairs(hipStream_t st, const DevParams &P, const DeviceState &d, const ProbeArgs &a, const ProbeScratch &s,
                                int *hdr, unsigned nwg)
 {
-    if (a.fields & PSAMD_PROBE_FAR) {
+    if (a.fields & PSAMD_PROBE_QUADRUPOLE) {
+        if constexpr (MATH != 0)       // (quadrupole contexts are far-monopole contexts, and the bit comes with PSAMD_PROBE_FAR)
+            k_probe_pairs<FIELDS, MATH, 3><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, PotFar{}, far_moments_of(P, d), a.out4);
+    } else if (a.fields & PSAMD_PROBE_FAR) {
         if constexpr (MATH != 0)       // (far-monopole contexts are created only with lean arithmetic and world 1)
             k_probe_pairs<FIELDS, MATH, 2><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, PotFar{}, far_moments_of(P, d), a.out4);
     } else if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
@@ -337,7 +367,7 @@ hipError_t launch_probe(hipStream_t st, const DevParams &P, const DeviceState &d
     k_probe_scatter<<<blocks, PROBE_THREADS, 0, st>>>(a.max_count, a.count_dev, s.code, s.counts, s.order);
     PS_LAUNCH_CHECK();
     const unsigned nwg = (unsigned)((a.max_count + 255) / 256);
-    const uint32_t what = a.fields & (PSAMD_PROBE_ACC | PSAMD_PROBE_PHI);      // (PSAMD_PROBE_FAR is a modifier)
+    const uint32_t what = a.fields & (PSAMD_PROBE_ACC | PSAMD_PROBE_PHI);      // (PSAMD_PROBE_FAR and PSAMD_PROBE_QUADRUPOLE are modifiers)
     if (what == PSAMD_PROBE_ACC) launch_probe_fields<PSAMD_PROBE_ACC>(st, P, d, a, s, hdr, nwg);
     else if (what == PSAMD_PROBE_PHI) launch_probe_fields<PSAMD_PROBE_PHI>(st, P, d, a, s, hdr, nwg);
     else launch_probe_fields<PSAMD_PROBE_ACC | PSAMD_PROBE_PHI>(st, P, d, a, s, hdr, nwg);

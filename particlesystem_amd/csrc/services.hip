@@ -199,16 +199,30 @@ static int frame_ready(psamd_ctx *c, const char *who)
 }
 
 static bool far_context(const psamd_ctx *c) { return (c->P.flags & (PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID)) != 0; }
+static bool quad_context(const psamd_ctx *c) { return (c->P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) != 0; }
+
+// the modifier bits this context kind knows: the far form on far-monopole contexts, its quadrupole form on quadrupole contexts
+static uint32_t potential_bits(const psamd_ctx *c)
+{
+    return (far_context(c) ? PSAMD_POTENTIAL_FAR : 0u) | (quad_context(c) ? PSAMD_POTENTIAL_QUADRUPOLE : 0u);
+}
+
+static uint32_t probe_far_bits(const psamd_ctx *c)
+{
+    return (far_context(c) ? PSAMD_PROBE_FAR : 0u) | (quad_context(c) ? PSAMD_PROBE_QUADRUPOLE : 0u);
+}
 
 // potential and probe promise exactly the bodies the force pass walks: with far monopoles (flat or as a pyramid) a
 // stencil-only answer would break that silently, and a caller written for the stencil's bodies is never handed another
 // quantity -- the monopole form is served only where it is asked for (PSAMD_POTENTIAL_FAR, PSAMD_PROBE_FAR)
-// ... and on a quadrupole context (PSAMD_FLAG_FAR_QUADRUPOLE) the far form is monopoles only: not that context's field either
-static int refuse_far_monopole(psamd_ctx *c, const char *who, bool far_asked)
+// ... and on a quadrupole context (PSAMD_FLAG_FAR_QUADRUPOLE) the far form alone is monopoles only, not that context's field
+// either: there the quadrupole form is served, where both bits ask for it (PSAMD_POTENTIAL_QUADRUPOLE, PSAMD_PROBE_QUADRUPOLE)
+static int refuse_far_monopole(psamd_ctx *c, const char *who, bool far_asked, bool quad_asked)
 {
-    if (c->P.flags & PSAMD_FLAG_FAR_QUADRUPOLE)
-        return fail(c, PSAMD_ERR_UNSUPPORTED, std::string(who) + ": the far form is monopoles only; a context with quadrupoles on the pyramid "
-                                              "(PSAMD_FLAG_FAR_QUADRUPOLE) is not served");
+    if (quad_context(c) && !(far_asked && quad_asked))
+        return fail(c, PSAMD_ERR_UNSUPPORTED, std::string(who) + ": on a context with quadrupoles on the pyramid (PSAMD_FLAG_FAR_QUADRUPOLE) only the "
+                                              "quadrupole far form is served (PSAMD_POTENTIAL_FAR | PSAMD_POTENTIAL_QUADRUPOLE, "
+                                              "PSAMD_PROBE_FAR | PSAMD_PROBE_QUADRUPOLE); the far form alone is monopoles only");
     if (far_context(c) && !far_asked)
         return fail(c, PSAMD_ERR_UNSUPPORTED, std::string(who) + ": on a context with far monopoles (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID) "
                                               "only the far form is served (PSAMD_POTENTIAL_FAR, psamd_download_potential_far, PSAMD_PROBE_FAR)");
@@ -216,9 +230,9 @@ static int refuse_far_monopole(psamd_ctx *c, const char *who, bool far_asked)
 }
 
 // ... and nothing of the plan is lent
-static int potential_ready(psamd_ctx *c, bool far_asked)
+static int potential_ready(psamd_ctx *c, uint32_t flags)
 {
-    PS_TRY(refuse_far_monopole(c, "potential", far_asked));
+    PS_TRY(refuse_far_monopole(c, "potential", (flags & PSAMD_POTENTIAL_FAR) != 0, (flags & PSAMD_POTENTIAL_QUADRUPOLE) != 0));
     PS_TRY(frame_ready(c, "potential"));
     const SlabPlan &pl = c->plan;
     if (c->P.world > 1 && (pl.lentin_lo < pl.lentin_hi || pl.lentout_lo < pl.lentout_hi))
@@ -227,34 +241,46 @@ static int potential_ready(psamd_ctx *c, bool far_asked)
     return PSAMD_OK;
 }
 
+// the spec's flags, of psamd_potential and of its host forms: no bit this context kind does not know, no modifier alone
+static int potential_flags(psamd_ctx *c, uint32_t flags)
+{
+    if (flags & ~potential_bits(c))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "potential: unknown flag bits (PSAMD_POTENTIAL_FAR belongs to far-monopole contexts, "
+                                              "PSAMD_POTENTIAL_QUADRUPOLE to quadrupole contexts)");
+    if ((flags & PSAMD_POTENTIAL_QUADRUPOLE) && !(flags & PSAMD_POTENTIAL_FAR))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "potential: PSAMD_POTENTIAL_QUADRUPOLE is a modifier of PSAMD_POTENTIAL_FAR");
+    return PSAMD_OK;
+}
+
 int psamd_potential(psamd_ctx *c, const psamd_potential_spec *spec)
 {
     if (!c || !spec) return PSAMD_ERR_INVALID_ARG;
-    // (PSAMD_POTENTIAL_FAR is a known bit on far-monopole contexts only)
-    if ((spec->flags & ~(far_context(c) ? PSAMD_POTENTIAL_FAR : 0u)) || spec->reserved != 0)
-        return fail(c, PSAMD_ERR_INVALID_ARG, "potential: unknown flag bits (PSAMD_POTENTIAL_FAR belongs to far-monopole contexts), or reserved not 0");
-    const bool far_asked = (spec->flags & PSAMD_POTENTIAL_FAR) != 0;
+    PS_TRY(potential_flags(c, spec->flags));
+    if (spec->reserved != 0) return fail(c, PSAMD_ERR_INVALID_ARG, "potential: reserved not 0");
     if (spec->capacity < 0) return fail(c, PSAMD_ERR_INVALID_ARG, "potential: capacity < 0");
     if (!aligned(spec->phi, 4) || (!spec->phi && spec->capacity > 0) || !aligned(spec->result_dev, 8))
         return fail(c, PSAMD_ERR_INVALID_ARG, "potential: phi missing or misaligned, or result_dev misaligned");
-    PS_TRY(potential_ready(c, far_asked));
-    PS_HIP(c, launch_potential(c->stream, c->P, c->d, spec->phi, spec->capacity, spec->result_dev, far_asked));
+    PS_TRY(potential_ready(c, spec->flags));
+    PS_HIP(c, launch_potential(c->stream, c->P, c->d, spec->phi, spec->capacity, spec->result_dev, spec->flags));
     return PSAMD_OK;
 }
 
 int psamd_potential_result_get(psamd_ctx *c, psamd_potential_result *out) { return read_own(c, out, c ? &c->d.pot_out->result : nullptr, sizeof *out); }
 
-// psamd_download_potential and psamd_download_potential_far
-static int download_potential(psamd_ctx *c, float *phi, int64_t capacity, psamd_potential_result *out, bool far_asked)
+// the one body of psamd_download_potential, psamd_download_potential_far and psamd_download_potential_flags; `checked`: the
+// flags are a caller's and are validated as psamd_potential validates them (the two old forms keep their statuses: on a
+// context without far monopoles the far form is PSAMD_ERR_UNSUPPORTED, behind the argument checks)
+static int download_potential(psamd_ctx *c, uint32_t flags, bool checked, float *phi, int64_t capacity, psamd_potential_result *out)
 {
     if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (checked) PS_TRY(potential_flags(c, flags));
     if (capacity < 0 || (!phi && capacity > 0)) return fail(c, PSAMD_ERR_INVALID_ARG, "download_potential: capacity < 0, or no array for it");
-    if (far_asked && !far_context(c))
+    if (!checked && (flags & PSAMD_POTENTIAL_FAR) && !far_context(c))
         return fail(c, PSAMD_ERR_UNSUPPORTED, "download_potential_far: the context has no far monopoles (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID)");
-    PS_TRY(potential_ready(c, far_asked));
+    PS_TRY(potential_ready(c, flags));
     const int64_t n = std::min<int64_t>(capacity, c->P.slots_total);
     PS_TRY(ensure_staging(c, std::max<size_t>((size_t)n * sizeof(float), 256)));
-    PS_HIP(c, launch_potential(c->stream, c->P, c->d, n > 0 ? (float *)c->staging : nullptr, n, nullptr, far_asked));
+    PS_HIP(c, launch_potential(c->stream, c->P, c->d, n > 0 ? (float *)c->staging : nullptr, n, nullptr, flags));
     PotOut got{};
     PS_HIP(c, hipMemcpyAsync(&got, c->d.pot_out, sizeof got, hipMemcpyDeviceToHost, c->stream));
     PS_HIP(c, hipStreamSynchronize(c->stream));
@@ -269,12 +295,17 @@ static int download_potential(psamd_ctx *c, float *phi, int64_t capacity, psamd_
 
 int psamd_download_potential(psamd_ctx *c, float *phi, int64_t capacity, psamd_potential_result *out)
 {
-    return download_potential(c, phi, capacity, out, false);
+    return download_potential(c, 0u, false, phi, capacity, out);
 }
 
 int psamd_download_potential_far(psamd_ctx *c, float *phi, int64_t capacity, psamd_potential_result *out)
 {
-    return download_potential(c, phi, capacity, out, true);
+    return download_potential(c, PSAMD_POTENTIAL_FAR, false, phi, capacity, out);
+}
+
+int psamd_download_potential_flags(psamd_ctx *c, uint32_t flags, float *phi, int64_t capacity, psamd_potential_result *out)
+{
+    return download_potential(c, flags, true, phi, capacity, out);
 }
 
 // ---- the field at chosen points (probe.hip) ----
@@ -295,18 +326,21 @@ static int grow_probe_scratch(psamd_ctx *c, ProbeScratch &s, int64_t max_count)
 int psamd_probe(psamd_ctx *c, const psamd_probe_spec *spec)
 {
     PS_TRY(service_args(c, spec));
-    // (PSAMD_PROBE_FAR is a known bit on far-monopole contexts only, and a modifier: it asks for no component)
+    // (PSAMD_PROBE_FAR is a known bit on far-monopole contexts only, PSAMD_PROBE_QUADRUPOLE on quadrupole contexts only, and both
+    // are modifiers: they ask for no component)
     if ((spec->fields & (PSAMD_PROBE_ACC | PSAMD_PROBE_PHI)) == 0 ||
-        (spec->fields & ~(PSAMD_PROBE_ACC | PSAMD_PROBE_PHI | (far_context(c) ? PSAMD_PROBE_FAR : 0u))) || spec->reserved != 0)
+        (spec->fields & ~(PSAMD_PROBE_ACC | PSAMD_PROBE_PHI | probe_far_bits(c))) || spec->reserved != 0)
         return fail(c, PSAMD_ERR_INVALID_ARG, "probe: fields without PSAMD_PROBE_ACC or PSAMD_PROBE_PHI or with unknown bits (PSAMD_PROBE_FAR belongs "
-                                              "to far-monopole contexts), or reserved not 0");
+                                              "to far-monopole contexts, PSAMD_PROBE_QUADRUPOLE to quadrupole contexts), or reserved not 0");
+    if ((spec->fields & PSAMD_PROBE_QUADRUPOLE) && !(spec->fields & PSAMD_PROBE_FAR))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "probe: PSAMD_PROBE_QUADRUPOLE is a modifier of PSAMD_PROBE_FAR");
     if (spec->max_count < 0 || spec->max_count > INT32_MAX) return fail(c, PSAMD_ERR_INVALID_ARG, "probe: max_count outside [0, 2^31)");
     if ((spec->max_count > 0 && (!spec->pos4 || !spec->out4)) || !aligned(spec->pos4, 16) || !aligned(spec->out4, 16) ||
         !aligned(spec->outcome_dev, 4) || !aligned(spec->count_dev, 8) || !aligned(spec->result_dev, 8))
         return fail(c, PSAMD_ERR_INVALID_ARG, "probe: pos4 or out4 missing, or an array misaligned");
     if ((c->P.flags & PSAMD_FLAG_ALL_PAIRS) && c->P.world > 1)
         return fail(c, PSAMD_ERR_UNSUPPORTED, "probe: all-pairs contexts are served on one context only (world == 1)");
-    PS_TRY(refuse_far_monopole(c, "probe", (spec->fields & PSAMD_PROBE_FAR) != 0));
+    PS_TRY(refuse_far_monopole(c, "probe", (spec->fields & PSAMD_PROBE_FAR) != 0, (spec->fields & PSAMD_PROBE_QUADRUPOLE) != 0));
     PS_TRY(frame_ready(c, "probe"));
     psamd_probe_result *res = spec->result_dev ? spec->result_dev : c->prb.own;
     if (spec->max_count == 0) return zero_result(c, c->prb.own, res, sizeof *res);

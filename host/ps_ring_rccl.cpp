@@ -8,7 +8,7 @@
 //       ps_ring_rccl --world W --rank r --device d --id-file /tmp/id --job J [--bench ...]
 //     rank 0 writes the communicator's ncclUniqueId to the file (tagged with the job's nonce J), the others wait for it.
 //   all slabs in ONE process on GPU 0 (what a one-GPU test box can run):
-//       ps_ring_rccl --world W --loopback [--n N] [--iters K] [--seed S] [--all-pairs] [--births]
+//       ps_ring_rccl --world W --loopback [--n N] [--iters K] [--seed S] [--all-pairs | --far flat|pyramid|quadrupole] [--births]
 //     The communicator has a single rank; every message is an ncclSend to self matched by
 //     an ncclRecv from self in the same group -- RCCL moves every byte, between the buffers of
 //     different contexts.  This mode also runs the whole system in one plain context and
@@ -104,12 +104,20 @@ int run_without_gpu(const Options &o)
 // the particles every slab is shown (each keeps its own segments'), and the configuration they share
 struct Cloud { psamd_config cfg0; std::vector<float> xyz, age, fert; };
 
+// --far: the far-field force model of the slabs and of the loopback check's plain context.  The slabs also say that this host
+// all-gathers the cell sums (PSAMD_FLAG_FAR_SLAB: allg_out into allg_in between slab_build and slab_pairs, ring_step.hpp)
+uint32_t far_flags(const Options &o)
+{
+    const uint32_t model[4] = {0u, PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID, PSAMD_FLAG_FAR_PYRAMID | PSAMD_FLAG_FAR_QUADRUPOLE};
+    return model[far_model(o)];
+}
+
 void make_config(const Options &o, psamd_config *cfg0)
 {
     psamd_default_config(cfg0);
     cfg0->chunk_factor = o.chunk_factor; cfg0->chunk_dim = o.chunk_dim;
     cfg0->max_particles_num = (int32_t)std::max<int64_t>(std::max<int64_t>(o.n, o.max_particles), 1 << 20);
-    cfg0->flags = (o.all_pairs ? PSAMD_FLAG_ALL_PAIRS : 0u) | (o.births ? PSAMD_FLAG_EXPLOSIONS : 0u) | (o.fast_math ? PSAMD_FLAG_FAST_MATH : 0u);
+    cfg0->flags = (o.all_pairs ? PSAMD_FLAG_ALL_PAIRS : 0u) | (o.births ? PSAMD_FLAG_EXPLOSIONS : 0u) | (o.fast_math ? PSAMD_FLAG_FAST_MATH : 0u) | far_flags(o);
     cfg0->halo_cap_cell = o.halo_cap_cell; cfg0->xfer_cap = o.xfer_cap;
     cfg0->seed = o.seed;
 }
@@ -138,6 +146,7 @@ int make_slabs(Ring &R, const Options &o, Cloud &cloud)
         Slab s; s.rank = r;
         psamd_config cfg = cloud.cfg0;
         cfg.device = o.device; cfg.rank = r; cfg.world = o.world;
+        if (far_flags(o)) cfg.flags |= PSAMD_FLAG_FAR_SLAB;
         if (o.break_sizes && r == 1) cfg.halo_cap_cell = (cfg.halo_cap_cell > 0 ? cfg.halo_cap_cell : 64) + 8;
         psamd_ctx *ctx = nullptr;
         PS_OK(ctx, psamd_create(&cfg, &ctx));

@@ -66,7 +66,8 @@ struct ClockWatch {
 };
 
 // force terms one pair pass evaluates: per visited particle its stencil's population (27 cells, not periodic:
-// app.cu:352-409), or -- all-pairs -- every listed body
+// app.cu:352-409), or -- all-pairs -- every listed body.  A far-field run (--far) counts the stencil's terms only: its far
+// bodies, one per cell or per member of the pyramid's far set, are left out, and the record says so (force_terms_count)
 double force_terms(const std::vector<int64_t> &n, const std::vector<int32_t> &f, int G, bool all_pairs)
 {
     double total = 0;
@@ -355,7 +356,9 @@ int print_record(Bench &B)
     put(r, "rccl_mb_rank0", "%.3f", R.moved / 1e6);
     put(r, "graphs", "%s", tf(o.graphs && grc == PSAMD_OK)); put(r, "graph_replays", "%lld", (long long)gl); put(r, "graph_captures", "%lld", (long long)gc);
     put(r, "side_stream", "%s", tf(o.side_stream != 0)); put(r, "overlap_interior", "%s", tf(o.overlap_interior));
-    put(r, "all_pairs", "%s", tf(o.all_pairs)); put(r, "fast_math", "%s", tf(o.fast_math)); put(r, "evolve", "%s", tf(o.evolve));
+    put(r, "all_pairs", "%s", tf(o.all_pairs)); put(r, "far", "\"%s\"", o.far.empty() ? "none" : o.far.c_str());
+    put(r, "force_terms_count", "\"%s\"", o.far.empty() ? "all" : "stencil terms only (the far bodies are not counted)");
+    put(r, "fast_math", "%s", tf(o.fast_math)); put(r, "evolve", "%s", tf(o.evolve));
     put(r, "halo_cap_cell", "%d", o.halo_cap_cell); put(r, "xfer_cap", "%d", o.xfer_cap); put(r, "side_stream_mode", "%d", o.side_stream);
     put(r, "shader_clock_mhz", "%s", B.clock.c_str());
     put(r, "sustained_steps", "%d", o.sustained_steps > o.steps ? o.sustained_steps : 0); put(r, "sustained_ms_per_step", "%.6f", B.sustained_ms);

@@ -14,6 +14,7 @@ struct Options {
     uint32_t seed = 2026;
     uint64_t job = 0;
     std::string id_file;
+    std::string far;                                                 // "", or the far-field force model: flat, pyramid, quadrupole
     bool loopback = false, all_pairs = false, births = false, graphs = false, bench = false, evolve = false, overlap_interior = false, fast_math = false;
     bool id_only = false, launch_check = false, routes = false;     // the hooks that need no GPU
     bool break_sizes = false;                                        // (test hook: rank 1 is created with other message sizes than its neighbours expect)
@@ -34,6 +35,10 @@ const struct { const char *name; int Options::*value; } kInts[] = {
     {"--chunk-dim", &Options::chunk_dim}, {"--halo-cap-cell", &Options::halo_cap_cell}, {"--xfer-cap", &Options::xfer_cap},
     {"--side-stream", &Options::side_stream}, {"--timing-period", &Options::timing_period}, {"--sustained-steps", &Options::sustained_steps}};
 
+// the far-field model of --far as a number: 0 none, 1 flat, 2 pyramid, 3 pyramid with quadrupoles (ps_ring_rccl.cpp turns it
+// into the context's flags; this header knows nothing of the library)
+inline int far_model(const Options &o) { return o.far == "flat" ? 1 : o.far == "pyramid" ? 2 : o.far == "quadrupole" ? 3 : 0; }
+
 // 0, or the exit status (2: an unknown option, or options that do not make a run)
 int parse_args(int argc, char **argv, Options &o)
 {
@@ -48,17 +53,25 @@ int parse_args(int argc, char **argv, Options &o)
         else if (a == "--max-particles") o.max_particles = std::atoll(next());
         else if (a == "--seed") o.seed = (uint32_t)std::atoll(next());
         else if (a == "--id-file") o.id_file = next();
+        else if (a == "--far") {
+            o.far = i + 1 < argc ? argv[++i] : "";
+            if (!far_model(o)) { std::fprintf(stderr, "--far takes flat, pyramid or quadrupole\n"); return 2; }
+        }
         else if (a == "--job") o.job = (uint64_t)std::strtoull(next(), nullptr, 10);
         else if (a == "--graphs") o.graphs = std::atoi(next()) != 0;
         else if (a == "--settle-seconds") o.settle_seconds = std::atof(next());
         else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
+    }
+    if (!o.far.empty() && o.all_pairs) {
+        std::fprintf(stderr, "--far and --all-pairs are two force models: choose one\n");
+        return 2;
     }
     o.side_stream = std::max(0, std::min(2, o.side_stream));
     o.timing_period = std::max(1, o.timing_period);
     o.sustained_steps = std::max(0, o.sustained_steps);
     if (o.world < 1 || o.rank < 0 || o.rank >= o.world || (!o.routes && !o.loopback && o.world > 1 && o.id_file.empty())) {
         std::fprintf(stderr, "usage: ps_ring_rccl --world W (--loopback | --rank r --id-file F --job J [--device d]) [--n N] [--iters K] [--seed S] "
-                             "[--all-pairs] [--births] [--graphs 0|1] [--side-stream 0|1|2] [--overlap-interior] [--bench --steps K --warmup W ...]\n");
+                             "[--all-pairs | --far flat|pyramid|quadrupole] [--births] [--graphs 0|1] [--side-stream 0|1|2] [--overlap-interior] [--bench --steps K --warmup W ...]\n");
         return 2;
     }
     if (o.device < 0) o.device = o.loopback ? 0 : o.rank;

@@ -6,7 +6,7 @@
 // rank r+1's halo_in[below]; halo_out[below] -> rank r-1's halo_in[above]); after slab_pairs the force records of lent
 // layers (force_out -> rank r-1's force_in); after slab_apply the particles that change owner, on the ring
 // (xfer_out[below] -> rank (r-1)%W's xfer_in[above], xfer_out[above] -> rank (r+1)%W's xfer_in[below]; hop two
-// likewise in worlds of four or more).  The status records, the snapshot blocks of an all-pairs run and the far
+// likewise in worlds of four or more).  The status records, the snapshot blocks of an all-pairs run (or the cell sums of a far-field run, in the same buffers) and the far
 // outboxes are all-gathered.  All sizes are fixed by the plan; a message of 0 bytes does not exist.
 #pragma once
 #include <cstdint>

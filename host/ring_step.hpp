@@ -4,7 +4,7 @@
 // Two HIP streams.  The stage kernels run on the COMPUTE stream -- with --graphs 1 each stage's kernels as
 // one captured hipGraph, so a rank's step is five submissions, not two dozen launches (measured: a graph
 // launch costs ~10 us on the GPU's timeline, the plain launches of a host that runs ahead cost nothing:
-// profiles/r4_ab_graphs.txt; off by default) --, every RCCL call on the TRANSFER stream; events order the two: the halo (and the all-pairs snapshot all-gather)
+// profiles/r4_ab_graphs.txt; off by default) --, every RCCL call on the TRANSFER stream; events order the two: the halo (and the all-gather of the all-pairs snapshot blocks or of a far slab's cell sums)
 // waits for slab_build and travels while the compute stream runs the interior pair pass (--overlap-interior)
 // or simply goes ahead; the all-gather of the status records lands before the first pair-stage call; force and
 // transfer messages fork off after slab_pairs / slab_apply and are joined before the stage that reads them.
@@ -127,7 +127,8 @@ int exchange(Ring &R, Phase ph, hipStream_t st)
 }
 
 // an all-gathered buffer pair: the status records, the snapshot blocks of an all-pairs run (between slab_build and
-// slab_pairs: SURVEY 8(e)'s "all-gather of positions once per step"), or the far outboxes of the transfer phase
+// slab_pairs: SURVEY 8(e)'s "all-gather of positions once per step") or in their place the cell sums of a far-field
+// run (--far), or the far outboxes of the transfer phase
 int gather(Ring &R, int out_slot, int in_slot, hipStream_t st)
 {
     const Slab &s0 = R.local[0];
@@ -179,7 +180,7 @@ int ring_step(Ring &R, Hook between)
         if (gather(R, STATUS_OUT, STATUS_IN, s_halo)) return 1;        // first: a 16-KB all-gather, and the interior pass waits for nothing else
         if (s_halo != R.compute) HIP_OK(hipEventRecord(R.ev_force, R.transfer));
         if (exchange(R, HALO, s_halo)) return 1;
-        if (gather(R, ALLG_OUT, ALLG_IN, s_halo)) return 1;            // all-pairs forces only
+        if (gather(R, ALLG_OUT, ALLG_IN, s_halo)) return 1;            // all-pairs forces (the snapshot blocks) and far-field slabs (the cell sums)
         if (s_halo != R.compute) HIP_OK(hipEventRecord(R.ev_halo, R.transfer));
     }
     if (R.overlap_interior) {

@@ -64,13 +64,19 @@ typedef enum psamd_status {
 #define PSAMD_FLAG_FAR_MONOPOLE 0x10u /* long-range gravity at a small multiple of the cutoff step's cost: the stencil first, in the
                                          reference's order, then every OTHER cell of the box as one body -- its total mass at its
                                          centre of mass.  See "long-range gravity" below.  Collisions stay short-range.  Not with
-                                         PSAMD_FLAG_ALL_PAIRS (PSAMD_ERR_INVALID_ARG); world == 1 only */
+                                         PSAMD_FLAG_ALL_PAIRS (PSAMD_ERR_INVALID_ARG); world == 1 only, unless PSAMD_FLAG_FAR_SLAB is set */
 #define PSAMD_FLAG_FAR_PYRAMID 0x20u  /* long-range gravity whose cost grows with log G instead of G^3: the stencil first, then coarser
                                          cells for farther mass -- a pyramid of monopoles.  See "a pyramid of monopoles" below.  Not
-                                         with PSAMD_FLAG_ALL_PAIRS or PSAMD_FLAG_FAR_MONOPOLE (PSAMD_ERR_INVALID_ARG); world == 1 only */
+                                         with PSAMD_FLAG_ALL_PAIRS or PSAMD_FLAG_FAR_MONOPOLE (PSAMD_ERR_INVALID_ARG); world == 1 only,
+                                         unless PSAMD_FLAG_FAR_SLAB is set */
 #define PSAMD_FLAG_FAR_QUADRUPOLE 0x40u /* a modifier of PSAMD_FLAG_FAR_PYRAMID (alone: PSAMD_ERR_INVALID_ARG): every cell of the
                                          pyramid also carries its second moments, and every far body adds its quadrupole term.  See
                                          "quadrupoles on the pyramid" below */
+#define PSAMD_FLAG_FAR_SLAB 0x80u     /* a modifier of PSAMD_FLAG_FAR_MONOPOLE and PSAMD_FLAG_FAR_PYRAMID (alone, or with
+                                         PSAMD_FLAG_ALL_PAIRS: PSAMD_ERR_INVALID_ARG): the host says that it all-gathers allg_out
+                                         into allg_in between slab_build and slab_pairs, so the far field is served with
+                                         world > 1.  With world == 1 no message exists and every byte is what the context
+                                         computes without the flag.  See "far field on slabs" below */
 
 /* Runtime form of the reference's compile-time configuration, common.h:12-70.
  * psamd_default_config() fills in the shipped values. */
@@ -466,8 +472,10 @@ typedef struct psamd_slab_buffers {
                                               every rank in the same step (config.xfer_cap_max); read it after psamd_slab_apply */
     void   *status_out, *status_in;        /* ALL-GATHERED once per step: status_in = world records of status_bytes each, by rank */
     int64_t status_bytes;
-    void   *allg_out, *allg_in;            /* PSAMD_FLAG_ALL_PAIRS only, ALL-GATHERED once per step between slab_build and slab_pairs:
-                                              the snapshot (x, y, z, w_eff) of every rank's own cells; allg_in = world blocks of allg_bytes */
+    void   *allg_out, *allg_in;            /* ALL-GATHERED once per step between slab_build and slab_pairs; allg_in = world blocks of
+                                              allg_bytes, by rank.  PSAMD_FLAG_ALL_PAIRS: the snapshot (x, y, z, w_eff) of every rank's
+                                              own cells.  PSAMD_FLAG_FAR_SLAB: the fp64 sums of every rank's own cells ("far field on
+                                              slabs" below).  Every other context: 0 bytes */
     int64_t allg_bytes;
     void   *xfer2_out[2], *xfer2_in[2];    /* same exchange as xfer_*, but between ranks TWO apart on the ring: out[0] -> rank-2's in[1],
                                               out[1] -> rank+2's in[0].  Only in worlds (>= 4 ranks) where some rank's whole state is one
@@ -486,8 +494,8 @@ int psamd_slab_buffers_get(psamd_ctx *ctx, psamd_slab_buffers *out);
 /* One step = build, [all-gather status_out into every rank's status_in -- it must have landed before the
  * FIRST pair-stage call, pairs_interior where that is used: the stage writes the particles' new accelerations
  * into their records and has to know whom the chunk lists' capacity rule takes out of the step;
- * exchange halo_out -> neighbours' halo_in; with PSAMD_FLAG_ALL_PAIRS the all-gather of allg_out into
- * allg_in, which must have landed], pairs, [force_out -> rank-1's force_in], apply, [xfer_out -> neighbours' xfer_in; where they exist xfer2_* likewise and the all-gather of far_out into far_in], finish.  The status record carries a rank's
+ * exchange halo_out -> neighbours' halo_in; with PSAMD_FLAG_ALL_PAIRS or PSAMD_FLAG_FAR_SLAB the all-gather of
+ * allg_out into allg_in, which must have landed], pairs, [force_out -> rank-1's force_in], apply, [xfer_out -> neighbours' xfer_in; where they exist xfer2_* likewise and the all-gather of far_out into far_in], finish.  The status record carries a rank's
  * sticky error bits, the slots the cell-overflow rule killed, which the reference frees into queue
  * record 0 wherever they were (ps.cpp:1523-1526), and the rank's part of every chunk's particle count
  * per segment type, from which all ranks reproduce the chunk lists' capacity rule (ps.cpp:1502-1508)
@@ -680,7 +688,8 @@ int psamd_remove_result_get(psamd_ctx *ctx, psamd_remove_result *out);
  * cuts; else PSAMD_ERR_UNSUPPORTED (the context stays usable): shipping phi of lent layers home would need a message of
  * its own.  The ranks' results combine like psamd_live_stats: counts and U add, the extrema take min and max.
  *
- * Far-monopole contexts (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID; always world == 1).  Without PSAMD_POTENTIAL_FAR
+ * Far-monopole contexts (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID; world == 1: with PSAMD_FLAG_FAR_SLAB and world > 1 every
+ * form of the call is PSAMD_ERR_UNSUPPORTED, see "far field on slabs").  Without PSAMD_POTENTIAL_FAR
  * psamd_potential and psamd_download_potential return PSAMD_ERR_UNSUPPORTED: a stencil-only phi is not the potential of
  * the field these contexts apply.  With PSAMD_POTENTIAL_FAR (host form: psamd_download_potential_far) a particle in cell c
  * sees the stencil lists of c exactly as above and, behind them, the far bodies the force pass of this context enters for
@@ -793,7 +802,8 @@ int psamd_download_potential_flags(psamd_ctx *ctx, uint32_t flags, float *phi, i
  * particle): equality with the force record is promised for cutoff contexts only.  With empty far cells the result is
  * the cutoff result bit for bit.  With world > 1 the call returns PSAMD_ERR_UNSUPPORTED; the context stays usable.
  *
- * Far-monopole contexts (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID; world == 1).  Without PSAMD_PROBE_FAR the call
+ * Far-monopole contexts (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID; world == 1: with PSAMD_FLAG_FAR_SLAB and world > 1 the
+ * call is PSAMD_ERR_UNSUPPORTED, see "far field on slabs").  Without PSAMD_PROBE_FAR the call
  * returns PSAMD_ERR_UNSUPPORTED.  With it (beside ACC and / or PHI; alone it is PSAMD_ERR_INVALID_ARG) a served probe in cell
  * c sees the stencil of c as above and then the far bodies the force pass enters for c, from moments the call forms itself
  * (psamd_potential's far form, "energy" above).  phi: that far form's terms and association.  Acceleration: the force
@@ -885,7 +895,7 @@ int psamd_probe_result_get(psamd_ctx *ctx, psamd_probe_result *out);
  * median particle's |a| is off by 0.2 %, the worst by 1-2 %; the cutoff alone leaves out 77-89 % for the median particle
  * (tests/test_far_monopole_cpu.py).  The device follows the model to 1e-5 relative (tests/test_gpu_far_monopole.py).
  *
- * Refusals.  psamd_create: with PSAMD_FLAG_ALL_PAIRS PSAMD_ERR_INVALID_ARG; with world > 1, with a softening length outside
+ * Refusals.  psamd_create: with PSAMD_FLAG_ALL_PAIRS PSAMD_ERR_INVALID_ARG; with world > 1 and without PSAMD_FLAG_FAR_SLAB, with a softening length outside
  * the lean range, or without the two-pass pair stage (collision radius not small against the cell) PSAMD_ERR_UNSUPPORTED.
  * psamd_potential, psamd_download_potential and psamd_probe without PSAMD_POTENTIAL_FAR / PSAMD_PROBE_FAR return
  * PSAMD_ERR_UNSUPPORTED on such a context, which stays usable: they promise exactly the stencil's bodies, and that is not this
@@ -942,7 +952,7 @@ int psamd_download_cell_moments(psamd_ctx *ctx, void *out_float4);
  * model to 1e-5 relative (tests/test_gpu_far_pyramid.py).
  *
  * Refusals mirror PSAMD_FLAG_FAR_MONOPOLE's.  psamd_create: with PSAMD_FLAG_ALL_PAIRS or PSAMD_FLAG_FAR_MONOPOLE
- * PSAMD_ERR_INVALID_ARG; with world > 1, a softening length outside the lean range, or without the two-pass pair stage
+ * PSAMD_ERR_INVALID_ARG; with world > 1 and without PSAMD_FLAG_FAR_SLAB, a softening length outside the lean range, or without the two-pass pair stage
  * PSAMD_ERR_UNSUPPORTED.  psamd_potential, psamd_download_potential and psamd_probe without PSAMD_POTENTIAL_FAR /
  * PSAMD_PROBE_FAR return PSAMD_ERR_UNSUPPORTED on such a context, which stays usable; with the bit they serve the stencil and
  * then the interaction set above, levels L down to 0, from moments the call forms itself.  The flag combines freely with FAST_MATH, EULER, EXPLOSIONS, drag, force_sign, graphs,
@@ -1031,6 +1041,45 @@ int psamd_download_level_moments(psamd_ctx *ctx, int32_t level, void *out_float4
  * cell index.  The validity window and error codes of psamd_download_level_moments; NULL arguments or a level outside [0, L]
  * PSAMD_ERR_INVALID_ARG; on a context without the flag PSAMD_ERR_UNSUPPORTED.  Waits for the context's stream. */
 int psamd_download_level_quadrupoles(psamd_ctx *ctx, int32_t level, void *out_float6);
+
+/* ---- far field on slabs (PSAMD_FLAG_FAR_SLAB) ----------------------------------- */
+/* The far field of PSAMD_FLAG_FAR_MONOPOLE and PSAMD_FLAG_FAR_PYRAMID (with or without PSAMD_FLAG_FAR_QUADRUPOLE) on the slab
+ * partition.  A rank needs its neighbours' halos, which it has, and the moments of every cell of the box: 32 or 80 bytes a
+ * cell.  The moments of a cell depend on the cell's own list alone, the far set of a particle on G and its cell alone, and the
+ * sums are fp64 sums in list order: the union of the ranks is one context's state, byte for byte, every step
+ * (tests/test_gpu_far_slab.py).
+ *
+ * The flag.  A far slab has one more message that must be all-gathered between psamd_slab_build and psamd_slab_pairs; a host
+ * written for the cutoff exchange that does not carry it would step with stale moments.  With the bit the host has said that it
+ * gathers.  Without it a far flag with world > 1 stays PSAMD_ERR_UNSUPPORTED; with it and world > 1 the context is created (the
+ * lean-range, two-pass and all-pairs refusals stay); with it and world == 1 no message exists and every byte is what the context
+ * computes without it; the flag with neither far flag is PSAMD_ERR_INVALID_ARG.  PSAMD_ABI_VERSION stays 8: the bit is additive.
+ *
+ * The message: allg_out / allg_in, the all-pairs slot (a context is never both).  allg_out, written by psamd_slab_build: 16
+ * header words -- [0] the rank's own cells (those of its state layers), [1] the planes, 4 or 10, [2] the sender's sticky error
+ * bits, [3] its first global cell -- then, 8-byte aligned, planes x allg_cells doubles, plane-major: S, Sx, Sy, Sz and with
+ * quadrupoles Sxx, Syy, Szz, Sxy, Sxz, Syz; a cell's index in a plane is its local index.  allg_cells is the largest state-layer
+ * cell count over all ranks, so allg_bytes = 64 + planes * allg_cells * 8 is the same on every rank under uneven cuts (the
+ * header is 64 bytes: nothing is rounded).  The sums are the one-context sums of "long-range gravity" and "quadrupoles on the
+ * pyramid": the first min(count, MAX_PARTICLES_PER_CELL) entries, list order, one addition per entry, unfused.
+ *
+ * psamd_slab_pairs checks every block's header against the plan of its rank (cells, first cell, planes), adopts the senders'
+ * error bits, scatters the sums to level 0 by global cell, forms level 0's X, Y, Z, M (and C) from them by the one-context
+ * operations and adds up the levels above: every rank builds the upper levels redundantly, O(cells).  A block that did not
+ * arrive or is another context's fails the step collectively ("a slab message does not match"), and is never followed: the
+ * plan's numbers bound every index.  A stale but well-formed block of the step before is NOT detected, as for all-pairs.
+ * There is no interior pass: psamd_slab_pairs_interior returns PSAMD_OK and does nothing (the far pass needs the gather).
+ * The records of lent layers travel home in force_out as they do on every slab.
+ *
+ * Downloads.  psamd_download_cell_moments, psamd_download_level_moments and psamd_download_level_quadrupoles are valid from
+ * psamd_slab_pairs until the frame ends; every rank returns the arrays of the whole box.
+ *
+ * Not served with world > 1, whatever bits are set: psamd_potential, psamd_download_potential and its _far and _flags forms,
+ * psamd_probe return PSAMD_ERR_UNSUPPORTED and the context stays usable.  Far slabs combine with FAST_MATH, EULER, EXPLOSIONS,
+ * drag, force_sign, graphs and run-ahead as slabs and far contexts do.
+ *
+ * Cost (scripts/far_slab_cost.py; profiles/far_slab_cost.txt): no machine with several GPUs was at hand, so the eight-rank
+ * figures there are projections from eight slabs stepped on ONE MI355X, as in DESIGN.md section 6. */
 
 /* ---- introspection -------------------------------------------------------- */
 int psamd_get_counters(psamd_ctx *ctx, psamd_counters *out);

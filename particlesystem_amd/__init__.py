@@ -35,6 +35,7 @@ FLAG_EULER = 0x8
 FLAG_FAR_MONOPOLE = 0x10
 FLAG_FAR_PYRAMID = 0x20
 FLAG_FAR_QUADRUPOLE = 0x40
+FLAG_FAR_SLAB = 0x80
 NUM_TIMERS = 9
 TIMER_NAMES = ("hist", "scan", "scatter", "sort_cells", "pairs", "apply", "lifecycle", "init_iframe", "collide")
 

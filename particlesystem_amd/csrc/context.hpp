@@ -108,6 +108,12 @@ namespace psamd {
 
 const char *status_text(int status);
 
+// what the far-field flags make of a context: far monopoles (flat or as a pyramid); one whose host has said that it
+// all-gathers the cell sums (PSAMD_FLAG_FAR_SLAB); the fp64 planes per cell
+inline bool far_context(uint32_t flags) { return (flags & (PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID)) != 0; }
+inline bool far_slab(uint32_t flags) { return (flags & PSAMD_FLAG_FAR_SLAB) && far_context(flags); }
+inline int far_planes(uint32_t flags) { return (flags & PSAMD_FLAG_FAR_QUADRUPOLE) ? 10 : 4; }
+
 // what the ledger's rules read of the context
 inline LedgerParams ledger_params(const psamd_ctx *c)
 {

@@ -127,6 +127,8 @@ static int derive_params(psamd_ctx *c, const psamd_config *cfg)
     P.drag = (float)cfg->drag;
     P.force_sign = cfg->force_sign < 0 ? -1.0f : 1.0f;
     if (cfg->drag < 0) return fail(c, PSAMD_ERR_INVALID_ARG, "drag must be >= 0");
+    if ((cfg->flags & PSAMD_FLAG_FAR_SLAB) && !(cfg->flags & (PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID)))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "PSAMD_FLAG_FAR_SLAB is a modifier of PSAMD_FLAG_FAR_MONOPOLE and PSAMD_FLAG_FAR_PYRAMID: set one of them too");
     fill_slab_params(g, c->plan, *cfg, P);
     P.status_words = STATUS_CHUNK_OFF + 4 * g.num_chunks;
     if (cfg->world > 1) {
@@ -134,7 +136,8 @@ static int derive_params(psamd_ctx *c, const psamd_config *cfg)
         // that crosses two layers in a step (from one ulp below a face, moved by exactly CELL_SIZE) can fly over
         // such a rank, to the rank beyond it -- those records get outboxes of their own, sent straight to rank +-2.
         // All-pairs: every rank's block of the all-gathered snapshot has the same size, room for the rank with the
-        // most cells / slots.
+        // most cells / slots.  A far slab (PSAMD_FLAG_FAR_SLAB): its block of the all-gathered cell sums likewise, room for the
+        // rank with the most cells.
         bool single = false;
         int cells = 0;
         int64_t slots = 0;
@@ -161,6 +164,10 @@ static int derive_params(psamd_ctx *c, const psamd_config *cfg)
             P.allg_cells = cells;
             P.allg_cap = (int)((slots + 63) & ~(int64_t)63);
             P.allg_block = MSG_HEADER_WORDS + P.allg_cells + 4 * P.allg_cap;
+        } else if (far_slab(cfg->flags)) {
+            // 16 header | 4 or 10 planes (S, Sx, Sy, Sz; Sxx, Syy, Szz, Sxy, Sxz, Syz) of allg_cells doubles
+            P.allg_cells = cells;
+            P.allg_block = (int)(far_slab_block_bytes(far_planes(cfg->flags), cells) / sizeof(int));
         }
     }
     auto bits_for = [](int64_t n) { int b = 1; while (((int64_t)1 << b) < n) b++; return b; };
@@ -200,7 +207,8 @@ static int derive_params(psamd_ctx *c, const psamd_config *cfg)
         const char *two = "far monopoles and all-pairs forces are two force models: choose one";
         const char *three = "the pyramid of monopoles, far monopoles and all-pairs forces are three force models: choose one";
         if (cfg->flags & PSAMD_FLAG_ALL_PAIRS) return fail(c, PSAMD_ERR_INVALID_ARG, mono ? two : three);
-        if (cfg->world > 1) return fail(c, PSAMD_ERR_UNSUPPORTED, who + is + "served on one context only (world == 1)");
+        if (cfg->world > 1 && !(cfg->flags & PSAMD_FLAG_FAR_SLAB))
+            return fail(c, PSAMD_ERR_UNSUPPORTED, who + is + "served on one context only (world == 1)");
         if (!P.lean_math) return fail(c, PSAMD_ERR_UNSUPPORTED, who + is + "built for the lean pair arithmetic only (EPS2 in its validated range)");
         if (!P.two_pass) return fail(c, PSAMD_ERR_UNSUPPORTED, who + (mono ? " need" : " needs") + " the two-pass pair stage (collision radius small against the cell)");
         if (mono && pyr) return fail(c, PSAMD_ERR_INVALID_ARG, three);
@@ -360,10 +368,21 @@ static int alloc_step_arrays(psamd_ctx *c)
         d.mom_cap = d.lev.off[d.lev.n];
         PS_HIP(c, dev_alloc(c, &d.cell_mom, planes * (size_t)d.mom_cap + 64));     // + slack: scalar loads fetch whole groups
         PS_HIP(c, dev_alloc(c, &d.cell_mom_j, (size_t)d.mom_cap));
-        if (pyramid) PS_HIP(c, dev_alloc(c, &d.lev_sum, planes * (size_t)d.mom_cap));
+        // (a slab keeps the sums on the flat method too: level 0 is scattered there from the gathered blocks)
+        const bool sums = pyramid || P.world > 1;
+        if (sums) PS_HIP(c, dev_alloc(c, &d.lev_sum, planes * (size_t)d.mom_cap));
         PS_HIP(c, hipMemsetAsync(d.cell_mom, 0, (planes * (size_t)d.mom_cap + 64) * sizeof(float), c->stream));
         PS_HIP(c, hipMemsetAsync(d.cell_mom_j, 0, (size_t)d.mom_cap * sizeof(int), c->stream));
-        if (pyramid) PS_HIP(c, hipMemsetAsync(d.lev_sum, 0, planes * (size_t)d.mom_cap * sizeof(double), c->stream));
+        if (sums) PS_HIP(c, hipMemsetAsync(d.lev_sum, 0, planes * (size_t)d.mom_cap * sizeof(double), c->stream));
+        if (P.world > 1) {
+            // what every rank's block of the gathered cell sums must say of itself: (first global cell, cells) by rank
+            const psamd_config &cf = g.cfg;
+            std::vector<int> first, cells, tab;
+            gather_block_cells(g.F, g.D, g.seg_base, g.seg_size_t, g.info_base, cf.world, cf.cuts[cf.world] != 0 ? cf.cuts : nullptr, &first, &cells);
+            for (int r = 0; r < cf.world; r++) { tab.push_back(first[(size_t)r]); tab.push_back(cells[(size_t)r]); }
+            PS_HIP(c, dev_alloc(c, &d.far_plan, tab.size()));
+            PS_HIP(c, hipMemcpy(d.far_plan, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+        }
     }
     return PSAMD_OK;
 }
@@ -428,6 +447,13 @@ static int alloc_slab_msgs(psamd_ctx *c)
             PS_HIP(c, hipMemsetAsync(d.gn, 0, ((size_t)g.num_cells + 1) * sizeof(int), c->stream));
         d.allg_in = c->msg[MSG_ALLG_IN].ptr;
     }
+    if (far_slab(P.flags)) {
+        // the cell sums of every rank's own cells (slab.hip, "far field on slabs"): the all-pairs slot, which a far context leaves free
+        const size_t block = (size_t)P.allg_block * sizeof(int);
+        PS_HIP(c, alloc_msg(c, MSG_ALLG_OUT, block));
+        PS_HIP(c, alloc_msg(c, MSG_ALLG_IN, block * P.world));
+        d.allg_in = c->msg[MSG_ALLG_IN].ptr;
+    }
     PS_HIP(c, alloc_msg(c, MSG_STATUS_OUT, (size_t)P.status_words * sizeof(int)));
     PS_HIP(c, alloc_msg(c, MSG_STATUS_IN, (size_t)P.status_words * sizeof(int) * P.world));
     d.status_out = c->msg[MSG_STATUS_OUT].ptr;
@@ -473,7 +499,8 @@ static void split_interior(psamd_ctx *c)
     for (int l = lo; l < hi; l++) if (own(l - 1) && own(l + 1)) { if (i1 == i0) i0 = l; i1 = l + 1; } else if (i1 > i0) break;
     c->P_int = P; c->P_rest = P;
     c->have_interior = P.world > 1 && P.two_pass && P.lean_math && i1 > i0 && (i1 - i0) < (hi - lo) + (pl.lentin_hi - pl.lentin_lo)
-                       && !(P.flags & PSAMD_FLAG_ALL_PAIRS);      // (an all-pairs pass needs the gathered snapshot: nothing to do before it lands)
+                       && !(P.flags & (PSAMD_FLAG_ALL_PAIRS | PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID));
+    // (an all-pairs pass needs the gathered snapshot, a far pass the gathered cell sums: nothing to do before they land)
     if (c->have_interior) {
         const int a = (i0 - pl.state_lo) * GG, b = (i1 - pl.state_lo) * GG;
         c->P_int.comp_lo[0] = a; c->P_int.comp_hi[0] = b;

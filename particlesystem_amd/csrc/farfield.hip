@@ -43,17 +43,25 @@ __device__ __forceinline__ float far_central(double Sab, double Sa, double Sb, d
     return (float)__dsub_rn(Sab, __dmul_rn(__ddiv_rn(Sa, S), Sb));
 }
 
-// One wave per cell of the box (world == 1: local cell == global cell).  The cell's list is the first
+// One wave per cell of the box (world == 1: local cell == global cell; a far slab: OWN, below).  The cell's list is the first
 // min(count, MAX_PARTICLES_PER_CELL) entries of the sorted snapshot; S, Sx, Sy, Sz are fp64 sums over it IN LIST ORDER
 // (entry 0 first, one addition per entry: the lanes fetch 64 entries at a time and every lane adds them one by one).  A
 // product of two fp32 values is exact in fp64, so nothing here depends on contraction.
-template <bool QUAD>
+//
+// OWN (a far slab, world > 1: PSAMD_FLAG_FAR_SLAB): one wave per OWN cell -- region 0, whose local index is the cell's
+// offset in the rank's block of the all-gathered message -- and only the sums are kept: `sums` is the block's payload, its
+// planes mom_cap = allg_cells doubles apart, `hdr` the block's header, which the first wave fills in.  The same loads, the
+// same products, the same additions in the same order as on one context: the same sums.  The float planes and mom_j of the
+// whole box are formed from the gathered sums (k_far_scatter).  The instances without OWN are what they were.
+template <bool QUAD, bool OWN>
 __global__ __launch_bounds__(256) void k_cell_moments(DevParams P, const int *__restrict__ cell_start, const float *__restrict__ snap,
                                                       float *__restrict__ mom, int *__restrict__ mom_j, int mom_cap,
-                                                      double *__restrict__ sums)      // (the pyramid keeps the fp64 sums; else null)
+                                                      double *__restrict__ sums,      // (the pyramid keeps the fp64 sums; else null)
+                                                      int *__restrict__ hdr, const FrameScalars *__restrict__ fs)
 {
     const int c = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    if (c >= P.num_cells) return;
+    if (OWN && c == 0 && lane == 0) { hdr[0] = P.n_own_cells; hdr[1] = QUAD ? 10 : 4; hdr[2] = fs->error; hdr[3] = P.reg_first[0] * P.G * P.G; }
+    if (c >= (OWN ? P.n_own_cells : P.num_cells)) return;
     const int b = cell_start[c], n = min(cell_start[c + 1] - b, P.max_per_cell);
     const size_t cap = (size_t)P.sorted_cap;
     double S = 0.0, Sx = 0.0, Sy = 0.0, Sz = 0.0;
@@ -79,6 +87,16 @@ __global__ __launch_bounds__(256) void k_cell_moments(DevParams P, const int *__
                 for (int f = 0; f < 6; f++) Q[f] = __dadd_rn(Q[f], lane_f64(q[f], k));
             }
         }
+    }
+    if (OWN) {
+        if (lane == 0) {
+            sums[c] = S; sums[mom_cap + c] = Sx; sums[2 * (size_t)mom_cap + c] = Sy; sums[3 * (size_t)mom_cap + c] = Sz;
+            if (QUAD) {
+#pragma unroll
+                for (int f = 0; f < 6; f++) sums[(4 + f) * (size_t)mom_cap + c] = Q[f];
+            }
+        }
+        return;
     }
     if (lane == 0) {
         const bool none = S == 0.0;          // an empty cell, or kids only
@@ -146,17 +164,10 @@ __global__ __launch_bounds__(256) void k_level_moments(const FarLevels lev, int 
     }
 }
 
-// The moments of the frame's snapshot, of the cells (far monopoles) or of every level (the pyramid, which keeps the fp64
-// sums): the pair stage forms them here, and so do psamd_potential and psamd_probe in their far form, whose window opens
-// before the pair stage has run -- the same kernels on the same snapshot, the same bits in the same buffers.
-void launch_far_moments(hipStream_t st, const DevParams &P, const DeviceState &d)
+// levels 1..L of the pyramid from level 0's sums
+static void launch_upper_levels(hipStream_t st, const DevParams &P, const DeviceState &d)
 {
-    const bool pyramid = (P.flags & PSAMD_FLAG_FAR_PYRAMID) != 0, quad = (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) != 0;
-    const unsigned cell_wgs = (unsigned)((P.num_cells + 3) / 4);
-    if (quad) k_cell_moments<true><<<cell_wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.cell_mom, d.cell_mom_j, d.mom_cap, d.lev_sum);
-    else k_cell_moments<false><<<cell_wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.cell_mom, d.cell_mom_j, d.mom_cap,
-                                                         pyramid ? d.lev_sum : nullptr);
-    if (!pyramid) return;
+    const bool quad = (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) != 0;
     const FarLevels &lev = d.lev;
     for (int l = 1; l < lev.n; l++) {
         const unsigned wgs = (unsigned)((lev.G[l] * lev.G[l] * lev.G[l] + 255) / 256);
@@ -164,6 +175,93 @@ void launch_far_moments(hipStream_t st, const DevParams &P, const DeviceState &d
         else k_level_moments<false><<<wgs, 256, 0, st>>>(lev, l, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap);
     }
 }
+
+// The moments of the frame's snapshot, of the cells (far monopoles) or of every level (the pyramid, which keeps the fp64
+// sums): the pair stage forms them here, and so do psamd_potential and psamd_probe in their far form, whose window opens
+// before the pair stage has run -- the same kernels on the same snapshot, the same bits in the same buffers.
+void launch_far_moments(hipStream_t st, const DevParams &P, const DeviceState &d)
+{
+    const bool pyramid = (P.flags & PSAMD_FLAG_FAR_PYRAMID) != 0, quad = (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) != 0;
+    const unsigned cell_wgs = (unsigned)((P.num_cells + 3) / 4);
+    if (quad) k_cell_moments<true, false><<<cell_wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.cell_mom, d.cell_mom_j, d.mom_cap, d.lev_sum, nullptr, nullptr);
+    else k_cell_moments<false, false><<<cell_wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.cell_mom, d.cell_mom_j, d.mom_cap,
+                                                                pyramid ? d.lev_sum : nullptr, nullptr, nullptr);
+    if (pyramid) launch_upper_levels(st, P, d);
+}
+
+// ---- far field on slabs (PSAMD_FLAG_FAR_SLAB, world > 1) ----
+// The moments of a cell depend on the cell's own list alone, and a level's on the level below: so every rank forms the fp64
+// sums of its OWN cells (k_cell_moments<., true>, in slab_build, straight into allg_out), the hosts all-gather the blocks --
+// 16 header words ([0] own cells, [1] planes, 4 or 10, [2] the sender's error bits, [3] its first global cell), then the
+// planes S, Sx, Sy, Sz (and Sxx, Syy, Szz, Sxy, Sxz, Syz), allg_cells doubles each -- and every rank scatters all blocks to
+// level 0 of lev_sum by global cell (k_far_scatter, in slab_pairs), forms level 0's float planes and mom_j from the sums by
+// k_cell_moments' own operations, and adds up the levels above with k_level_moments as one context does: redundantly on
+// every rank, O(cells).  Afterwards every rank holds the moment arrays of one context, bit for bit.
+// By a kernel trace (profiles/far_slab_cost.txt: N = 2^20 on 16^3 cells, eight slabs one at a time on one MI355X; a rank and
+// step, pyramid / quadrupoles): k_cell_moments<., OWN> 20-21 / 34-38 us for the two or three own layers (the whole box on
+// one context: 54 / 116 us), k_far_scatter 5-6.5 / 5-8 us, the two upper levels together 9-10 / 11 us, as on one context:
+// latency of small kernels, about 2 % of the rank's pair stage.
+hipError_t launch_far_own_sums(hipStream_t st, const DevParams &P, const DeviceState &d, int *msg)
+{
+    const unsigned wgs = (unsigned)((std::max(P.n_own_cells, 1) + 3) / 4);
+    double *pay = reinterpret_cast<double *>(msg + MSG_HEADER_WORDS);
+    if (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) k_cell_moments<true, true><<<wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, nullptr, nullptr, P.allg_cells, pay, msg, d.fs);
+    else k_cell_moments<false, true><<<wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, nullptr, nullptr, P.allg_cells, pay, msg, d.fs);
+    return hipGetLastError();
+}
+
+// One thread per (gathered block, cell of it).  A block is taken only if its header says what the plan says of its rank
+// (far_plan: first global cell, cells; the planes of this context) -- and the plan's numbers, not the header's, bound every
+// index: a block that did not arrive, or another context's, raises ERR_SLAB_MISMATCH and is left out, it is never followed.
+// (A well-formed block of the step before is not told from this step's.)  The senders' error bits are adopted as
+// k_allg_index adopts them.
+template <bool QUAD>
+__global__ __launch_bounds__(256) void k_far_scatter(DevParams P, const int *__restrict__ all, const int *__restrict__ far_plan,
+                                                     float *__restrict__ mom, int *__restrict__ mom_j, double *__restrict__ sums,
+                                                     int mom_cap, FrameScalars *fs)
+{
+    const int r = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    const int *hdr = all + (size_t)r * P.allg_block;
+    const int first = far_plan[2 * r], ncell = far_plan[2 * r + 1];
+    const bool plan_ok = first >= 0 && ncell >= 0 && ncell <= P.allg_cells && first + ncell <= P.num_cells_global && first + ncell <= mom_cap;
+    if (!plan_ok || hdr[0] != ncell || hdr[3] != first || hdr[1] != (QUAD ? 10 : 4)) {
+        if (j == 0) atomicOr(&fs->error, ERR_SLAB_MISMATCH);
+        return;
+    }
+    if (j == 0 && hdr[2]) atomicOr(&fs->error, hdr[2]);
+    if (j >= ncell) return;
+    const double *pay = reinterpret_cast<const double *>(hdr + MSG_HEADER_WORDS);
+    const size_t pc = (size_t)P.allg_cells, cap = (size_t)mom_cap;
+    const int c = first + j;
+    const double S = pay[j], Sx = pay[pc + j], Sy = pay[2 * pc + j], Sz = pay[3 * pc + j];
+    const bool none = S == 0.0;
+    sums[c] = S; sums[cap + c] = Sx; sums[2 * cap + c] = Sy; sums[3 * cap + c] = Sz;
+    mom[c] = none ? 0.f : (float)(Sx / S);
+    mom[cap + c] = none ? 0.f : (float)(Sy / S);
+    mom[2 * cap + c] = none ? 0.f : (float)(Sz / S);
+    mom[3 * cap + c] = none ? 0.f : (float)S;
+    const int GG = P.G * P.G, i3 = c / GG, rem = c - i3 * GG, i1 = rem / P.G;
+    mom_j[c] = (i3 << 20) | (i1 << 10) | (rem - i1 * P.G);
+    if (QUAD) {
+        const double Sa[3] = {Sx, Sy, Sz};
+#pragma unroll
+        for (int f = 0; f < 6; f++) {
+            const double q = pay[(4 + f) * pc + j];
+            sums[(4 + f) * cap + c] = q;
+            mom[(4 + f) * cap + c] = none ? 0.f : far_central(q, Sa[QUAD_A[f]], Sa[QUAD_B[f]], S);
+        }
+    }
+}
+
+hipError_t launch_far_gathered(hipStream_t st, const DevParams &P, const DeviceState &d)
+{
+    const dim3 grid((unsigned)((std::max(P.allg_cells, 1) + 255) / 256), (unsigned)P.world);
+    if (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) k_far_scatter<true><<<grid, 256, 0, st>>>(P, d.allg_in, d.far_plan, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap, d.fs);
+    else k_far_scatter<false><<<grid, 256, 0, st>>>(P, d.allg_in, d.far_plan, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap, d.fs);
+    if (P.flags & PSAMD_FLAG_FAR_PYRAMID) launch_upper_levels(st, P, d);
+    return hipGetLastError();
+}
+
 
 // (the pyramid's instances at 6 waves a SIMD, not the flat ones' 7: the parent compare per body costs registers -- at 7 the
 // compiler's report shows 68 bytes of scratch a lane in the exact instance, at 6 it shows 8 (80 VGPRs); by that report, not
@@ -183,7 +281,16 @@ constexpr int QUAD_WAVES = 5;
 // to a chain of its own per block -- from +0, in index order, behind the group's pair terms -- whose sums add up in block
 // order to +0 like the monopoles'; the part is RN(monopole sum + quadrupole sum).  The six C planes lie behind the four of
 // mom, so they come through the same __restrict__ argument as wave-uniform loads.
-template <int MODE, bool PYRAMID, bool QUAD>
+//
+// SLAB (a far slab, world > 1): dense_cell holds LOCAL cells -- the lent-in layers first, which lie below the own layers in
+// the box -- so the lane's coordinates come from the region tables (cell_coords) and the wave's box from the lowest and the
+// highest GLOBAL cell among its lanes.  The moments are the whole box's on every rank (k_far_scatter), the far set depends on
+// the particle's global cell alone: the same chains as on one context.  A compile-time parameter: the world == 1
+// instances are what they were.  By the compiler's report (VGPRs / bytes of scratch a lane; fast, exact): the world == 1
+// instances take 72/72, 72/28 (flat), 79/0, 80/0 (pyramid), 93/0, 96/8 (quadrupoles), as before the parameter existed; the
+// slab instances 72/84, 72/28, 79/0, 80/0, 94/0, 96/8 -- the region walk costs the flat fast one 12 bytes of scratch and
+// the quadrupole fast one a register, at the same waves a SIMD.
+template <int MODE, bool PYRAMID, bool QUAD, bool SLAB>
 __global__ __launch_bounds__(256, QUAD ? QUAD_WAVES : PYRAMID ? PYRAMID_WAVES : BALANCED_WAVES) void k_far_walk(DevParams P, const SnapSoa snap4,
                                                                                              const int *__restrict__ act_start,
                                                                                              const int *__restrict__ dense_gi,
@@ -213,7 +320,9 @@ __global__ __launch_bounds__(256, QUAD ? QUAD_WAVES : PYRAMID ? PYRAMID_WAVES : 
     const int gi = dense_gi[rr], c = dense_cell[rr];
     const float4 me = snap4[gi];
     const int GG = P.G * P.G;
-    const int i3 = c / GG, irem = c - i3 * GG, i1 = irem / P.G, i2 = irem - i1 * P.G;      // (world == 1: local cell == global cell)
+    int i1, i2, i3, cg = c;                                 // (world == 1: local cell == global cell)
+    if (SLAB) { cell_coords(P, c, i1, i2, i3); cg = (i3 * P.G + i1) * P.G + i2; }
+    else { i3 = c / GG; const int irem = c - i3 * GG; i1 = irem / P.G; i2 = irem - i1 * P.G; }
     const int a1 = i1 >> l, a2 = i2 >> l, a3 = i3 >> l;     // the lane's cell of this level
     const PairCtx ctx = {me.x, me.y, me.z, 0.f, 0, gi, false};
     const float eps2f = (float)P.eps2;
@@ -222,7 +331,7 @@ __global__ __launch_bounds__(256, QUAD ? QUAD_WAVES : PYRAMID ? PYRAMID_WAVES : 
     // or to take.  Scalar arithmetic.
     FarBox box = {0, P.G - 1, 0, P.G - 1, 0, 0};
     {
-        const int c_hi = __builtin_amdgcn_readfirstlane(wave_max_i(c)), c_lo = __builtin_amdgcn_readfirstlane(-wave_max_i(-c));
+        const int c_hi = __builtin_amdgcn_readfirstlane(wave_max_i(cg)), c_lo = __builtin_amdgcn_readfirstlane(-wave_max_i(-cg));
         box.lo3 = c_lo / GG; box.hi3 = c_hi / GG;
         if (box.lo3 == box.hi3) {
             const int ra = c_lo - box.lo3 * GG, rb = c_hi - box.hi3 * GG;
@@ -268,22 +377,33 @@ __global__ __launch_bounds__(256, QUAD ? QUAD_WAVES : PYRAMID ? PYRAMID_WAVES : 
     }
 }
 
-template <bool PYRAMID, bool QUAD>
-static void launch_far_walk(hipStream_t st, unsigned wgs, const DevParams &P, const DeviceState &d, bool fast, const FarCells &far)
+template <bool PYRAMID, bool QUAD, bool SLAB>
+static void launch_far_walk_as(hipStream_t st, unsigned wgs, const DevParams &P, const DeviceState &d, bool fast, const FarCells &far)
 {
     const SnapSoa snap4{d.snap_soa, (size_t)P.sorted_cap};
     const FarMoments m = far_moments_of(P, d);
-    if (fast) k_far_walk<2, PYRAMID, QUAD><<<wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, m, m.mom, m.mom_j);
-    else k_far_walk<1, PYRAMID, QUAD><<<wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, m, m.mom, m.mom_j);
+    if (fast) k_far_walk<2, PYRAMID, QUAD, SLAB><<<wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, m, m.mom, m.mom_j);
+    else k_far_walk<1, PYRAMID, QUAD, SLAB><<<wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, m, m.mom, m.mom_j);
+}
+
+// (a slab's instances where the context is one: world > 1)
+template <bool PYRAMID, bool QUAD>
+static void launch_far_walk(hipStream_t st, unsigned wgs, const DevParams &P, const DeviceState &d, bool fast, const FarCells &far)
+{
+    if (P.world > 1) launch_far_walk_as<PYRAMID, QUAD, true>(st, wgs, P, d, fast, far);
+    else launch_far_walk_as<PYRAMID, QUAD, false>(st, wgs, P, d, fast, far);
 }
 
 // What ran before is the stencil's chain (the two-pass pair stage: contexts with either flag are created only with it, only
-// with lean arithmetic and only with world == 1); now the moments, the walk by (dense task, part) items, the parts' sum.
+// with lean arithmetic); now the moments, the walk by (dense task, part) items, the parts' sum.  A far slab (world > 1) has
+// its moments already: psamd_slab_pairs formed them from the gathered sums (launch_far_gathered) before the pair stage; its
+// dense tasks go over every cell the rank computes, lent-in layers included (comp_count), and the parts' sum lands where
+// the cutoff pass left the record -- a lent layer's records then travel home in force_out.
 void launch_far_field(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound)
 {
     const bool pyramid = (P.flags & PSAMD_FLAG_FAR_PYRAMID) != 0;
     const int parts = pyramid ? d.lev.n : ALLP_PARTS;
-    launch_far_moments(st, P, d);
+    if (P.world == 1) launch_far_moments(st, P, d);
     FarCells far;
     far.part_acc = d.part_acc; far.part_plane = (unsigned long long)d.part_tasks * 64;
     const int64_t dense_bound = far_dense_bound(P, d, live_bound);

@@ -198,6 +198,9 @@ struct DeviceState {
     // the fp64 sums S, Sx, Sy, Sz the levels add up
     FarLevels lev;
     double *lev_sum = nullptr;    // [4][mom_cap]; with quadrupoles [10][mom_cap]: the raw Sxx, Syy, Szz, Sxy, Sxz, Syz behind
+    // a far slab (PSAMD_FLAG_FAR_SLAB, world > 1; allg_in above is its gathered cell sums): (first global cell, cells) of
+    // every rank's state layers, and lev_sum also on the flat method
+    int *far_plan = nullptr;      // [world][2]
     DevCounters *ctr = nullptr;
     // psamd_export_live: per tile of SLOT_TILE owned slots, the live count and the statistics' partials; the context's own result record
     int *exp_count = nullptr;
@@ -276,6 +279,11 @@ hipError_t launch_outbox_close(hipStream_t st, const DevParams &P, const DeviceS
 hipError_t launch_inbox_merge(hipStream_t st, const DevParams &P, const DeviceState &d, const int *const msgs[5]);
 hipError_t launch_allg_pack(hipStream_t st, const DevParams &P, const DeviceState &d, int *msg);
 hipError_t launch_allg_index(hipStream_t st, const DevParams &P, const DeviceState &d);
+// a far slab's message (farfield.hip): the fp64 sums of the own cells from the snapshot, straight into the block that is
+// all-gathered (slab_build); then, from the gathered blocks of all ranks, level 0 of the box and the levels above it
+// (slab_pairs) -- after which the moments are those of one context
+hipError_t launch_far_own_sums(hipStream_t st, const DevParams &P, const DeviceState &d, int *msg);
+hipError_t launch_far_gathered(hipStream_t st, const DevParams &P, const DeviceState &d);
 // the chunk lists' capacity rule over all ranks' status records (start of the pair stage)
 hipError_t launch_chunk_census(hipStream_t st, const DevParams &P, const DeviceState &d, const int *status_all);
 // status records of all ranks (error bits, cell-overflow kills, the transfer messages' next capacity) + the force records of the lent-out layers (force_msg, may be null)

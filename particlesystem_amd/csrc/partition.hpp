@@ -205,4 +205,29 @@ inline SlabPlan make_slab_plan(int F, int D, const int seg_base[5], const int se
     return p;
 }
 
+// An all-gathered message is `world` blocks of ONE size, whatever the cuts: room for the rank whose state layers hold the
+// most cells.  Returns that cell count (0: some rank has no valid plan); first / cells (may be null): the first global
+// cell and the cell count of every rank's state layers -- what its block of a far slab's cell sums must say of itself.
+inline int gather_block_cells(int F, int D, const int seg_base[5], const int seg_size_t[4], const int info_base[5], int world,
+                              const int *cuts_in, std::vector<int> *first = nullptr, std::vector<int> *cells = nullptr)
+{
+    const int GG = F * D * F * D;
+    int most = 0;
+    if (first) first->assign((size_t)std::max(world, 0), 0);
+    if (cells) cells->assign((size_t)std::max(world, 0), 0);
+    for (int r = 0; r < world; r++) {
+        const SlabPlan p = make_slab_plan(F, D, seg_base, seg_size_t, info_base, r, world, cuts_in);
+        if (!p.valid) return 0;
+        const int n = (p.state_hi - p.state_lo) * GG;
+        if (first) (*first)[(size_t)r] = p.state_lo * GG;
+        if (cells) (*cells)[(size_t)r] = n;
+        most = std::max(most, n);
+    }
+    return most;
+}
+
+// A far slab's block of cell sums (PSAMD_FLAG_FAR_SLAB): the 16-word header, then `planes` planes of `cells` doubles.  The
+// header is 64 bytes, so the payload is 8-byte aligned and the block a whole number of doubles with no rounding.
+inline size_t far_slab_block_bytes(int planes, int cells) { return 64 + (size_t)planes * (size_t)cells * sizeof(double); }
+
 }  // namespace psamd

@@ -198,18 +198,17 @@ static int frame_ready(psamd_ctx *c, const char *who)
     return PSAMD_OK;
 }
 
-static bool far_context(const psamd_ctx *c) { return (c->P.flags & (PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID)) != 0; }
 static bool quad_context(const psamd_ctx *c) { return (c->P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) != 0; }
 
 // the modifier bits this context kind knows: the far form on far-monopole contexts, its quadrupole form on quadrupole contexts
 static uint32_t potential_bits(const psamd_ctx *c)
 {
-    return (far_context(c) ? PSAMD_POTENTIAL_FAR : 0u) | (quad_context(c) ? PSAMD_POTENTIAL_QUADRUPOLE : 0u);
+    return (far_context(c->P.flags) ? PSAMD_POTENTIAL_FAR : 0u) | (quad_context(c) ? PSAMD_POTENTIAL_QUADRUPOLE : 0u);
 }
 
 static uint32_t probe_far_bits(const psamd_ctx *c)
 {
-    return (far_context(c) ? PSAMD_PROBE_FAR : 0u) | (quad_context(c) ? PSAMD_PROBE_QUADRUPOLE : 0u);
+    return (far_context(c->P.flags) ? PSAMD_PROBE_FAR : 0u) | (quad_context(c) ? PSAMD_PROBE_QUADRUPOLE : 0u);
 }
 
 // potential and probe promise exactly the bodies the force pass walks: with far monopoles (flat or as a pyramid) a
@@ -223,9 +222,18 @@ static int refuse_far_monopole(psamd_ctx *c, const char *who, bool far_asked, bo
         return fail(c, PSAMD_ERR_UNSUPPORTED, std::string(who) + ": on a context with quadrupoles on the pyramid (PSAMD_FLAG_FAR_QUADRUPOLE) only the "
                                               "quadrupole far form is served (PSAMD_POTENTIAL_FAR | PSAMD_POTENTIAL_QUADRUPOLE, "
                                               "PSAMD_PROBE_FAR | PSAMD_PROBE_QUADRUPOLE); the far form alone is monopoles only");
-    if (far_context(c) && !far_asked)
+    if (far_context(c->P.flags) && !far_asked)
         return fail(c, PSAMD_ERR_UNSUPPORTED, std::string(who) + ": on a context with far monopoles (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID) "
                                               "only the far form is served (PSAMD_POTENTIAL_FAR, psamd_download_potential_far, PSAMD_PROBE_FAR)");
+    return PSAMD_OK;
+}
+
+// the far field on slabs (PSAMD_FLAG_FAR_SLAB, world > 1) serves the step alone: the far forms of potential and probe there
+// need the lent layers' and the window's rules worked out, and the stencil-only forms are not this context's field
+static int refuse_far_slab(psamd_ctx *c, const char *who)
+{
+    if (far_context(c->P.flags) && c->P.world > 1)
+        return fail(c, PSAMD_ERR_UNSUPPORTED, std::string(who) + ": a far-field context on slabs (PSAMD_FLAG_FAR_SLAB, world > 1) serves the step only");
     return PSAMD_OK;
 }
 
@@ -255,6 +263,7 @@ static int potential_flags(psamd_ctx *c, uint32_t flags)
 int psamd_potential(psamd_ctx *c, const psamd_potential_spec *spec)
 {
     if (!c || !spec) return PSAMD_ERR_INVALID_ARG;
+    PS_TRY(refuse_far_slab(c, "potential"));
     PS_TRY(potential_flags(c, spec->flags));
     if (spec->reserved != 0) return fail(c, PSAMD_ERR_INVALID_ARG, "potential: reserved not 0");
     if (spec->capacity < 0) return fail(c, PSAMD_ERR_INVALID_ARG, "potential: capacity < 0");
@@ -273,9 +282,10 @@ int psamd_potential_result_get(psamd_ctx *c, psamd_potential_result *out) { retu
 static int download_potential(psamd_ctx *c, uint32_t flags, bool checked, float *phi, int64_t capacity, psamd_potential_result *out)
 {
     if (!c) return PSAMD_ERR_INVALID_ARG;
+    PS_TRY(refuse_far_slab(c, "download_potential"));
     if (checked) PS_TRY(potential_flags(c, flags));
     if (capacity < 0 || (!phi && capacity > 0)) return fail(c, PSAMD_ERR_INVALID_ARG, "download_potential: capacity < 0, or no array for it");
-    if (!checked && (flags & PSAMD_POTENTIAL_FAR) && !far_context(c))
+    if (!checked && (flags & PSAMD_POTENTIAL_FAR) && !far_context(c->P.flags))
         return fail(c, PSAMD_ERR_UNSUPPORTED, "download_potential_far: the context has no far monopoles (PSAMD_FLAG_FAR_MONOPOLE, PSAMD_FLAG_FAR_PYRAMID)");
     PS_TRY(potential_ready(c, flags));
     const int64_t n = std::min<int64_t>(capacity, c->P.slots_total);
@@ -326,6 +336,7 @@ static int grow_probe_scratch(psamd_ctx *c, ProbeScratch &s, int64_t max_count)
 int psamd_probe(psamd_ctx *c, const psamd_probe_spec *spec)
 {
     PS_TRY(service_args(c, spec));
+    PS_TRY(refuse_far_slab(c, "probe"));
     // (PSAMD_PROBE_FAR is a known bit on far-monopole contexts only, PSAMD_PROBE_QUADRUPOLE on quadrupole contexts only, and both
     // are modifiers: they ask for no component)
     if ((spec->fields & (PSAMD_PROBE_ACC | PSAMD_PROBE_PHI)) == 0 ||

@@ -417,7 +417,10 @@ int psamd_slab_build(psamd_ctx *c)
         int r = enq_init_iframe(c);
         if (r == PSAMD_OK) r = enq_build_grid(c);
         if (r != PSAMD_OK) return r;
-        if (c->msg[MSG_ALLG_OUT].ptr) PS_HIP(c, launch_allg_pack(c->stream, c->P, c->d, c->msg[MSG_ALLG_OUT].ptr));
+        // what is all-gathered before the pair stage: the own snapshot (all-pairs) or the own cells' fp64 sums (a far slab)
+        if (c->msg[MSG_ALLG_OUT].ptr)
+            PS_HIP(c, far_context(c->P.flags) ? launch_far_own_sums(c->stream, c->P, c->d, c->msg[MSG_ALLG_OUT].ptr)
+                                        : launch_allg_pack(c->stream, c->P, c->d, c->msg[MSG_ALLG_OUT].ptr));
         int *const halo_out[2] = {c->msg[MSG_HALO_OUT].ptr, c->msg[MSG_HALO_OUT + 1].ptr};
         if (c->P.world > 1) PS_HIP(c, launch_pack_halos(c->stream, c->P, c->d, c->halo_out_c0, c->halo_out_cells, halo_out, c->pack_off));
         return (int)PSAMD_OK;
@@ -460,7 +463,8 @@ int psamd_slab_pairs(psamd_ctx *c)
         // from the rank below: halo layer (region 1), then lent layers (region 2); from the rank above: halo layer (region 3)
         PS_HIP(c, launch_unpack_halos(c->stream, P, c->d, c->halo_in_cells[0], c->msg[MSG_HALO_IN].ptr, c->unpack_off[0],
                                       c->halo_in_cells[1], c->msg[MSG_HALO_IN + 1].ptr, c->unpack_off[1]));
-        if (c->msg[MSG_ALLG_IN].ptr) PS_HIP(c, launch_allg_index(c->stream, P, c->d));      // all-pairs: the gathered snapshot, by global cell
+        // all-pairs: the gathered snapshot, by global cell; a far slab: the gathered cell sums become the moments of the whole box
+        if (c->msg[MSG_ALLG_IN].ptr) PS_HIP(c, far_context(P.flags) ? launch_far_gathered(c->stream, P, c->d) : launch_allg_index(c->stream, P, c->d));
         // the chunk lists' capacity rule over all ranks (the status records have landed): which particles the step leaves alone
         if (!second) PS_HIP(c, launch_chunk_census(c->stream, P, c->d, c->msg[MSG_STATUS_IN].ptr));
         const int r = enq_pairs(c, Pp, hint, true, !second);

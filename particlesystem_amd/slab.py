@@ -26,7 +26,7 @@ import numpy as np
 
 # message slots, as in psamd_slab_msg_download: out/in x below/above; the status record is all-gathered
 HALO_OUT, HALO_IN, FORCE_OUT, FORCE_IN, XFER_OUT, XFER_IN, STATUS_OUT, STATUS_IN = 0, 2, 4, 5, 6, 8, 10, 11
-ALLG_OUT, ALLG_IN = 12, 13          # all-pairs forces only: every rank's snapshot block, all-gathered between build and pairs
+ALLG_OUT, ALLG_IN = 12, 13          # all-gathered between build and pairs: every rank's snapshot block (all-pairs forces) or cell sums (far-field slabs, FLAG_FAR_SLAB)
 XFER2_OUT, XFER2_IN = 14, 16        # particles changing owner to a rank TWO away (worlds where a single-layer rank can be flown over)
 FAR_OUT, FAR_IN = 18, 19            # ... to any other rank: a small outbox, all-gathered in the transfer phase (births on, world >= 4)
 BELOW, ABOVE = 0, 1
@@ -58,9 +58,17 @@ def _bytes(sysr, slot):
         return 0
 
 
-def step_local(ranks, overlap_interior=False):
-    """One step of a whole system whose ranks all live in this process (tests)."""
+def step_local(ranks, overlap_interior=False, one_at_a_time=False):
+    """One step of a whole system whose ranks all live in this process (tests).  one_at_a_time: a rank's build and pair stage
+    have run before the next rank's are enqueued (measurements: the ranks' streams otherwise share the one GPU, and a rank's
+    timers and kernel times hold another rank's work)."""
     world = len(ranks)
+
+    def each(call):
+        for s in ranks:
+            call(s)
+            if one_at_a_time:
+                s.msg_download(STATUS_OUT)     # (a download waits for the rank's stream, mid-frame too)
 
     def deliver(phase):
         for r, sysr in enumerate(ranks):
@@ -77,16 +85,14 @@ def step_local(ranks, overlap_interior=False):
             for s in ranks:
                 s.msg_upload(in_slot, every)
 
-    for s in ranks:
-        s.slab_build()
+    each(lambda s: s.slab_build())
     gather(STATUS_OUT, STATUS_IN)             # before the first pair-stage call: its chunk census needs every rank's record
     if overlap_interior:
         for s in ranks:
             s.slab_pairs_interior()   # (in a real run: while the halo travels)
     deliver("halo")
     gather(ALLG_OUT, ALLG_IN)
-    for s in ranks:
-        s.slab_pairs()
+    each(lambda s: s.slab_pairs())
     deliver("force")
     for s in ranks:
         s.slab_apply()
@@ -159,7 +165,7 @@ class HostRing(_Ring):
         self._gather(STATUS_OUT, STATUS_IN)
 
     def gather_snapshot(self):
-        """all-pairs forces: every rank's snapshot block to every rank (synchronous here)"""
+        """all-pairs forces: every rank's snapshot block to every rank; far-field slabs: every rank's cell sums (synchronous here)"""
         self._gather(ALLG_OUT, ALLG_IN)
 
     def finish_snapshot(self, work):
@@ -257,8 +263,8 @@ class DeviceRing(_Ring):
                 work.wait()
 
     def gather_snapshot(self):
-        """all-pairs forces: start the all-gather of the snapshot blocks (RCCL ncclAllGather over xGMI); the
-        pair stage needs it, so finish_snapshot() comes before slab_pairs"""
+        """all-pairs forces: start the all-gather of the snapshot blocks (RCCL ncclAllGather over xGMI) -- far-field
+        slabs: of the cell sums, in the same buffers; the pair stage needs it, so finish_snapshot() comes before slab_pairs"""
         import torch
         if self.dist is None or ALLG_OUT not in self.t or self.world == 1:
             return None
@@ -284,7 +290,7 @@ class DeviceRing(_Ring):
             s.slab_build()
             status = self.gather_status()      # first: the pair stage's chunk census needs every rank's record
             halo = self.start("halo")
-            snap = self.gather_snapshot()      # all-pairs forces only
+            snap = self.gather_snapshot()      # all-pairs forces and far-field slabs only
             self.finish_status(status)
             if self.overlap_interior:
                 s.slab_pairs_interior()      # cells whose stencil lies in the own layers: no halo needed

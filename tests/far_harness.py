@@ -1,13 +1,17 @@
-"""What the far-field suites share (far_force_suite.py, test_gpu_far_*.py, test_far_*_cpu.py): the small contexts,
-one frame of any far context, the clouds, and the two checks of a feature's C surface.  The numpy model is far_model.py."""
+"""What the far-field suites share (far_force_suite.py, far_field_suite.py, test_gpu_far_*.py, test_far_*_cpu.py): the small
+contexts, one frame of any far context, the clouds, what the field services' tests read their results with (test_gpu_potential.py
+and test_gpu_probe.py take `bits` from here too), the two checks of a feature's C surface and the checks of the method without a
+GPU.  The numpy model is far_model.py."""
 import collections
 import ctypes
+import functools
 import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
+import torch
 
 import far_model as F
 import particlesystem_amd as ps
@@ -24,7 +28,15 @@ GRID = {4: dict(max_particles_num=16384, chunk_factor=1, chunk_dim=4),
         16: dict(max_particles_num=16384, chunk_factor=4, chunk_dim=4, x_factor=8)}      # (x_factor: lists of 40, for 4 a cell in the mean)
 INVALID_ARG, STATE, UNSUPPORTED = 1, 8, 9
 
+DEV = torch.device("cuda", 0)
+
 Frame = collections.namedtuple("Frame", "order f lists mom cen")
+
+
+def make(G, flags, **over):
+    g = ps.ParticleSystem(ps.default_config(flags=flags, collision_radius=1e-6, **GRID[G], **over))
+    assert g.sizes.grid_dim == G
+    return g
 
 
 def open_frame(g):
@@ -144,6 +156,43 @@ def model_frame(G, flags, seed, n, xyz=None, kids=True):
     return fr.f, where[fr.order], [where[l] for l in fr.lists], xyz, w_eff, kid
 
 
+def body_cloud(n, seed, G):
+    """kids among the adults (they exert nothing and get the field at their own place), unequal masses"""
+    rng = np.random.default_rng(seed)
+    age = rng.uniform(15 / 7, 7.5, n).astype(np.float32)
+    age[::17] = 0.5
+    return dict(xyz=box_cloud(n, seed, G), age=age, w=rng.uniform(20.0, 100.0, n).astype(np.float32), fert_age=np.float32(1e6))
+
+
+# ---- the field services' results (psamd_potential, psamd_probe) ----------------------------------------------------------------------
+
+def bits(a):
+    a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def by_fill(ids, phi):
+    """phi pairs with the live particles in ascending slot id: back to the order of the fill"""
+    out = np.empty(len(ids), np.float32)
+    out[np.argsort(ids)] = np.asarray(phi.cpu().numpy() if isinstance(phi, torch.Tensor) else phi)
+    return out
+
+
+def pos4_of(xyz):
+    p = np.zeros((len(xyz), 4), np.float32)
+    p[:, :3] = xyz
+    return torch.from_numpy(p).to(DEV)
+
+
+def record(res):
+    return {k: res[k] for k in res if k != "phi"}
+
+
+def served(g, far):
+    """the potential and the probe keywords of a context's own far form"""
+    return dict(far=far, quadrupole=bool(g.cfg.flags & ps.FLAG_FAR_QUADRUPOLE))
+
+
 def status_of_create(**over):
     with pytest.raises(ps.PsamdError) as e:
         ps.ParticleSystem(ps.default_config(**over))
@@ -206,6 +255,42 @@ def method_against_the_direct_sum(method, kind, G):
           % (kind, len(xyz), G, method, np.median(far), far.max(), "the pyramid of monopoles" if method == "quadrupole" else "the stencil alone",
              np.median(beside), beside.max()))
     return far, beside
+
+
+@functools.lru_cache(maxsize=None)
+def phi_against_the_direct_sum(kind, G):
+    """8192 bodies of equal mass, 400 of them sampled: {a method, or "stencil": the relative deviations of its fp64 phi from the fp64
+    direct sum over all bodies}.  Computed once, never changed."""
+    xyz, w, lists = cloud_frame(kind, G)
+    pick = np.random.default_rng(13).choice(len(xyz), 400, replace=False)
+    cell = F.cells_of(xyz, G)[pick]
+    want = F.direct_phi(xyz, w, EPS2, pick)
+    dev = {method: F.phi64(lists, xyz, w, G, EPS2, xyz[pick], cell, pick, method) for method in F.METHODS}
+    dev["stencil"] = F.phi64(lists, xyz, w, G, EPS2, xyz[pick], cell, pick, "flat", far=False)
+    return {k: np.abs(got - want) / np.abs(want) for k, got in dev.items()}
+
+
+def two_forms_of_the_model_agree(method):
+    """the fp32 association against the fp64 form, both signs of w; kids among the points (w_eff 0: they see every body).  The
+    bound is one for every method (far_model.ALLOW): a quadrupole term is a small part of phi, and its own rounding -- some ten
+    operations of 2^-24 each on a term of at most a few 1e-3 of phi -- is far below what the monopole chains are allowed"""
+    G = 8
+    xyz, w, lists = cloud_frame("uniform", G, 4096)
+    w = w.copy()
+    w[::17] = 0.0
+    pick = np.concatenate([np.arange(0, 170, 17), np.random.default_rng(14).choice(len(xyz), 190, replace=False)])
+    cell = F.cells_of(xyz, G)[pick]
+    for sign in (1.0, -1.0):
+        a = F.phi64(lists, xyz, np.float32(sign) * w, G, EPS2, xyz[pick], cell, pick, method)
+        b = F.phi32(lists, xyz, np.float32(sign) * w, G, EPS2, xyz[pick], cell, pick, method)
+        rel = np.abs(b - a) / np.abs(a)
+        beside = ""
+        if method == "quadrupole":
+            part = F.quad_sum64(lists, xyz, np.float32(sign) * w, G, EPS2, xyz[pick], cell)
+            beside = " (the quadrupole part: median %.3g of |phi|)" % np.median(np.abs(part / a))
+            assert np.abs(part).min() > 0
+        print("%s, sign %+.0f: fp32 association against fp64, max %.3g%s" % (method, sign, rel.max(), beside))
+        assert b.dtype == np.float32 and (np.sign(a) == -sign).all() and rel.max() < F.ALLOW
 
 
 def hand_made_pyramid():

@@ -1,6 +1,7 @@
 """The far field restated in numpy from the definitions in include/psamd.h ("long-range gravity", "a pyramid of monopoles",
-"quadrupoles on the pyramid", "energy") -- not from the library's code.  Shared by the test_far_*_cpu.py suites, far_force_suite.py,
-test_gpu_far_potential.py and scripts/far_*_cost.py; tests/golden/far_model.json pins what it computes (scripts/far_model_golden.py).
+"quadrupoles on the pyramid", "energy", "the field at chosen points") -- not from the library's code.  Shared by the
+test_far_*_cpu.py suites, far_force_suite.py, far_field_suite.py and scripts/far_*.py; tests/golden/far_model.json and
+tests/golden/far_field_quadrupole.json pin what it computes (scripts/far_model_golden.py).
 
 A METHOD is one of
     flat         PSAMD_FLAG_FAR_MONOPOLE: one monopole per cell beyond the stencil -- a pyramid of one level
@@ -19,7 +20,12 @@ the walk (levels top down, index order within a level), cumsum for the sequentia
 
 Two forms of the potential: phi64 is the method in fp64; phi32 is the device's association -- fp32 terms, fp32 chains of at most
 64 from +0 per stencil cell and per block of 64 level cells, carried on in fp64 -- with correctly rounded fp32 sqrt and division
-where the device has the hardware reciprocal square root (ALLOW says what that may cost)."""
+where the device has the hardware reciprocal square root (ALLOW says what that may cost).
+
+The potential's sums run over w * u and phi = -sum.  In that convention a far body (X, Y, Z, M != 0, C) of the quadrupole method
+adds its monopole term M u and the quadrupole term
+    t_q = 1.5 (d.C.d) u^5 - 0.5 T u^3,      d = (X, Y, Z) - x,  u = (d.d + eps2)^(-1/2),  T = Cxx + Cyy + Czz,
+the term whose gradient is quad_pull's a_q."""
 import numpy as np
 
 METHODS = ("flat", "pyramid", "quadrupole")
@@ -191,12 +197,18 @@ def _pull(at, bodies, mass, eps2):
     return (d * (mass / (r2 * np.sqrt(r2)))[:, :, None]).sum(1)
 
 
+def _matrices(cen):
+    """float64 [b, 3, 3]: the symmetric matrices of the six planes `cen` [b, 6]"""
+    C = np.empty((len(cen), 3, 3))
+    for f, (a, b) in enumerate(PLANES):
+        C[:, a, b] = C[:, b, a] = cen[:, f]
+    return C
+
+
 def quad_pull(at, bodies, cen, eps2):
     """fp64 quadrupole acceleration at the points `at` [t, 3] from `bodies` [b, 3] with the central moments `cen` [b, 6]:
     a_q = -3 (C d) u^5 + 7.5 (d.C.d) u^7 d - 1.5 T u^5 d, d = body - point, u = (d.d + eps2)^(-1/2), T = Cxx + Cyy + Czz"""
-    C = np.empty((len(bodies), 3, 3))
-    for f, (a, b) in enumerate(PLANES):
-        C[:, a, b] = C[:, b, a] = cen[:, f]
+    C = _matrices(cen)
     d = bodies[None, :, :] - at[:, None, :]
     u = 1.0 / np.sqrt((d * d).sum(2) + eps2)
     Cd = np.einsum("bij,tbj->tbi", C, d)
@@ -204,6 +216,16 @@ def quad_pull(at, bodies, cen, eps2):
     T = np.trace(C, axis1=1, axis2=2)[None, :]
     u5, u7 = u ** 5, u ** 7
     return (-3.0 * Cd * u5[:, :, None] + ((7.5 * dCd * u7 - 1.5 * T * u5)[:, :, None]) * d).sum(1)
+
+
+def quad_terms64(at, bodies, cen, eps2):
+    """fp64 [t, b]: t_q of every body at every point"""
+    C = _matrices(np.asarray(cen, np.float64))
+    d = bodies[None, :, :] - at[:, None, :]
+    u = 1.0 / np.sqrt((d * d).sum(2) + eps2)
+    dCd = (np.einsum("bij,tbj->tbi", C, d) * d).sum(2)
+    T = np.trace(C, axis1=1, axis2=2)[None, :]
+    return 1.5 * dCd * u ** 5 - 0.5 * T * u ** 3
 
 
 def _by_cell(lists, G, cell, method, moments, far):
@@ -274,16 +296,29 @@ def quad_accel(lists, xyz, w_eff, G, eps2, targets, moments=None):
 
 
 def accel64(lists, xyz, w_eff, G, eps2, at, cell, method, moments=None):
-    """fp64 acceleration at probes (no own entry): the stencil's listed bodies, then the far set's members"""
-    assert method in ("flat", "pyramid"), "the library has no far probe on a quadrupole context"
+    """fp64 acceleration at probes (no own entry): the stencil's listed bodies, the far set's monopoles, then their quadrupole
+    terms where the method has them"""
+    assert method in METHODS, method
     at = np.asarray(at, np.float32).astype(np.float64)
-    return _accel(lists, xyz, w_eff, G, eps2, at, cell, method, moments, ("near", "mono"))
+    return _accel(lists, xyz, w_eff, G, eps2, at, cell, method, moments, ("near", "mono", "quad") if method == "quadrupole" else ("near", "mono"))
+
+
+def quad_sum64(lists, xyz, w_eff, G, eps2, at, cell, moments=None):
+    """fp64 [t]: the sum of t_q over the far set's members (M != 0) of every point's cell -- phi's quadrupole part is minus this"""
+    at = np.asarray(at, np.float32).astype(np.float64)
+    if moments is None:
+        moments = level_moments(lists, xyz, w_eff, G, "quadrupole")
+    out = np.zeros(len(at))
+    for _, mine, _, members in _by_cell(lists, G, cell, "quadrupole", moments, True):
+        m = _gather(moments[0], members, 4)
+        out[mine] = quad_terms64(at[mine], m[:, :3], _gather(moments[1], members, 6), eps2).sum(1)
+    return out
 
 
 def phi64(lists, xyz, w_eff, G, eps2, at, cell, own, method, moments=None, far=True):
     """fp64: phi = -(sum over the stencil's listed bodies except `own`, then over the far set's members with M != 0) of
-    w / sqrt(r.r + eps2), the moments float32-rounded as the device has them"""
-    assert method in ("flat", "pyramid"), "the library has no far potential on a quadrupole context"
+    w / sqrt(r.r + eps2), the moments float32-rounded as the device has them; quadrupole: minus the members' quadrupole terms"""
+    assert method in METHODS, method
     pos = np.asarray(xyz, np.float32).astype(np.float64)
     w = np.asarray(w_eff, np.float32).astype(np.float64)
     at = np.asarray(at, np.float32).astype(np.float64)
@@ -301,6 +336,8 @@ def phi64(lists, xyz, w_eff, G, eps2, at, cell, own, method, moments=None, far=T
             d = m[None, :, :3] - at[mine][:, None, :]
             s = s + (m[None, :, 3] / np.sqrt((d * d).sum(2) + eps2)).sum(1)
         out[mine] = -s
+        if far and method == "quadrupole":
+            out[mine] -= quad_terms64(at[mine], m[:, :3], _gather(moments[1], members, 6), eps2).sum(1)
     return out
 
 
@@ -311,6 +348,35 @@ def _terms32(at, bodies, mass, eps2f):
     return mass[None, :] * (np.float32(1.0) / np.sqrt(d2 + eps2f))
 
 
+def _fma(a, b, c):
+    """float32 fma(a, b, c): the product of two fp32 values is exact in fp64; the sum is rounded in fp64 and then to fp32 (a
+    double rounding, which differs from one rounding in rare last bits: the model is held to a tolerance, not to bits)"""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def quad_terms32(at, bodies, cen, eps2f):
+    """float32 [t, b]: the header's fp32 operation sequence for t_q, with a correctly rounded 1 / sqrt where the device has the
+    hardware reciprocal square root"""
+    f32 = np.float32
+    at, bodies, cen = np.asarray(at, f32), np.asarray(bodies, f32), np.asarray(cen, f32)
+    d = bodies[None, :, :] - at[:, None, :]
+    dx, dy, dz = d[:, :, 0], d[:, :, 1], d[:, :, 2]
+    r2 = (dx * dx + dy * dy) + dz * dz
+    u = f32(1.0) / np.sqrt(r2 + f32(eps2f))
+    u2 = u * u
+    u3 = u2 * u
+    u5 = u3 * u2
+    cxx, cyy, czz, cxy, cxz, cyz = (np.broadcast_to(cen[None, :, k], dx.shape) for k in range(6))
+    gx = _fma(cxz, dz, _fma(cxy, dy, cxx * dx))
+    gy = _fma(cyz, dz, _fma(cyy, dy, cxy * dx))
+    gz = _fma(czz, dz, _fma(cyz, dy, cxz * dx))
+    q = _fma(gz, dz, _fma(gy, dy, gx * dx))
+    T = (cxx + cyy) + czz
+    t = _fma(f32(1.5) * u5, q, (f32(-0.5) * T) * u3)
+    assert t.dtype == f32
+    return t
+
+
 def _chains(acc, t):
     """the terms t [points, bodies] in fp32 chains of at most 64 from +0 (add.accumulate is sequential), carried in fp64"""
     for j0 in range(0, t.shape[1], 64):
@@ -319,8 +385,10 @@ def _chains(acc, t):
 
 def phi32(lists, xyz, w_eff, G, eps2, at, cell, own, method, moments=None, far=True):
     """float32: the device's association.  The stencil's cells are taken in index order, not the reference's: a cell's
-    chains do not depend on it, only the order of the fp64 carries does"""
-    assert method in ("flat", "pyramid"), "the library has no far potential on a quadrupole context"
+    chains do not depend on it, only the order of the fp64 carries does.  Quadrupole: behind a block's monopole chain comes that
+    block's quadrupole chain -- one fp32 chain from +0, in index order, over the same members --, each carried into the fp64 sum
+    by an addition of its own"""
+    assert method in METHODS, method
     pos = np.asarray(xyz, np.float32)
     w = np.asarray(w_eff, np.float32)
     at = np.asarray(at, np.float32)
@@ -339,8 +407,11 @@ def phi32(lists, xyz, w_eff, G, eps2, at, cell, own, method, moments=None, far=T
                 _chains(acc, t)
         for lvl, J in members:
             for b in np.unique(J >> 6):                                   # a block of 64 consecutive indices: one chain
-                m = moments[0][lvl][J[(J >> 6) == b]]
-                acc += np.add.accumulate(_terms32(at[mine], m[:, :3], m[:, 3], eps2f), axis=1, dtype=np.float32)[:, -1].astype(np.float64)
+                Jb = J[(J >> 6) == b]
+                m = moments[0][lvl][Jb]
+                _chains(acc, _terms32(at[mine], m[:, :3], m[:, 3], eps2f))
+                if method == "quadrupole":
+                    _chains(acc, quad_terms32(at[mine], m[:, :3], moments[1][lvl][Jb], eps2f))
         out[mine] = (-acc).astype(np.float32)
     return out
 

@@ -1,7 +1,8 @@
-"""PSAMD_POTENTIAL_QUADRUPOLE / PSAMD_PROBE_QUADRUPOLE without a GPU: the C surface (the two bits, psamd_download_potential_flags,
-the layouts that must not move, the keyword-only `quadrupole` of the four Python methods), the potential's quadrupole term
-against the force term it must be the potential of, the METHOD against an fp64 direct sum over all bodies, the model's two
-forms against each other, and the limit in which every C is an exact zero (far_quad_field_model.py).
+"""PSAMD_POTENTIAL_QUADRUPOLE / PSAMD_PROBE_QUADRUPOLE without a GPU (test_far_model_cpu.py has the two bits,
+psamd_download_potential_flags and the layouts that must not move): the keyword-only `quadrupole` of the four Python methods, the
+potential's quadrupole term against the force term it must be the potential of, the METHOD against an fp64 direct sum over all
+bodies, the model's two forms against each other (far_harness.py has the check, once for every method), and the limit in which
+every C is an exact zero (far_model.py).
 
 Measured with the seeds below, 8192 bodies, 400 sampled per cloud, median / maximum relative deviation of the far phi from the
 direct sum -- pyramid; quadrupole; the ratio of the medians:
@@ -17,26 +18,11 @@ import numpy as np
 import pytest
 
 import far_model as F
-import far_quad_field_model as Q
 import particlesystem_amd as ps
-from far_harness import EPS2, INVALID_ARG, c_prints, cloud_frame, declared_exported_bound, low_corner
+from far_harness import EPS2, low_corner, phi_against_the_direct_sum, two_forms_of_the_model_agree
 
 
 # ---- 1. the C surface -------------------------------------------------------------------------------------------------------
-
-def test_the_two_bits_the_new_host_form_and_the_layouts_that_stay(tmp_path):
-    got = c_prints(tmp_path,
-                   'printf("%u %u %u %u %d %zu %zu\\n", PSAMD_POTENTIAL_QUADRUPOLE, PSAMD_PROBE_QUADRUPOLE, '
-                   'PSAMD_POTENTIAL_QUADRUPOLE & PSAMD_POTENTIAL_FAR, '
-                   'PSAMD_PROBE_QUADRUPOLE & (PSAMD_PROBE_ACC | PSAMD_PROBE_PHI | PSAMD_PROBE_FAR), PSAMD_ABI_VERSION, '
-                   'sizeof(psamd_potential_spec), sizeof(psamd_probe_spec));\n'
-                   'printf("%d %d\\n", psamd_abi_version(), psamd_download_potential_flags(NULL, PSAMD_POTENTIAL_FAR | PSAMD_POTENTIAL_QUADRUPOLE, NULL, 0, NULL));\n')
-    assert got == [0x2, 0x8, 0, 0, 8, 32, 56, 8, INVALID_ARG]
-    assert (ps.POTENTIAL_QUADRUPOLE, ps.PROBE_QUADRUPOLE) == (0x2, 0x8)
-    lib = declared_exported_bound(["psamd_download_potential_flags"])
-    assert lib.psamd_download_potential_flags(None, ps.POTENTIAL_FAR | ps.POTENTIAL_QUADRUPOLE, None, 0, None) == INVALID_ARG
-    assert lib.psamd_download_potential_flags(None, 0, None, 0, None) == INVALID_ARG
-
 
 @pytest.mark.parametrize("name", ["potential", "download_potential", "energy", "probe"])
 def test_quadrupole_is_keyword_only_and_off_by_default(name):
@@ -61,7 +47,7 @@ def test_the_gradient_of_the_potential_term_is_the_force_term():
     for k in range(3):
         e = np.zeros(3)
         e[k] = h
-        grad[:, k] = (Q.quad_terms64(at + e, bodies, cen, EPS2).sum(1) - Q.quad_terms64(at - e, bodies, cen, EPS2).sum(1)) / (2 * h)
+        grad[:, k] = (F.quad_terms64(at + e, bodies, cen, EPS2).sum(1) - F.quad_terms64(at - e, bodies, cen, EPS2).sum(1)) / (2 * h)
     want = F.quad_pull(at, bodies, cen, EPS2)
     rel = F.rel_dev(grad, want)
     print("central-difference gradient of the sum of t_q against quad_pull: max %.3g relative" % rel.max())
@@ -73,39 +59,17 @@ def test_the_gradient_of_the_potential_term_is_the_force_term():
 @pytest.mark.parametrize("G", [8, 10])
 @pytest.mark.parametrize("kind", ["uniform", "clustered"])
 def test_the_method_against_the_direct_sum(kind, G):
-    xyz, w, lists = cloud_frame(kind, G)
-    pick = np.random.default_rng(13).choice(len(xyz), 400, replace=False)
-    cell = F.cells_of(xyz, G)[pick]
-    want = F.direct_phi(xyz, w, EPS2, pick)
-    moments = F.level_moments(lists, xyz, w, G, "quadrupole")
-    dev = lambda got: np.abs(got - want) / np.abs(want)
-    pyr = dev(F.phi64(lists, xyz, w, G, EPS2, xyz[pick], cell, pick, "pyramid", (moments[0], None)))
-    quad = dev(Q.phi64(lists, xyz, w, G, EPS2, xyz[pick], cell, pick, moments))
-    print("%s cloud, %d bodies on %d^3 cells: far phi as a pyramid median %.3g max %.3g; with quadrupoles median %.3g max %.3g; "
-          "ratio of the medians %.2f" % (kind, len(xyz), G, np.median(pyr), pyr.max(), np.median(quad), quad.max(), np.median(quad) / np.median(pyr)))
+    dev = phi_against_the_direct_sum(kind, G)
+    pyr, quad = dev["pyramid"], dev["quadrupole"]
+    print("%s cloud, 8192 bodies on %d^3 cells: far phi as a pyramid median %.3g max %.3g; with quadrupoles median %.3g max %.3g; "
+          "ratio of the medians %.2f" % (kind, G, np.median(pyr), pyr.max(), np.median(quad), quad.max(), np.median(quad) / np.median(pyr)))
     assert np.median(quad) <= 0.5 * np.median(pyr)
 
 
 # ---- 4. the model's two forms -----------------------------------------------------------------------------------------------
 
 def test_the_two_forms_of_the_model_agree():
-    """the fp32 association against the fp64 form, both signs of w; kids among the points (w_eff 0: they see every body).  The
-    bound is the monopole forms' (far_model.ALLOW): a quadrupole term is a small part of phi, and its own rounding -- some ten
-    operations of 2^-24 each on a term of at most a few 1e-3 of phi -- is far below what the monopole chains are allowed"""
-    G = 8
-    xyz, w, lists = cloud_frame("uniform", G, 4096)
-    w = w.copy()
-    w[::17] = 0.0
-    pick = np.concatenate([np.arange(0, 170, 17), np.random.default_rng(14).choice(len(xyz), 190, replace=False)])
-    cell = F.cells_of(xyz, G)[pick]
-    for sign in (1.0, -1.0):
-        a = Q.phi64(lists, xyz, np.float32(sign) * w, G, EPS2, xyz[pick], cell, pick)
-        b = Q.phi32(lists, xyz, np.float32(sign) * w, G, EPS2, xyz[pick], cell, pick)
-        part = Q.quad_sum64(lists, xyz, np.float32(sign) * w, G, EPS2, xyz[pick], cell)
-        rel = np.abs(b - a) / np.abs(a)
-        print("quadrupole, sign %+.0f: fp32 association against fp64, max %.3g (the quadrupole part: median %.3g of |phi|)"
-              % (sign, rel.max(), np.median(np.abs(part / a))))
-        assert b.dtype == np.float32 and (np.sign(a) == -sign).all() and np.abs(part).min() > 0 and rel.max() < F.ALLOW
+    two_forms_of_the_model_agree("quadrupole")
 
 
 # ---- 5. every C an exact zero -------------------------------------------------------------------------------------------------
@@ -124,6 +88,6 @@ def test_one_adult_a_cell_is_the_pyramid_phi():
     idx = np.arange(len(xyz))
     moments = F.level_moments(lists, xyz, w, G, "quadrupole")
     assert len(moments[1]) == 1 and not moments[1][0].any() and (moments[0][0][:, 3] != 0).all()
-    got = Q.phi32(lists, xyz, w, G, EPS2, xyz, cell, idx, moments)
+    got = F.phi32(lists, xyz, w, G, EPS2, xyz, cell, idx, "quadrupole", moments)
     want = F.phi32(lists, xyz, w, G, EPS2, xyz, cell, idx, "pyramid", (moments[0], None))
     assert np.array_equal(got, want) and np.abs(got).min() > 0

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import particlesystem_amd as ps
+from far_harness import bits
 from particlesystem_amd import slab
 from util import SENTINEL, capacities, cloud, hip_runtime, ragged
 
@@ -37,11 +38,6 @@ def kid_age(cfg):
 def frame(g):
     g.init_iframe()
     g.build_grid()
-
-
-def bits(a):
-    a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def by_id(g, res=None, capacity=None):

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import particlesystem_amd as ps
+from far_harness import bits
 from particlesystem_amd import slab
 from util import cloud
 
@@ -36,11 +37,6 @@ def kid_age(cfg):
 def frame(g):
     g.init_iframe()
     g.build_grid()
-
-
-def bits(a):
-    a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def dev4(xyz):

@@ -872,7 +872,7 @@ int psamd_probe_result_get(psamd_ctx *ctx, psamd_probe_result *out);
  * entry 0 first, one addition per entry, every sum started at +0; each product of two fp32 values is exact in fp64, so a
  * fused multiply-add changes nothing.  M_c = (float)S, X_c = (float)(Sx / S), Y_c and Z_c likewise (fp64 division, one
  * rounding to fp32).  If S == 0 -- an empty cell, or kids only -- M_c = X_c = Y_c = Z_c = 0.  A host that repeats these
- * operations gets the same bits (tests/far_monopole_model.py does).
+ * operations gets the same bits (tests/far_model.py does).
  *
  * Far acceleration.  For every particle the force pass serves (no kid, no collision this step), in cell c_i: the cells of
  * the box are walked in global index order; a cell contributes the one body (X_c, Y_c, Z_c, M_c) through the context's own
@@ -925,7 +925,7 @@ int psamd_download_cell_moments(psamd_ctx *ctx, void *out_float4);
  * min(count, MAX_PARTICLES_PER_CELL) entries of the cell in list order, with the force pass's w_eff; the fp64 sums are kept.
  * A level-(l+1) cell's four fp64 sums are its existing children's fp64 sums, added one at a time in ascending child index,
  * each sum started at +0 (additions only: contraction cannot matter).  At every level M = (float)S, X = (float)(Sx / S), Y
- * and Z likewise; S == 0 gives four zeros.  A host that repeats this gets the same bits (tests/far_pyramid_model.py does).
+ * and Z likewise; S == 0 gives four zeros.  A host that repeats this gets the same bits (tests/far_model.py does).
  *
  * Interaction set of a particle in cell i that the force pass serves (no kid, no collision this step):
  *   at the top level, every level-L cell J with max-norm |J - (i >> L)| > 1;
@@ -986,7 +986,7 @@ int psamd_download_level_moments(psamd_ctx *ctx, int32_t level, void *out_float4
  * Level l + 1: the children's sums added in ascending child index to +0 (raw moments about the origin need no shift).
  * At every level, in fp64 and unfused, C_ab = (float)(S_ab - RN(RN(S_a / S) * S_b)), a the first index of the plane's name;
  * S == 0 gives six zeros.  A cell with one adult gives six exact zeros (both products round the same real number).  M, X, Y,
- * Z are the pyramid context's bit for bit.  A host that repeats this gets the same bits (tests/far_quadrupole_model.py does).
+ * Z are the pyramid context's bit for bit.  A host that repeats this gets the same bits (tests/far_model.py does).
  *
  * The quadrupole term of a member (X, Y, Z, M != 0, C) on a particle at x: the second-order Taylor term of the softened
  * kernel about the centre of mass (the first-order term vanishes there),

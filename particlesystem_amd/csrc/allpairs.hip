@@ -1,5 +1,5 @@
 // allpairs.hip -- the far field of the all-pairs forces (PSAMD_FLAG_ALL_PAIRS, not in the reference)
-#include "pair_math.hpp"
+#include "pot_walk.hpp"
 
 namespace psamd {
 
@@ -48,32 +48,6 @@ __global__ __launch_bounds__(256) void k_allp_dense(DevParams P, const int *__re
     for (int i = lane; i < n; i += 64) { dense_gi[o + i] = active_list[base + i]; dense_cell[o + i] = c; }
 }
 
-// n bodies from four planes of a snapshot (wave-uniform pointers: scalar loads), added to (ax, ay, az) in list order
-template <int MODE, int NQ>
-__device__ __forceinline__ void walk_far(const DevParams &P, const PairCtx &ctx, const float *__restrict__ sx, const float *__restrict__ sy,
-                                         const float *__restrict__ sz, const float *__restrict__ sw, int n, float eps2f,
-                                         float &ax, float &ay, float &az)
-{
-    int flag = 0, jj = 0;
-    for (; jj + NQ <= n; jj += NQ) {
-        v2f qx[NQ / 2], qy[NQ / 2], qz[NQ / 2], qw[NQ / 2];
-#pragma unroll
-        for (int i = 0; i < NQ / 2; i++) {
-            qx[i] = v2f{sx[jj + 2 * i], sx[jj + 2 * i + 1]};
-            qy[i] = v2f{sy[jj + 2 * i], sy[jj + 2 * i + 1]};
-            qz[i] = v2f{sz[jj + 2 * i], sz[jj + 2 * i + 1]};
-            qw[i] = v2f{sw[jj + 2 * i], sw[jj + 2 * i + 1]};
-        }
-        if (MODE == 1) pairsN_exact_lean<NQ>(P, ctx, qx, qy, qz, qw, 0, nullptr, nullptr, ax, ay, az, flag);
-        else (void)pairsN_fast<NQ>(ctx, qx, qy, qz, qw, eps2f, ax, ay, az);
-    }
-    for (; jj < n; jj++) {
-        const float4 q = make_float4(sx[jj], sy[jj], sz[jj], sw[jj]);
-        if (MODE == 1) pair1_exact_lean(P, ctx, q, 0, nullptr, nullptr, ax, ay, az, flag);
-        else (void)pair_fast(ctx.xi, ctx.yi, ctx.zi, q, eps2f, ax, ay, az);
-    }
-}
-
 template <int MODE, int NQ>
 __global__ __launch_bounds__(256, BALANCED_WAVES) void k_allp_far(DevParams P, const SnapSoa snap4, const int *__restrict__ act_start,
                                                                         const int *__restrict__ dense_gi, const int *__restrict__ dense_cell,
@@ -101,7 +75,7 @@ __global__ __launch_bounds__(256, BALANCED_WAVES) void k_allp_far(DevParams P, c
     const PairCtx ctx = {me.x, me.y, me.z, 0.f, 0, gi, false};
     const float eps2f = (float)P.eps2;
     const size_t plane = (size_t)far.plane;
-    const int nblk = (P.num_cells_global + 63) >> 6, GG = P.G * P.G;
+    const int nblk = (P.num_cells_global + 63) >> 6;
     const int blk_lo = nblk * part / ALLP_PARTS, blk_hi = nblk * (part + 1) / ALLP_PARTS;
     float px = 0.f, py = 0.f, pz = 0.f;                     // the part's sum
     for (int blk = blk_lo; blk < blk_hi; blk++) {
@@ -110,10 +84,11 @@ __global__ __launch_bounds__(256, BALANCED_WAVES) void k_allp_far(DevParams P, c
         const int c2 = blk * 64 + lane;
         int f_nb = 0, f_cnt = 0, f_j = 0;
         if (c2 < P.num_cells_global) {
-            const int j3 = c2 / GG, rem = c2 - j3 * GG, j1 = rem / P.G, j2 = rem - j1 * P.G;
+            int j1, j2, j3;
+            global_coords(P, c2, j1, j2, j3);
             f_nb = far_start[c2];
             f_cnt = far_n ? far_n[c2] : min(far_start[c2 + 1] - f_nb, P.max_per_cell);
-            f_j = (j3 << 20) | (j1 << 10) | j2;
+            f_j = pack_cell(j3, j1, j2);
         }
         for (int q0 = 0; q0 < 64; q0 += ALLP_CHUNK) {
             int n[ALLP_CHUNK], nb[ALLP_CHUNK];
@@ -128,21 +103,21 @@ __global__ __launch_bounds__(256, BALANCED_WAVES) void k_allp_far(DevParams P, c
                     if (total == 0) first = nb[q]; else adjacent = adjacent && nb[q] == first + total;
                     total += n[q];
                 }
-                hit[q] = n[q] > 0 && abs((j >> 20) - i3) <= 1 && abs(((j >> 10) & 1023) - i1) <= 1 && abs((j & 1023) - i2) <= 1;
+                hit[q] = n[q] > 0 && abs(packed_i3(j) - i3) <= 1 && abs(packed_i1(j) - i1) <= 1 && abs(packed_i2(j) - i2) <= 1;
                 any_hit |= hit[q];
             }
             if (total == 0) continue;
             float ax = 0.f, ay = 0.f, az = 0.f;
             if (adjacent && !__any(any_hit)) {
                 const float *sx = far_buf + first;
-                walk_far<MODE, NQ>(P, ctx, sx, sx + plane, sx + 2 * plane, sx + 3 * plane, total, eps2f, ax, ay, az);
+                acc_walk<MODE, NQ>(P, ctx, sx, sx + plane, sx + 2 * plane, sx + 3 * plane, total, eps2f, ax, ay, az);
             } else {
 #pragma unroll
                 for (int q = 0; q < ALLP_CHUNK; q++) {
                     if (n[q] == 0) continue;
                     const float kx = ax, ky = ay, kz = az;
                     const float *sx = far_buf + nb[q];
-                    walk_far<MODE, NQ>(P, ctx, sx, sx + plane, sx + 2 * plane, sx + 3 * plane, n[q], eps2f, ax, ay, az);
+                    acc_walk<MODE, NQ>(P, ctx, sx, sx + plane, sx + 2 * plane, sx + 3 * plane, n[q], eps2f, ax, ay, az);
                     if (hit[q]) { ax = kx; ay = ky; az = kz; }      // a cell of this lane's own stencil: the cutoff pass has it
                 }
             }
@@ -200,20 +175,17 @@ void launch_far_combine(hipStream_t st, const DevParams &P, const DeviceState &d
 // with lean arithmetic); now every other cell (k_allp_far) and the sum.  fast: the tolerance mode's arithmetic.
 void launch_allpairs_far(hipStream_t st, const DevParams &P, const DeviceState &d, bool fast, int64_t live_bound)
 {
-    // where the far cells are found: the own snapshot (one GPU: local cell == global cell, lengths from consecutive starts) or the
-    // all-gathered snapshot of all ranks with its index by global cell.
+    // where the far cells are found: pot_far_of (pot_walk.hpp)
     FarCells far;
-    const bool gathered = P.world > 1;
-    const float *far_buf = gathered ? reinterpret_cast<const float *>(d.allg_in) : d.snap_soa;
-    const int *far_start = gathered ? d.gstart : d.cell_start, *far_n = gathered ? d.gn : nullptr;
-    far.plane = gathered ? (unsigned long long)P.allg_cap : (unsigned long long)P.sorted_cap;
+    const PotFar src = pot_far_of(P, d, P.world > 1);
+    far.plane = src.plane;
     far.part_acc = d.part_acc; far.part_plane = (unsigned long long)d.part_tasks * 64;
     const int64_t dense_bound = far_dense_bound(P, d, live_bound);
     launch_dense_order(st, P, d);
     const SnapSoa snap4{d.snap_soa, (size_t)P.sorted_cap};
     const unsigned far_wgs = (unsigned)((dense_bound * ALLP_PARTS + 3) / 4);
-    if (fast) k_allp_far<2, 8><<<far_wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, far_buf, far_start, far_n);
-    else k_allp_far<1, 8><<<far_wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, far_buf, far_start, far_n);
+    if (fast) k_allp_far<2, 8><<<far_wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, src.buf, src.start, src.n);
+    else k_allp_far<1, 8><<<far_wgs, 256, 0, st>>>(P, snap4, d.act_start, d.dense_gi, d.dense_cell, far, src.buf, src.start, src.n);
     launch_far_combine(st, P, d, far, ALLP_PARTS, dense_bound);
 }
 

@@ -129,11 +129,8 @@ __global__ __launch_bounds__(256, CAP <= 1024 ? 6 : 3) void k_collide_cell(DevPa
     const int nbins = nb * nb * nb;
     // what one force task of this cell walks: the population of its stencil (the last wave, while the others' loads fly)
     if (wv == 3) {
-        int n = 0;
-        if (lane < STENCIL) {
-            const int nc = local_cell(P, i3 + c_stencil[lane][2], i1 + c_stencil[lane][1], i2 + c_stencil[lane][0]);
-            if (nc >= 0) n = min(cell_start[nc + 1] - cell_start[nc], P.max_per_cell);
-        }
+        int first, n;
+        stencil_ranges(P, cell_start, i1, i2, i3, lane, first, n);
         n = wave_incl_scan(n);
         if (lane == 63) task_cost[c] = n;
     }

@@ -177,6 +177,7 @@ static int derive_params(psamd_ctx *c, const psamd_config *cfg)
     {
         // (r.r + eps2)^3 over every pair of in-box positions, with slack for one wrap of drift
         const double lo = cfg->eps2 * cfg->eps2 * cfg->eps2, hi = std::pow(max_d2(g) + cfg->eps2, 3.0);
+        // (scripts/field_bits.py's "probe-cutoff-8-generic" relies on eps2 = 1e-8 lying below this range: move the range, move the case)
         P.lean_math = (lo > std::ldexp(1.0, -60) && hi < std::ldexp(1.0, 60)) ? 1 : 0;
         // Collision flags before forces (lean modes): a collision needs two bodies within
         // COLLISION_RADIUS, so only bodies that close to a cell face concern the cell beyond it;

@@ -149,9 +149,25 @@ PS_HD int local_cell(const DevParams &P, int i3, int i1, int i2)
     return -1;
 }
 
+// (i1, i2, i3) of global cell gc = (i3 * G + i1) * G + i2
+PS_HD void global_coords(const DevParams &P, int gc, int &i1, int &i2, int &i3)
+{
+    const int GG = P.G * P.G;
+    i3 = gc / GG;
+    const int rem = gc - i3 * GG;
+    i1 = rem / P.G; i2 = rem - i1 * P.G;
+}
+
+// A cell's coordinates in one word, (i3 << 20) | (i1 << 10) | i2 (at most 1024 cells an axis): what the far walks keep per
+// cell of a level (mom_j) and per cell of a block.
+PS_HD int pack_cell(int i3, int i1, int i2) { return (i3 << 20) | (i1 << 10) | i2; }
+PS_HD int packed_i3(int j) { return j >> 20; }
+PS_HD int packed_i1(int j) { return (j >> 10) & 1023; }
+PS_HD int packed_i2(int j) { return j & 1023; }
+
 PS_HD int local_of_global(const DevParams &P, int gc)
 {
-    const int GG = P.G * P.G, i3 = gc / GG, rem = gc - i3 * GG;
+    const int GG = P.G * P.G, i3 = gc / GG, rem = gc - i3 * GG;      // (the layer alone: the place inside it is kept whole)
     for (int r = 0; r < 4; r++) {
         const int l = i3 - P.reg_first[r];
         if (l >= 0 && l < P.reg_layers[r]) return P.reg_base[r] + l * GG + rem;

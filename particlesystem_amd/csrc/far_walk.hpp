@@ -14,7 +14,7 @@
 namespace psamd {
 
 // Where a far-field context finds the moments the pair stage's own kernels form (farfield.hip): four planes X, Y, Z, M of
-// mom_cap and the packed coordinates (i3 << 20) | (i1 << 10) | i2, every level padded with zeros to whole blocks of 64.
+// mom_cap and the packed coordinates (pack_cell), every level padded with zeros to whole blocks of 64.
 // nparts: the partial sums the force pass deals a level's blocks to (16 flat, 1 pyramid) -- the probe's acceleration
 // repeats them.  A level's size and place follow from nlev and G (far_level): a few scalar operations.
 struct FarMoments {
@@ -80,7 +80,7 @@ __device__ __forceinline__ void far_blocks(const FarLevel &v, const FarBox &b, i
 // particle's parent (a coarser level has it).
 __device__ __forceinline__ bool far_leaves_out(bool top, int j, int a1, int a2, int a3)
 {
-    const int J3 = j >> 20, J1 = (j >> 10) & 1023, J2 = j & 1023;
+    const int J3 = packed_i3(j), J1 = packed_i1(j), J2 = packed_i2(j);
     const bool adj = abs(J3 - a3) <= 1 && abs(J1 - a1) <= 1 && abs(J2 - a2) <= 1;
     const bool par = top || (abs((J3 >> 1) - (a3 >> 1)) <= 1 && abs((J1 >> 1) - (a1 >> 1)) <= 1 && abs((J2 >> 1) - (a2 >> 1)) <= 1);
     return adj || !par;
@@ -128,6 +128,7 @@ __device__ __forceinline__ void far_block_chain(const DevParams &P, const PairCt
     for (int g = 0; g < 64; g += 8) {
         if (((evalm >> g) & 0xffull) == 0ull) continue;
         v2f qx[4], qy[4], qz[4], qw[4];
+        // (load_group, spelled out: through the call the fast instances of k_far_walk come out with other code)
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             qx[i] = v2f{sx[g + 2 * i], sx[g + 2 * i + 1]};

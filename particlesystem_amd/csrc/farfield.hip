@@ -104,8 +104,9 @@ __global__ __launch_bounds__(256) void k_cell_moments(DevParams P, const int *__
         mom[mom_cap + c] = none ? 0.f : (float)(Sy / S);
         mom[2 * mom_cap + c] = none ? 0.f : (float)(Sz / S);
         mom[3 * mom_cap + c] = none ? 0.f : (float)S;
-        const int GG = P.G * P.G, i3 = c / GG, rem = c - i3 * GG, i1 = rem / P.G;
-        mom_j[c] = (i3 << 20) | (i1 << 10) | (rem - i1 * P.G);
+        int i1, i2, i3;
+        global_coords(P, c, i1, i2, i3);
+        mom_j[c] = pack_cell(i3, i1, i2);
         if (sums) { sums[c] = S; sums[mom_cap + c] = Sx; sums[2 * (size_t)mom_cap + c] = Sy; sums[3 * (size_t)mom_cap + c] = Sz; }
         if (QUAD) {
             const double Sa[3] = {Sx, Sy, Sz};
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(256) void k_level_moments(const FarLevels lev, int 
     mom[cap + o] = none ? 0.f : (float)(Sy / S);
     mom[2 * cap + o] = none ? 0.f : (float)(Sz / S);
     mom[3 * cap + o] = none ? 0.f : (float)S;
-    mom_j[o] = (k3 << 20) | (k1 << 10) | k2;
+    mom_j[o] = pack_cell(k3, k1, k2);
     if (QUAD) {
         const double Sa[3] = {Sx, Sy, Sz};
 #pragma unroll
@@ -171,8 +172,8 @@ static void launch_upper_levels(hipStream_t st, const DevParams &P, const Device
     const FarLevels &lev = d.lev;
     for (int l = 1; l < lev.n; l++) {
         const unsigned wgs = (unsigned)((lev.G[l] * lev.G[l] * lev.G[l] + 255) / 256);
-        if (quad) k_level_moments<true><<<wgs, 256, 0, st>>>(lev, l, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap);
-        else k_level_moments<false><<<wgs, 256, 0, st>>>(lev, l, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap);
+        const auto launch = [&](auto kernel) { kernel<<<wgs, 256, 0, st>>>(lev, l, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap); };
+        if (quad) launch(k_level_moments<true>); else launch(k_level_moments<false>);
     }
 }
 
@@ -183,9 +184,10 @@ void launch_far_moments(hipStream_t st, const DevParams &P, const DeviceState &d
 {
     const bool pyramid = (P.flags & PSAMD_FLAG_FAR_PYRAMID) != 0, quad = (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) != 0;
     const unsigned cell_wgs = (unsigned)((P.num_cells + 3) / 4);
-    if (quad) k_cell_moments<true, false><<<cell_wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.cell_mom, d.cell_mom_j, d.mom_cap, d.lev_sum, nullptr, nullptr);
-    else k_cell_moments<false, false><<<cell_wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.cell_mom, d.cell_mom_j, d.mom_cap,
-                                                                pyramid ? d.lev_sum : nullptr, nullptr, nullptr);
+    const auto launch = [&](auto kernel) {      // (the pyramid keeps the fp64 sums: a quadrupole context is one)
+        kernel<<<cell_wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, d.cell_mom, d.cell_mom_j, d.mom_cap, pyramid ? d.lev_sum : nullptr, nullptr, nullptr);
+    };
+    if (quad) launch(k_cell_moments<true, false>); else launch(k_cell_moments<false, false>);
     if (pyramid) launch_upper_levels(st, P, d);
 }
 
@@ -205,8 +207,8 @@ hipError_t launch_far_own_sums(hipStream_t st, const DevParams &P, const DeviceS
 {
     const unsigned wgs = (unsigned)((std::max(P.n_own_cells, 1) + 3) / 4);
     double *pay = reinterpret_cast<double *>(msg + MSG_HEADER_WORDS);
-    if (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) k_cell_moments<true, true><<<wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, nullptr, nullptr, P.allg_cells, pay, msg, d.fs);
-    else k_cell_moments<false, true><<<wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, nullptr, nullptr, P.allg_cells, pay, msg, d.fs);
+    const auto launch = [&](auto kernel) { kernel<<<wgs, 256, 0, st>>>(P, d.cell_start, d.snap_soa, nullptr, nullptr, P.allg_cells, pay, msg, d.fs); };
+    if (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) launch(k_cell_moments<true, true>); else launch(k_cell_moments<false, true>);
     return hipGetLastError();
 }
 
@@ -240,8 +242,9 @@ __global__ __launch_bounds__(256) void k_far_scatter(DevParams P, const int *__r
     mom[cap + c] = none ? 0.f : (float)(Sy / S);
     mom[2 * cap + c] = none ? 0.f : (float)(Sz / S);
     mom[3 * cap + c] = none ? 0.f : (float)S;
-    const int GG = P.G * P.G, i3 = c / GG, rem = c - i3 * GG, i1 = rem / P.G;
-    mom_j[c] = (i3 << 20) | (i1 << 10) | (rem - i1 * P.G);
+    int i1, i2, i3;
+    global_coords(P, c, i1, i2, i3);
+    mom_j[c] = pack_cell(i3, i1, i2);
     if (QUAD) {
         const double Sa[3] = {Sx, Sy, Sz};
 #pragma unroll
@@ -256,8 +259,8 @@ __global__ __launch_bounds__(256) void k_far_scatter(DevParams P, const int *__r
 hipError_t launch_far_gathered(hipStream_t st, const DevParams &P, const DeviceState &d)
 {
     const dim3 grid((unsigned)((std::max(P.allg_cells, 1) + 255) / 256), (unsigned)P.world);
-    if (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) k_far_scatter<true><<<grid, 256, 0, st>>>(P, d.allg_in, d.far_plan, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap, d.fs);
-    else k_far_scatter<false><<<grid, 256, 0, st>>>(P, d.allg_in, d.far_plan, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap, d.fs);
+    const auto launch = [&](auto kernel) { kernel<<<grid, 256, 0, st>>>(P, d.allg_in, d.far_plan, d.cell_mom, d.cell_mom_j, d.lev_sum, d.mom_cap, d.fs); };
+    if (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) launch(k_far_scatter<true>); else launch(k_far_scatter<false>);
     if (P.flags & PSAMD_FLAG_FAR_PYRAMID) launch_upper_levels(st, P, d);
     return hipGetLastError();
 }
@@ -322,7 +325,7 @@ __global__ __launch_bounds__(256, QUAD ? QUAD_WAVES : PYRAMID ? PYRAMID_WAVES : 
     const int GG = P.G * P.G;
     int i1, i2, i3, cg = c;                                 // (world == 1: local cell == global cell)
     if (SLAB) { cell_coords(P, c, i1, i2, i3); cg = (i3 * P.G + i1) * P.G + i2; }
-    else { i3 = c / GG; const int irem = c - i3 * GG; i1 = irem / P.G; i2 = irem - i1 * P.G; }
+    else global_coords(P, c, i1, i2, i3);
     const int a1 = i1 >> l, a2 = i2 >> l, a3 = i3 >> l;     // the lane's cell of this level
     const PairCtx ctx = {me.x, me.y, me.z, 0.f, 0, gi, false};
     const float eps2f = (float)P.eps2;
@@ -350,7 +353,7 @@ __global__ __launch_bounds__(256, QUAD ? QUAD_WAVES : PYRAMID ? PYRAMID_WAVES : 
         const int base = lev.off + blk * 64;
         const int jp = m.mom_j[base + lane];
         const bool nz = m.mom[3 * (size_t)m.mom_cap + base + lane] != 0.f;
-        const int j3 = jp >> 20, j1 = (jp >> 10) & 1023, j2 = jp & 1023;
+        const int j3 = packed_i3(jp), j1 = packed_i1(jp), j2 = packed_i2(jp);
         const unsigned long long nearm = __ballot(nz && j3 >= box.lo3 && j3 <= box.hi3 && j1 >= box.lo1 && j1 <= box.hi1 && j2 >= box.lo2 && j2 <= box.hi2);
         const unsigned long long evalm = top ? __ballot(nz) : nearm;      // (below the top level no lane has a body outside the box)
         if (evalm == 0ull) continue;                        // (a chain of nothing is +0, and the part's sum never is -0)

@@ -107,13 +107,7 @@ __device__ __forceinline__ void pairs_task(const DevParams &P, const int *__rest
             // on a 1/8 share.)
             for (; jj + NQ <= n; jj += NQ) {
                 v2f qx[NQ / 2], qy[NQ / 2], qz[NQ / 2], qw[NQ / 2];
-#pragma unroll
-                for (int i = 0; i < NQ / 2; i++) {
-                    qx[i] = v2f{sx[jj + 2 * i], sx[jj + 2 * i + 1]};
-                    qy[i] = v2f{sy[jj + 2 * i], sy[jj + 2 * i + 1]};
-                    qz[i] = v2f{sz[jj + 2 * i], sz[jj + 2 * i + 1]};
-                    qw[i] = v2f{sw[jj + 2 * i], sw[jj + 2 * i + 1]};
-                }
+                load_group<NQ>(sx, sy, sz, sw, jj, qx, qy, qz, qw);
                 // (The compiler lets the masses' load sink to its use, behind the reciprocal square roots; pinned up
                 // here with the coordinates' loads -- four in one batch -- the pass took the same time, 2.13 ms.)
                 if (MODE == 1)

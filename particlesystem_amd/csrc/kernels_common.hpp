@@ -79,6 +79,22 @@ static __constant__ signed char c_stencil[27][3] = {
     {-1, +1, +1}, {0, +1, +1}, {+1, +1, +1},
 };
 
+// Lane k (< STENCIL) looks neighbour cell k of the stencil of local cell (i1, i2, i3) up, once for the wave: its range in the
+// sorted order -- the start nb and the count, clamped to MAX_PARTICLES_PER_CELL -- or an empty range where this rank does
+// not hold the cell; the other lanes get an empty range.  A walk hands the ranges out by readlane, in the reference's order.
+__device__ __forceinline__ void stencil_ranges(const DevParams &P, const int *cell_start, int i1, int i2, int i3,
+                                               int lane, int &nb, int &cnt)
+{
+    nb = 0; cnt = 0;
+    if (lane < STENCIL) {
+        const int nc = local_cell(P, i3 + c_stencil[lane][2], i1 + c_stencil[lane][1], i2 + c_stencil[lane][0]);
+        if (nc >= 0) {
+            nb = cell_start[nc];
+            cnt = min(cell_start[nc + 1] - nb, P.max_per_cell);
+        }
+    }
+}
+
 // Blocks are dealt round-robin over the 8 XCDs (b and b+8 share an L2).  Give each
 // XCD one contiguous run of tasks so neighbouring cells' tiles hit the same L2.
 __device__ __forceinline__ int xcd_contiguous(int b, int nb)

@@ -333,6 +333,53 @@ __device__ __forceinline__ void pair1_exact_lean(const DevParams &P, const PairC
     ax += rx * s; ay += ry * s; az += rz * s;
 }
 
+// NQ bodies from jj on of four planes of a snapshot (wave-uniform pointers: scalar loads), two to a register pair
+template <int NQ>
+__device__ __forceinline__ void load_group(const float *sx, const float *sy, const float *sz, const float *sw, int jj, v2f (&qx)[NQ / 2], v2f (&qy)[NQ / 2],
+                                           v2f (&qz)[NQ / 2], v2f (&qw)[NQ / 2])
+{
+#pragma unroll
+    for (int i = 0; i < NQ / 2; i++) {
+        qx[i] = v2f{sx[jj + 2 * i], sx[jj + 2 * i + 1]};
+        qy[i] = v2f{sy[jj + 2 * i], sy[jj + 2 * i + 1]};
+        qz[i] = v2f{sz[jj + 2 * i], sz[jj + 2 * i + 1]};
+        qw[i] = v2f{sw[jj + 2 * i], sw[jj + 2 * i + 1]};
+    }
+}
+
+// n bodies of one list (four planes, wave-uniform pointers) added to (ax, ay, az) in list order by the context's pair form:
+// force.hip's walk_cell without its collision work -- the far cells of an all-pairs context (allpairs.hip), a probe's
+// acceleration (probe.hip).  MATH 1: pairsN_exact_lean, and pair1_exact_lean for the ragged tail; 2: the fast forms;
+// 0: pair_exact one body at a time, a massless body skipped as k_pairs<0> skips it.
+template <int MATH, int NQ>
+__device__ __forceinline__ void acc_walk(const DevParams &P, const PairCtx &ctx, const float *__restrict__ sx, const float *__restrict__ sy,
+                                         const float *__restrict__ sz, const float *__restrict__ sw, int n, float eps2f,
+                                         float &ax, float &ay, float &az)
+{
+    int flag = 0, jj = 0;
+    if (MATH != 0) {
+        for (; jj + NQ <= n; jj += NQ) {
+            v2f qx[NQ / 2], qy[NQ / 2], qz[NQ / 2], qw[NQ / 2];
+            // (load_group, spelled out: through the call k_allp_far<2, 8> comes out with other branches)
+#pragma unroll
+            for (int i = 0; i < NQ / 2; i++) {
+                qx[i] = v2f{sx[jj + 2 * i], sx[jj + 2 * i + 1]};
+                qy[i] = v2f{sy[jj + 2 * i], sy[jj + 2 * i + 1]};
+                qz[i] = v2f{sz[jj + 2 * i], sz[jj + 2 * i + 1]};
+                qw[i] = v2f{sw[jj + 2 * i], sw[jj + 2 * i + 1]};
+            }
+            if (MATH == 1) pairsN_exact_lean<NQ>(P, ctx, qx, qy, qz, qw, 0, nullptr, nullptr, ax, ay, az, flag);
+            else (void)pairsN_fast<NQ>(ctx, qx, qy, qz, qw, eps2f, ax, ay, az);
+        }
+    }
+    for (; jj < n; jj++) {
+        const float4 q = make_float4(sx[jj], sy[jj], sz[jj], sw[jj]);
+        if (MATH == 1) pair1_exact_lean(P, ctx, q, 0, nullptr, nullptr, ax, ay, az, flag);
+        else if (MATH == 2) (void)pair_fast(ctx.xi, ctx.yi, ctx.zi, q, eps2f, ax, ay, az);
+        else if (q.w != 0.0f) (void)pair_exact(ctx.xi, ctx.yi, ctx.zi, q, P.eps2, ax, ay, az);
+    }
+}
+
 // Bodies in the stencil of local cell (i1, i2, i3) that are no kids, counted by one wave.  For the particle
 // whose own position is not a number: the lean force walks let a particle meet itself and the kids because
 // r * 0 adds nothing -- not so when r is no number.  The reference skips both (ps.cpp:1258,

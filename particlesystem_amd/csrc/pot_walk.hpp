@@ -21,13 +21,7 @@ __device__ __forceinline__ void pot_group(const PairCtx &ctx, const float *__res
 {
     constexpr int NQ = 8;
     v2f qx[NQ / 2], qy[NQ / 2], qz[NQ / 2], qw[NQ / 2];
-#pragma unroll
-    for (int i = 0; i < NQ / 2; i++) {
-        qx[i] = v2f{sx[jj + 2 * i], sx[jj + 2 * i + 1]};
-        qy[i] = v2f{sy[jj + 2 * i], sy[jj + 2 * i + 1]};
-        qz[i] = v2f{sz[jj + 2 * i], sz[jj + 2 * i + 1]};
-        qw[i] = v2f{sw[jj + 2 * i], sw[jj + 2 * i + 1]};
-    }
+    load_group<NQ>(sx, sy, sz, sw, jj, qx, qy, qz, qw);
     PairRows<NQ> r;
     pairs_dist<NQ, false>(ctx, qx, qy, qz, 0.f, r);
     const v2f eps = {eps2f, eps2f};
@@ -82,13 +76,21 @@ __device__ __forceinline__ void pot_walk(const PairCtx &ctx, const float *__rest
     }
 }
 
-// where an all-pairs context finds the cells beyond the stencil (allpairs.hip, launch_allpairs_far)
+// where an all-pairs context finds the cells beyond the stencil: the own snapshot (world 1: cells by local == global index,
+// lengths from consecutive starts, padded) or the all-gathered snapshot of all ranks with its index by global cell (the
+// force pass and psamd_potential on world > 1; a probe reads the own snapshot always)
 struct PotFar {
     const float *buf;
     const int *start, *n;
     unsigned long long plane;
     int padded;
 };
+
+inline PotFar pot_far_of(const DevParams &P, const DeviceState &d, bool gathered)
+{
+    if (gathered) return PotFar{reinterpret_cast<const float *>(d.allg_in), d.gstart, d.gn, (unsigned long long)P.allg_cap, 0};
+    return PotFar{d.snap_soa, d.cell_start, nullptr, (unsigned long long)P.sorted_cap, 1};
+}
 
 // Far-field contexts (PSAMD_POTENTIAL_FAR, PSAMD_PROBE_FAR; far_walk.hpp says where the moments are and which are members).
 // One block of 64 level cells (wave-uniform pointers to its moments: scalar loads): the members' terms -- pot_group's, on

@@ -104,14 +104,8 @@ __global__ __launch_bounds__(POT_THREADS) void k_pot_pairs(DevParams P, const in
     cell_coords(P, c, i1, i2, i3);
     const float eps2f = (float)P.eps2;
     const PairCtx ctx = {mx, my, mz, 0.f, 0, gi, false};
-    int my_nb = 0, my_cnt = 0;
-    if (lane < STENCIL) {
-        const int nc = local_cell(P, i3 + c_stencil[lane][2], i1 + c_stencil[lane][1], i2 + c_stencil[lane][0]);
-        if (nc >= 0) {
-            my_nb = cell_start[nc];
-            my_cnt = min(cell_start[nc + 1] - my_nb, P.max_per_cell);
-        }
-    }
+    int my_nb, my_cnt;
+    stencil_ranges(P, cell_start, i1, i2, i3, lane, my_nb, my_cnt);
     double acc = 0.0;
     {   // the own cell first, as the stencil has it
         const float *sx = snap_soa + base;
@@ -127,12 +121,13 @@ __global__ __launch_bounds__(POT_THREADS) void k_pot_pairs(DevParams P, const in
         // every other cell of the box in global index order, 64 cell ranges to a vector load (allpairs.hip); the wave's
         // particles share one cell, so the cells of its stencil are left out for the whole wave
         const size_t plane = (size_t)far.plane;
-        const int nblk = (P.num_cells_global + 63) >> 6, GG = P.G * P.G;
+        const int nblk = (P.num_cells_global + 63) >> 6;
         for (int blk = 0; blk < nblk; blk++) {
             const int c2 = blk * 64 + lane;
             int f_nb = 0, f_cnt = 0;
             if (c2 < P.num_cells_global) {
-                const int j3 = c2 / GG, rem = c2 - j3 * GG, j1 = rem / P.G, j2 = rem - j1 * P.G;
+                int j1, j2, j3;
+                global_coords(P, c2, j1, j2, j3);
                 f_nb = far.start[c2];
                 f_cnt = far.n ? far.n[c2] : min(far.start[c2 + 1] - f_nb, P.max_per_cell);
                 if (abs(j3 - i3) <= 1 && abs(j1 - i1) <= 1 && abs(j2 - i2) <= 1) f_cnt = 0;
@@ -294,23 +289,16 @@ hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceStat
     if (want_phi) { const hipError_t e = launch_fill_int(st, reinterpret_cast<int *>(d.pot_slot), 0x7fc00000, (size_t)P.slots_total); if (e != hipSuccess) return e; }
     const int ntask = P.n_own_cells * P.slices;
     if (ntask > 0) {
-        if (flags & PSAMD_POTENTIAL_QUADRUPOLE) {
-            launch_far_moments(st, P, d);
-            PS_LAUNCH_CHECK();
-            k_pot_pairs<3><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, PotFar{}, far_moments_of(P, d), d.pot_sorted);
-        } else if (flags & PSAMD_POTENTIAL_FAR) {
-            launch_far_moments(st, P, d);
-            PS_LAUNCH_CHECK();
-            k_pot_pairs<2><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, PotFar{}, far_moments_of(P, d), d.pot_sorted);
-        } else if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
-            // the own snapshot (cells by local == global index) or the gathered one with its index by global cell
-            const bool gathered = P.world > 1;
-            const PotFar far{gathered ? reinterpret_cast<const float *>(d.allg_in) : d.snap_soa, gathered ? d.gstart : d.cell_start,
-                             gathered ? d.gn : nullptr, gathered ? (unsigned long long)P.allg_cap : (unsigned long long)P.sorted_cap,
-                             gathered ? 0 : 1};
-            k_pot_pairs<1><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, far, FarMoments{}, d.pot_sorted);
-        } else
-            k_pot_pairs<0><<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, PotFar{}, FarMoments{}, d.pot_sorted);
+        const bool far_form = (flags & (PSAMD_POTENTIAL_FAR | PSAMD_POTENTIAL_QUADRUPOLE)) != 0, allp = !far_form && (P.flags & PSAMD_FLAG_ALL_PAIRS);
+        if (far_form) { launch_far_moments(st, P, d); PS_LAUNCH_CHECK(); }
+        const auto launch = [&](auto kernel) {
+            kernel<<<(ntask + 3) / 4, POT_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, d.snap_age, d.sorted_id, d.pos4, allp ? pot_far_of(P, d, P.world > 1) : PotFar{},
+                                                            far_form ? far_moments_of(P, d) : FarMoments{}, d.pot_sorted);
+        };
+        if (flags & PSAMD_POTENTIAL_QUADRUPOLE) launch(k_pot_pairs<3>);
+        else if (flags & PSAMD_POTENTIAL_FAR) launch(k_pot_pairs<2>);
+        else if (allp) launch(k_pot_pairs<1>);
+        else launch(k_pot_pairs<0>);
         PS_LAUNCH_CHECK();
     }
     if (ntiles > 0) {

@@ -15,12 +15,12 @@
 //                    distinct cells among its lanes one after the other; for each, ALL lanes walk that cell's stencil --
 //                    the bodies are wave-uniform (scalar) loads of the four planes, eight to a group, as in force.hip and
 //                    potential.hip -- and the lanes that belong to the cell store their four words at the end.  (No lane
-//                    is switched off during a walk: the stencil lookup is handed out by readlane from lanes 0..26, and
+//                    is switched off during a walk: the stencil lookup (stencil_ranges) is handed out by readlane, and
 //                    a lane of another cell only computes numbers nobody keeps.)
 //   k_probe_finish   the result record
 //
 // Acceleration: one fp32 chain per component from +0, every body added in list order by the context's own pair form
-// (pair_math.hpp; scan = false: no collision work).  On the lean exact path a probe on an adult of a cutoff context
+// (pair_math.hpp, acc_walk).  On the lean exact path a probe on an adult of a cutoff context
 // repeats that particle's force chain operation for operation: the same bits as its force record (the own term is r * s
 // with r = 0).  Potential: pot_walk.hpp, potential.hip's association unchanged.  All-pairs: each far cell's terms in fp32
 // chains of at most POT_CHAIN that start at +0 with the cell and are carried on in fp64, a = (float)((double)a_stencil +
@@ -126,46 +126,6 @@ __global__ __launch_bounds__(PROBE_THREADS) void k_probe_scatter(int64_t max_cou
     if (lc >= 0) order[atomicAdd(&counts[lc], 1)] = (int)i64;      // (below the served count, which is at most n <= the scratch's room)
 }
 
-// n bodies of one list (wave-uniform pointers: scalar loads) added to the chains in list order by the context's pair
-// form: force.hip's walk_cell without its collision work.  MATH 1: pairsN_exact_lean's three parts and pair1_exact_lean
-// for the ragged tail; 2: the fast forms; 0: pair_exact one body at a time, a massless body skipped as k_pairs<0> skips it.
-template <int MATH>
-__device__ __forceinline__ void probe_acc_walk(const DevParams &P, const PairCtx &ctx, const float *__restrict__ sx,
-                                               const float *__restrict__ sy, const float *__restrict__ sz,
-                                               const float *__restrict__ sw, int n, float eps2f, float &ax, float &ay, float &az)
-{
-    constexpr int NQ = 8;
-    int jj = 0, flag = 0;
-    if (MATH != 0) {
-        for (; jj + NQ <= n; jj += NQ) {
-            v2f qx[NQ / 2], qy[NQ / 2], qz[NQ / 2], qw[NQ / 2];
-#pragma unroll
-            for (int i = 0; i < NQ / 2; i++) {
-                qx[i] = v2f{sx[jj + 2 * i], sx[jj + 2 * i + 1]};
-                qy[i] = v2f{sy[jj + 2 * i], sy[jj + 2 * i + 1]};
-                qz[i] = v2f{sz[jj + 2 * i], sz[jj + 2 * i + 1]};
-                qw[i] = v2f{sw[jj + 2 * i], sw[jj + 2 * i + 1]};
-            }
-            PairRows<NQ> r;
-            if (MATH == 1) {
-                v2f sc[NQ / 2];
-                pairs_dist<NQ, false>(ctx, qx, qy, qz, 0.f, r);
-                pairs_scale_exact<NQ, true>(P, ctx, r, qw, 0, nullptr, nullptr, sc, flag);
-                pairs_add<NQ>(r, sc, ax, ay, az);
-            } else {
-                pairs_dist<NQ, true>(ctx, qx, qy, qz, eps2f, r);
-                pairs_finish_fast<NQ>(r, qw, ax, ay, az);
-            }
-        }
-    }
-    for (; jj < n; jj++) {
-        const float4 q = make_float4(sx[jj], sy[jj], sz[jj], sw[jj]);
-        if (MATH == 1) pair1_exact_lean(P, ctx, q, 0, nullptr, nullptr, ax, ay, az, flag);
-        else if (MATH == 2) (void)pair_fast(ctx.xi, ctx.yi, ctx.zi, q, eps2f, ax, ay, az);
-        else if (q.w != 0.0f) (void)pair_exact(ctx.xi, ctx.yi, ctx.zi, q, P.eps2, ax, ay, az);
-    }
-}
-
 __device__ __forceinline__ bool probe_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 // VGPRs / waves per SIMD as the compiler reports them for gfx950, no instance with scratch (cutoff | all-pairs | far
@@ -209,20 +169,14 @@ __global__ __launch_bounds__(PROBE_THREADS) void k_probe_pairs(DevParams P, cons
         todo &= ~mine;
         int i1, i2, i3;
         cell_coords(P, c, i1, i2, i3);
-        int my_nb = 0, my_cnt = 0;
-        if (lane < STENCIL) {
-            const int nc = local_cell(P, i3 + c_stencil[lane][2], i1 + c_stencil[lane][1], i2 + c_stencil[lane][0]);
-            if (nc >= 0) {
-                my_nb = cell_start[nc];
-                my_cnt = min(cell_start[nc + 1] - my_nb, P.max_per_cell);
-            }
-        }
+        int my_nb, my_cnt;
+        stencil_ranges(P, cell_start, i1, i2, i3, lane, my_nb, my_cnt);
         float ax = 0.f, ay = 0.f, az = 0.f;
         double acc = 0.0;
         for (int k = 0; k < STENCIL; k++) {                 // the stencil, in the reference's order
             const int nb = __builtin_amdgcn_readlane(my_nb, k), n = __builtin_amdgcn_readlane(my_cnt, k);
             const float *sx = snap_soa + nb;
-            if (FIELDS & PSAMD_PROBE_ACC) probe_acc_walk<MATH>(P, ctx, sx, sx + cap, sx + 2 * cap, sx + 3 * cap, n, eps2f, ax, ay, az);
+            if (FIELDS & PSAMD_PROBE_ACC) acc_walk<MATH, 8>(P, ctx, sx, sx + cap, sx + 2 * cap, sx + 3 * cap, n, eps2f, ax, ay, az);
             if (FIELDS & PSAMD_PROBE_PHI) pot_walk<false>(ctx, sx, sx + cap, sx + 2 * cap, sx + 3 * cap, n, 0, eps2f, true, acc);
         }
         if (FAR >= 2) {
@@ -274,13 +228,14 @@ __global__ __launch_bounds__(PROBE_THREADS) void k_probe_pairs(DevParams P, cons
             // every other cell of the box in global index order (k_pot_pairs<1>'s walk); the cells of THIS cell's
             // stencil are left out for this cell's turn
             const size_t plane = (size_t)far.plane;
-            const int nblk = (P.num_cells_global + 63) >> 6, GG = P.G * P.G;
+            const int nblk = (P.num_cells_global + 63) >> 6;
             double fx = 0.0, fy = 0.0, fz = 0.0;
             for (int blk = 0; blk < nblk; blk++) {
                 const int c2 = blk * 64 + lane;
                 int f_nb = 0, f_cnt = 0;
                 if (c2 < P.num_cells_global) {
-                    const int j3 = c2 / GG, rem = c2 - j3 * GG, j1 = rem / P.G, j2 = rem - j1 * P.G;
+                    int j1, j2, j3;
+                    global_coords(P, c2, j1, j2, j3);
                     f_nb = far.start[c2];
                     f_cnt = far.n ? far.n[c2] : min(far.start[c2 + 1] - f_nb, P.max_per_cell);
                     if (abs(j3 - i3) <= 1 && abs(j1 - i1) <= 1 && abs(j2 - i2) <= 1) f_cnt = 0;
@@ -292,8 +247,8 @@ __global__ __launch_bounds__(PROBE_THREADS) void k_probe_pairs(DevParams P, cons
                     if (FIELDS & PSAMD_PROBE_ACC) {
                         for (int j0 = 0; j0 < n; j0 += POT_CHAIN) {
                             float cx = 0.f, cy = 0.f, cz = 0.f;
-                            probe_acc_walk<MATH>(P, ctx, sx + j0, sx + plane + j0, sx + 2 * plane + j0, sx + 3 * plane + j0,
-                                                 min(POT_CHAIN, n - j0), eps2f, cx, cy, cz);
+                            acc_walk<MATH, 8>(P, ctx, sx + j0, sx + plane + j0, sx + 2 * plane + j0, sx + 3 * plane + j0,
+                                              min(POT_CHAIN, n - j0), eps2f, cx, cy, cz);
                             fx += (double)cx; fy += (double)cy; fz += (double)cz;
                         }
                     }
@@ -329,19 +284,19 @@ template <int FIELDS, int MATH>
 static void launch_probe_pairs(hipStream_t st, const DevParams &P, const DeviceState &d, const ProbeArgs &a, const ProbeScratch &s,
                                int *hdr, unsigned nwg)
 {
-    if (a.fields & PSAMD_PROBE_QUADRUPOLE) {
-        if constexpr (MATH != 0)       // (quadrupole contexts are far-monopole contexts, and the bit comes with PSAMD_PROBE_FAR)
-            k_probe_pairs<FIELDS, MATH, 3><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, PotFar{}, far_moments_of(P, d), a.out4);
-    } else if (a.fields & PSAMD_PROBE_FAR) {
-        if constexpr (MATH != 0)       // (far-monopole contexts are created only with lean arithmetic and world 1)
-            k_probe_pairs<FIELDS, MATH, 2><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, PotFar{}, far_moments_of(P, d), a.out4);
-    } else if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
-        if constexpr (MATH != 0) {     // (a context with all-pairs forces is created only with lean arithmetic; world 1: the own snapshot, cells by local == global index)
-            const PotFar far{d.snap_soa, d.cell_start, nullptr, (unsigned long long)P.sorted_cap, 1};
-            k_probe_pairs<FIELDS, MATH, 1><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, far, FarMoments{}, a.out4);
-        }
-    } else
-        k_probe_pairs<FIELDS, MATH, 0><<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, PotFar{}, FarMoments{}, a.out4);
+    const bool far_form = (a.fields & (PSAMD_PROBE_FAR | PSAMD_PROBE_QUADRUPOLE)) != 0, allp = !far_form && (P.flags & PSAMD_FLAG_ALL_PAIRS);
+    const auto launch = [&](auto kernel) {
+        kernel<<<nwg, PROBE_THREADS, 0, st>>>(P, d.cell_start, d.snap_soa, a.pos4, s.code, s.order, hdr, allp ? pot_far_of(P, d, false) : PotFar{},
+                                              far_form ? far_moments_of(P, d) : FarMoments{}, a.out4);
+    };
+    // (quadrupole contexts are far-monopole contexts, and the bit comes with PSAMD_PROBE_FAR; far-monopole and all-pairs contexts
+    // are created only with lean arithmetic, and probed on world 1 only: the own snapshot)
+    if constexpr (MATH != 0) {
+        if (a.fields & PSAMD_PROBE_QUADRUPOLE) return launch(k_probe_pairs<FIELDS, MATH, 3>);
+        if (a.fields & PSAMD_PROBE_FAR) return launch(k_probe_pairs<FIELDS, MATH, 2>);
+        if (allp) return launch(k_probe_pairs<FIELDS, MATH, 1>);
+    }
+    if (!far_form && !allp) launch(k_probe_pairs<FIELDS, MATH, 0>);
 }
 
 template <int FIELDS>

@@ -34,7 +34,7 @@ OF_FLAGS = {MONO: "flat", PYR: "pyramid", QUAD: "quadrupole"}          # (far_mo
 #   pot, mod    the bits of its own far form: psamd_potential's flags, psamd_probe's modifiers
 #   beyond      the next bit the potential / the probe does not know on such a context
 #   seed        a scene on G^3 cells is the cloud of seed + G ...
-#   bodies      ... of {G: bodies}
+#   bodies      ... of {G: bodies}; 24 and 36 are far_harness.DEEP's grids of four and five levels (test_gpu_far_rough.py)
 #   phi         the cases of phi_and_U_follow_the_model: {node id: (G, sign)}
 #   confined    (G, bodies) of the confined cloud; G None: the default context's 16^3
 #   probes      the cases of the probes' two checks: {node id: (G, FAST or 0)}
@@ -46,11 +46,12 @@ METHODS = {
         phi={"%d-%s-flat" % c: c for c in [(8, 1.0), (8, -1.0), (10, 1.0), (16, 1.0), (16, -1.0)]}, confined=(None, 3000),
         probes={"flat-8": (8, 0), "flat-16": (16, 0)}, capture=False, strangers=(0, ps.FLAG_ALL_PAIRS)),
     "pyramid": dict(
-        flags=PYR, pot=ps.POTENTIAL_FAR, mod=PFAR, beyond=(0x2, 0x8), seed=40, bodies={8: 6000, 10: 8000, 16: 16384},
+        flags=PYR, pot=ps.POTENTIAL_FAR, mod=PFAR, beyond=(0x2, 0x8), seed=40, bodies={8: 6000, 10: 8000, 16: 16384, 24: 13824, 36: 16000},
         phi={"%d-%s-pyramid" % c: c for c in [(8, 1.0), (8, -1.0), (10, 1.0), (16, 1.0), (16, -1.0)]}, confined=(None, 3000),
         probes={"pyramid-10": (10, 0), "pyramid-16": (16, 0)}, capture=False, strangers=(0, ps.FLAG_ALL_PAIRS)),
     "quadrupole": dict(
-        flags=QUAD, pot=PQ, mod=PFAR | PQUAD, beyond=(0x4, 0x10), seed=60, bodies={6: 3456, 8: 8192, 10: 16000, 16: 16384},
+        flags=QUAD, pot=PQ, mod=PFAR | PQUAD, beyond=(0x4, 0x10), seed=60,
+        bodies={6: 3456, 8: 8192, 10: 16000, 16: 16384, 24: 13824, 36: 16000},
         phi={"%d-%s" % c: c for c in [(6, 1.0), (6, -1.0), (8, 1.0), (8, -1.0), (10, 1.0), (10, -1.0)]}, confined=(8, 320),
         probes={"%d-%s" % (G, "fast" if fast else "exact"): (G, fast) for G in (8, 10, 16) for fast in (0, FAST)}, capture=True,
         strangers=(0, ps.FLAG_ALL_PAIRS, MONO, PYR)),

@@ -2,13 +2,15 @@
 test_gpu_far_pyramid.py, test_gpu_far_quadrupole.py; include/psamd.h: "long-range gravity", "a pyramid of monopoles", "quadrupoles on
 the pyramid"): the moment planes of every level bit for bit against the numpy model (far_model.py), no far cell (the cutoff
 context's bytes), the force records against the model's fp64 sums (1e-5 relative, the project's bar for sums of this kind), the
-far part alone, lanes of one wave under different parents, fast math, determinism and the refusals.
+far part alone, lanes of one wave under different parents, fast math, determinism and the refusals; and, for
+test_gpu_far_rough.py, the same against the model on rough frames (section 7: deep grids, collisions, clumps, repulsion).
 
 METHODS has one row per method.  Every check below is written once and takes the method; tests_of(method) makes the row's
 cases of them into test functions, which the method's suite takes into its namespace beside the tests only that method has.
 The three suites stay three files so that every test keeps the node id it has had.  The contexts, grids and clouds are
 far_harness.py's (8^3 cells of about 16 bodies unless noted)."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -16,7 +18,8 @@ import pytest
 import far_model as F
 import oracle_py as O
 import particlesystem_amd as ps
-from far_harness import GRID, INVALID_ARG, STATE, UNSUPPORTED, box_cloud, crowd_and_nursery, frame, index_of, lively, model_frame, status_of_create
+from far_harness import (DEEP, GRID, INVALID_ARG, STATE, UNSUPPORTED, box_cloud, crowd_and_nursery, frame, index_of, lively, model_frame,
+                         rough_bodies, rough_frame, status_of_create, waves_of)
 from util import assert_same_particles, oracle_cfg_from
 
 MONO, PYR, QUADRUPOLE = ps.FLAG_FAR_MONOPOLE, ps.FLAG_FAR_PYRAMID, ps.FLAG_FAR_QUADRUPOLE
@@ -64,6 +67,15 @@ METHODS = {
 
 # ---- 1. moments -------------------------------------------------------------------------------------------------------
 
+def planes_are_the_models(got, want, dims, width, what):
+    """every level's planes, every word"""
+    for l, (have, exp) in enumerate(zip(got, want)):
+        assert have.shape == exp.shape == (dims[l] ** 3, width)
+        bad = np.nonzero((have.view(np.uint32) != exp.view(np.uint32)).any(1))[0]
+        assert len(bad) == 0, ("level %d: %s differ from the model in %d cells, first %d: device %r model %r"
+                               % (l, what, len(bad), bad[0], have[bad[0]], exp[bad[0]]))
+
+
 def moments_of_every_level_equal_the_model_bit_for_bit(method, G, n, sign):
     """kids among the adults, unequal masses, one cell of kids only (its planes are all zeros); on 8^3 one cell with more
     particles than its list holds (only the first MAX_PARTICLES_PER_CELL count; the list is longer than 64, so the sums take a
@@ -95,20 +107,14 @@ def moments_of_every_level_equal_the_model_bit_for_bit(method, G, n, sign):
     assert np.array_equal(want_mom[0], F.level_moments(lists, xyz, w_eff, G, "flat")[0][0]) and cells.tobytes() == fr.mom[0].tobytes()
     assert not want_mom[0][kids_only].any() and want_mom[0][full, 3] != 0 and (want_mom[0][:, 3] != 0).sum() > 400
     assert len(fr.mom) == len(want_mom) == len(dims) and (fr.cen is None) == (want_cen is None)
-    for l, (have, exp) in enumerate(zip(fr.mom, want_mom)):
-        assert have.shape == exp.shape == (dims[l] ** 3, 4)
-        bad = np.nonzero((have.view(np.uint32) != exp.view(np.uint32)).any(1))[0]
-        assert len(bad) == 0, ("level %d: moments differ from the model in %d cells, first %d: device %r model %r"
-                               % (l, len(bad), bad[0], have[bad[0]], exp[bad[0]]))
-        assert (exp[:, 3] != 0).all() or l == 0
+    planes_are_the_models(fr.mom, want_mom, dims, 4, "moments")
+    for exp in want_mom:
+        assert (exp[:, 3] != 0).all() or exp is want_mom[0]
         assert ((exp[:, 3] > 0) == (sign > 0))[exp[:, 3] != 0].all()
     if want_cen is not None:
         assert not want_cen[0][kids_only].any() and want_cen[0][full].all()
-        for l, (have, exp) in enumerate(zip(fr.cen, want_cen)):
-            assert have.shape == exp.shape == (dims[l] ** 3, 6)
-            bad = np.nonzero((have.view(np.uint32) != exp.view(np.uint32)).any(1))[0]
-            assert len(bad) == 0, ("level %d: second moments differ from the model in %d cells, first %d: device %r model %r"
-                                   % (l, len(bad), bad[0], have[bad[0]], exp[bad[0]]))
+        planes_are_the_models(fr.cen, want_cen, dims, 6, "second moments")
+        for exp in want_cen:
             diag = exp[:, :3]
             assert (np.sign(diag[diag != 0]) == sign).all() and (diag != 0).any()      # (Caa has M's sign)
 
@@ -325,6 +331,169 @@ def refusals(method):
         assert download(b, 0, vp) == UNSUPPORTED
         b.calc_forces_apply()
         b.close()
+
+
+# ---- 7. the rough frames (test_gpu_far_rough.py) ------------------------------------------------------------------------------------
+# Deep grids, collisions at the default radius, clumps, repulsion: the frames are far_harness.rough_frame's, one per (cloud, grid,
+# flags), and the model's moments of each are formed once.  Every bar is REL.
+
+@functools.lru_cache(maxsize=None)
+def rough_moments(kind, G, method, sign=1.0):
+    s = rough_frame(kind, G, METHODS[method]["flags"], sign)
+    return F.level_moments(s.lists, s.xyz, s.w_eff, G, method)
+
+
+def rough_planes_are_the_models(method, s, moments, G):
+    dims = F.levels(G, method)
+    want_mom, want_cen = moments
+    assert len(s.mom) == len(want_mom) == len(dims) and (s.cen is None) == (want_cen is None)
+    planes_are_the_models(s.mom, want_mom, dims, 4, "moments")
+    if want_cen is not None:
+        assert len(s.cen) == len(dims)
+        planes_are_the_models(s.cen, want_cen, dims, 6, "second moments")
+    return dims, [int((m[:, 3] != 0).sum()) for m in want_mom]
+
+
+def deep_moments_equal_the_model_bit_for_bit(method, G):
+    """Four and five levels (far_harness.DEEP): far_level's padded offsets behind level 2, k_level_moments over three and four upper
+    levels, on 36^3 two odd levels below the top -- 9 and 5 -- whose last parents have one child an axis.  A level's planes read at
+    another level's offset, or a ragged parent that took a child of the next row, differ in whole cells"""
+    n, levels, cap = DEEP[G]
+    cfg = ps.default_config(**GRID[G])
+    assert ps.far_levels(cfg) == levels == F.levels_of(G) and ps.describe(cfg)[0].max_per_cell == cap
+    s = rough_frame("deep", G, METHODS[method]["flags"])
+    dims, filled = rough_planes_are_the_models(method, s, rough_moments("deep", G, method), G)
+    print("%s, %d bodies on %d^3 cells: levels %r, cells with mass %r, every word the model's" % (METHODS[method]["name"], n, G, dims, filled))
+    assert len(s.idx) == n and s.kid.sum() > 400 and all(filled) and (method == "flat" or filled[-1] == dims[-1] ** 3)
+
+
+def deep_sample(s, G):
+    """the served adults (positions in the sorted order) whose records are compared: every particle of the first and of the last
+    wave, of every wave that crosses an i3-layer boundary -- its box falls back to the full range on the other axes --, and 1024
+    more by a seeded choice; beside them the number of crossing waves"""
+    served = np.nonzero(~s.kid[s.idx])[0]
+    _, span = waves_of(F.cells_of(s.xyz[s.idx[served]], G), G)
+    wave = np.arange(len(served)) // 64
+    crossing = np.nonzero(span > 1)[0]
+    pick = (wave == 0) | (wave == wave[-1]) | np.isin(wave, crossing)
+    pick[np.random.default_rng(93).choice(len(served), 1024, replace=False)] = True
+    return served[pick], len(crossing)
+
+
+def sampled_records_against_the_model(method, s, G, kind, at):
+    """(the relative deviation of the records `at` -- positions in the sorted order -- from the model, of the stencil alone)"""
+    want = F.accel(s.lists, s.xyz, s.w_eff, G, 0.2, s.idx[at], method, rough_moments(kind, G, method))
+    near = F.accel(s.lists, s.xyz, s.w_eff, G, 0.2, s.idx[at], method, far=False)
+    return F.rel_dev(s.f[at, :3].astype(np.float64), want), F.rel_dev(near, want)
+
+
+def deep_force_records_follow_the_model(method, G, fast=0):
+    """The walk on four and five levels: far_box below the top with l = 1 and 2 (the shift by l + 1), far_blocks of levels that are
+    neither the top nor level 0, and the wave box's fall-back -- at one body a cell or fewer a wave's 64 served particles span a
+    whole layer, and the waves that cross to the next layer take the full range on the other two axes.  Flat on 20^3: 125 blocks,
+    so the sixteen parts are ragged, floor(125 p / 16).  The far part is nearly all of |a| here (the stencil alone is off by more
+    than 0.9 for the median particle), so a level left out or taken twice cannot hide.
+    Measured on an MI355X: see CHANGELOG.md"""
+    flags = METHODS[method]["flags"] | fast
+    s = rough_frame("deep", G, flags)
+    at, crossing = deep_sample(s, G)
+    rel, alone = sampled_records_against_the_model(method, s, G, "deep", at)
+    print("%s, %d bodies on %d^3 cells, flags %#x: %d records sampled, %d waves cross a layer; max relative deviation from the model "
+          "%.3g (the stencil alone: median %.3g)" % (METHODS[method]["name"], len(s.idx), G, flags, len(at), crossing, rel.max(), np.median(alone)))
+    assert (s.f[:, 3].view(np.int32) == 0).all() and not s.f[s.kid[s.idx], :3].any() and crossing >= G // 2
+    assert np.median(alone) > 0.9
+    assert rel.max() < REL
+    if fast:
+        again = rough_frame.__wrapped__("deep", G, flags)
+        assert again.f.tobytes() == s.f.tobytes()
+
+
+def collisions_at_the_default_radius(method):
+    """8192 bodies on 8^3 cells at collision_radius 0.4 (far_harness.COLLIDE_SEED), a far context and a cutoff context on the same
+    fill.  The served subset -- dense_gi, the r index of part_acc -- now skips collided adults as well as kids, and a collided adult
+    still exerts (w_eff looks at the age alone).  (a) the flag words are the cutoff context's, and the oracle's; (b) every record
+    that is not served, a kid's or a flagged one, is the cutoff context's 16 bytes; (c) every served record follows the model
+    with the collided adults' mass in; (d) the planes are the model's with that mass in, bit for bit; (e) the test can tell: at
+    least 200 adults collided, and the model without their mass is more than 10 * REL away from the device for more than half of
+    the served particles"""
+    G = 8
+    s, s0 = rough_frame("collide", G, METHODS[method]["flags"]), rough_frame("collide", G, 0)
+    assert np.array_equal(s.idx, s0.idx)
+    flag, kid = s.f[:, 3].view(np.int32), s.kid[s.idx]
+    assert flag.tobytes() == s0.f[:, 3].view(np.int32).tobytes() == oracle_flags_of_the_colliding_cloud(G).tobytes()      # (a)
+    served, collided = ~kid & (flag == 0), ~kid & (flag != 0)
+    assert s.f[~served].tobytes() == s0.f[~served].tobytes() and (flag[kid] == 0).all()      # (b)
+    assert collided.sum() >= 200 and kid.sum() > 400                      # (e)
+    rough_planes_are_the_models(method, s, rough_moments("collide", G, method), G)      # (d)
+    at = np.nonzero(served)[0]
+    want = F.accel(s.lists, s.xyz, s.w_eff, G, 0.2, s.idx[at], method, rough_moments("collide", G, method))
+    rel = F.rel_dev(s.f[at, :3].astype(np.float64), want)                 # (c)
+    less = s.w_eff.copy()
+    less[s.idx[collided]] = 0.0
+    without = F.accel(s.lists, s.xyz, less, G, 0.2, s.idx[at], method)
+    away = F.rel_dev(s.f[at, :3].astype(np.float64), without)
+    print("%s, %d bodies on %d^3 cells at the default collision radius: %d adults collided, %d served; max relative deviation from the "
+          "model %.3g; from the model without the collided adults' mass: median %.3g, %.3f of the served beyond 10 * REL"
+          % (METHODS[method]["name"], len(s.idx), G, collided.sum(), len(at), rel.max(), np.median(away), (away > 10 * REL).mean()))
+    assert rel.max() < REL
+    assert (away > 10 * REL).mean() > 0.5                                 # (e)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_flags_of_the_colliding_cloud(G):
+    """the flag words of the sorted order from the CPU oracle (the reference's own scan)"""
+    c, over = rough_bodies("collide", G)
+    o = O.System(oracle_cfg_from(ps.default_config(**{**GRID[G], **over})))
+    o.fill(c["xyz"], age=c["age"], fert_age=c["fert_age"], w=c["w"])
+    o.init_iframe(); o.build_grid()
+    f = np.zeros((o.sorted_count(), 4), np.float32)
+    o.calc_pairs(0, len(f), f)
+    o.close()
+    return f[:, 3].view(np.int32).copy()
+
+
+def clumps_follow_the_model_whole_and_in_the_far_part(method, kind):
+    """8^3 cells, six Gaussian clusters (far_harness.clustered(4096, 12): the fullest cell holds 44, the corners none) and
+    rough_cloud(), the same clusters with one cell filled to 65 adults and 36 adults alone in three layers.  Check 1: every whole
+    record against the model at REL -- the stencil's serial fp32 chain, the reference's own, is at most 5.3e-6 of |a| from the model's
+    fp64 stencil sum on the clusters and 2.9e-6 on the rough cloud (measured with the CPU oracle), the far part adds 1-2e-6.  Check
+    2: the far part alone, the record minus the cutoff context's record on the same fill, over the whole |a|: a wrong mask cannot
+    hide behind a large stencil sum.  rough_cloud(): some wave's box is a single cell (no lane falls back), and some wave spans
+    three or more i3 layers (every lane falls back on two axes): asserted from the sorted cells.  On the plain clusters no wave can
+    do either -- at most 44 bodies a cell, more than 64 served a layer"""
+    G = 8
+    s, s0 = rough_frame(kind, G, METHODS[method]["flags"]), rough_frame(kind, G, 0)
+    assert np.array_equal(s.idx, s0.idx) and (s.f[:, 3].view(np.int32) == 0).all()
+    at = np.nonzero(~s.kid[s.idx])[0]
+    cells, span = waves_of(F.cells_of(s.xyz[s.idx[at]], G), G)
+    if kind == "rough":
+        assert cells[0] == 1 and span.max() >= 3
+    whole = F.accel(s.lists, s.xyz, s.w_eff, G, 0.2, s.idx[at], method, rough_moments(kind, G, method))
+    far = whole - F.accel(s.lists, s.xyz, s.w_eff, G, 0.2, s.idx[at], method, far=False)
+    rel = F.rel_dev(s.f[at, :3].astype(np.float64), whole)
+    got = s.f[at, :3].astype(np.float64) - s0.f[at, :3].astype(np.float64)
+    part = np.linalg.norm(got - far, axis=1) / np.linalg.norm(whole, axis=1)
+    print("%s, %s cloud, %d bodies on %d^3 cells: a wave's cells %d..%d, layers up to %d; max relative deviation from the model %.3g; "
+          "the far part alone, over |a|: %.3g" % (METHODS[method]["name"], kind, len(s.idx), G, cells.min(), cells.max(), span.max(), rel.max(), part.max()))
+    assert np.abs(far).max() > 0 and rel.max() < REL
+    assert part.max() < REL
+
+
+def repulsion_in_the_force_records(method, G):
+    """force_sign = -1 on 8^3 and 10^3 cells, about 16 bodies a cell: the records against the model with w_eff = -w -- the sign rides
+    on the moments' M and, for quadrupoles, on C -- and every served record points away from the model's attractive record"""
+    s = rough_frame("repel", G, METHODS[method]["flags"], -1.0)
+    at = np.nonzero(~s.kid[s.idx])[0]
+    assert (s.w_eff[~s.kid] < 0).all() and (s.f[:, 3].view(np.int32) == 0).all()
+    want = F.accel(s.lists, s.xyz, s.w_eff, G, 0.2, s.idx[at], method, rough_moments("repel", G, method, -1.0))
+    pull = F.accel(s.lists, s.xyz, -s.w_eff, G, 0.2, s.idx[at], method)
+    got = s.f[at, :3].astype(np.float64)
+    rel = F.rel_dev(got, want)
+    cos = (got * pull).sum(1) / (np.linalg.norm(got, axis=1) * np.linalg.norm(pull, axis=1))
+    print("%s, repulsion, %d bodies on %d^3 cells: max relative deviation from the model %.3g; cosine to the attractive record at most %.6f"
+          % (METHODS[method]["name"], len(s.idx), G, rel.max(), cos.max()))
+    assert rel.max() < REL
+    assert ((got * pull).sum(1) < 0).all()
 
 
 # ---- the cases of a row as tests ------------------------------------------------------------------------------------------------

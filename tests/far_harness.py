@@ -20,12 +20,20 @@ from util import cloud, hip_runtime  # noqa: F401  (hip_runtime: for the suites 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # the small contexts hold max_particles_num=16384; the grids are 4^3 (one level), 6^3 (levels 6, 3), 8^3 (8, 4), 10^3 (10, 5, 3: an odd
-# level with a ragged parent) and 16^3 (16, 8, 4)
+# level with a ragged parent) and 16^3 (16, 8, 4); the deep grids (DEEP) are 20^3, 24^3, 32^3 and 36^3
 GRID = {4: dict(max_particles_num=16384, chunk_factor=1, chunk_dim=4),
         6: dict(max_particles_num=16384, chunk_factor=2, chunk_dim=3),
         8: dict(max_particles_num=16384, chunk_factor=2, chunk_dim=4),
         10: dict(max_particles_num=16384, chunk_factor=2, chunk_dim=5),
-        16: dict(max_particles_num=16384, chunk_factor=4, chunk_dim=4, x_factor=8)}      # (x_factor: lists of 40, for 4 a cell in the mean)
+        16: dict(max_particles_num=16384, chunk_factor=4, chunk_dim=4, x_factor=8),      # (x_factor: lists of 40, for 4 a cell in the mean)
+        20: dict(max_particles_num=16384, chunk_factor=5, chunk_dim=4, x_factor=8),
+        24: dict(max_particles_num=16384, chunk_factor=6, chunk_dim=4, x_factor=8),
+        32: dict(max_particles_num=16384, chunk_factor=8, chunk_dim=4, x_factor=8),
+        36: dict(max_particles_num=16384, chunk_factor=9, chunk_dim=4, x_factor=8)}
+# the deep grids, four and five levels: G -> (bodies of its uniform cloud, the levels, the lists' cap).  20^3: an odd level (5) with a
+# ragged parent, and flat 125 blocks over 16 parts; 24^3: the grid of the benchmark's cloud at N = 2^22; 36^3: two odd levels below the
+# top (9 and 5).  About one body a cell or fewer: a wave's 64 served particles span a layer of cells or more
+DEEP = {20: (8000, [20, 10, 5, 3], 24), 24: (13824, [24, 12, 6, 3], 16), 32: (16384, [32, 16, 8, 4], 8), 36: (16000, [36, 18, 9, 5, 3], 8)}
 INVALID_ARG, STATE, UNSUPPORTED = 1, 8, 9
 
 DEV = torch.device("cuda", 0)
@@ -162,6 +170,91 @@ def body_cloud(n, seed, G):
     age = rng.uniform(15 / 7, 7.5, n).astype(np.float32)
     age[::17] = 0.5
     return dict(xyz=box_cloud(n, seed, G), age=age, w=rng.uniform(20.0, 100.0, n).astype(np.float32), fert_age=np.float32(1e6))
+
+
+# ---- the rough frames (test_gpu_far_rough.py): deep grids, collisions, clumps, repulsion ------------------------------------------------
+
+RoughFrame = collections.namedtuple("RoughFrame", "f idx lists mom cen xyz w w_eff kid")
+
+
+def rough_cloud():
+    """8^3 cells: clustered(4096, 12) without its bodies in cell 0 and in the layers i3 >= 5, then 65 adults in cell 0 -- the first
+    cell of the sorted order, one short of its list's cap: the first wave's 64 served particles are in ONE cell -- and 36 adults
+    spread over the layers i3 = 5, 6, 7: fewer than 64 behind layer 4, so the last wave spans three layers or more.
+    (xyz, age)"""
+    G = 8
+    rng = np.random.default_rng(91)
+    xyz = clustered(4096, 12, G * 2.5 * 0.9995)
+    cell = F.cells_of(xyz, G)
+    xyz = xyz[(cell != 0) & (cell // (G * G) < 5)]
+    age = rng.uniform(15 / 7, 7.5, len(xyz)).astype(np.float32)
+    age[::17] = 0.5
+    crowd = (low_corner(0, 0, 0, G) + rng.uniform(0.05, 4.95, (65, 3))).astype(np.float32)
+    haze = rng.uniform(-19.9, 19.9, (36, 3))
+    haze[:, 2] = rng.uniform(-19.9, -5.1, 36)                             # (i3 ~ -z: layers 5..7)
+    xyz = np.concatenate([crowd, xyz, haze.astype(np.float32)])
+    age = np.concatenate([np.full(65, 3.0, np.float32), age, np.full(36, 3.0, np.float32)])
+    layer = F.cells_of(xyz, G) // (G * G)
+    assert (F.cells_of(crowd, G) == 0).all() and (layer[-36:] >= 5).all() and (layer >= 5).sum() == 36
+    return xyz, age
+
+
+@functools.lru_cache(maxsize=None)
+def rough_bodies(kind, G):
+    """(the fill of a rough frame, what its configuration has beside GRID[G]).  Every cloud has unequal masses and kids
+    (age[::17] = 0.5) among the adults.
+    deep     DEEP's uniform cloud on a deep grid
+    collide  lively's cloud of 8192 on 8^3 cells at the DEFAULT collision radius, 0.4
+    clump    clustered(4096, 12) on 8^3 cells
+    rough    rough_cloud() on 8^3 cells
+    repel    a uniform cloud, about 16 bodies a cell (for force_sign = -1)"""
+    over = dict(collision_radius=1e-6)
+    if kind == "collide":
+        c, over = lively(8192, COLLIDE_SEED, G), {}
+        c["age"] = np.random.default_rng(COLLIDE_SEED).uniform(15 / 7, 7.5, 8192).astype(np.float32)      # (adults: the more to collide)
+        c["age"][::17] = 0.5
+        return c, over
+    rng = np.random.default_rng(92 + G)
+    if kind == "deep":
+        return body_cloud(DEEP[G][0], 90 + G, G), over
+    if kind == "repel":
+        return body_cloud(16 * G ** 3, 95 + G, G), over
+    xyz, age = rough_cloud() if kind == "rough" else (clustered(4096, 12, G * 2.5 * 0.9995), None)
+    if age is None:
+        age = rng.uniform(15 / 7, 7.5, len(xyz)).astype(np.float32)
+        age[::17] = 0.5
+    return dict(xyz=xyz, age=age, w=rng.uniform(20.0, 100.0, len(xyz)).astype(np.float32), fert_age=np.float32(1e6)), over
+
+
+COLLIDE_SEED = 65          # (chosen with the oracle on the CPU: 260 of the 7710 adults collide)
+
+
+@functools.lru_cache(maxsize=None)
+def rough_frame(kind, G, flags, sign=1.0):
+    """one frame of rough_bodies(kind, G) on a context of `flags`: the records in sorted order, their index into the fill, the lists
+    as indices into the fill, the planes of every level; positions, masses, w_eff (force_sign folded in, kids 0; a collided adult
+    keeps its mass) and the kid mask in the order of the fill.  Computed once, never changed."""
+    c, over = rough_bodies(kind, G)
+    g = ps.ParticleSystem(ps.default_config(flags=flags, force_sign=sign, **{**GRID[G], **over}))
+    assert g.sizes.grid_dim == G
+    ids = g.fill_particles(**c)
+    fr = frame(g)
+    where = index_of(g, ids)
+    assert len(fr.order) == len(ids) and g.counters["cell_overflow_kills"] == 0
+    g.close()
+    kid = c["age"] < 1.5
+    w_eff = np.where(kid, np.float32(0.0), np.float32(sign) * c["w"]).astype(np.float32)
+    return RoughFrame(fr.f, where[fr.order], [where[l] for l in fr.lists], fr.mom, fr.cen, c["xyz"], c["w"], w_eff, kid)
+
+
+def waves_of(cells, G):
+    """the dense tasks of the force walk -- the served particles' cells in sorted order, 64 to a wave --: per wave (the number of
+    cells, the i3 layers from its lowest to its highest cell)"""
+    assert (np.diff(cells) >= 0).all()
+    first = np.arange(0, len(cells), 64)
+    layer = cells // (G * G)
+    return (np.array([len(np.unique(cells[k:k + 64])) for k in first]),
+            np.maximum.reduceat(layer, first) - np.minimum.reduceat(layer, first) + 1)
 
 
 # ---- the field services' results (psamd_potential, psamd_probe) ----------------------------------------------------------------------

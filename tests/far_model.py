@@ -123,9 +123,14 @@ def coverage(c, G, method, members=None):
     n[stencil_cells(c, G)] += 1
     cube = n.reshape(G, G, G)                                         # [i3, i1, i2]; i >> lvl == j: i in [j << lvl, (j + 1) << lvl)
     dims = levels(G, method)
-    for lvl, J in (far_set(c, G, method) if members is None else members):
-        j1, j2, j3 = coords(J, dims[lvl])
-        cube[j3 << lvl:(j3 + 1) << lvl, j1 << lvl:(j1 + 1) << lvl, j2 << lvl:(j2 + 1) << lvl] += 1
+    members = far_set(c, G, method) if members is None else members
+    for lvl, Gl in enumerate(dims):                                   # a level at a time: its members counted on the level's own cube,
+        J = np.array([j for l, j in members if l == lvl], np.int64)      # every level cell then spread over the cells under it
+        if len(J):
+            level = np.bincount(J, minlength=Gl ** 3).reshape(Gl, Gl, Gl)
+            for axis in range(3):
+                level = np.repeat(level, 1 << lvl, axis=axis)
+            cube += level[:G, :G, :G]
     return n
 
 

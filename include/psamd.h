@@ -318,6 +318,39 @@ typedef struct psamd_probe_spec {
     psamd_probe_result *result_dev;   /* optional out (device), 8-byte aligned; NULL: the context's own record only */
 } psamd_probe_spec;           /* 56 bytes */
 
+/* psamd_update: which words of a particle an entry carries (see "changing particles in place" below). */
+#define PSAMD_UPDATE_VEL   0x1u    /* vel4[k].xyz -> the particle's vx, vy, vz                          */
+#define PSAMD_UPDATE_AGE   0x2u    /* vel4[k].w   -> age                                                */
+#define PSAMD_UPDATE_MASS  0x4u    /* w[k]        -> w (pos4.w; x, y, z keep their bits)                */
+#define PSAMD_UPDATE_FERT  0x8u    /* fert_age[k] -> fertility age (acc4.w; ax, ay, az keep their bits) */
+#define PSAMD_UPDATE_ADD          0x100u  /* modifier of VEL: v = RN(v + vel4[k]) per component, fp32, one rounding, no clamp (a kick) */
+#define PSAMD_UPDATE_EXPORT_ORDER 0x200u  /* entry k belongs to the k-th live owned particle in ascending slot id; ids must be NULL    */
+
+/* What psamd_update did. */
+typedef struct psamd_update_result {
+    int64_t done;             /* n: entries examined                                                          */
+    int64_t updated;          /* outcome 0                                                                    */
+    int64_t not_live, foreign, invalid, duplicate;   /* outcomes 1, 2, 3, 4                                   */
+} psamd_update_result;        /* 48 bytes */
+
+/* What psamd_update reads and where it writes (device pointers; none of them inside the context's own arrays). */
+typedef struct psamd_update_spec {
+    uint32_t fields;          /* PSAMD_UPDATE_VEL | _AGE | _MASS | _FERT, at least one; PSAMD_UPDATE_ADD and
+                                 PSAMD_UPDATE_EXPORT_ORDER beside them                                         */
+    int32_t  reserved;        /* 0                                                                            */
+    const int32_t *ids;       /* by id: int32[max_count] slot ids, 4-byte aligned, required if max_count > 0;
+                                 NULL with PSAMD_UPDATE_EXPORT_ORDER                                          */
+    const void    *vel4;      /* float4[max_count] vx, vy, vz, age, 16-byte aligned; required with VEL or AGE
+                                 (if max_count > 0); ignored otherwise                                        */
+    const float   *w;         /* float[max_count]; required with MASS, ignored otherwise                      */
+    const float   *fert_age;  /* float[max_count]; required with FERT, ignored otherwise                      */
+    int64_t  max_count;       /* entries the arrays hold; sizes the launches; 0 <= max_count < 2^31           */
+    const int64_t *count_dev; /* optional device int64: n = clamp(*count_dev, 0, max_count), read by the
+                                 kernels; NULL: n = max_count                                                 */
+    int32_t *outcome_dev;     /* optional out, int32[max_count]: every entry's outcome code                   */
+    psamd_update_result *result_dev;   /* optional out (device), 8-byte aligned; NULL: the context's own record only */
+} psamd_update_spec;          /* 72 bytes */
+
 typedef struct psamd_ctx psamd_ctx;
 
 /* ---- lifetime ------------------------------------------------------------ */
@@ -651,6 +684,82 @@ int psamd_inject_result_get(psamd_ctx *ctx, psamd_inject_result *out);
  * psamd_remove_result_get: the last remove's record, into host memory; waits for the context's stream. */
 int psamd_remove(psamd_ctx *ctx, const psamd_remove_spec *spec);
 int psamd_remove_result_get(psamd_ctx *ctx, psamd_remove_result *out);
+
+/* ---- changing particles in place ---------------------------------------------- */
+/* psamd_update: new words for particles that stay where they are -- velocity (set, or added: a kick), age, mass,
+ * fertility age -- at the point of the stream where the call is made.  It is what hands a caller's own force to the
+ * particles without leaving the device: psamd_probe (or an external potential, a thermostat, a push from a UI) gives the
+ * caller a field, the caller forms dv, PSAMD_UPDATE_VEL | PSAMD_UPDATE_ADD applies it.  Positions are not served: a
+ * particle that changes its cell is a psamd_remove plus a psamd_inject.  Not in the reference; a context that is never
+ * updated computes what it always did.
+ *
+ * What is written.  Only the words the fields name, with the k-th entry's values: PSAMD_UPDATE_VEL vx, vy, vz = vel4[k].xyz;
+ * PSAMD_UPDATE_AGE age = vel4[k].w; PSAMD_UPDATE_MASS w = w[k]; PSAMD_UPDATE_FERT fertility age = fert_age[k].  Every other
+ * word of the slot keeps its bits (x, y, z beside w; ax, ay, az beside the fertility age; cell, flags), and so does every
+ * other slot.  Values are written as given, bit for bit: NaNs with their payloads, infinities, -0, denormals.  With
+ * PSAMD_UPDATE_ADD (a modifier of VEL; without VEL it is PSAMD_ERR_INVALID_ARG) each velocity component becomes
+ * RN(v + vel4[k].c): one fp32 addition, no fused operation, no clamp -- the next step's MAX_V clamp acts as it always does.
+ * Only the arrays the fields name are read, and of the context's arrays only those are written: SET stores without
+ * loading, a kick loads and stores vel4.  T_DATA mirror rows, the queues and their QUEUE_INFO records, the counters and the
+ * host's bound of the live count are not touched.  The caller's arrays must not lie inside the context's own
+ * (psamd_device_view_get).
+ *
+ * By id (without PSAMD_UPDATE_EXPORT_ORDER): the entries [0, n) of `ids` are examined in entry order.  Every entry gets
+ * an outcome, written to outcome_dev if given (entries at or past n are not touched):
+ *     0  updated
+ *     1  the slot is not live (0 <= cell < num_cells, what psamd_live_count counts)
+ *     2  a valid id whose slot this context does not own
+ *     3  an id outside [0, container_size)
+ *     4  a later occurrence of an id this call has already updated: nothing is written for it -- THE FIRST OCCURRENCE
+ *        WINS, whatever the fields (also with ADD: a particle is kicked once per call)
+ * This is psamd_remove's claim rule on psamd_remove's claim words; a call leaves them as it found them, so updates and
+ * removes follow one another in any order.
+ *
+ * By export order (PSAMD_UPDATE_EXPORT_ORDER; ids must be NULL): entry k belongs to the k-th live owned particle in
+ * ascending global slot id -- the pairing of psamd_export_live's arrays, of psamd_potential's phi[] and so of a
+ * psamd_probe on an export's pos4.  Entries at or past the live count get outcome 1 and count in `not_live`; live
+ * particles past n are left alone; foreign, invalid and duplicate are 0.  The caller keeps the live set unchanged between
+ * the export and the update (no step, inject, remove, upload or restore in between).  This is the streaming form: the
+ * launches cover every owned slot, the entries are read and the slots written in contiguous runs.
+ *
+ * The frame.  The snapshot psamd_build_grid leaves holds x, y, z, w_eff and age; it holds no velocity and no fertility
+ * age, and the pair stage reads neither.  So a call whose fields are within VEL | FERT (with or without ADD) leaves the
+ * frame as it is: it keeps no host bookkeeping, allocates nothing in steady use, may be captured into a graph, and is
+ * valid at every point but one (below).  Placed between psamd_calc_forces_pairs and psamd_calc_forces_apply (or
+ * psamd_slab_pairs and psamd_slab_apply) the velocity it leaves is the one this step integrates, and the step's bytes are
+ * those of the same update made before psamd_build_grid.  A call with MASS or AGE ends a frame in progress exactly as
+ * psamd_remove does: psamd_calc_forces then refuses with PSAMD_ERR_STATE until psamd_build_grid has run again, and such a
+ * call is refused while the context's stream is being captured (PSAMD_ERR_STATE).  Between psamd_slab_apply and
+ * psamd_slab_finish every form returns PSAMD_ERR_STATE and the context stays usable: the departing particles are staged
+ * there, and an update of the slot they leave would be lost.  psamd_step cannot be interposed, as for the other services.
+ *
+ * Slabs (world > 1).  By id every rank is given all entries and updates its own slots: exactly one rank answers 0 for a
+ * live id, the others 2; the ranks' results add; the union of the ranks' states is the state of one context given the same
+ * call.  By export order a rank's entries are its own export's.
+ *
+ * Everything is enqueued on the context's stream (psamd_get_stream): nothing waits and nothing is read back.  By id, scratch
+ * per entry grows only when max_count exceeds every earlier psamd_update's -- that growth may wait for the device, and while
+ * the stream is being captured it is refused with PSAMD_ERR_STATE; by export order there is none.  A graph that holds a
+ * captured update by id is void once a later psamd_update by id has grown that scratch (the graph holds the old address):
+ * make the largest call first, or capture again.  No other service touches it.
+ * *result_dev and the context's own record are written by the time the stream reaches the end of the call.  The call returns
+ * PSAMD_OK once the work is enqueued; only the result record reports what happened.
+ *
+ * Cost on an MI355X at N = 2^20 (profiles/update_cost.txt; host clock around the call plus psamd_synchronize), a kick
+ * (VEL | ADD): 52 us by id for 65 536 live ids, 47 us by export order for all 321 670 live particles, beside 60 us of
+ * psamd_export_live of VEL on the same context; the host route (download_particles, the addition in numpy,
+ * upload_particles) takes 27.0 ms there.
+ *
+ * PSAMD_ERR_INVALID_ARG: a NULL context or spec, no field bit, an unknown bit, ADD without VEL, reserved != 0, max_count
+ * outside [0, 2^31), by id ids NULL with max_count > 0, by export order ids not NULL, an array the fields name NULL with
+ * max_count > 0, vel4 not 16-byte aligned, ids / w / fert_age / outcome_dev not 4-byte aligned, count_dev or result_dev not
+ * 8-byte aligned.  PSAMD_ERR_STATE: the context is wedged, the call falls between psamd_slab_apply and psamd_slab_finish, or
+ * the stream is being captured and the call has MASS or AGE or needs its scratch to grow.  max_count == 0 writes a zero
+ * result and launches nothing else.
+ *
+ * psamd_update_result_get: the last update's record, into host memory; waits for the context's stream. */
+int psamd_update(psamd_ctx *ctx, const psamd_update_spec *spec);
+int psamd_update_result_get(psamd_ctx *ctx, psamd_update_result *out);
 
 /* ---- energy ------------------------------------------------------------------ */
 /* The potential of every particle in the frame's cell lists, and the potential energy, formed on the device from what

@@ -185,6 +185,31 @@ def merge_remove(results):
     return {n: sum(int(r[n]) for r in results) for n, _ in RemoveResult._fields_}
 
 
+# psamd_update: the words an entry carries, the two modifiers, and the outcome codes of the entries
+UPDATE_VEL, UPDATE_AGE, UPDATE_MASS, UPDATE_FERT = 0x1, 0x2, 0x4, 0x8
+UPDATE_ADD, UPDATE_EXPORT_ORDER = 0x100, 0x200
+UPDATED, UPDATE_NOT_LIVE, UPDATE_FOREIGN, UPDATE_INVALID, UPDATE_DUPLICATE = 0, 1, 2, 3, 4
+
+
+class UpdateResult(_Record):
+    """psamd_update_result: what psamd_update did."""
+    _fields_ = [(n, C.c_int64) for n in ("done", "updated", "not_live", "foreign", "invalid", "duplicate")]
+
+
+class Update(C.Structure):
+    """psamd_update_spec: what psamd_update reads and where it writes (device pointers)."""
+    _fields_ = [("fields", C.c_uint32), ("reserved", C.c_int32), ("ids", C.c_void_p), ("vel4", C.c_void_p), ("w", C.c_void_p),
+                ("fert_age", C.c_void_p), ("max_count", C.c_int64), ("count_dev", C.c_void_p), ("outcome_dev", C.c_void_p),
+                ("result_dev", C.c_void_p)]
+
+
+def merge_update(results):
+    """The result of an update by id on a system from its ranks' (dicts of update() / update_result()): every count adds
+    (each rank is given all entries, so `done` adds up to world * n)."""
+    results = list(results)
+    return {n: sum(int(r[n]) for r in results) for n, _ in UpdateResult._fields_}
+
+
 class PotentialResult(_Record):
     """psamd_potential_result: counts, the potential energy U and the extrema of phi."""
     _fields_ = [("listed", C.c_int64), ("nonfinite", C.c_int64), ("potential", C.c_double),
@@ -352,6 +377,8 @@ ABI = [
     ("psamd_inject_result_get", C.c_int, [_vp, C.POINTER(InjectResult)]),
     ("psamd_remove", C.c_int, [_vp, C.POINTER(Remove)]),
     ("psamd_remove_result_get", C.c_int, [_vp, C.POINTER(RemoveResult)]),
+    ("psamd_update", C.c_int, [_vp, C.POINTER(Update)]),
+    ("psamd_update_result_get", C.c_int, [_vp, C.POINTER(UpdateResult)]),
     ("psamd_potential", C.c_int, [_vp, C.POINTER(Potential)]),
     ("psamd_potential_result_get", C.c_int, [_vp, C.POINTER(PotentialResult)]),
     ("psamd_download_potential", C.c_int, [_vp, _vp, _i64, C.POINTER(PotentialResult)]),
@@ -836,6 +863,54 @@ class ParticleSystem:
         """psamd_remove_result_get: the last remove's record as a dict"""
         r = RemoveResult()
         self._ck(self.lib.psamd_remove_result_get(self.h, C.byref(r)))
+        return r.to_dict()
+
+    # ---- changing particles in place (include/psamd.h) --------------------------
+    def update(self, ids=None, vel4=None, w=None, fert_age=None, age=False, add=False, count=None, outcome=False, *, fields=None):
+        """psamd_update from torch device tensors.  ids: an int32 [m] tensor of slot ids, or None: export order -- entry k
+        belongs to the k-th live particle of export_live().  The words come from the arrays that are given: vel4 float32
+        [m, 4] sets vx, vy, vz (add=True: adds to them, a kick) and, with age=True, the age from its fourth column; w float32
+        [m] the mass; fert_age float32 [m] the fertility age.  fields: the PSAMD_UPDATE_* bits themselves, instead of what the
+        arrays imply (UPDATE_AGE alone reads vel4's fourth column only; the order bit still follows ids).  count: None (all m
+        entries) or a 1-element int64 device tensor that work on torch's current stream may write just before.  Returns the
+        result record as a dict (done, updated, not_live, foreign, invalid, duplicate) and, with outcome=True, "outcome": an
+        int32 device tensor of m entries (UPDATED .. UPDATE_DUPLICATE; -1 at and past the count).  Waits for the context's
+        stream.  torch must have been imported before the library was loaded."""
+        import torch
+        dev = torch.device("cuda", int(self.cfg.device))
+        given = [t for t in (ids, vel4, w, fert_age) if t is not None]
+        assert given, "update: no array"
+        m = int(given[0].shape[0])
+
+        def ptr(t, dtype, shape):
+            if t is None:
+                return None
+            assert t.is_cuda and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(), "update: bad tensor"
+            return t.data_ptr() if m > 0 else None
+        if fields is None:
+            fields = ((UPDATE_VEL if vel4 is not None else 0) | (UPDATE_AGE if age else 0) | (UPDATE_ADD if add else 0) |
+                      (UPDATE_MASS if w is not None else 0) | (UPDATE_FERT if fert_age is not None else 0))
+        spec = Update(fields=int(fields) & ~UPDATE_EXPORT_ORDER | (UPDATE_EXPORT_ORDER if ids is None else 0), max_count=m)
+        spec.ids = ptr(ids, torch.int32, (m,))
+        spec.vel4 = ptr(vel4, torch.float32, (m, 4))
+        spec.w = ptr(w, torch.float32, (m,))
+        spec.fert_age = ptr(fert_age, torch.float32, (m,))
+        if count is not None:
+            assert count.dtype == torch.int64 and tuple(count.shape) == (1,) and count.is_cuda, "update: bad count tensor"
+            spec.count_dev = count.data_ptr()
+        out = torch.full((max(m, 1),), -1, dtype=torch.int32, device=dev) if outcome else None
+        spec.outcome_dev = None if out is None else out.data_ptr()
+        with self._on_stream(dev):
+            self._ck(self.lib.psamd_update(self.h, C.byref(spec)))
+        res = self.update_result()
+        if out is not None:
+            res["outcome"] = out[:m]
+        return res
+
+    def update_result(self):
+        """psamd_update_result_get: the last update's record as a dict"""
+        r = UpdateResult()
+        self._ck(self.lib.psamd_update_result_get(self.h, C.byref(r)))
         return r.to_dict()
 
     # ---- energy (include/psamd.h) -----------------------------------------------

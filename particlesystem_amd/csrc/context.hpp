@@ -75,6 +75,7 @@ struct psamd_ctx {
     InjectScratch inj{};              // its scratch: inj.e grows with max_count, the rest is fixed
     RemoveScratch rem{};              // psamd_remove's scratch: rem.e grows with max_count, the rest is fixed
     ProbeScratch prb{};               // psamd_probe's scratch: code / order grow with max_count, the counters are fixed
+    UpdateScratch upd{};              // psamd_update's scratch: code grows with max_count, the rest is fixed (by id it borrows rem.claim)
     // timing
     int timing = 0;                    // 0 off, 1 pair pass / apply / life cycle, 2 every stage
     int timing_period = 1;             // events are recorded on every timing_period-th step since set_timing

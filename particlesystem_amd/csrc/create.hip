@@ -385,6 +385,11 @@ static int alloc_step_arrays(psamd_ctx *c)
             PS_HIP(c, hipMemcpy(d.far_plan, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
         }
     }
+    // psamd_update's fixed scratch and result record (behind everything older, which stays where it was)
+    PS_HIP(c, dev_alloc(c, &c->upd.hdr, UPDATE_HDR_WORDS));
+    PS_HIP(c, dev_alloc(c, &c->upd.tile_live, (size_t)slot_tiles(P.slots_total)));
+    PS_HIP(c, dev_alloc(c, &c->upd.own, 1));
+    PS_HIP(c, hipMemsetAsync(c->upd.own, 0, sizeof(psamd_update_result), c->stream));
     return PSAMD_OK;
 }
 
@@ -593,7 +598,7 @@ int psamd_destroy(psamd_ctx *c)
     if (c->staging) (void)hipFree(c->staging);
     for (const EntryScratch &e : {c->inj.e, c->rem.e})
         for (void *p : {(void *)e.ent, (void *)e.tcount, (void *)e.tile_out}) if (p) (void)hipFree(p);
-    for (void *p : {(void *)c->prb.code, (void *)c->prb.order}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->prb.code, (void *)c->prb.order, (void *)c->upd.code}) if (p) (void)hipFree(p);
     if (c->h_fs) (void)hipHostFree(c->h_fs);
     if (c->ev_made) for (auto &set : c->ev) for (auto &e : set) (void)hipEventDestroy(e);
     if (c->d.ev_fork) (void)hipEventDestroy(c->d.ev_fork);

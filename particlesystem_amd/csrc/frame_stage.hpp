@@ -83,5 +83,7 @@ constexpr bool pairs_done(Stage s) { return ((bit(ST_PAIRS) | bit(ST_SLAB_PAIRS)
 constexpr bool interior_passed(Stage s) { return s == ST_SLAB_INTERIOR; }
 // potential and probe: a frame is built, its particles have not moved, and -- a slab of several -- the halos are in
 constexpr bool field_window(Stage s, int world) { return world > 1 ? s == ST_SLAB_PAIRS : built(s) && s != ST_SLAB_APPLIED; }
+// update: a slot still holds the particle that the caller means -- between slab_apply and slab_finish the departing ones are staged
+constexpr bool update_window(Stage s) { return s != ST_SLAB_APPLIED; }
 
 }  // namespace psamd

@@ -74,6 +74,28 @@ struct RemoveScratch {
     psamd_remove_result *own;    // the context's own result record (psamd_remove_result_get)
 };
 
+// psamd_update (update.hip): the caller's arrays and the scratch.  By id the claims are psamd_remove's claim words (the two
+// services are ordered by the stream and each leaves the claims as it found them); code grows with a call's max_count (the
+// host: grow_update_scratch, services.hip), the rest is sized at creation
+constexpr int UPDATE_HDR_WORDS = 5;
+struct UpdateArgs {
+    uint32_t fields;
+    const int *ids;
+    const float4 *vel4;
+    const float *w, *fert_age;
+    int64_t max_count;
+    const int64_t *count_dev;
+    int *outcome;
+    psamd_update_result *result;
+};
+struct UpdateScratch {
+    int *code;        // [cap] by id, per entry: the storage index of its slot, or -1 - outcome
+    int64_t cap;      // entries there is room for
+    int *hdr;         // [UPDATE_HDR_WORDS] by id: the entries with the outcomes 0 .. 4
+    int *tile_live;   // [tiles of slots] by export order: the tile's live slots
+    psamd_update_result *own;    // the context's own result record (psamd_update_result_get)
+};
+
 // psamd_potential (potential.hip): the sorted order of the own cells in tiles of POT_TILE (tile t goes with tile t of the
 // owned slots); per tile of the sorted order the partials of U (fp64), of phi's extrema and of the counts
 constexpr int POT_TILE = SLOT_TILE;
@@ -317,5 +339,12 @@ hipError_t launch_remove_ids(hipStream_t st, const DevParams &P, const SegLayout
                              const RemoveScratch &s);
 hipError_t launch_remove_box(hipStream_t st, const DevParams &P, const SegLayout &S, const DeviceState &d, int nrec, const float lo[3],
                              const float hi[3], bool outside, psamd_remove_result *result, const RemoveScratch &s);
+
+// psamd_update by id (max_count > 0; claim: psamd_remove's claim words): the first
+// occurrences' claims, the writes and outcomes, the result record; by export order: the tiles' live counts, then the writes,
+// the outcomes and the result record
+hipError_t launch_update_ids(hipStream_t st, const DevParams &P, const DeviceState &d, const UpdateArgs &a, const UpdateScratch &s,
+                             int *claim);
+hipError_t launch_update_order(hipStream_t st, const DevParams &P, const DeviceState &d, const UpdateArgs &a, const UpdateScratch &s);
 
 }  // namespace psamd

@@ -1,5 +1,5 @@
 // multisplit.hpp -- the deterministic stable multisplit of a tile of entries by queue record, shared by inject.hip and
-// remove.hip (device-inline only).
+// remove.hip, and the entry front they share with update.hip (device-inline only).
 //
 // A tile of ENTRY_TILE = SPLIT_THREADS * SPLIT_GROUPS entries is ranked by one workgroup of 16 waves; wave w holds the
 // entries [(w * SPLIT_GROUPS + g) * 64, + 64), g = 0 .. SPLIT_GROUPS - 1, one to a lane.  An entry's key is its record (>= 0), or a negative
@@ -28,6 +28,17 @@ __device__ __forceinline__ int entry_count(const int64_t *count_dev, int64_t max
     return (int)(v < 0 ? 0 : v > max_count ? max_count : v);
 }
 __device__ __forceinline__ int entry_tiles(int n) { return (int)(((int64_t)n + ENTRY_TILE - 1) / ENTRY_TILE); }
+
+// An entry that names a slot by its id (remove.hip, update.hip): the storage index of the slot if the entry can act on it
+// (valid id, owned, live now), else -1 - outcome.  The three outcomes are the same numbers in both services' headers.
+enum { ID_NOT_LIVE = 1, ID_FOREIGN = 2, ID_INVALID = 3 };
+__device__ __forceinline__ int remove_classify(const DevParams &P, int id, const int *__restrict__ cell)
+{
+    if (id < 0 || id >= P.container) return -1 - ID_INVALID;
+    const int si = slot_index(P, id);
+    if (si < 0) return -1 - ID_FOREIGN;
+    return slot_live(P, cell[si]) ? si : -1 - ID_NOT_LIVE;
+}
 
 // a lane's rank among the group's lanes of the same record, the group's count of that record and the lane that will
 // account for it (the lowest)

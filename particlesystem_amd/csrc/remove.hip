@@ -32,16 +32,8 @@
 namespace psamd {
 
 // outcome codes (include/psamd.h); an entry that removes nothing is kept as -1 - code in its record word
-enum { REM_REMOVED = 0, REM_NOT_LIVE = 1, REM_FOREIGN = 2, REM_INVALID = 3, REM_DROPPED = 4 };
-
-// the storage index of an entry's slot if the entry can remove it (valid id, owned, live now), else -1 - outcome
-__device__ __forceinline__ int remove_classify(const DevParams &P, int id, const int *__restrict__ cell)
-{
-    if (id < 0 || id >= P.container) return -1 - REM_INVALID;
-    const int si = slot_index(P, id);
-    if (si < 0) return -1 - REM_FOREIGN;
-    return slot_live(P, cell[si]) ? si : -1 - REM_NOT_LIVE;
-}
+// (remove_classify, multisplit.hpp, answers with the codes 1, 2, 3)
+enum { REM_REMOVED = 0, REM_NOT_LIVE = ID_NOT_LIVE, REM_FOREIGN = ID_FOREIGN, REM_INVALID = ID_INVALID, REM_DROPPED = 4 };
 
 // a free slot as k_unpack_aos writes it (psamd_snapshot_restore relies on free slots being all-zero)
 __device__ __forceinline__ void remove_reset(int si, float4 *d_pos4, float4 *d_vel4, float4 *d_acc4, int *d_cell, uint8_t *d_pflags)

@@ -1,5 +1,5 @@
 // services.hip -- the host side of the on-stream services: psamd_export_live (export.hip), psamd_inject (inject.hip),
-// psamd_remove (remove.hip), psamd_potential (potential.hip), psamd_probe (probe.hip), their host-array forms and their result records.
+// psamd_remove (remove.hip), psamd_update (update.hip), psamd_potential (potential.hip), psamd_probe (probe.hip), their host-array forms and their result records.
 // A service enqueues its launches on the context's stream and returns; nothing here enqueues a stage of the step.
 #include "context.hpp"
 
@@ -187,6 +187,57 @@ int psamd_remove(psamd_ctx *c, const psamd_remove_spec *spec)
 }
 
 int psamd_remove_result_get(psamd_ctx *c, psamd_remove_result *out) { return read_own(c, out, c ? c->rem.own : nullptr, sizeof *out); }
+
+// ---- changing particles in place (update.hip) ----
+// the entries' codes for max_count entries: grows only, and not under a capture (grow_probe_scratch's rule)
+static int grow_update_scratch(psamd_ctx *c, UpdateScratch &s, int64_t max_count)
+{
+    if (max_count <= s.cap) return PSAMD_OK;
+    PS_TRY(refuse_capture(c, "update", "max_count exceeds every earlier call's: the scratch would have to grow"));
+    if (s.code) PS_HIP(c, hipFree(s.code));
+    s.code = nullptr; s.cap = 0;
+    const int64_t room = (max_count + ENTRY_TILE - 1) / ENTRY_TILE * ENTRY_TILE;
+    PS_HIP(c, hipMalloc((void **)&s.code, (size_t)room * sizeof(int)));
+    s.cap = room;
+    return PSAMD_OK;
+}
+
+int psamd_update(psamd_ctx *c, const psamd_update_spec *spec)
+{
+    PS_TRY(service_args(c, spec));
+    const uint32_t words = PSAMD_UPDATE_VEL | PSAMD_UPDATE_AGE | PSAMD_UPDATE_MASS | PSAMD_UPDATE_FERT, f = spec->fields;
+    const bool order = (f & PSAMD_UPDATE_EXPORT_ORDER) != 0, some = spec->max_count > 0;
+    if ((f & words) == 0 || (f & ~(words | PSAMD_UPDATE_ADD | PSAMD_UPDATE_EXPORT_ORDER)) || ((f & PSAMD_UPDATE_ADD) && !(f & PSAMD_UPDATE_VEL)) ||
+        spec->reserved != 0)
+        return fail(c, PSAMD_ERR_INVALID_ARG, "update: no field bit, unknown bits, ADD without VEL, or reserved not 0");
+    if (spec->max_count < 0 || spec->max_count > INT32_MAX) return fail(c, PSAMD_ERR_INVALID_ARG, "update: max_count outside [0, 2^31)");
+    if (!aligned(spec->ids, 4) || !aligned(spec->vel4, 16) || !aligned(spec->w, 4) || !aligned(spec->fert_age, 4) ||
+        !aligned(spec->outcome_dev, 4) || !aligned(spec->count_dev, 8) || !aligned(spec->result_dev, 8))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "update: an array misaligned");
+    if (order ? spec->ids != nullptr : some && !spec->ids)
+        return fail(c, PSAMD_ERR_INVALID_ARG, "update: ids missing, or given with PSAMD_UPDATE_EXPORT_ORDER");
+    if (some && (((f & (PSAMD_UPDATE_VEL | PSAMD_UPDATE_AGE)) && !spec->vel4) || ((f & PSAMD_UPDATE_MASS) && !spec->w) ||
+                 ((f & PSAMD_UPDATE_FERT) && !spec->fert_age)))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "update: an array the fields name is missing");
+    if (!update_window(c->stage))
+        return fail(c, PSAMD_ERR_STATE, "update: between slab_apply and slab_finish the departing particles are staged (an update of the "
+                                        "slots they leave would be lost)");
+    // the snapshot holds w_eff and age: a new mass or age ends the frame in progress, velocity and fertility age do not
+    const bool ends = (f & (PSAMD_UPDATE_MASS | PSAMD_UPDATE_AGE)) != 0;
+    if (ends) PS_TRY(refuse_capture(c, "update", "a new mass or age ends the host's frame in progress: a replay would bypass that"));
+    psamd_update_result *res = spec->result_dev ? spec->result_dev : c->upd.own;
+    if (!some) return zero_result(c, c->upd.own, res, sizeof *res);
+    const UpdateArgs a{f, spec->ids, (const float4 *)spec->vel4, spec->w, spec->fert_age, spec->max_count, spec->count_dev, spec->outcome_dev, res};
+    if (order) PS_HIP(c, launch_update_order(c->stream, c->P, c->d, a, c->upd));
+    else {
+        PS_TRY(grow_update_scratch(c, c->upd, spec->max_count));
+        PS_HIP(c, launch_update_ids(c->stream, c->P, c->d, a, c->upd, c->rem.claim));
+    }
+    if (ends) end_frame(c);
+    return PSAMD_OK;
+}
+
+int psamd_update_result_get(psamd_ctx *c, psamd_update_result *out) { return read_own(c, out, c ? c->upd.own : nullptr, sizeof *out); }
 
 // ---- energy (potential.hip) ----
 // a frame is built, its particles have not moved, and -- a slab -- the halos are in (potential and probe)

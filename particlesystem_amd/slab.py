@@ -58,10 +58,11 @@ def _bytes(sysr, slot):
         return 0
 
 
-def step_local(ranks, overlap_interior=False, one_at_a_time=False):
+def step_local(ranks, overlap_interior=False, one_at_a_time=False, after_pairs=None, after_apply=None):
     """One step of a whole system whose ranks all live in this process (tests).  one_at_a_time: a rank's build and pair stage
     have run before the next rank's are enqueued (measurements: the ranks' streams otherwise share the one GPU, and a rank's
-    timers and kernel times hold another rank's work)."""
+    timers and kernel times hold another rank's work).  after_pairs / after_apply: called with the ranks once every rank has
+    run slab_pairs / slab_apply (a service placed inside the step: a probe, an update)."""
     world = len(ranks)
 
     def each(call):
@@ -93,9 +94,13 @@ def step_local(ranks, overlap_interior=False, one_at_a_time=False):
     deliver("halo")
     gather(ALLG_OUT, ALLG_IN)
     each(lambda s: s.slab_pairs())
+    if after_pairs is not None:
+        after_pairs(ranks)
     deliver("force")
     for s in ranks:
         s.slab_apply()
+    if after_apply is not None:
+        after_apply(ranks)
     deliver("xfer")
     gather(FAR_OUT, FAR_IN)
     for s in ranks:

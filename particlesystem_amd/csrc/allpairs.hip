@@ -58,8 +58,11 @@ __global__ __launch_bounds__(256, BALANCED_WAVES) void k_allp_far(DevParams P, c
     const int n_act = act_start[comp_count(P)];
     const int ntask = min((n_act + 63) >> 6, (int)(far.part_plane >> 6));      // (the partial sums' room: never short, see create.hip)
     const int nitem = ntask * ALLP_PARTS, nwg = (nitem + 3) >> 2;
-    // (the launch is sized from the host's bound of the live count, the items from the device's own count: a launch
-    // that is too small for them -- it should not be -- takes several rounds instead of leaving particles out)
+    // (the launch is sized from the host's bound of the live count, the items from the device's own count.  The bound
+    // covers the particles alive whatever is in flight -- StepLedger::alive_at_most, held to that by
+    // tests/test_step_ledger_cpu.py -- so one round does; should a launch still be too small for them it takes several
+    // rounds instead of leaving particles out: tests/test_gpu_state_swap.py ran these rounds on the library whose bound
+    // an upload, a fill or a restore behind a step could leave too low)
     for (int b = blockIdx.x; b < nwg; b += gridDim.x) {
     // part-major: an XCD's contiguous eighth of the items is two parts -- an eighth of the far bodies, which then sit in its L2
     const int slot = xcd_contiguous(b, nwg) * 4 + wave;

@@ -16,8 +16,15 @@
 //
 // HINTS come from the last record READ, which with run-ahead is not the last step's: every unread step may have added a
 // child per particle (explosions on) and a slab its arrivals, so alive_at_most() doubles per unread step and adds the
-// messages' room.  Only the all-pairs far pass sizes a launch from it that must cover every particle; every other
-// figure is a hint whose miss only costs time.
+// messages' room.  It is an upper bound of the particles alive at the next build_grid WHATEVER is in flight
+// (tests/test_step_ledger_cpu.py holds it to a simulated population): a call that changes the particles between two
+// steps -- fill, inject, upload, snapshot_restore -- is booked under the last step enqueued, and the record of that step
+// or of an earlier one, read afterwards, speaks of the particles before the call: a fill or an inject is added to what
+// such a record says (tally_), after an upload or a restore such a record leaves the bound alone and only a later step's
+// sets it again (reset_step_).  The far walks and their combine size a launch from the bound that should cover every
+// particle (far_dense_bound; they go by the device's own count in rounds, so a launch that is too small would cost
+// time, not particles); every other figure is a hint whose miss only costs time.  The other hints (tasks, packs, the
+// longest list, last_live()) follow the last record read as they are: stale by a call for a step or two, then right.
 //
 // VERDICTS.  A record that carries error bits asks for a verdict (absorb() says so; step.hip fetches the status and
 // its text).  The first verdict of a reading call is held (hold_verdict) and released by the next call that reports
@@ -67,7 +74,8 @@ public:
     int seq() const { return seq_; }
     int seen() const { return seen_; }
     int due() const { return run_ahead_ ? seq_ - 1 : seq_; }    // the record the call that enqueued step seq() waits for
-    void resync(int device_seq) { seq_ = seen_ = device_seq; }  // a launch failed between a record's publishing and enqueued()
+    // a launch failed between a record's publishing and enqueued(): records may have gone unread, the bound is unknown
+    void resync(int device_seq) { seq_ = seen_ = device_seq; reset_bound(-1, 0); }
 
     // The record of step seen() + 1 was read.  Whether it asks for a verdict: never while `raised`, the reading call has one.
     bool absorb(const FrameScalars &r, const LedgerParams &p, bool raised)
@@ -79,12 +87,15 @@ public:
         const bool two = interior_steps_.erase(s) != 0;                   // (in two passes: the record holds the second pass's count)
         tasks_last_ = two ? tasks_now * p.comp / std::max(1, p.comp_rest) : tasks_now;
         packs_last_ = two ? (int64_t)r.n_merged * p.comp / std::max(1, p.comp_rest) : r.n_merged;
-        live_bound_ = std::min<int64_t>(p.slots_total, (int64_t)r.live + r.n_moves);   // births and arrivals <= moves
-        // ... and what was injected after this step was enqueued (the record's live count does not include it)
-        for (auto it = inject_tally_.begin(); it != inject_tally_.end();) {
-            if (it->first < s) { it = inject_tally_.erase(it); continue; }
-            live_bound_ = std::min<int64_t>(p.slots_total, live_bound_ + it->second);
-            ++it;
+        if (s > reset_step_) {           // (else: enqueued before an upload or a restore, whose particles it does not know)
+            live_bound_ = std::min<int64_t>(p.slots_total, (int64_t)r.live + r.n_moves);   // births and arrivals <= moves
+            bound_step_ = s;
+            // ... and what was filled or injected after this step was enqueued (the record's live count does not include it)
+            for (auto it = tally_.begin(); it != tally_.end();) {
+                if (it->first < s) { it = tally_.erase(it); continue; }
+                live_bound_ = std::min<int64_t>(p.slots_total, live_bound_ + it->second);
+                ++it;
+            }
         }
         processed_total_ += r.live;
         max_bucket_seen_ = std::max<int64_t>(max_bucket_seen_, r.max_bucket);
@@ -107,7 +118,7 @@ public:
     int64_t alive_at_most(const LedgerParams &p, bool graphs) const
     {
         int64_t b = live_bound_ >= 0 ? live_bound_ : p.slots_total;
-        for (int k = seen_; k < seq_ && b < p.slots_total; k++) b = (p.explosions ? 2 * b : b) + msg_room(p);
+        for (int k = bound_step_; k < seq_ && b < p.slots_total; k++) b = (p.explosions ? 2 * b : b) + msg_room(p);
         b = std::min(b, p.slots_total);
         return graphs ? std::min<int64_t>((b + 65535) & ~(int64_t)65535, std::max<int64_t>(p.slots_total, 65536)) : b;
     }
@@ -136,17 +147,23 @@ public:
     }
 
     // ---- what the other units did ----
-    void filled(int64_t placed) { if (live_bound_ >= 0) live_bound_ += placed; }
-    void uploaded() { live_bound_ = -1; }
-    // every entry counts, also when the record of a step enqueued before the call is read later: tallied under the last
-    // step enqueued until the record of the step after it -- the first that counts the entries -- has been read
-    void injected(const LedgerParams &p, int64_t max_count)
+    // every particle placed counts, also when the record of a step enqueued before the call is read later: tallied under
+    // the last step enqueued until the record of the step after it -- the first that counts them -- has been read
+    void filled(int64_t placed)                  // (what was placed found a free slot: no more than the slots)
+    {
+        if (live_bound_ >= 0) live_bound_ += placed;
+        tally_[seq_] += placed;
+    }
+    void injected(const LedgerParams &p, int64_t max_count)      // (every entry may be placed, or none)
     {
         if (live_bound_ >= 0) live_bound_ = std::min(p.slots_total, live_bound_ + max_count);
-        inject_tally_[seq_] += max_count;
+        tally_[seq_] += max_count;
     }
-    void snapshot_saved() { snapshot_live_bound_ = live_bound_; }
-    void snapshot_restored() { live_bound_ = snapshot_live_bound_; }
+    void uploaded() { reset_bound(-1, 0); }
+    // the snapshot holds the particles of this moment: the bound and the steps whose growth alive_at_most() adds to it now,
+    // which it adds again after the restore
+    void snapshot_saved() { snapshot_live_bound_ = live_bound_; snapshot_growth_steps_ = seq_ - bound_step_; }
+    void snapshot_restored() { reset_bound(snapshot_live_bound_, snapshot_growth_steps_); }
     void frame_live(int live) { live_at_build_ = live; }       // read from the device's own record inside a frame
 
     // ---- for the getters ----
@@ -157,6 +174,16 @@ public:
 
 private:
     static int64_t msg_room(const LedgerParams &p) { return 2 * (int64_t)p.xfer_cap + 2 * (int64_t)p.xfer2_cap + (int64_t)p.far_cap * p.world; }
+    // The particles were replaced behind the last step enqueued: `bound` of them at most (-1: unknown) before the growth of
+    // `growth_steps` steps.  The records of the steps enqueued so far do not know them and what was tallied for those
+    // records went with the particles it counted.
+    void reset_bound(int64_t bound, int growth_steps)
+    {
+        live_bound_ = bound;
+        reset_step_ = seq_;
+        bound_step_ = seq_ - growth_steps;
+        tally_.clear();
+    }
 
     int seq_ = 0, seen_ = 0, run_ahead_ = 1;
     FrameScalars last_{};
@@ -164,8 +191,11 @@ private:
     bool interior_ran_ = false;
     std::set<int> interior_steps_;           // the steps in two passes whose records have not been read yet
     int64_t tasks_last_ = 0, packs_last_ = 0;    // force tasks of the last step read (all passes); of which packs of partly filled slices
-    int64_t live_bound_ = 0, snapshot_live_bound_ = 0;     // live particles at the next build_grid at most (-1: unknown)
-    std::map<int, int64_t> inject_tally_;    // step k -> max_count of the injects enqueued after it
+    int64_t live_bound_ = 0, snapshot_live_bound_ = 0;     // live particles once step bound_step_ has run, at most (-1: unknown)
+    int bound_step_ = 0;                     // ... the steps after it are the ones alive_at_most() adds the growth of
+    int snapshot_growth_steps_ = 0;          // ... of the saved bound: seq() - bound_step_ at the save
+    int reset_step_ = 0;                    // the last step enqueued before the particles were last replaced (upload, restore)
+    std::map<int, int64_t> tally_;           // step k -> particles the fills and injects enqueued after it placed at most
     std::map<int, int> cap_decisions_;       // step -> the transfer capacity all ranks agreed on in it
     int64_t processed_total_ = 0, max_bucket_seen_ = 0;
     int pending_status_ = 0;                 // the held verdict and its text

@@ -2,9 +2,12 @@
 
 step_ledger_dump.cpp -- a stand-alone program, built with the address and undefined-behaviour sanitizers -- reads scripts
 of operations and prints, after every one, all the ledger lets the host see.  `Old` below holds the fields the context
-had before (scalars_seq, scalars_seen, last, live_bound, inject_tally, cap_decisions, pending_status ...) with the
+had before (scalars_seq, scalars_seen, last, live_bound, the tally, cap_decisions, pending_status ...) with the
 statements of step.hip, io.hip and services.hip that read and wrote them, one for one; both sides take the same
-scripts and every printed field is compared after every operation.
+scripts and every printed field is compared after every operation.  Where the ledger's rules have changed since (the live
+bound across fill, upload and restore) `Old` was changed with them, line for line: it says HOW the ledger computes, and
+would agree with it on a rule that is wrong.  WHETHER the live bound is a bound is checked against `World`, the particles
+themselves (the live_bound tests): the bound a step is sized from is never below the particles alive at its build.
 
 A script is what a host does to one context: `step` is finish_step (the step is enqueued, the records due are read, the
 verdict is returned), `rec` the device publishing a step's record into one of the two host records, `read U` a bare
@@ -41,7 +44,7 @@ def cfg_line(g):
 
 
 class Old:
-    """the context's fields and the parent's statements over them (c-> is self., c->P. is self.P.)"""
+    """the context's fields and the statements over them (c-> is self., c->P. is self.P.), kept in step with the ledger's rules"""
 
     def __init__(self, g):
         self.P = SimpleNamespace(world=g.world, explosions=bool(g.expl), slots_total=g.slots, xfer_cap=g.xfer, xfer2_cap=g.xfer2, far_cap=g.far,
@@ -56,7 +59,8 @@ class Old:
         self.interior_steps = set()
         self.tasks_last = self.packs_last = 0
         self.live_bound = self.snapshot_live_bound = 0
-        self.inject_tally = {}
+        self.bound_step = self.reset_step = self.snapshot_growth_steps = 0
+        self.tally = {}
         self.cap_decisions = {}
         self.processed_total = self.max_bucket_seen = 0
         self.bucket_cap0 = 2048
@@ -86,12 +90,14 @@ class Old:
             self.interior_steps.discard(s)
             self.tasks_last = tasks_now * self.comp // max(1, self.comp_rest) if two else tasks_now
             self.packs_last = r.n_merged * self.comp // max(1, self.comp_rest) if two else r.n_merged
-            self.live_bound = min(self.P.slots_total, r.live + r.n_moves)
-            for k in sorted(self.inject_tally):
-                if k < s:
-                    del self.inject_tally[k]
-                    continue
-                self.live_bound = min(self.P.slots_total, self.live_bound + self.inject_tally[k])
+            if s > self.reset_step:
+                self.live_bound = min(self.P.slots_total, r.live + r.n_moves)
+                self.bound_step = s
+                for k in sorted(self.tally):
+                    if k < s:
+                        del self.tally[k]
+                        continue
+                    self.live_bound = min(self.P.slots_total, self.live_bound + self.tally[k])
             self.processed_total += r.live
             self.max_bucket_seen = max(self.max_bucket_seen, r.max_bucket)
             if self.P.world > 1 and r.xfer_cap_next > 0:
@@ -126,7 +132,7 @@ class Old:
     def live_bound_of(self, graphs):
         P = self.P
         b = self.live_bound if self.live_bound >= 0 else P.slots_total
-        k = self.scalars_seen
+        k = self.bound_step
         while k < self.scalars_seq and b < P.slots_total:
             if P.explosions:
                 b *= 2
@@ -169,25 +175,34 @@ class Old:
 
     def resync_scalars(self, device_seq):
         self.scalars_seq = self.scalars_seen = device_seq
+        self.reset_bound(-1, 0)
+
+    def reset_bound(self, bound, growth_steps):
+        self.live_bound = bound
+        self.reset_step = self.scalars_seq
+        self.bound_step = self.scalars_seq - growth_steps
+        self.tally.clear()
 
     # ---- io.hip, services.hip ----
     def fill_particles(self, placed):
         if self.live_bound >= 0:
             self.live_bound += placed
+        self.tally[self.scalars_seq] = self.tally.get(self.scalars_seq, 0) + placed
 
     def upload_particles(self):
-        self.live_bound = -1
+        self.reset_bound(-1, 0)
 
     def inject(self, max_count):
         if self.live_bound >= 0:
             self.live_bound = min(self.P.slots_total, self.live_bound + max_count)
-        self.inject_tally[self.scalars_seq] = self.inject_tally.get(self.scalars_seq, 0) + max_count
+        self.tally[self.scalars_seq] = self.tally.get(self.scalars_seq, 0) + max_count
 
     def snapshot_save(self):
         self.snapshot_live_bound = self.live_bound
+        self.snapshot_growth_steps = self.scalars_seq - self.bound_step
 
     def snapshot_restore(self):
-        self.live_bound = self.snapshot_live_bound
+        self.reset_bound(self.snapshot_live_bound, self.snapshot_growth_steps)
 
     # ---- a script's line, and what the program prints after it ----
     def run(self, line):
@@ -260,15 +275,19 @@ def ledger(tmp_path_factory):
 
 
 # ---- fixed-seed random scripts ----
-def random_script(rng, g, n_ops=60):
+def random_script(rng, g, n_ops=60, world=None):
     """A host's calls in any order a host may make them, and the device publishing records in order: early (as soon as
-    the step is enqueued), on time (just before the call that waits for it) or late (after a call peeked and missed it)."""
+    the step is enqueued), on time (just before the call that waits for it) or late (after a call peeked and missed it).
+    With a `world` (World below) the calls act on its particles too and the records are the ones its steps wrote."""
     lines, seq, seen, arrived, ra = [], 0, 0, 0, g.ra       # arrived: the last record the device has published
 
     def publish(upto):
         nonlocal arrived
         while arrived < upto:
             arrived += 1
+            if world:
+                lines.append(rec_line(world.records.pop(arrived)))
+                continue
             err = rng.choice((0, 0, 0, 0, 0, 64, 512))
             lines.append(rec_line(record(arrived, live=rng.randrange(0, g.slots), n_moves=rng.randrange(0, 3000),
                                          n_tasks2=rng.choice((0, rng.randrange(1, 9000))), n_merged=rng.randrange(0, 700),
@@ -284,10 +303,14 @@ def random_script(rng, g, n_ops=60):
     while len(lines) < n_ops:
         op = rng.choice(("step",) * 8 + ("rec",) * 4 + ("read", "drainq", "drain", "fill", "upload", "inject", "inject", "save", "restore", "build", "build",
                                                         "resync", "ra", "framelive"))
+        if world and not world.call(op, lines):
+            continue                                # (the call and its amount are the world's, or the world has no such call)
         if op == "step":
             if g.world > 1 and rng.random() < 0.5:
                 lines.append("build")
             seq += 1
+            if world:
+                world.step(seq)                     # (the bound this step is sized from is the one after the line before)
             if rng.random() < 0.3:
                 publish(seq)                        # (the step's launches are out before the host books it)
             read(seq - 1 if ra else seq)
@@ -342,6 +365,115 @@ def test_random_scripts_leave_every_field_equal(ledger):
         states = ledger(g, lines)
         assert all(int(s["unread"]) <= 2 for s in states)
     assert len(met) == 8
+
+
+# ---- the live bound against the particles themselves ----
+class World:
+    """The truth beside a script: `pop`, the particles alive, by the rules of the device and not of the ledger.
+      step     pop becomes anything in [0, min(slots, (2 pop if explosions else pop) + room)]: a child per particle at most,
+               and the messages' room (StepLedger::msg_room, restated from the config: the records carry no capacity
+               decision, so the capacity stays the config's); the step's record holds pop at its build and any
+               n_moves >= the growth
+      fill n   + n, inject n: + anything in [0, n]; both stop at `slots`
+      upload   anything in [0, slots];  save / restore: store pop / put it back
+    `at_build` lists pop at every step's build, in the order of the script's step lines."""
+
+    def __init__(self, rng, g):
+        self.rng, self.g = rng, g
+        self.room = 2 * g.xfer + 2 * g.xfer2 + g.far * g.world
+        self.pop, self.saved = 0, None
+        self.at_build, self.records = [], {}
+
+    def step(self, s):
+        rng, g, before = self.rng, self.g, self.pop
+        top = min(g.slots, (2 * before if g.expl else before) + self.room)
+        self.pop = rng.choice((top, top, before, before, before // 2, rng.randint(0, top), rng.randint(0, top)))
+        self.at_build.append(before)
+        self.records[s] = record(s, live=before, n_moves=max(0, self.pop - before) + rng.choice((0, 0, rng.randrange(0, 40))),
+                                 n_tasks2=rng.choice((0, rng.randrange(1, 9000))), n_merged=rng.randrange(0, 700),
+                                 max_bucket=rng.choice((0, 100, 2049, 4097)), max_cell_raw=rng.choice((0, 961)))
+
+    def call(self, op, lines):
+        """a call that changes the particles: its line, with an amount of the world's choosing (False: done here, or
+        not a call of this world -- resync, a failed launch, leaves the particles in no state the rules describe)"""
+        rng, g = self.rng, self.g
+        if op in ("fill", "inject"):
+            n = rng.choice((0, 1, 777, g.slots // 3, g.slots // 2, g.slots))
+            self.pop = min(g.slots, self.pop + (n if op == "fill" else rng.choice((0, n, rng.randint(0, n)))))
+            lines.append("%s %d" % (op, n))
+        elif op == "upload":
+            self.pop = rng.choice((g.slots, g.slots // 2, rng.randint(0, g.slots), rng.randint(0, 100)))
+            lines.append(op)
+        elif op == "save":
+            self.saved = self.pop
+            lines.append(op)
+        elif op == "restore":
+            if self.saved is not None:              # (psamd_snapshot_restore without a snapshot is refused before the ledger hears of it)
+                self.pop = self.saved
+                lines.append(op)
+        else:
+            return op != "resync"
+        return False
+
+
+def bound_shortfalls(states, lines, at_build):
+    """[(line number, bound, pop)] for every step whose bound -- the one printed after the line before it, graphs off or
+    on -- was below the particles alive at its build"""
+    steps = [k for k, line in enumerate(lines) if line.startswith("step")]
+    assert len(steps) == len(at_build)
+    short = []
+    for k, pop in zip(steps, at_build):
+        bg, bn = (int(v) for v in states[k - 1]["bound"].split("/")) if k else (0, 0)       # (a fresh ledger: 0 of 0 particles)
+        if min(bg, bn) < pop:
+            short.append((k, min(bg, bn), pop))
+    return short
+
+
+def hand_script(*items):
+    """(lines, pop at the build of every step): a step is written ("step 0", pop at its build)"""
+    return [i if isinstance(i, str) else i[0] for i in items], [i[1] for i in items if not isinstance(i, str)]
+
+
+# a call that changes the particles while a record from before it is unread: what the record says no longer holds
+HAND_SCRIPTS = {
+    # the record of step 1 (1000 alive, 10 moves) is read by the call that enqueues step 2, after the upload of 50 000
+    "upload": (config(ra=1), hand_script("fill 1000", ("step 0", 1000), rec_line(record(1, live=1000, n_moves=10)), "upload", ("step 0", 50000),
+                                         rec_line(record(2, live=50000)), ("step 0", 50000))),
+    "fill": (config(ra=1), hand_script("fill 1000", ("step 0", 1000), rec_line(record(1, live=1000, n_moves=10)), "fill 49000", ("step 0", 50000),
+                                       rec_line(record(2, live=50000)), ("step 0", 50000))),
+    # 50 000 saved, the context brought down to 1000 and stepped, the snapshot put back with that step's record unread
+    "restore": (config(ra=1), hand_script("fill 50000", "save", "upload", ("step 0", 1000), rec_line(record(1, live=1000)), "restore", ("step 0", 50000),
+                                          rec_line(record(2, live=50000)), ("step 0", 50000))),
+    # explosions: step 1 doubles 1000 to 2000 and its record is unread at the save; everything is read before the restore
+    "save": (config(ra=1, expl=1), hand_script("fill 1000", ("step 0", 1000), "save", rec_line(record(1, live=1000, n_moves=1000)), "drain", "upload",
+                                               "restore", ("step 0", 2000))),
+}
+
+
+@pytest.mark.parametrize("name", sorted(HAND_SCRIPTS))
+def test_live_bound_covers_the_particles_alive_hand_scripts(ledger, name):
+    g, (lines, at_build) = HAND_SCRIPTS[name]
+    assert bound_shortfalls(ledger(g, lines), lines, at_build) == []
+
+
+def test_live_bound_covers_the_particles_alive_random_scripts(ledger):
+    """240 scripts with a world beside them: worlds 1 and 2, explosions on and off, run-ahead 0 and 1.  The generator must
+    put fill, upload and restore behind an unread record often enough for the property to mean something."""
+    met, behind = set(), {"fill": 0, "upload": 0, "restore": 0}
+    for k in range(240):
+        rng = random.Random(12000 + k)
+        g = random_config(rng, k)
+        met.add((g.world, g.expl, g.ra))
+        world = World(rng, g)
+        lines = random_script(rng, g, world=world)
+        states = ledger(g, lines)
+        assert bound_shortfalls(states, lines, world.at_build) == [], (k, cfg_line(g), lines)
+        for line, before in zip(lines[1:], states):
+            op = line.split()[0]
+            if op in behind and int(before["seq"]) > int(before["seen"]):
+                behind[op] += 1
+    assert len(met) == 8
+    assert min(behind.values()) >= 20, behind
 
 
 # ---- named cases ----

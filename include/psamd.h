@@ -351,6 +351,24 @@ typedef struct psamd_update_spec {
     psamd_update_result *result_dev;   /* optional out (device), 8-byte aligned; NULL: the context's own record only */
 } psamd_update_spec;          /* 72 bytes */
 
+/* What psamd_deposit did (see "mass on a lattice" below). */
+typedef struct psamd_deposit_result {
+    int64_t voxels;           /* voxels this context wrote                                                    */
+    int64_t bodies;           /* listed finite bodies of this context's served cells                          */
+    int64_t skipped;          /* listed bodies of those cells with a non-finite word                          */
+    double  mass;             /* fp64 sum of this context's voxel sums (before the float rounding), fixed order */
+    double  vmax;             /* largest voxel value written; -inf if none                                    */
+} psamd_deposit_result;       /* 40 bytes */
+
+/* What psamd_deposit writes and where (device pointers). */
+typedef struct psamd_deposit_spec {
+    uint32_t flags;           /* 0                                                                            */
+    int32_t  refine;          /* k: voxels per cell edge, 1, 2 or 4                                           */
+    float   *out;             /* float[capacity], 4-byte aligned, required                                    */
+    int64_t  capacity;        /* >= (grid_dim * refine)^3                                                     */
+    psamd_deposit_result *result_dev;  /* optional out (device), 8-byte aligned; NULL: the context's own record only */
+} psamd_deposit_spec;         /* 32 bytes */
+
 typedef struct psamd_ctx psamd_ctx;
 
 /* ---- lifetime ------------------------------------------------------------ */
@@ -969,6 +987,83 @@ int psamd_download_potential_flags(psamd_ctx *ctx, uint32_t flags, float *phi, i
  * psamd_probe_result_get: the last probe's record, into host memory; waits for the context's stream. */
 int psamd_probe(psamd_ctx *ctx, const psamd_probe_spec *spec);
 int psamd_probe_result_get(psamd_ctx *ctx, psamd_probe_result *out);
+
+/* ---- mass on a lattice ---------------------------------------------------------- */
+/* psamd_deposit: the source of the field psamd_probe serves, as a field -- the mass density of the frame on a regular
+ * lattice, cloud-in-cell, for a volume renderer, a clump or void analysis, a particle-mesh solver of the caller's, or
+ * Poisson's equation checked against psamd_probe's phi on the same nodes.  The bodies are sorted by cell, so every voxel
+ * is GATHERED from the 27-cell stencil of its cell in a fixed order: no floating-point atomic, the same bytes from run to
+ * run and with graphs on or off, and on slabs every voxel formed entirely on one rank.  Not in the reference; the step's
+ * arithmetic is untouched, no force record, particle or queue is written, and PSAMD_ABI_VERSION stays 8.
+ *
+ * Lattice.  refine = k in {1, 2, 4} voxels per cell edge: M = G k voxels per axis (G = grid_dim), h = cell_size / k.  The
+ * axes are the cell axes of the locate rule, (q1, q2, q3) = (-y, x, -z).  Voxel (n1, n2, n3) has index (n3 M + n1) M + n2 --
+ * the cell index's order; as a [M][M][M] array it is indexed [n3][n1][n2] -- its centre lies at q_a = (n_a + 1/2 - (G / 2) k) h
+ * with G / 2 the integer division of the cell rule, and it belongs to cell (n_a div k).
+ *
+ * Bodies.  Those the force pass walks: of every cell the first min(count, MAX_PARTICLES_PER_CELL) entries of the sorted
+ * snapshot (x, y, z, w_eff), with mass m = |w_eff|: force_sign does not enter, as in psamd_potential's U.  A kid has
+ * w_eff = 0 and adds nothing, as it adds nothing to the force: the volume is the density of GRAVITATING mass, not of all
+ * live particles.  A body with any of x, y, z, w_eff not finite adds nothing and counts in `skipped`, once, by its own cell.
+ *
+ * Weights.  All in fp32, every operation rounded on its own, nothing fused.  Per axis, with s the signed coordinate (-y, x,
+ * -z: exact), inv_h = (float)((double)k / cell_size) and off = (float)((G / 2) k) - 0.5f (exact):
+ *     t = RN(s inv_h);  u = RN(t + off);  u_c = min(max(u, 0), M - 1);  n0 = (int)floor(u_c);  f = u_c - n0  (exact)
+ * and the body gives the weight RN(1 - f) to voxel n0 and f to n0 + 1 of that axis; a weight for n0 + 1 == M is zero and
+ * dropped.  The clamp folds mass beyond the outermost voxel centres onto the face voxels: the deposit conserves mass and is
+ * not periodic (nor is the stencil).  A body's term for a voxel is RN(RN(RN(W1 W2) W3) m).
+ *
+ * Stencil rule.  A body of cell c contributes only to voxels whose cell lies within one cell of c on every axis.  That is
+ * always so for particles the step itself places (the margin is at least 1/8 cell against a few ulp); it is stated because
+ * uploaded records may carry a cell that does not fit their position, and it is what makes the gather over the 27-cell
+ * stencil complete.  A voxel is decided by u alone (n0 and n0 + 1), never by re-deriving the body's cell.
+ *
+ * Sum.  A voxel's value is (float) of the fp64 sum of its terms.  Association: one wave forms the voxel; lane l of its 64
+ * takes entries l, l + 64, l + 128 ... of every list and adds its terms from +0 in fp64 -- the stencil's cells in the
+ * reference's order (the cell itself first), a cell's entries in list order -- and the 64 lane sums close in a butterfly: every
+ * lane adds the sum of lane l ^ 32, then of l ^ 16, ^ 8, ^ 4, ^ 2, ^ 1.  The order depends on the voxel and on the lists'
+ * lengths alone: not on the launch, the rank or the plan.  A voxel nobody reaches is +0.0f.  Against the same terms summed
+ * in any other order only the last rounding can differ: 1 ulp.
+ *
+ * Result.  voxels: those this context wrote, its compute cells times k^3; bodies / skipped: the listed bodies of those cells
+ * that are finite / are not; mass: the fp64 sum of this context's voxel sums before their rounding to float -- per task (a
+ * cell's block of at most 2 x 2 x 2 voxels: 1, 1, 8 tasks a cell for k = 1, 2, 4; the blocks by (n3, n1, n2), the cells in the
+ * force pass's order) the voxels in (n3, n1, n2) order, four tasks at a time, those partials in one serial chain; vmax: the
+ * largest float written as a double, -inf if none.  The total mass equals the bodies' within 2^-21 relative (four roundings
+ * of a term).
+ *
+ * Slabs.  A rank writes the voxels of its compute cells -- psamd_probe's rule, lent-in layers included: exactly one rank
+ * serves every voxel on any plan, group-aligned or not -- at their index in the FULL lattice and leaves every other entry of
+ * `out` alone.  The union of the ranks' writes is one context's array bit for bit; voxels, bodies, skipped and mass add over
+ * the ranks, vmax takes the maximum.  Every context kind is served alike -- cutoff, PSAMD_FLAG_FAST_MATH, all-pairs, the three
+ * far methods and far slabs (PSAMD_FLAG_FAR_SLAB): the quantity depends on the lists alone.
+ *
+ * Valid in psamd_potential's window: world == 1 from psamd_build_grid until the frame ends, world > 1 between
+ * psamd_slab_pairs and psamd_slab_apply; elsewhere PSAMD_ERR_STATE, also for a wedged context.  The call neither ends nor
+ * disturbs the frame, the force records or the step.
+ *
+ * Everything is enqueued on the context's stream (psamd_get_stream): nothing waits, nothing is read back, no host
+ * bookkeeping; PSAMD_OK says the work is enqueued, only the result record says what happened.  The scratch (48 bytes per
+ * compute cell: the partials of mass, vmax and the counts) is allocated at psamd_create, so the call allocates nothing and
+ * may always be captured into a graph.  *result_dev and the context's own record (psamd_deposit_result_get) are written by
+ * the time the stream reaches the end of the call.
+ *
+ * psamd_download_deposit: the same pass into host memory -- staged on the device, the stream waited for, the WHOLE lattice
+ * copied (capacity >= M^3 floats).  On a slab the entries of voxels the rank does not serve are +0, so the ranks' arrays
+ * add up to one context's exactly (every voxel has one non-zero contributor).  `result` may be NULL.
+ *
+ * Cost on an MI355X at N = 2^20 on 16^3 cells (scripts/deposit_cost.py; profiles/deposit_cost.txt), measured: 0.066 ms at refine 1
+ * (4 096 voxels), 0.078 ms at refine 2 (32 768), 0.33 ms at refine 4 (262 144), beside 0.51 ms of psamd_potential on the same frame
+ * in the same run (host clock around the call plus psamd_synchronize, the stream idle before it).  At refine 4 a cell's eight
+ * blocks each walk the cell's 27 lists.
+ *
+ * PSAMD_ERR_INVALID_ARG: a NULL context or spec, flags != 0, refine not 1, 2 or 4, out NULL or not 4-byte aligned,
+ * capacity < M^3, result_dev not 8-byte aligned.
+ *
+ * psamd_deposit_result_get: the last deposit's record, into host memory; waits for the context's stream. */
+int psamd_deposit(psamd_ctx *ctx, const psamd_deposit_spec *spec);
+int psamd_deposit_result_get(psamd_ctx *ctx, psamd_deposit_result *out);
+int psamd_download_deposit(psamd_ctx *ctx, int32_t refine, float *out, int64_t capacity, psamd_deposit_result *result);
 
 /* ---- long-range gravity (PSAMD_FLAG_FAR_MONOPOLE) ------------------------------ */
 /* The cutoff pass leaves most of a long-range force out; PSAMD_FLAG_ALL_PAIRS has all of it at O(N^2).  With this flag a

@@ -277,6 +277,27 @@ def merge_probe(results):
             "nonfinite": sum(int(r["nonfinite"]) for r in results)}
 
 
+class DepositResult(_Record):
+    """psamd_deposit_result: what psamd_deposit wrote and of which bodies."""
+    _fields_ = [("voxels", C.c_int64), ("bodies", C.c_int64), ("skipped", C.c_int64), ("mass", C.c_double), ("vmax", C.c_double)]
+
+
+class DepositSpec(C.Structure):
+    """psamd_deposit_spec: what psamd_deposit writes and where (device pointers)."""
+    _fields_ = [("flags", C.c_uint32), ("refine", C.c_int32), ("out", C.c_void_p), ("capacity", C.c_int64), ("result_dev", C.c_void_p)]
+
+
+def merge_deposit(results):
+    """The deposit of a system from its ranks' (dicts of deposit(result=True)[1] / download_deposit()[1]): voxels, bodies,
+    skipped and mass add, in rank order; vmax takes the maximum.  (The arrays: every voxel is written by one rank, into the
+    full lattice; the host forms are +0 elsewhere and add.)"""
+    results = list(results)
+    out = {n: sum(int(r[n]) for r in results) for n in ("voxels", "bodies", "skipped")}
+    out["mass"] = float(sum(float(r["mass"]) for r in results))
+    out["vmax"] = float(max(float(r["vmax"]) for r in results))
+    return out
+
+
 def merge_live_stats(stats):
     """The statistics of a system from its ranks' (dicts of live_stats() / export_live()["stats"]): counts and sums
     add, in rank order; the box and the ages take the minima and maxima."""
@@ -386,6 +407,9 @@ ABI = [
     ("psamd_download_potential_flags", C.c_int, [_vp, C.c_uint32, _vp, _i64, C.POINTER(PotentialResult)]),
     ("psamd_probe", C.c_int, [_vp, C.POINTER(ProbeSpec)]),
     ("psamd_probe_result_get", C.c_int, [_vp, C.POINTER(ProbeResult)]),
+    ("psamd_deposit", C.c_int, [_vp, C.POINTER(DepositSpec)]),
+    ("psamd_deposit_result_get", C.c_int, [_vp, C.POINTER(DepositResult)]),
+    ("psamd_download_deposit", C.c_int, [_vp, C.c_int32, _vp, _i64, C.POINTER(DepositResult)]),
 ]
 
 _lib = None
@@ -1013,6 +1037,41 @@ class ParticleSystem:
         r = ProbeResult()
         self._ck(self.lib.psamd_probe_result_get(self.h, C.byref(r)))
         return r.to_dict()
+
+    # ---- mass on a lattice (include/psamd.h) ------------------------------------
+    def deposit(self, refine=1, out=None, result=False):
+        """psamd_deposit: the mass density of the frame that is built (after build_grid; a slab: between slab_pairs and
+        slab_apply) on the lattice of `refine` voxels per cell edge, cloud-in-cell: a float32 torch device tensor of shape
+        (M, M, M), M = grid_dim * refine, indexed [n3, n1, n2] (the cell axes: -z, -y, x).  out: such a tensor to write
+        into (a slab rank writes the voxels of its compute cells and leaves the others as they are); None: a fresh one of
+        zeros.  result=True: (tensor, the record as a dict).  Waits for the context's stream.  torch must have been
+        imported before the library was loaded."""
+        import torch
+        dev = torch.device("cuda", int(self.cfg.device))
+        m = int(self.sizes.grid_dim) * int(refine)
+        if out is None:
+            out = torch.zeros((m, m, m), dtype=torch.float32, device=dev)
+        assert out.dtype == torch.float32 and tuple(out.shape) == (m, m, m) and out.is_contiguous() and out.is_cuda, "deposit: bad out tensor"
+        rec = torch.zeros(C.sizeof(DepositResult), dtype=torch.uint8, device=dev)
+        spec = DepositSpec(flags=0, refine=int(refine), out=out.data_ptr(), capacity=out.numel(), result_dev=rec.data_ptr())
+        with self._on_stream(dev):
+            self._ck(self.lib.psamd_deposit(self.h, C.byref(spec)))
+        return (out, DepositResult.from_device(rec).to_dict()) if result else out
+
+    def deposit_result(self):
+        """psamd_deposit_result_get: the last deposit's record as a dict"""
+        r = DepositResult()
+        self._ck(self.lib.psamd_deposit_result_get(self.h, C.byref(r)))
+        return r.to_dict()
+
+    def download_deposit(self, refine=1):
+        """psamd_download_deposit, the numpy form of deposit(): (float32 array [M, M, M] of the whole lattice -- on a slab +0
+        where another rank serves the voxel -- and the record as a dict)"""
+        m = int(self.sizes.grid_dim) * int(refine)
+        out = np.full((max(m, 1),) * 3, np.nan, np.float32)
+        r = DepositResult()
+        self._ck(self.lib.psamd_download_deposit(self.h, int(refine), _ptr(out), out.size, C.byref(r)))
+        return out, r.to_dict()
 
     def device_view(self):
         v = DeviceView()

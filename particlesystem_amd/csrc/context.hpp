@@ -76,6 +76,7 @@ struct psamd_ctx {
     RemoveScratch rem{};              // psamd_remove's scratch: rem.e grows with max_count, the rest is fixed
     ProbeScratch prb{};               // psamd_probe's scratch: code / order grow with max_count, the counters are fixed
     UpdateScratch upd{};              // psamd_update's scratch: code grows with max_count, the rest is fixed (by id it borrows rem.claim)
+    DepositScratch dep{};             // psamd_deposit's scratch: fixed (the geometry and the plan size it)
     // timing
     int timing = 0;                    // 0 off, 1 pair pass / apply / life cycle, 2 every stage
     int timing_period = 1;             // events are recorded on every timing_period-th step since set_timing

@@ -390,6 +390,11 @@ static int alloc_step_arrays(psamd_ctx *c)
     PS_HIP(c, dev_alloc(c, &c->upd.tile_live, (size_t)slot_tiles(P.slots_total)));
     PS_HIP(c, dev_alloc(c, &c->upd.own, 1));
     PS_HIP(c, hipMemsetAsync(c->upd.own, 0, sizeof(psamd_update_result), c->stream));
+    // psamd_deposit's scratch and result record: a partial per workgroup of tasks at refine 4, the most there are (the
+    // compute cells are the plan's: fixed)
+    PS_HIP(c, dev_alloc(c, &c->dep.parts, ((size_t)comp_count(P) * 8 + DEPOSIT_WG_TASKS - 1) / DEPOSIT_WG_TASKS));
+    PS_HIP(c, dev_alloc(c, &c->dep.own, 1));
+    PS_HIP(c, hipMemsetAsync(c->dep.own, 0, sizeof(psamd_deposit_result), c->stream));
     return PSAMD_OK;
 }
 

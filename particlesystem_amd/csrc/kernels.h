@@ -131,6 +131,30 @@ struct ProbeScratch {
     psamd_probe_result *own;    // the context's own result record (psamd_probe_result_get)
 };
 
+// psamd_deposit (deposit.hip): the lattice, what the caller gave, and the scratch.  A task is (compute cell, block of at most
+// 2 x 2 x 2 voxels of it): 1, 1 or 8 tasks a cell for refine 1, 2, 4; four tasks to a workgroup, whose partials are one entry
+constexpr int DEPOSIT_WG_TASKS = 4;
+inline int deposit_cell_tasks(int refine) { return refine == 4 ? 8 : 1; }
+struct DepositArgs {
+    int32_t refine;   // k: voxels per cell edge (1, 2 or 4)
+    int32_t M;        // G * k voxels per axis
+    float inv_h;      // (float)((double)k / cell_size)
+    float off;        // (float)((G / 2) * k) - 0.5f
+    float top;        // (float)(M - 1)
+    float *out;       // [M^3] the lattice, voxel (n1, n2, n3) at (n3 * M + n1) * M + n2
+    psamd_deposit_result *result;   // the caller's record (may be null)
+};
+struct DepositPart {  // what a workgroup's (up to) four tasks saw, merged in task order
+    double mass;      // the tasks' voxel sums (fp64, before the rounding to float), in task and voxel order
+    float vmax;       // the largest float written; -inf: none
+    int bodies, skipped;    // of the tasks that count their own cell's list (a cell's first task)
+    int pad;
+};
+struct DepositScratch {
+    DepositPart *parts;     // [ceil(compute cells * 8 / 4)]: room for refine 4, sized at creation
+    psamd_deposit_result *own;    // the context's own result record (psamd_deposit_result_get)
+};
+
 // Container layout by segment type (slots and QUEUE_INFO records), device copy.
 struct SegLayout {
     int32_t seg_base[5];
@@ -327,6 +351,10 @@ hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceStat
 // psamd_probe (max_count > 0): locate + count, the cells' prefix, the cell-major order, the pair pass (one probe to a lane), the
 // result record
 hipError_t launch_probe(hipStream_t st, const DevParams &P, const DeviceState &d, const ProbeArgs &a, const ProbeScratch &s);
+
+// psamd_deposit: the gather over the compute cells' tasks, then the result record (mass, vmax and the counts over the
+// workgroups' partials in task order)
+hipError_t launch_deposit(hipStream_t st, const DevParams &P, const DeviceState &d, const DepositArgs &a, const DepositScratch &s);
 
 // psamd_inject: locate + rank, the records' prefix, the first queue failure, the placement, the commit of the queues and
 // the result record (max_count > 0)

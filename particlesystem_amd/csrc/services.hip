@@ -1,5 +1,5 @@
 // services.hip -- the host side of the on-stream services: psamd_export_live (export.hip), psamd_inject (inject.hip),
-// psamd_remove (remove.hip), psamd_update (update.hip), psamd_potential (potential.hip), psamd_probe (probe.hip), their host-array forms and their result records.
+// psamd_remove (remove.hip), psamd_update (update.hip), psamd_potential (potential.hip), psamd_probe (probe.hip), psamd_deposit (deposit.hip), their host-array forms and their result records.
 // A service enqueues its launches on the context's stream and returns; nothing here enqueues a stage of the step.
 #include "context.hpp"
 
@@ -413,5 +413,57 @@ int psamd_probe(psamd_ctx *c, const psamd_probe_spec *spec)
 }
 
 int psamd_probe_result_get(psamd_ctx *c, psamd_probe_result *out) { return read_own(c, out, c ? c->prb.own : nullptr, sizeof *out); }
+
+// ---- mass on a lattice (deposit.hip) ----
+// the lattice of refine k on this context's grid, or nothing (refine not 1, 2 or 4)
+static bool deposit_lattice(const psamd_ctx *c, int32_t refine, DepositArgs &a, int64_t &voxels)
+{
+    if (refine != 1 && refine != 2 && refine != 4) return false;
+    const int G = c->P.G;
+    a.refine = refine; a.M = G * refine;
+    a.inv_h = (float)((double)refine / c->P.cell_size);
+    a.off = (float)((G / 2) * refine) - 0.5f;
+    a.top = (float)(a.M - 1);
+    voxels = (int64_t)a.M * a.M * a.M;
+    return true;
+}
+
+int psamd_deposit(psamd_ctx *c, const psamd_deposit_spec *spec)
+{
+    PS_TRY(service_args(c, spec));
+    DepositArgs a{};
+    int64_t voxels = 0;
+    if (spec->flags != 0) return fail(c, PSAMD_ERR_INVALID_ARG, "deposit: flags must be 0");
+    if (!deposit_lattice(c, spec->refine, a, voxels)) return fail(c, PSAMD_ERR_INVALID_ARG, "deposit: refine is not 1, 2 or 4");
+    if (!spec->out || !aligned(spec->out, 4) || !aligned(spec->result_dev, 8))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "deposit: out missing or misaligned, or result_dev misaligned");
+    if (spec->capacity < voxels) return fail(c, PSAMD_ERR_INVALID_ARG, "deposit: capacity is less than (grid_dim * refine)^3");
+    PS_TRY(frame_ready(c, "deposit"));
+    a.out = spec->out; a.result = spec->result_dev;
+    PS_HIP(c, launch_deposit(c->stream, c->P, c->d, a, c->dep));
+    return PSAMD_OK;
+}
+
+int psamd_deposit_result_get(psamd_ctx *c, psamd_deposit_result *out) { return read_own(c, out, c ? c->dep.own : nullptr, sizeof *out); }
+
+// the same pass into the staging buffer, zeroed first: the voxels this rank does not serve are +0 in the host's array
+int psamd_download_deposit(psamd_ctx *c, int32_t refine, float *out, int64_t capacity, psamd_deposit_result *result)
+{
+    PS_TRY(service_args(c, out));
+    DepositArgs a{};
+    int64_t voxels = 0;
+    if (!deposit_lattice(c, refine, a, voxels)) return fail(c, PSAMD_ERR_INVALID_ARG, "download_deposit: refine is not 1, 2 or 4");
+    if (capacity < voxels) return fail(c, PSAMD_ERR_INVALID_ARG, "download_deposit: capacity is less than (grid_dim * refine)^3");
+    PS_TRY(frame_ready(c, "download_deposit"));
+    const size_t bytes = (size_t)voxels * sizeof(float);
+    PS_TRY(ensure_staging(c, std::max<size_t>(bytes, 256)));
+    PS_HIP(c, hipMemsetAsync(c->staging, 0, bytes, c->stream));
+    a.out = (float *)c->staging; a.result = nullptr;
+    PS_HIP(c, launch_deposit(c->stream, c->P, c->d, a, c->dep));
+    PS_HIP(c, hipMemcpyAsync(out, c->staging, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (result) PS_HIP(c, hipMemcpyAsync(result, c->dep.own, sizeof *result, hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    return PSAMD_OK;
+}
 
 }  // extern "C"

@@ -161,6 +161,12 @@ class Inject(C.Structure):
                 ("result_dev", C.c_void_p)]
 
 
+def _merge_counts(results, cls):
+    """every field of the ranks' records (dicts) added up"""
+    results = list(results)
+    return {n: sum(int(r[n]) for r in results) for n, _ in cls._fields_}
+
+
 # psamd_remove: the flags, and the outcome codes of the entries of a removal by id
 REMOVE_BOX, REMOVE_OUTSIDE = 0x1, 0x2
 REMOVED, REMOVE_NOT_LIVE, REMOVE_FOREIGN, REMOVE_INVALID, REMOVE_DROPPED = 0, 1, 2, 3, 4
@@ -181,8 +187,7 @@ class Remove(C.Structure):
 def merge_remove(results):
     """The result of a removal on a system from its ranks' (dicts of remove() / remove_result()): every count adds (by id
     each rank is given all entries, so `done` adds up to world * n)."""
-    results = list(results)
-    return {n: sum(int(r[n]) for r in results) for n, _ in RemoveResult._fields_}
+    return _merge_counts(results, RemoveResult)
 
 
 # psamd_update: the words an entry carries, the two modifiers, and the outcome codes of the entries
@@ -206,8 +211,7 @@ class Update(C.Structure):
 def merge_update(results):
     """The result of an update by id on a system from its ranks' (dicts of update() / update_result()): every count adds
     (each rank is given all entries, so `done` adds up to world * n)."""
-    results = list(results)
-    return {n: sum(int(r[n]) for r in results) for n, _ in UpdateResult._fields_}
+    return _merge_counts(results, UpdateResult)
 
 
 class PotentialResult(_Record):
@@ -497,6 +501,28 @@ def describe(cfg):
     return sizes, table, pkg, qi, q
 
 
+# ---- the services' Python front: a torch device tensor checked, as the pointer the C spec takes -------------------------------------
+def _tensor_ptr(who, t, dtype, shape, dev=None, what="tensor"):
+    """None for None; dev: the device the tensor must be on as well (where the service compares devices)"""
+    if t is None:
+        return None
+    assert t.is_cuda and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous() and (dev is None or t.device == dev), \
+        "%s: bad %s" % (who, what)
+    return t.data_ptr()
+
+
+def _count_ptr(who, count, dev=None):
+    """the one-element int64 device count"""
+    import torch
+    return _tensor_ptr(who, count, torch.int64, (1,), dev, "count tensor")
+
+
+def _outcome(m, dev):
+    """the int32 codes of m entries, -1 until the service writes them"""
+    import torch
+    return torch.full((max(m, 1),), -1, dtype=torch.int32, device=dev)
+
+
 class ParticleSystem:
     """One psamd context: the reference's nine buffers, resident on one MI355X."""
 
@@ -514,6 +540,12 @@ class ParticleSystem:
             raise PsamdError(st, msg)
         self.sizes = Sizes()
         self._ck(self.lib.psamd_get_sizes(self.h, C.byref(self.sizes)))
+
+    def _own_record(self, cls, fn):
+        """the record the context keeps of a service's last call, as a dict"""
+        r = cls()
+        self._ck(fn(self.h, C.byref(r)))
+        return r.to_dict()
 
     def _ck(self, st):
         if st != 0:
@@ -808,9 +840,7 @@ class ParticleSystem:
 
     def live_stats(self):
         """psamd_live_stats_get as a dict (momentum, mass_moment, lo, hi: float64 arrays of 3)"""
-        s = LiveStats()
-        self._ck(self.lib.psamd_live_stats_get(self.h, C.byref(s)))
-        return s.to_dict()
+        return self._own_record(LiveStats, self.lib.psamd_live_stats_get)
 
     # ---- putting particles in (include/psamd.h) --------------------------------
     def inject(self, pos4, vel4=None, fert_age=None, count=None, ids=False):
@@ -821,18 +851,12 @@ class ParticleSystem:
         import torch
         dev = pos4.device
         m = int(pos4.shape[0])
-
-        def ptr(t, dtype, shape):
-            if t is None:
-                return None
-            assert t.device == dev and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(), "inject: bad tensor"
-            return t.data_ptr()
         spec = Inject(max_count=m)
-        spec.pos4 = ptr(pos4, torch.float32, (m, 4))
-        spec.vel4 = ptr(vel4, torch.float32, (m, 4))
-        spec.fert_age = ptr(fert_age, torch.float32, (m,))
-        spec.count_dev = ptr(count, torch.int64, (1,))
-        out_ids = torch.full((max(m, 1),), -1, dtype=torch.int32, device=dev) if ids else None
+        spec.pos4 = _tensor_ptr("inject", pos4, torch.float32, (m, 4), dev)
+        spec.vel4 = _tensor_ptr("inject", vel4, torch.float32, (m, 4), dev)
+        spec.fert_age = _tensor_ptr("inject", fert_age, torch.float32, (m,), dev)
+        spec.count_dev = _tensor_ptr("inject", count, torch.int64, (1,), dev)
+        out_ids = _outcome(m, dev) if ids else None
         spec.ids_dev = None if out_ids is None else out_ids.data_ptr()
         with self._on_stream(dev):
             self._ck(self.lib.psamd_inject(self.h, C.byref(spec)))
@@ -843,9 +867,7 @@ class ParticleSystem:
 
     def inject_result(self):
         """psamd_inject_result_get: the last inject's {"done", "placed", "status"}"""
-        r = InjectResult()
-        self._ck(self.lib.psamd_inject_result_get(self.h, C.byref(r)))
-        return r.to_dict()
+        return self._own_record(InjectResult, self.lib.psamd_inject_result_get)
 
     # ---- taking particles out (include/psamd.h) ---------------------------------
     def remove(self, ids=None, count=None, box=None, outside=False, outcome=False):
@@ -867,14 +889,12 @@ class ParticleSystem:
         else:
             assert ids is not None and not outside, "remove: ids or box"
             m = int(ids.shape[0])
-            assert ids.dtype == torch.int32 and ids.dim() == 1 and ids.is_contiguous() and ids.is_cuda, "remove: bad ids tensor"
+            p = _tensor_ptr("remove", ids, torch.int32, (m,), what="ids tensor")
             spec.max_count = m
-            spec.ids = ids.data_ptr() if m > 0 else None
-            if count is not None:
-                assert count.dtype == torch.int64 and tuple(count.shape) == (1,) and count.is_cuda, "remove: bad count tensor"
-                spec.count_dev = count.data_ptr()
+            spec.ids = p if m > 0 else None
+            spec.count_dev = _count_ptr("remove", count)
             if outcome:
-                out = torch.full((max(m, 1),), -1, dtype=torch.int32, device=dev)
+                out = _outcome(m, dev)
                 spec.outcome_dev = out.data_ptr()
         with self._on_stream(dev):
             self._ck(self.lib.psamd_remove(self.h, C.byref(spec)))
@@ -885,9 +905,7 @@ class ParticleSystem:
 
     def remove_result(self):
         """psamd_remove_result_get: the last remove's record as a dict"""
-        r = RemoveResult()
-        self._ck(self.lib.psamd_remove_result_get(self.h, C.byref(r)))
-        return r.to_dict()
+        return self._own_record(RemoveResult, self.lib.psamd_remove_result_get)
 
     # ---- changing particles in place (include/psamd.h) --------------------------
     def update(self, ids=None, vel4=None, w=None, fert_age=None, age=False, add=False, count=None, outcome=False, *, fields=None):
@@ -907,10 +925,8 @@ class ParticleSystem:
         m = int(given[0].shape[0])
 
         def ptr(t, dtype, shape):
-            if t is None:
-                return None
-            assert t.is_cuda and t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous(), "update: bad tensor"
-            return t.data_ptr() if m > 0 else None
+            p = _tensor_ptr("update", t, dtype, shape)
+            return p if m > 0 else None
         if fields is None:
             fields = ((UPDATE_VEL if vel4 is not None else 0) | (UPDATE_AGE if age else 0) | (UPDATE_ADD if add else 0) |
                       (UPDATE_MASS if w is not None else 0) | (UPDATE_FERT if fert_age is not None else 0))
@@ -919,10 +935,8 @@ class ParticleSystem:
         spec.vel4 = ptr(vel4, torch.float32, (m, 4))
         spec.w = ptr(w, torch.float32, (m,))
         spec.fert_age = ptr(fert_age, torch.float32, (m,))
-        if count is not None:
-            assert count.dtype == torch.int64 and tuple(count.shape) == (1,) and count.is_cuda, "update: bad count tensor"
-            spec.count_dev = count.data_ptr()
-        out = torch.full((max(m, 1),), -1, dtype=torch.int32, device=dev) if outcome else None
+        spec.count_dev = _count_ptr("update", count)
+        out = _outcome(m, dev) if outcome else None
         spec.outcome_dev = None if out is None else out.data_ptr()
         with self._on_stream(dev):
             self._ck(self.lib.psamd_update(self.h, C.byref(spec)))
@@ -933,9 +947,7 @@ class ParticleSystem:
 
     def update_result(self):
         """psamd_update_result_get: the last update's record as a dict"""
-        r = UpdateResult()
-        self._ck(self.lib.psamd_update_result_get(self.h, C.byref(r)))
-        return r.to_dict()
+        return self._own_record(UpdateResult, self.lib.psamd_update_result_get)
 
     # ---- energy (include/psamd.h) -----------------------------------------------
     def potential(self, phi=False, capacity=None, far=False, *, quadrupole=False):
@@ -967,9 +979,7 @@ class ParticleSystem:
 
     def potential_result(self):
         """psamd_potential_result_get: the last potential call's record"""
-        r = PotentialResult()
-        self._ck(self.lib.psamd_potential_result_get(self.h, C.byref(r)))
-        return r.to_dict()
+        return self._own_record(PotentialResult, self.lib.psamd_potential_result_get)
 
     def download_potential(self, phi=True, capacity=None, far=False, *, quadrupole=False):
         """psamd_download_potential (far=True: psamd_download_potential_far; quadrupole=True: psamd_download_potential_flags
@@ -1014,15 +1024,13 @@ class ParticleSystem:
         import torch
         dev = pos4.device
         m = int(pos4.shape[0])
-        assert pos4.dtype == torch.float32 and tuple(pos4.shape) == (m, 4) and pos4.is_contiguous() and pos4.is_cuda, "probe: bad pos4 tensor"
+        p = _tensor_ptr("probe", pos4, torch.float32, (m, 4), what="pos4 tensor")
         spec = ProbeSpec(fields=(PROBE_ACC if acc else 0) | (PROBE_PHI if phi else 0) | (PROBE_FAR if far else 0) |
                          (PROBE_QUADRUPOLE if quadrupole else 0), max_count=m)
         out4 = torch.zeros((max(m, 1), 4), dtype=torch.float32, device=dev)
-        spec.pos4, spec.out4 = (pos4.data_ptr(), out4.data_ptr()) if m > 0 else (None, None)
-        if count is not None:
-            assert count.dtype == torch.int64 and tuple(count.shape) == (1,) and count.device == dev, "probe: bad count tensor"
-            spec.count_dev = count.data_ptr()
-        codes = torch.full((max(m, 1),), -1, dtype=torch.int32, device=dev) if outcome else None
+        spec.pos4, spec.out4 = (p, out4.data_ptr()) if m > 0 else (None, None)
+        spec.count_dev = _count_ptr("probe", count, dev)
+        codes = _outcome(m, dev) if outcome else None
         spec.outcome_dev = None if codes is None else codes.data_ptr()
         with self._on_stream(dev):
             self._ck(self.lib.psamd_probe(self.h, C.byref(spec)))
@@ -1034,9 +1042,7 @@ class ParticleSystem:
 
     def probe_result(self):
         """psamd_probe_result_get: the last probe's record as a dict"""
-        r = ProbeResult()
-        self._ck(self.lib.psamd_probe_result_get(self.h, C.byref(r)))
-        return r.to_dict()
+        return self._own_record(ProbeResult, self.lib.psamd_probe_result_get)
 
     # ---- mass on a lattice (include/psamd.h) ------------------------------------
     def deposit(self, refine=1, out=None, result=False):
@@ -1051,18 +1057,16 @@ class ParticleSystem:
         m = int(self.sizes.grid_dim) * int(refine)
         if out is None:
             out = torch.zeros((m, m, m), dtype=torch.float32, device=dev)
-        assert out.dtype == torch.float32 and tuple(out.shape) == (m, m, m) and out.is_contiguous() and out.is_cuda, "deposit: bad out tensor"
+        p = _tensor_ptr("deposit", out, torch.float32, (m, m, m), what="out tensor")
         rec = torch.zeros(C.sizeof(DepositResult), dtype=torch.uint8, device=dev)
-        spec = DepositSpec(flags=0, refine=int(refine), out=out.data_ptr(), capacity=out.numel(), result_dev=rec.data_ptr())
+        spec = DepositSpec(flags=0, refine=int(refine), out=p, capacity=out.numel(), result_dev=rec.data_ptr())
         with self._on_stream(dev):
             self._ck(self.lib.psamd_deposit(self.h, C.byref(spec)))
         return (out, DepositResult.from_device(rec).to_dict()) if result else out
 
     def deposit_result(self):
         """psamd_deposit_result_get: the last deposit's record as a dict"""
-        r = DepositResult()
-        self._ck(self.lib.psamd_deposit_result_get(self.h, C.byref(r)))
-        return r.to_dict()
+        return self._own_record(DepositResult, self.lib.psamd_deposit_result_get)
 
     def download_deposit(self, refine=1):
         """psamd_download_deposit, the numpy form of deposit(): (float32 array [M, M, M] of the whole lattice -- on a slab +0

@@ -17,7 +17,9 @@ host-side plumbing only; it computes nothing.  Three transports:
     pair-stage call, the halo travels beside the interior pass if that is asked for (overlap_interior).
   * ``HostRing``    torch.distributed P2P (gloo) through host copies of the messages: for tests,
     and for several processes that share one GPU.
-  * ``step_local``  all ranks live in one process (tests): messages are copied rank to rank.
+  * ``step_local``  all ranks live in one process (tests): messages are copied rank to rank.  Its three stages
+    (``to_pairs``, ``apply_stage``, ``finish_stage``) and their transports (``deliver``, ``gather``) are module-level,
+    for a caller that places a service between two stages or sends the messages of one phase alone.
 
 A "rank" is anything with the stage calls and ``msg_bytes / msg_download / msg_upload``
 (``particlesystem_amd.ParticleSystem``; the CPU tests drive a host stand-in the same way).
@@ -58,53 +60,71 @@ def _bytes(sysr, slot):
         return 0
 
 
-def step_local(ranks, overlap_interior=False, one_at_a_time=False, after_pairs=None, after_apply=None):
-    """One step of a whole system whose ranks all live in this process (tests).  one_at_a_time: a rank's build and pair stage
-    have run before the next rank's are enqueued (measurements: the ranks' streams otherwise share the one GPU, and a rank's
-    timers and kernel times hold another rank's work).  after_pairs / after_apply: called with the ranks once every rank has
-    run slab_pairs / slab_apply (a service placed inside the step: a probe, an update)."""
-    world = len(ranks)
+def deliver(ranks, phase):
+    """copy every message of the phase from its sender's outbox into the peer's inbox (fixed sizes: both must agree)"""
+    for r, sysr in enumerate(ranks):
+        for ph, out_slot, peer, in_slot in routes(r, len(ranks)):
+            n = _bytes(sysr, out_slot)
+            if ph != phase or n == 0:
+                continue
+            assert ranks[peer].msg_bytes(in_slot) == n, (phase, r, peer, n, ranks[peer].msg_bytes(in_slot))
+            ranks[peer].msg_upload(in_slot, sysr.msg_download(out_slot))
 
+
+def gather(ranks, out_slot, in_slot):
+    """an "all-gather": every rank's out slot, in rank order, into every rank's in slot"""
+    if len(ranks) > 1 and _bytes(ranks[0], out_slot):
+        every = np.concatenate([s.msg_download(out_slot) for s in ranks])
+        for s in ranks:
+            s.msg_upload(in_slot, every)
+
+
+def to_pairs(ranks, overlap_interior=False, one_at_a_time=False, before_pairs=None):
+    """The step up to and including slab_pairs on every rank.  before_pairs: called with no arguments once every message
+    of the pair stage has arrived, just before the slab_pairs calls."""
     def each(call):
         for s in ranks:
             call(s)
             if one_at_a_time:
                 s.msg_download(STATUS_OUT)     # (a download waits for the rank's stream, mid-frame too)
 
-    def deliver(phase):
-        for r, sysr in enumerate(ranks):
-            for ph, out_slot, peer, in_slot in routes(r, world):
-                n = _bytes(sysr, out_slot)
-                if ph != phase or n == 0:
-                    continue
-                assert ranks[peer].msg_bytes(in_slot) == n, (phase, r, peer, n, ranks[peer].msg_bytes(in_slot))
-                ranks[peer].msg_upload(in_slot, sysr.msg_download(out_slot))
-
-    def gather(out_slot, in_slot):                                                # the "all-gathers"
-        if world > 1 and _bytes(ranks[0], out_slot):
-            every = np.concatenate([s.msg_download(out_slot) for s in ranks])
-            for s in ranks:
-                s.msg_upload(in_slot, every)
-
     each(lambda s: s.slab_build())
-    gather(STATUS_OUT, STATUS_IN)             # before the first pair-stage call: its chunk census needs every rank's record
+    gather(ranks, STATUS_OUT, STATUS_IN)      # before the first pair-stage call: its chunk census needs every rank's record
     if overlap_interior:
         for s in ranks:
             s.slab_pairs_interior()   # (in a real run: while the halo travels)
-    deliver("halo")
-    gather(ALLG_OUT, ALLG_IN)
+    deliver(ranks, "halo")
+    gather(ranks, ALLG_OUT, ALLG_IN)
+    if before_pairs is not None:
+        before_pairs()
     each(lambda s: s.slab_pairs())
-    if after_pairs is not None:
-        after_pairs(ranks)
-    deliver("force")
+
+
+def apply_stage(ranks):
+    deliver(ranks, "force")
     for s in ranks:
         s.slab_apply()
-    if after_apply is not None:
-        after_apply(ranks)
-    deliver("xfer")
-    gather(FAR_OUT, FAR_IN)
+
+
+def finish_stage(ranks):
+    deliver(ranks, "xfer")
+    gather(ranks, FAR_OUT, FAR_IN)
     for s in ranks:
         s.slab_finish()
+
+
+def step_local(ranks, overlap_interior=False, one_at_a_time=False, after_pairs=None, after_apply=None):
+    """One step of a whole system whose ranks all live in this process (tests).  one_at_a_time: a rank's build and pair stage
+    have run before the next rank's are enqueued (measurements: the ranks' streams otherwise share the one GPU, and a rank's
+    timers and kernel times hold another rank's work).  after_pairs / after_apply: called with the ranks once every rank has
+    run slab_pairs / slab_apply (a service placed inside the step: a probe, an update)."""
+    to_pairs(ranks, overlap_interior, one_at_a_time)
+    if after_pairs is not None:
+        after_pairs(ranks)
+    apply_stage(ranks)
+    if after_apply is not None:
+        after_apply(ranks)
+    finish_stage(ranks)
 
 
 class _Ring:

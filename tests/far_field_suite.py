@@ -16,8 +16,9 @@ import torch
 
 import far_model as F
 import particlesystem_amd as ps
-from far_harness import (DEV, INVALID_ARG, STATE, UNSUPPORTED, bits, body_cloud, box_cloud, by_fill, fill_lists, hip_runtime, make, open_frame,
+from far_harness import (DEV, INVALID_ARG, STATE, UNSUPPORTED, bits, body_cloud, box_cloud, by_fill, fill_lists, make, open_frame,
                          pos4_of, record, served)
+from service_harness import captured
 from util import assert_same_particles
 
 MONO, PYR = ps.FLAG_FAR_MONOPOLE, ps.FLAG_FAR_PYRAMID
@@ -235,19 +236,14 @@ def the_calls_are_captured_into_a_graph_and_replay_on_a_later_frame(method):
     rec = torch.zeros(C.sizeof(ps.PotentialResult), dtype=torch.uint8, device=DEV)
     torch.cuda.synchronize()
     spec = ps.Potential(flags=row["pot"], phi=phi.data_ptr(), capacity=cap, result_dev=rec.data_ptr())
-    hip = hip_runtime()
-    stream = C.c_void_p(g.stream())
-    graph, exe = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamBeginCapture(stream, 2) == 0                      # hipStreamCaptureModeRelaxed
-    rc = g.lib.psamd_potential(g.h, C.byref(spec))
-    rp = g.lib.psamd_probe(g.h, C.byref(pspec)) if row["capture"] else 0
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0 and rc == 0 and rp == 0
-    assert hip.hipGraphInstantiate(C.byref(exe), graph, None, None, 0) == 0
+    with captured(g) as cap:
+        rc = g.lib.psamd_potential(g.h, C.byref(spec))
+        rp = g.lib.psamd_probe(g.h, C.byref(pspec)) if row["capture"] else 0
+    assert rc == 0 and rp == 0
     g.calc_forces()
     g.step(2)
     open_frame(g)                                                         # another frame: the graph holds nothing of the one it was captured in
-    assert hip.hipGraphLaunch(exe, stream) == 0
-    assert hip.hipStreamSynchronize(stream) == 0
+    cap.launch()
     replayed = ps.PotentialResult.from_buffer_copy(rec.cpu().numpy().tobytes()).to_dict()
     eager = g.potential(phi=True, **how)
     assert replayed == record(eager) == g.potential_result()
@@ -258,7 +254,7 @@ def the_calls_are_captured_into_a_graph_and_replay_on_a_later_frame(method):
         again = g.probe(pts, **how)
         assert probed == {k: again[k] for k in probed} and probed["served"] == m
         assert np.array_equal(bits(out4), bits(again["out4"])) and np.abs(out4.cpu().numpy()).min() > 0
-    assert hip.hipGraphExecDestroy(exe) == 0 and hip.hipGraphDestroy(graph) == 0
+    cap.close()
     g.calc_forces()
     g.synchronize()
     g.close()

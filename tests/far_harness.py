@@ -1,6 +1,6 @@
 """What the far-field suites share (far_force_suite.py, far_field_suite.py, test_gpu_far_*.py, test_far_*_cpu.py): the small
-contexts, one frame of any far context, the clouds, what the field services' tests read their results with (test_gpu_potential.py
-and test_gpu_probe.py take `bits` from here too), the two checks of a feature's C surface and the checks of the method without a
+contexts, one frame of any far context, the clouds, what the field services' tests read their results with, the two checks of a
+feature's C surface and the checks of the method without a
 GPU.  The numpy model is far_model.py."""
 import collections
 import ctypes
@@ -15,7 +15,9 @@ import torch
 
 import far_model as F
 import particlesystem_amd as ps
-from util import cloud, hip_runtime  # noqa: F401  (hip_runtime: for the suites that capture a far call into a graph)
+from service_harness import DEV, bits, open_frame  # noqa: F401  (for the suites)
+from service_harness import ERR_INVALID_ARG as INVALID_ARG, ERR_STATE as STATE, ERR_UNSUPPORTED as UNSUPPORTED  # noqa: F401
+from util import cloud
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -34,10 +36,6 @@ GRID = {4: dict(max_particles_num=16384, chunk_factor=1, chunk_dim=4),
 # ragged parent, and flat 125 blocks over 16 parts; 24^3: the grid of the benchmark's cloud at N = 2^22; 36^3: two odd levels below the
 # top (9 and 5).  About one body a cell or fewer: a wave's 64 served particles span a layer of cells or more
 DEEP = {20: (8000, [20, 10, 5, 3], 24), 24: (13824, [24, 12, 6, 3], 16), 32: (16384, [32, 16, 8, 4], 8), 36: (16000, [36, 18, 9, 5, 3], 8)}
-INVALID_ARG, STATE, UNSUPPORTED = 1, 8, 9
-
-DEV = torch.device("cuda", 0)
-
 Frame = collections.namedtuple("Frame", "order f lists mom cen")
 
 
@@ -45,11 +43,6 @@ def make(G, flags, **over):
     g = ps.ParticleSystem(ps.default_config(flags=flags, collision_radius=1e-6, **GRID[G], **over))
     assert g.sizes.grid_dim == G
     return g
-
-
-def open_frame(g):
-    """a frame up to the window of the on-stream services, before the pair stage"""
-    g.init_iframe(); g.build_grid()
 
 
 def frame(g, apply=True, slab=False):
@@ -258,11 +251,6 @@ def waves_of(cells, G):
 
 
 # ---- the field services' results (psamd_potential, psamd_probe) ----------------------------------------------------------------------
-
-def bits(a):
-    a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
 
 def by_fill(ids, phi):
     """phi pairs with the live particles in ascending slot id: back to the order of the fill"""

@@ -15,46 +15,16 @@ import torch
 import deposit_model as D
 import particlesystem_amd as ps
 from particlesystem_amd import slab
+from service_harness import DEV, ERR_INVALID_ARG, ERR_STATE, bits, captured, dev_read, open_frame, state
 
 pytestmark = pytest.mark.gpu
 
-ERR_INVALID_ARG, ERR_STATE = 1, 8
-DEV = torch.device("cuda", 0)
 CS = 5.0
 GRIDS = {8: dict(max_particles_num=16384, chunk_factor=2, chunk_dim=4),      # lists of 66
          9: dict(max_particles_num=16384, chunk_factor=3, chunk_dim=3),      # lists of 46; G / 2 = 4: the box is not centred
          16: dict(max_particles_num=16384, chunk_factor=4, chunk_dim=4, x_factor=8)}     # lists of 40
 QUIET = dict(collision_radius=1e-6, drag=0.0)          # nothing collides
 NAN_FILL = 0x7fc0dead                                # what no deposit writes
-
-
-def bits(a):
-    a = a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def hip_runtime():
-    """the HIP runtime torch loaded (the library is bound to the same copy)"""
-    for line in open("/proc/self/maps"):
-        if "libamdhip64.so" in line:
-            hip = C.CDLL(line.split()[-1])
-            break
-    else:
-        raise RuntimeError("no HIP runtime in this process")
-    vp = C.c_void_p
-    for name, args in (("hipStreamBeginCapture", [vp, C.c_int]), ("hipStreamEndCapture", [vp, C.POINTER(vp)]),
-                       ("hipGraphInstantiate", [C.POINTER(vp), vp, vp, vp, C.c_size_t]), ("hipGraphLaunch", [vp, vp]),
-                       ("hipStreamSynchronize", [vp]), ("hipGraphExecDestroy", [vp]), ("hipGraphDestroy", [vp]),
-                       ("hipMemcpy", [vp, vp, C.c_size_t, C.c_int])):
-        getattr(hip, name).restype = C.c_int
-        getattr(hip, name).argtypes = args
-    return hip
-
-
-def dev_read(ptr, count, dtype):
-    out = np.zeros(count, dtype)
-    assert hip_runtime().hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), out.nbytes, 2) == 0      # device to host
-    return out
 
 
 def snapshot(g):
@@ -69,11 +39,6 @@ def snapshot(g):
 
 def model(g, snap, refine, exact=False):
     return D.deposit(*snap, g.sizes.grid_dim, CS, g.sizes.max_per_cell, refine, exact=exact)
-
-
-def frame(g):
-    g.init_iframe()
-    g.build_grid()
 
 
 def rough_cloud(G, cap, seed=3):
@@ -138,7 +103,7 @@ def built(clouds):
                 a = int(live[np.nonzero(p["cell"][live] == 0)[0][0]])
                 p["x"][a] = np.nan
                 g.upload_particles(p[a:a + 1], first=a)
-            frame(g)
+            open_frame(g)
             made[G] = (g, snapshot(g))
         return made[G]
     yield get
@@ -195,13 +160,12 @@ def stepped(graphs, steps=3):
     g.fill_particles(xyz, age=rng.uniform(0.2, 9.0, n).astype(np.float32), fert_age=np.float32(1e6),
                      vxyz=rng.uniform(-8, 8, (n, 3)).astype(np.float32))
     g.step(steps)
-    frame(g)
+    open_frame(g)
     return g
 
 
 def state_of(g):
-    qi, q = g.download_queues()
-    return g.download_particles().tobytes(), qi.tobytes(), q.tobytes()
+    return [a.tobytes() for a in state(g)]
 
 
 @pytest.mark.parametrize("refine", D.REFINES)
@@ -213,19 +177,15 @@ def test_same_bytes_twice_through_a_graph_and_after_the_pair_stage(refine):
     assert ra["bodies"] > 3000 and np.array_equal(bits(a), bits(b)) and ra == rb
     assert state_of(g) == before, "the deposit touched particles or queues"
     # captured into a caller's graph (nothing is allocated by the call) and replayed
-    hip = hip_runtime()
     out2 = torch.full_like(a, float("nan"))
     rec = torch.zeros(C.sizeof(ps.DepositResult), dtype=torch.uint8, device=DEV)
-    torch.cuda.synchronize()
     spec = ps.DepositSpec(refine=refine, out=out2.data_ptr(), capacity=out2.numel(), result_dev=rec.data_ptr())
-    stream, graph, exe = C.c_void_p(g.stream()), C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamBeginCapture(stream, 2) == 0           # hipStreamCaptureModeRelaxed
-    rc = g.lib.psamd_deposit(g.h, C.byref(spec))
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0 and rc == 0
-    assert hip.hipGraphInstantiate(C.byref(exe), graph, None, None, 0) == 0
-    assert hip.hipGraphLaunch(exe, stream) == 0 and hip.hipStreamSynchronize(stream) == 0
+    with captured(g) as cap:
+        rc = g.lib.psamd_deposit(g.h, C.byref(spec))
+    assert rc == 0
+    cap.launch()
     assert np.array_equal(bits(out2), bits(a)) and ps.DepositResult.from_device(rec).to_dict() == ra
-    assert hip.hipGraphExecDestroy(exe) == 0 and hip.hipGraphDestroy(graph) == 0
+    cap.close()
     # after the pair stage: the same bytes, and the force records are left alone
     g.calc_forces_pairs()
     listed = int(g.download_cellgrid()[:, 0].sum())
@@ -253,7 +213,7 @@ KINDS = {"fast math": ps.FLAG_FAST_MATH, "all-pairs": ps.FLAG_ALL_PAIRS, "flat":
 def test_every_context_kind_returns_the_cutoff_bytes(clouds):
     def run(flags):
         g = system(8, clouds[8], flags)
-        frame(g)
+        open_frame(g)
         out = [g.deposit(k, result=True) for k in D.REFINES]
         g.calc_forces()
         g.synchronize()
@@ -267,40 +227,6 @@ def test_every_context_kind_returns_the_cutoff_bytes(clouds):
 
 
 # ---- 4. slabs ------------------------------------------------------------------------------------------------------------------
-
-def deliver(ranks, phase):
-    for r, s in enumerate(ranks):
-        for ph, out_slot, peer, in_slot in slab.routes(r, len(ranks)):
-            if ph == phase and s.msg_bytes(out_slot):
-                ranks[peer].msg_upload(in_slot, s.msg_download(out_slot))
-
-
-def gather(ranks, out_slot, in_slot):
-    if len(ranks) > 1 and ranks[0].msg_bytes(out_slot):
-        every = np.concatenate([s.msg_download(out_slot) for s in ranks])
-        for s in ranks:
-            s.msg_upload(in_slot, every)
-
-
-def slab_until_pairs(ranks):
-    for s in ranks:
-        s.slab_build()
-    gather(ranks, slab.STATUS_OUT, slab.STATUS_IN)
-    deliver(ranks, "halo")
-    gather(ranks, slab.ALLG_OUT, slab.ALLG_IN)
-    for s in ranks:
-        s.slab_pairs()
-
-
-def slab_rest(ranks):
-    deliver(ranks, "force")
-    for s in ranks:
-        s.slab_apply()
-    deliver(ranks, "xfer")
-    gather(ranks, slab.FAR_OUT, slab.FAR_IN)
-    for s in ranks:
-        s.slab_finish()
-
 
 def slab_cloud(G, n, seed=61):
     rng = np.random.default_rng(seed)
@@ -350,14 +276,15 @@ def test_slabs_give_the_single_context_bytes(world, cuts):
         if step:
             one.step(1)
             slab.step_local(ranks)
-        frame(one)
-        slab_until_pairs(ranks)
+        open_frame(one)
+        slab.to_pairs(ranks)
         for refine in D.REFINES:
             want, res = one.deposit(refine, result=True)
             assert res["voxels"] == (16 * refine) ** 3 and res["bodies"] > 7000
             union_of(ranks, refine, want, res)
         one.calc_forces()
-        slab_rest(ranks)
+        slab.apply_stage(ranks)
+        slab.finish_stage(ranks)
     assert sum(s.live_count() for s in ranks) == one.live_count() > 7000       # the steps went on
     one.close()
     for s in ranks:
@@ -376,15 +303,17 @@ def test_a_far_slab_is_served_and_the_step_after_matches_a_run_without_the_call(
     one = ps.ParticleSystem(ps.default_config(flags=flags, **GRIDS[8]))
     one.fill_particles(**inputs)
     with_call, without = world2(), world2()
-    frame(one)
-    slab_until_pairs(with_call)
-    slab_until_pairs(without)
+    open_frame(one)
+    slab.to_pairs(with_call)
+    slab.to_pairs(without)
     for refine in D.REFINES:
         want, res = one.deposit(refine, result=True)
         union_of(with_call, refine, want, res)
     one.calc_forces()
-    slab_rest(with_call)
-    slab_rest(without)
+    slab.apply_stage(with_call)
+    slab.finish_stage(with_call)
+    slab.apply_stage(without)
+    slab.finish_stage(without)
     slab.step_local(with_call)
     slab.step_local(without)
     for a, b in zip(with_call, without):
@@ -436,7 +365,7 @@ def test_window_and_arguments(clouds):
     g.calc_forces()
     assert call() == ERR_STATE                                    # the frame has ended
     g.step(1)
-    frame(g)
+    open_frame(g)
     assert call() == 0
     g.synchronize()
     g.close()
@@ -456,16 +385,14 @@ def test_a_slab_outside_its_window_is_refused():
     for s in ranks:
         s.slab_build()
     assert all(refused(s) for s in ranks)                        # before slab_pairs: the halos are not in yet
-    gather(ranks, slab.STATUS_OUT, slab.STATUS_IN)
-    deliver(ranks, "halo")
+    slab.gather(ranks, slab.STATUS_OUT, slab.STATUS_IN)
+    slab.deliver(ranks, "halo")
     for s in ranks:
         s.slab_pairs()
     assert sum(s.deposit(1, result=True)[1]["voxels"] for s in ranks) == 16 ** 3
-    deliver(ranks, "force")
-    for s in ranks:
-        s.slab_apply()
+    slab.apply_stage(ranks)
     assert all(refused(s) for s in ranks)                        # after slab_apply
-    deliver(ranks, "xfer")
+    slab.deliver(ranks, "xfer")
     for s in ranks:
         s.slab_finish()
     slab.step_local(ranks)                                        # the contexts stay usable

@@ -15,33 +15,13 @@ import torch
 import particlesystem_amd as ps
 from particlesystem_amd import _build as psbuild
 from particlesystem_amd.slab import step_local
-from util import GOLDEN, O, SENTINEL, capacities, cloud, explosion_rng, g2_cloud, oracle_cfg_from, ragged
+from service_harness import captured, host, start
+from util import GOLDEN, O, SENTINEL, capacities, cloud, g2_cloud, ragged
 
 pytestmark = pytest.mark.gpu
 
 ALL = ps.EXPORT_ALL
 SUMS = ("mass", "momentum", "kinetic", "mass_moment", "age_sum")
-
-
-def start(seed=11, graphs=False, run_ahead=1, oracle=False, **over):
-    """the G2 cloud with explosions: births, relocations and collisions from the first steps on"""
-    xyz = g2_cloud()
-    rng = np.random.default_rng(seed)
-    age = rng.uniform(2.0, 9.0, len(xyz)).astype(np.float32)
-    fert = rng.uniform(3.0, 12.0, len(xyz)).astype(np.float32)
-    v = rng.uniform(-20, 20, xyz.shape).astype(np.float32)
-    g = ps.ParticleSystem(ps.default_config(flags=ps.FLAG_EXPLOSIONS, seed=seed, **over))
-    g.set_graphs(graphs)
-    g.set_run_ahead(run_ahead)
-    g.fill_particles(xyz, age=age, fert_age=fert, vxyz=v)
-    if not oracle:
-        return g
-    o = O.System(oracle_cfg_from(g.cfg))
-    o.set_rng(explosion_rng(seed))
-    ids = o.fill(xyz, age=age, fert_age=fert)
-    p = o.particles
-    p["vx"][ids], p["vy"][ids], p["vz"][ids] = v.T
-    return g, o
 
 
 def sync(g):
@@ -59,10 +39,6 @@ def fields_of(rec):
             "vel4": np.stack([rec["vx"], rec["vy"], rec["vz"], rec["age"]], 1),
             "acc4": np.stack([rec["ax"], rec["ay"], rec["az"], rec["fertility_age"]], 1),
             "id": rec["id"].astype(np.int32), "cell": rec["cell"].astype(np.int32)}
-
-
-def host(a):
-    return a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
 def same_bits(a, b, what):
@@ -316,23 +292,6 @@ def test_slab_union_equals_the_single_context(world):
         s.close()
 
 
-def hip_runtime():
-    """the HIP runtime torch loaded (the library is bound to the same copy)"""
-    for line in open("/proc/self/maps"):
-        if "libamdhip64.so" in line:
-            hip = C.CDLL(line.split()[-1])
-            break
-    else:
-        raise RuntimeError("no HIP runtime in this process")
-    vp = C.c_void_p
-    for name, args in (("hipStreamBeginCapture", [vp, C.c_int]), ("hipStreamEndCapture", [vp, C.POINTER(vp)]),
-                       ("hipGraphInstantiate", [C.POINTER(vp), vp, vp, vp, C.c_size_t]), ("hipGraphLaunch", [vp, vp]),
-                       ("hipStreamSynchronize", [vp]), ("hipGraphExecDestroy", [vp]), ("hipGraphDestroy", [vp])):
-        getattr(hip, name).restype = C.c_int
-        getattr(hip, name).argtypes = args
-    return hip
-
-
 def test_export_follows_the_step_in_stream_order_and_replays_from_a_graph():
     g, o = start(seed=16, graphs=True, run_ahead=1, oracle=True)
     cap = g.owned_slots()
@@ -346,9 +305,7 @@ def test_export_follows_the_step_in_stream_order_and_replays_from_a_graph():
     # step 5 and the export back to back: no synchronisation in between
     assert g.lib.psamd_step(g.h, 5) == 0
     assert g.lib.psamd_export_live(g.h, C.byref(spec)) == 0
-    hip = hip_runtime()
-    stream = C.c_void_p(g.stream())
-    assert hip.hipStreamSynchronize(stream) == 0
+    sync(g)
     o.step(5)
     want = o.particles[o.particles["cell"] >= 0]
     n = int(count.item())
@@ -356,17 +313,14 @@ def test_export_follows_the_step_in_stream_order_and_replays_from_a_graph():
     same_bits(pos[:n], fields_of(want)["pos4"], "step 5: positions")
     same_bits(ids[:n], fields_of(want)["id"], "step 5: ids")
     # the export alone, captured into a graph on the context's stream (two kernel nodes, one after the other)
-    graph, exe = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamBeginCapture(stream, 2) == 0       # hipStreamCaptureModeRelaxed
-    rc = g.lib.psamd_export_live(g.h, C.byref(spec))
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0 and rc == 0
-    assert hip.hipGraphInstantiate(C.byref(exe), graph, None, None, 0) == 0
+    with captured(g) as cap:
+        rc = g.lib.psamd_export_live(g.h, C.byref(spec))
+    assert rc == 0
     g.step(1)
     count.fill_(-1)
     pos.fill_(0.0)
     torch.cuda.synchronize()
-    assert hip.hipGraphLaunch(exe, stream) == 0
-    assert hip.hipStreamSynchronize(stream) == 0
+    cap.launch()
     got = g.download_live(ps.EXPORT_POS | ps.EXPORT_ID)
     n = int(count.item())
     assert n == got["count"]
@@ -374,7 +328,7 @@ def test_export_follows_the_step_in_stream_order_and_replays_from_a_graph():
     same_bits(ids[:n], got["id"], "graph replay after step 6: ids")
     o.step(1)
     assert n == int((o.particles["cell"] >= 0).sum())
-    assert hip.hipGraphExecDestroy(exe) == 0 and hip.hipGraphDestroy(graph) == 0
+    cap.close()
     g.close(); o.close()
 
 

@@ -12,7 +12,7 @@ import pytest
 import particlesystem_amd as ps
 from far_harness import GRID, INVALID_ARG, UNSUPPORTED, box_cloud, status_of_create
 from particlesystem_amd import slab
-from particlesystem_amd.slab import merge_owned, step_local
+from particlesystem_amd.slab import apply_stage, finish_stage, merge_owned, step_local, to_pairs
 from util import assert_same_particles
 
 pytestmark = pytest.mark.gpu
@@ -103,47 +103,6 @@ def test_union_of_far_slabs_is_one_context_every_step(method, G, world, cuts):
     close(*ranks)
 
 
-# ---- the step cut open: up to the pair stage, and the rest ---------------------------------------------------------------------
-
-def deliver(ranks, phase):
-    for r, g in enumerate(ranks):
-        for ph, out_slot, peer, in_slot in slab.routes(r, len(ranks)):
-            if ph == phase and g.msg_bytes(out_slot):
-                ranks[peer].msg_upload(in_slot, g.msg_download(out_slot))
-
-
-def gather(ranks, out_slot, in_slot):
-    if ranks[0].msg_bytes(out_slot):
-        every = np.concatenate([g.msg_download(out_slot) for g in ranks])
-        for g in ranks:
-            g.msg_upload(in_slot, every)
-
-
-def to_the_pair_stage(ranks, spoil=None):
-    for g in ranks:
-        g.slab_build()
-    gather(ranks, slab.STATUS_OUT, slab.STATUS_IN)
-    deliver(ranks, "halo")
-    gather(ranks, slab.ALLG_OUT, slab.ALLG_IN)
-    if spoil:
-        spoil()
-    for g in ranks:
-        g.slab_pairs()
-
-
-def apply_stage(ranks):
-    deliver(ranks, "force")
-    for g in ranks:
-        g.slab_apply()
-
-
-def finish_stage(ranks):
-    deliver(ranks, "xfer")
-    gather(ranks, slab.FAR_OUT, slab.FAR_IN)
-    for g in ranks:
-        g.slab_finish()
-
-
 # ---- 2. the moments on every rank ---------------------------------------------------------------------------------------------------
 
 def moments_of(g):
@@ -166,7 +125,7 @@ def test_every_rank_holds_the_moments_of_one_context(method, G, world, cuts, sig
     one.init_iframe(); one.build_grid(); one.calc_forces_pairs()
     want = moments_of(one)
     ranks, _ = slabs(G, world, cuts, flags, force_sign=sign)
-    to_the_pair_stage(ranks)
+    to_pairs(ranks)
     for r, g in enumerate(ranks):
         got = moments_of(g)
         assert sorted(got) == sorted(want)
@@ -210,7 +169,7 @@ def test_force_records_of_every_computed_cell_are_one_contexts(method, G, world,
     want = records_by_slot(one)
     assert one.counters["cell_overflow_kills"] == 0
     ranks, plans = slabs(G, world, cuts, flags)
-    to_the_pair_stage(ranks)
+    to_pairs(ranks)
     own = lent = 0
     for g, p in zip(ranks, plans):
         got = records_by_slot(g, (max(p.cut_lo, p.state_lo), min(p.cut_hi, p.state_hi)))
@@ -329,7 +288,7 @@ def test_a_block_left_out_is_loud():
         ranks[1].msg_upload(ps.MSG_ALLG_IN, words)
 
     with pytest.raises(ps.PsamdError, match="does not match"):
-        to_the_pair_stage(ranks, spoil)
+        to_pairs(ranks, before_pairs=spoil)
         apply_stage(ranks); finish_stage(ranks)
         for g in ranks:
             g.synchronize()
@@ -349,7 +308,7 @@ def test_services_are_refused_and_the_step_completes(method):
     want, _ = one_context_steps(G, flags)
     ranks, plans = slabs(G, world, None, flags)
     quad = method == "quadrupole"
-    to_the_pair_stage(ranks)
+    to_pairs(ranks)
     for g in ranks:
         with pytest.raises(ps.PsamdError) as e:
             g.potential(far=True, quadrupole=quad)

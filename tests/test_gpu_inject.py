@@ -12,90 +12,11 @@ import torch
 
 import particlesystem_amd as ps
 from particlesystem_amd.slab import merge_owned, step_local
-from util import O, assert_same_particles, cloud, explosion_rng, g2_cloud, oracle_cfg_from
+from service_harness import (DEV, ERR_INVALID_ARG, ERR_OUTSIDE_BOX, ERR_QUEUE_EMPTY, ERR_STATE, OK, batch, captured, dev, fill, inject,
+                             many_records, same_as_fill, same_state, start)
+from util import assert_same_particles, cloud
 
 pytestmark = pytest.mark.gpu
-
-OK, INVALID, OUTSIDE, QEMPTY, STATE = 0, 1, 5, 6, 8
-DEV = torch.device("cuda", 0)
-
-
-def start(seed=11, graphs=False, run_ahead=1, oracle=False, **over):
-    """the G2 cloud with explosions (as tests/test_gpu_export.py starts): births, relocations and collisions at once"""
-    xyz = g2_cloud()
-    rng = np.random.default_rng(seed)
-    age = rng.uniform(2.0, 9.0, len(xyz)).astype(np.float32)
-    fert = rng.uniform(3.0, 12.0, len(xyz)).astype(np.float32)
-    v = rng.uniform(-20, 20, xyz.shape).astype(np.float32)
-    over.setdefault("flags", ps.FLAG_EXPLOSIONS)
-    g = ps.ParticleSystem(ps.default_config(seed=seed, **over))
-    g.set_graphs(graphs)
-    g.set_run_ahead(run_ahead)
-    g.fill_particles(xyz, age=age, fert_age=fert, vxyz=v)
-    if not oracle:
-        return g
-    o = O.System(oracle_cfg_from(g.cfg))
-    o.set_rng(explosion_rng(seed))
-    ids = o.fill(xyz, age=age, fert_age=fert)
-    p = o.particles
-    p["vx"][ids], p["vy"][ids], p["vz"][ids] = v.T
-    return g, o
-
-
-def batch(g, n, seed):
-    """n entries inside the box: pos4 (x, y, z, w), vel4 (vx, vy, vz, age), fert_age -- numpy float32"""
-    rng = np.random.default_rng(seed)
-    xyz = g.uniform_cloud(n, seed)
-    pos4 = np.concatenate([xyz, rng.uniform(0.5, 2.0, (n, 1)).astype(np.float32)], 1)
-    vel4 = np.concatenate([rng.uniform(-20, 20, (n, 3)), rng.uniform(0.0, 9.0, (n, 1))], 1).astype(np.float32)
-    fert = rng.uniform(3.0, 12.0, n).astype(np.float32)
-    return np.ascontiguousarray(pos4), np.ascontiguousarray(vel4), fert
-
-
-def fill(g, pos4, vel4=None, fert=None):
-    """psamd_fill_particles of the same entries: (status, done, ids[:done])"""
-    n = len(pos4)
-    xyz = np.ascontiguousarray(pos4[:, :3])
-    w = np.ascontiguousarray(pos4[:, 3])
-    vxyz = None if vel4 is None else np.ascontiguousarray(vel4[:, :3])
-    age = None if vel4 is None else np.ascontiguousarray(vel4[:, 3])
-    fert = None if fert is None else np.ascontiguousarray(fert)
-    ids = np.full(max(n, 1), -7, np.int32)
-    done = C.c_int64(-1)
-    st = g.lib.psamd_fill_particles(g.h, n, ps._ptr(xyz), ps._ptr(vxyz), ps._ptr(w), ps._ptr(age), ps._ptr(fert),
-                                    ps._ptr(ids), C.byref(done))
-    return st, done.value, ids[:done.value]
-
-
-def dev(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def inject(g, pos4, vel4=None, fert=None, count=None):
-    r = g.inject(dev(pos4), dev(vel4), dev(fert), count=count, ids=True)
-    r["ids"] = r["ids"].cpu().numpy()
-    return r
-
-
-def state(g):
-    qi, q = g.download_queues()
-    return g.download_particles(), qi, q
-
-
-def same_state(a, b, what):
-    pa, qia, qa = state(a)
-    pb, qib, qb = state(b)
-    assert_same_particles(pa, pb, what + ": particles")
-    assert qia.tobytes() == qib.tobytes(), what + ": QUEUE_INFO records differ"
-    assert np.array_equal(qa, qb), what + ": queues differ"
-
-
-def same_as_fill(f, r, what, placed=None):
-    st, done, ids = f
-    assert (r["status"], r["done"]) == (st, done), (what, r, st, done)
-    assert np.array_equal(r["ids"][:done], ids), what + ": ids"
-    assert (r["ids"][done:] == -1).all(), what + ": ids at and after the stop"
-    assert r["placed"] == (int((ids >= 0).sum()) if placed is None else placed), (what, r["placed"])
 
 
 @pytest.mark.parametrize("graphs", [False, True])
@@ -168,7 +89,7 @@ def test_stops_where_fill_stops():
         pos4[i, :3] = bad
         f = fill(a, pos4, vel4, fert)
         r = inject(b, pos4, vel4, fert)
-        assert f[0] == OUTSIDE and f[1] == i, (k, f[:2])
+        assert f[0] == ERR_OUTSIDE_BOX and f[1] == i, (k, f[:2])
         same_as_fill(f, r, "outside entry %r at %d" % (bad, i))
         same_state(a, b, "outside entry %r at %d" % (bad, i))
         base, vel4, fert = batch(a, 9000, 20 + k)
@@ -184,7 +105,7 @@ def test_stops_where_fill_stops():
     fert = rng.uniform(3.0, 12.0, len(pos4)).astype(np.float32)
     f = fill(a, pos4, vel4, fert)
     r = inject(b, pos4, vel4, fert)
-    assert f[0] == QEMPTY and 500 <= f[1] < 500 + m, f[:2]
+    assert f[0] == ERR_QUEUE_EMPTY and 500 <= f[1] < 500 + m, f[:2]
     same_as_fill(f, r, "queue runs empty")
     same_state(a, b, "queue runs empty")
     a.step(3)
@@ -318,21 +239,6 @@ def test_export_round_trip():
         g.close()
 
 
-def hip_runtime():
-    for line in open("/proc/self/maps"):
-        if "libamdhip64.so" in line:
-            hip = C.CDLL(line.split()[-1])
-            break
-    else:
-        raise RuntimeError("no HIP runtime in this process")
-    vp = C.c_void_p
-    for name, args in (("hipStreamBeginCapture", [vp, C.c_int]), ("hipStreamEndCapture", [vp, C.POINTER(vp)]),
-                       ("hipGraphGetNodes", [vp, vp, C.POINTER(C.c_size_t)]), ("hipGraphDestroy", [vp])):
-        getattr(hip, name).restype = C.c_int
-        getattr(hip, name).argtypes = args
-    return hip
-
-
 def test_arguments_and_capture():
     a, b = start(seed=18), start(seed=18)
     a.step(1)
@@ -351,13 +257,13 @@ def test_arguments_and_capture():
             setattr(s, k, v)
         return s
     lib = b.lib
-    assert lib.psamd_inject(None, C.byref(spec())) == INVALID
-    assert lib.psamd_inject(b.h, None) == INVALID
+    assert lib.psamd_inject(None, C.byref(spec())) == ERR_INVALID_ARG
+    assert lib.psamd_inject(b.h, None) == ERR_INVALID_ARG
     for bad in (dict(flags=1), dict(reserved=1), dict(max_count=-1), dict(max_count=1 << 31), dict(pos4=None),
                 dict(pos4=raw.data_ptr() + 4), dict(vel4=raw.data_ptr() + 8), dict(fert_age=tf.data_ptr() + 2),
                 dict(ids_dev=ids.data_ptr() + 2), dict(result_dev=res.data_ptr() + 4), dict(count_dev=cnt.data_ptr() + 4)):
-        assert lib.psamd_inject(b.h, C.byref(spec(**bad))) == INVALID, bad
-    assert lib.psamd_inject_result_get(b.h, None) == INVALID
+        assert lib.psamd_inject(b.h, C.byref(spec(**bad))) == ERR_INVALID_ARG, bad
+    assert lib.psamd_inject_result_get(b.h, None) == ERR_INVALID_ARG
     # max_count == 0: a zero result, nothing else
     r0 = inject(b, pos4, vel4, fert)
     assert r0["done"] == 1000
@@ -369,17 +275,12 @@ def test_arguments_and_capture():
     assert res[:3].cpu().tolist() == [0, 0, 0]
     same_state(a, b, "max_count 0")
     # capture: refused, the graph stays empty, the state untouched
-    hip = hip_runtime()
-    stream = C.c_void_p(b.stream())
-    graph = C.c_void_p()
-    assert hip.hipStreamBeginCapture(stream, 2) == 0       # hipStreamCaptureModeRelaxed
-    rc = lib.psamd_inject(b.h, C.byref(spec()))
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0
-    assert rc == STATE, rc
+    with captured(b) as cap:
+        rc = lib.psamd_inject(b.h, C.byref(spec()))
+    assert rc == ERR_STATE, rc
     assert b"captured" in lib.psamd_last_error(b.h)
-    nodes = C.c_size_t(99)
-    assert hip.hipGraphGetNodes(graph, None, C.byref(nodes)) == 0 and nodes.value == 0
-    assert hip.hipGraphDestroy(graph) == 0
+    assert cap.nodes() == 0
+    cap.close()
     same_state(a, b, "after the refused capture")
     a.step(2)
     b.step(2)
@@ -388,17 +289,7 @@ def test_arguments_and_capture():
         g.close()
 
 
-# ---- more queue records than the tile's counts have room for in LDS ---------------------------------------------------------
-# queue_infos = (2 * chunk_factor + 1)^3 = 9261 > 8192: the tile counts live in the tile's row in global memory
-
-MANY_RECORDS = dict(chunk_factor=10, chunk_dim=3, x_factor=2, max_particles_num=27000)
-
-
-def many_records():
-    g = ps.ParticleSystem(ps.default_config(**MANY_RECORDS))
-    assert g.sizes.queue_info_size > 8192, g.sizes.queue_info_size
-    return g
-
+# ---- more queue records than the tile's counts have room for in LDS (service_harness.many_records) -------------------------------
 
 def test_more_than_8192_queue_records():
     a, b = many_records(), many_records()

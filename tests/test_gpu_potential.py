@@ -20,24 +20,14 @@ import pytest
 import torch
 
 import particlesystem_amd as ps
-from far_harness import bits
 from particlesystem_amd import slab
-from util import SENTINEL, capacities, cloud, hip_runtime, ragged
+from service_harness import ERR_INVALID_ARG, ERR_STATE, ERR_UNSUPPORTED, bits, captured, kid_age, open_frame, slab_inputs
+from util import SENTINEL, capacities, cloud, ragged
 
 pytestmark = pytest.mark.gpu
 
 REL = 1e-5
-ERR_INVALID_ARG, ERR_STATE, ERR_UNSUPPORTED = 1, 8, 9
 SMALL = dict(chunk_factor=2, chunk_dim=4)          # an 8^3 grid of 5-unit cells: the box is [-20, 20)^3
-
-
-def kid_age(cfg):
-    return cfg.life_steps * cfg.dt / 10.0           # KID_AGE = PARTICLE_LIFE / 10, PARTICLE_LIFE = 300 * DT (common.h:58-59)
-
-
-def frame(g):
-    g.init_iframe()
-    g.build_grid()
 
 
 def by_id(g, res=None, capacity=None):
@@ -131,7 +121,7 @@ def pair_system(extra=(), **over):
     xyz = np.array([(1.0, 1.0, 1.0), (2.5, 1.0, 1.0)] + [e[0] for e in extra], np.float32)
     age = np.array([3.0, 3.0] + [e[1] for e in extra], np.float32)
     ids = g.fill_particles(xyz, age=age, fert_age=np.float32(1e6))
-    frame(g)
+    open_frame(g)
     return g, ids
 
 
@@ -191,7 +181,7 @@ def test_uniform_cloud_against_the_fp64_direct_sum(per_cell):
     age = rng.uniform(0.2, 9.0, n).astype(np.float32)            # one in seven is a kid
     w = rng.uniform(20.0, 100.0, n).astype(np.float32)
     g.fill_particles(cloud(n, 40 + per_cell, 20.0), age=age, w=w, fert_age=np.float32(1e6))
-    frame(g)
+    open_frame(g)
     phi, ids, res = by_id(g)
     fr = Frame(g)
     assert res["listed"] == g.live_count() == len(ids) == n
@@ -212,7 +202,7 @@ def test_clump_that_fills_cells_to_their_capacity():
     clump = np.concatenate([c + rng.uniform(0.05, 4.95, (cap + 6, 3)) for c in corner])      # six more than each list holds
     xyz = np.concatenate([clump, cloud(3000, 6)]).astype(np.float32)
     g.fill_particles(xyz, age=np.float32(3.0), fert_age=np.float32(1e6))
-    frame(g)
+    open_frame(g)
     phi, ids, res = by_id(g)
     fr = Frame(g)
     assert (fr.count == cap).sum() >= 8 and g.counters["cell_overflow_kills"] >= 48
@@ -229,7 +219,7 @@ def test_phi_pairs_with_the_export_entry_for_entry():
     xyz = cloud(n, 7)
     g.fill_particles(xyz, age=np.float32(3.0), fert_age=np.float32(1e6), vxyz=cloud(n, 8, 30.0))
     g.step(3)                                                   # collisions free slots: the live ids are no longer 0..n-1 in fill order
-    frame(g)
+    open_frame(g)
     res = g.potential(phi=True)
     ex = g.export_live(ps.EXPORT_ID | ps.EXPORT_POS)
     live = g.live_count()
@@ -258,7 +248,7 @@ def stepped(graphs, steps=4, n=60000):
     g.set_graphs(graphs)
     g.fill_particles(cloud(n, 21), age=np.float32(3.0), fert_age=np.float32(1e6), vxyz=cloud(n, 22, 20.0))
     g.step(steps)
-    frame(g)
+    open_frame(g)
     return g
 
 
@@ -287,24 +277,19 @@ def test_the_call_is_captured_into_a_graph_and_replays_on_a_later_frame():
     rec = torch.zeros(C.sizeof(ps.PotentialResult), dtype=torch.uint8, device=dev)
     torch.cuda.synchronize()
     spec = ps.Potential(phi=phi.data_ptr(), capacity=cap, result_dev=rec.data_ptr())
-    hip = hip_runtime()
-    stream = C.c_void_p(g.stream())
-    graph, exe = C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamBeginCapture(stream, 2) == 0       # hipStreamCaptureModeRelaxed
-    rc = g.lib.psamd_potential(g.h, C.byref(spec))
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0 and rc == 0
-    assert hip.hipGraphInstantiate(C.byref(exe), graph, None, None, 0) == 0
+    with captured(g) as cap:
+        rc = g.lib.psamd_potential(g.h, C.byref(spec))
+    assert rc == 0
     g.calc_forces()
     g.step(2)
-    frame(g)                                                    # another frame: the graph holds nothing of the one it was captured in
-    assert hip.hipGraphLaunch(exe, stream) == 0
-    assert hip.hipStreamSynchronize(stream) == 0
+    open_frame(g)                                                    # another frame: the graph holds nothing of the one it was captured in
+    cap.launch()
     replayed = ps.PotentialResult.from_buffer_copy(rec.cpu().numpy().tobytes()).to_dict()
     eager = g.potential(phi=True)
     assert replayed == {k: eager[k] for k in eager if k != "phi"} == g.potential_result()
     assert replayed["listed"] == len(eager["phi"]) > 0
     assert np.array_equal(bits(phi[:len(eager["phi"])]), bits(eager["phi"]))
-    assert hip.hipGraphExecDestroy(exe) == 0 and hip.hipGraphDestroy(graph) == 0
+    cap.close()
     g.calc_forces()
     g.synchronize()
     g.close()
@@ -319,7 +304,7 @@ def test_all_pairs_cloud_inside_a_block_of_cells_is_the_cutoff_result():
     for flags in (0, ps.FLAG_ALL_PAIRS):
         g = ps.ParticleSystem(ps.default_config(max_particles_num=1 << 18, flags=flags))
         g.fill_particles(xyz, age=np.float32(3.0), fert_age=np.float32(1e6))
-        frame(g)
+        open_frame(g)
         got.append(g.potential(phi=True))
         assert (Frame(g).count > 0).sum() == 8
         g.close()
@@ -358,7 +343,7 @@ def test_all_pairs_spread_cloud_against_the_fp64_direct_sum():
     g = ps.ParticleSystem(ps.default_config(max_particles_num=n, flags=ps.FLAG_ALL_PAIRS))
     w = np.random.default_rng(32).uniform(20.0, 100.0, n).astype(np.float32)
     g.fill_particles(cloud(n, 33), age=np.float32(3.0), w=w, fert_age=np.float32(1e6))
-    frame(g)
+    open_frame(g)
     phi, ids, res = by_id(g)
     fr = Frame(g)
     assert res["listed"] == n == len(fr.listed) and res["nonfinite"] == 0
@@ -382,7 +367,7 @@ def test_a_particle_whose_position_is_no_number():
     victim = int(np.nonzero(p["cell"] == 0)[0][0])              # cell 0 is where the reference files such a position (grid.hip, k_unpack_aos)
     p["x"][victim] = p["y"][victim] = p["z"][victim] = np.nan
     g.upload_particles(p)
-    frame(g)
+    open_frame(g)
     phi, ids, res = by_id(g)
     fr = Frame(g)
     ref = fr.phi_cutoff()
@@ -398,51 +383,9 @@ def test_a_particle_whose_position_is_no_number():
 
 # ---- slabs ------------------------------------------------------------------------------------------------------------
 
-def slab_until_pairs(ranks):
-    """particlesystem_amd.slab.step_local up to and including slab_pairs"""
-    world = len(ranks)
-    for s in ranks:
-        s.slab_build()
-    gather(ranks, slab.STATUS_OUT, slab.STATUS_IN)
-    deliver(ranks, "halo")
-    gather(ranks, slab.ALLG_OUT, slab.ALLG_IN)
-    for s in ranks:
-        s.slab_pairs()
-    return world
-
-
-def slab_rest(ranks):
-    deliver(ranks, "force")
-    for s in ranks:
-        s.slab_apply()
-    deliver(ranks, "xfer")
-    gather(ranks, slab.FAR_OUT, slab.FAR_IN)
-    for s in ranks:
-        s.slab_finish()
-
-
-def deliver(ranks, phase):
-    for r, s in enumerate(ranks):
-        for ph, out_slot, peer, in_slot in slab.routes(r, len(ranks)):
-            if ph == phase and s.msg_bytes(out_slot):
-                ranks[peer].msg_upload(in_slot, s.msg_download(out_slot))
-
-
-def gather(ranks, out_slot, in_slot):
-    if len(ranks) > 1 and ranks[0].msg_bytes(out_slot):
-        every = np.concatenate([s.msg_download(out_slot) for s in ranks])
-        for s in ranks:
-            s.msg_upload(in_slot, every)
-
-
-def slab_inputs(n=50000):
-    rng = np.random.default_rng(61)
-    return cloud(n, 61), rng.uniform(0.2, 9.0, n).astype(np.float32), cloud(n, 62, 20.0)
-
-
 @pytest.mark.parametrize("cuts,flags", [([0, 7, 16], 0), ([0, 3, 7, 11, 16], 0), ([0, 7, 16], ps.FLAG_ALL_PAIRS)])
 def test_slabs_give_the_single_context_bytes(cuts, flags):
-    xyz, age, v = slab_inputs(50000 if not flags else 20000)
+    xyz, age, v = slab_inputs(50000 if not flags else 20000, 61)
     over = dict(flags=flags, max_particles_num=1 << 18) if flags else dict(flags=flags)
     one = ps.ParticleSystem(ps.default_config(**over))
     one.fill_particles(xyz, age=age, fert_age=np.float32(1e6), vxyz=v)
@@ -454,9 +397,9 @@ def test_slabs_give_the_single_context_bytes(cuts, flags):
         if step:
             one.step(1)
             slab.step_local(ranks)
-        frame(one)
+        open_frame(one)
         want, ids, res = by_id(one)
-        slab_until_pairs(ranks)
+        slab.to_pairs(ranks)
         union = np.full(one.sizes.container_size, np.nan, np.float32)
         parts, seen = [], 0
         for s in ranks:
@@ -474,25 +417,27 @@ def test_slabs_give_the_single_context_bytes(cuts, flags):
         assert merged["phi_min"] == res["phi_min"] and merged["phi_max"] == res["phi_max"]
         assert abs(merged["potential"] - res["potential"]) <= 1e-12 * abs(res["potential"]), (merged, res)
         one.calc_forces()
-        slab_rest(ranks)
+        slab.apply_stage(ranks)
+        slab.finish_stage(ranks)
     one.close()
     for s in ranks:
         s.close()
 
 
 def test_a_plan_that_lends_a_layer_is_refused_and_the_step_goes_on():
-    xyz, age, v = slab_inputs(30000)
+    xyz, age, v = slab_inputs(30000, 61)
     ranks = [ps.ParticleSystem(ps.default_config(rank=r, world=2, cuts=[0, 8, 16])) for r in range(2)]
     plans = [s.slab_plan() for s in ranks]
     assert plans[0].lentout_lo < plans[0].lentout_hi and plans[1].lentin_lo < plans[1].lentin_hi
     for s in ranks:
         s.fill_particles(xyz, age=age, fert_age=np.float32(1e6), vxyz=v)
-    slab_until_pairs(ranks)
+    slab.to_pairs(ranks)
     for s in ranks:
         with pytest.raises(ps.PsamdError) as e:
             s.potential()
         assert e.value.status == ERR_UNSUPPORTED and "plan" in str(e.value)
-    slab_rest(ranks)
+    slab.apply_stage(ranks)
+    slab.finish_stage(ranks)
     slab.step_local(ranks)
     for s in ranks:
         s.synchronize()
@@ -502,7 +447,7 @@ def test_a_plan_that_lends_a_layer_is_refused_and_the_step_goes_on():
 
 
 def test_a_slab_outside_its_window_is_refused():
-    xyz, age, v = slab_inputs(20000)
+    xyz, age, v = slab_inputs(20000, 61)
     ranks = [ps.ParticleSystem(ps.default_config(rank=r, world=2, cuts=[0, 7, 16])) for r in range(2)]
     for s in ranks:
         s.fill_particles(xyz, age=age, fert_age=np.float32(1e6), vxyz=v)
@@ -515,16 +460,14 @@ def test_a_slab_outside_its_window_is_refused():
     for s in ranks:
         s.slab_build()
     assert all(refused(s) for s in ranks)                        # the halos are not in yet
-    gather(ranks, slab.STATUS_OUT, slab.STATUS_IN)
-    deliver(ranks, "halo")
+    slab.gather(ranks, slab.STATUS_OUT, slab.STATUS_IN)
+    slab.deliver(ranks, "halo")
     for s in ranks:
         s.slab_pairs()
     assert all(s.potential()["listed"] > 0 for s in ranks)
-    deliver(ranks, "force")
-    for s in ranks:
-        s.slab_apply()
+    slab.apply_stage(ranks)
     assert all(refused(s) for s in ranks)
-    deliver(ranks, "xfer")
+    slab.deliver(ranks, "xfer")
     for s in ranks:
         s.slab_finish()
         s.close()
@@ -573,7 +516,7 @@ def test_state_and_arguments():
 
 def test_ragged_last_tile_pairs_with_the_export():
     g, rec = ragged(seed=33)
-    frame(g)
+    open_frame(g)
     phi, ids, res = by_id(g)
     fr = Frame(g)
     live = g.live_count()
@@ -586,7 +529,7 @@ def test_ragged_last_tile_pairs_with_the_export():
 
 def test_ragged_capacity_cuts():
     g, rec = ragged(seed=34)
-    frame(g)
+    open_frame(g)
     full = g.potential(phi=True)
     live = g.live_count()
     assert len(full["phi"]) == live == full["listed"]

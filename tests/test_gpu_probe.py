@@ -16,27 +16,16 @@ import pytest
 import torch
 
 import particlesystem_amd as ps
-from far_harness import bits
 from particlesystem_amd import slab
+from service_harness import DEV, ERR_INVALID_ARG, ERR_STATE, ERR_UNSUPPORTED, bits, captured, kid_age, open_frame, slab_inputs
 from util import cloud
 
 pytestmark = pytest.mark.gpu
 
 REL = 1e-5
-ERR_INVALID_ARG, ERR_STATE, ERR_UNSUPPORTED = 1, 8, 9
 SMALL = dict(chunk_factor=2, chunk_dim=4)          # an 8^3 grid of 5-unit cells: the box is [-20, 20)^3
 QUIET = dict(collision_radius=0.0, drag=0.0)       # nothing collides: every adult gets a force record
 QNAN = 0x7fc00000
-DEV = torch.device("cuda", 0)
-
-
-def kid_age(cfg):
-    return cfg.life_steps * cfg.dt / 10.0
-
-
-def frame(g):
-    g.init_iframe()
-    g.build_grid()
 
 
 def dev4(xyz):
@@ -166,23 +155,6 @@ def raw_probe(g, pos4, max_count=None, count=None, fields=3, out4=None, outcome=
     return spec
 
 
-def hip_runtime():
-    """the HIP runtime torch loaded (the library is bound to the same copy)"""
-    for line in open("/proc/self/maps"):
-        if "libamdhip64.so" in line:
-            hip = C.CDLL(line.split()[-1])
-            break
-    else:
-        raise RuntimeError("no HIP runtime in this process")
-    vp = C.c_void_p
-    for name, args in (("hipStreamBeginCapture", [vp, C.c_int]), ("hipStreamEndCapture", [vp, C.POINTER(vp)]),
-                       ("hipGraphInstantiate", [C.POINTER(vp), vp, vp, vp, C.c_size_t]), ("hipGraphLaunch", [vp, vp]),
-                       ("hipStreamSynchronize", [vp]), ("hipGraphExecDestroy", [vp]), ("hipGraphDestroy", [vp])):
-        getattr(hip, name).restype = C.c_int
-        getattr(hip, name).argtypes = args
-    return hip
-
-
 @pytest.fixture(scope="module")
 def the_cloud():
     return boundary_cloud()
@@ -196,7 +168,7 @@ def test_a_probe_on_a_particle_repeats_its_force_record_and_its_potential(the_cl
     xyz, age, w = the_cloud
     g = system(xyz, age, w, force_sign=sign)
     g.set_graphs(graphs)
-    frame(g)
+    open_frame(g)
     ref = Ref(g)
     assert sorted(set(ref.count.tolist())) == [0] + list(COUNTS) and len(xyz) > 1400
     ex = g.export_live(ps.EXPORT_POS | ps.EXPORT_VEL | ps.EXPORT_ID)
@@ -208,18 +180,14 @@ def test_a_probe_on_a_particle_repeats_its_force_record_and_its_potential(the_cl
     got = res["out4"].cpu().numpy()
     if graphs:
         # the probe itself captured on a second call (no scratch grows), replayed: the same bytes
-        hip = hip_runtime()
         out2 = torch.zeros((n, 4), dtype=torch.float32, device=DEV)
-        torch.cuda.synchronize()
         spec = ps.ProbeSpec(fields=3, max_count=n, pos4=pos4.data_ptr(), out4=out2.data_ptr())
-        stream, graph, exe = C.c_void_p(g.stream()), C.c_void_p(), C.c_void_p()
-        assert hip.hipStreamBeginCapture(stream, 2) == 0       # hipStreamCaptureModeRelaxed
-        rc = g.lib.psamd_probe(g.h, C.byref(spec))
-        assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0 and rc == 0
-        assert hip.hipGraphInstantiate(C.byref(exe), graph, None, None, 0) == 0
-        assert hip.hipGraphLaunch(exe, stream) == 0 and hip.hipStreamSynchronize(stream) == 0
+        with captured(g) as cap:
+            rc = g.lib.psamd_probe(g.h, C.byref(spec))
+        assert rc == 0
+        cap.launch()
         assert np.array_equal(bits(out2), bits(got))
-        assert hip.hipGraphExecDestroy(exe) == 0 and hip.hipGraphDestroy(graph) == 0
+        cap.close()
     # the potential on the same frame
     pot = g.potential(phi=True)
     phi = pot["phi"].cpu().numpy()
@@ -266,7 +234,7 @@ def lattice_points():
 def test_lattice_nodes_on_faces_and_in_empty_cells(the_cloud):
     xyz, age, w = the_cloud
     g = system(xyz, age, w)
-    frame(g)
+    open_frame(g)
     pts = lattice_points()
     res = g.probe(dev4(pts), outcome=True)
     cell = locate(pts, 8, 5.0)
@@ -284,7 +252,7 @@ def test_lattice_nodes_on_faces_and_in_empty_cells(the_cloud):
 def test_outcomes_counts_and_untouched_entries(the_cloud):
     xyz, age, w = the_cloud
     g = system(xyz, age, w)
-    frame(g)
+    open_frame(g)
     rng = np.random.default_rng(41)
     L = np.float32(20.0)
     inf, nan = np.float32(np.inf), np.float32(np.nan)
@@ -342,7 +310,7 @@ def test_outcomes_counts_and_untouched_entries(the_cloud):
 def test_a_probe_depends_on_its_position_and_the_frame_alone(the_cloud):
     xyz, age, w = the_cloud
     g = system(xyz, age, w)
-    frame(g)
+    open_frame(g)
     rng = np.random.default_rng(51)
     pts = np.concatenate([xyz[::3], rng.uniform(-20, 20, (300, 3)).astype(np.float32)])
     a = g.probe(dev4(pts))["out4"].cpu().numpy()
@@ -374,7 +342,7 @@ def test_fast_math_stays_within_the_bound_of_the_exact_probe(the_cloud):
     out = []
     for flags in (0, ps.FLAG_FAST_MATH):
         g = system(xyz, age, w, flags=flags)
-        frame(g)
+        open_frame(g)
         pos4 = g.export_live(ps.EXPORT_POS)["pos4"].contiguous()
         r = g.probe(pos4)
         assert r["served"] == len(xyz) and r["nonfinite"] == 0
@@ -398,7 +366,7 @@ def test_all_pairs_inside_a_block_of_cells_is_the_cutoff_result():
     got = []
     for flags in (0, ps.FLAG_ALL_PAIRS):
         g = system(xyz, np.float32(3.0), np.float32(60.0), flags=flags)
-        frame(g)
+        open_frame(g)
         assert (Ref(g).count > 0).sum() == 8
         r = g.probe(dev4(pts))
         assert r["served"] == len(pts)
@@ -413,7 +381,7 @@ def test_all_pairs_spread_cloud_against_the_fp64_direct_sum():
     age = np.full(n, 3.0, np.float32)
     age[::31] = 0.5
     g = system(cloud(n, 73, 20.0), age, rng.uniform(20.0, 100.0, n).astype(np.float32), flags=ps.FLAG_ALL_PAIRS)
-    frame(g)
+    open_frame(g)
     t = (np.arange(8) * 5.0 - 17.5).astype(np.float32)           # 512 lattice probes, the cells' centres
     X, Y, Z = np.meshgrid(t, t, t, indexing="ij")
     pts = np.stack([X.ravel(), Y.ravel(), Z.ravel()], 1)
@@ -425,49 +393,10 @@ def test_all_pairs_spread_cloud_against_the_fp64_direct_sum():
 
 # ---- 8: slabs ------------------------------------------------------------------------------------------------------------------
 
-def deliver(ranks, phase):
-    for r, s in enumerate(ranks):
-        for ph, out_slot, peer, in_slot in slab.routes(r, len(ranks)):
-            if ph == phase and s.msg_bytes(out_slot):
-                ranks[peer].msg_upload(in_slot, s.msg_download(out_slot))
-
-
-def gather(ranks, out_slot, in_slot):
-    if len(ranks) > 1 and ranks[0].msg_bytes(out_slot):
-        every = np.concatenate([s.msg_download(out_slot) for s in ranks])
-        for s in ranks:
-            s.msg_upload(in_slot, every)
-
-
-def slab_until_pairs(ranks):
-    for s in ranks:
-        s.slab_build()
-    gather(ranks, slab.STATUS_OUT, slab.STATUS_IN)
-    deliver(ranks, "halo")
-    gather(ranks, slab.ALLG_OUT, slab.ALLG_IN)
-    for s in ranks:
-        s.slab_pairs()
-
-
-def slab_rest(ranks):
-    deliver(ranks, "force")
-    for s in ranks:
-        s.slab_apply()
-    deliver(ranks, "xfer")
-    gather(ranks, slab.FAR_OUT, slab.FAR_IN)
-    for s in ranks:
-        s.slab_finish()
-
-
-def slab_inputs(n):
-    rng = np.random.default_rng(81)
-    return cloud(n, 81), rng.uniform(0.2, 9.0, n).astype(np.float32), cloud(n, 82, 20.0)
-
-
 @pytest.mark.parametrize("cuts", [[0, 7, 16], [0, 8, 16], [0, 3, 7, 11, 16]])
 def test_slabs_merge_to_the_single_context_bytes(cuts):
     n = 20000
-    xyz, age, v = slab_inputs(n)
+    xyz, age, v = slab_inputs(n, 81)
     rng = np.random.default_rng(83)
     pts = np.concatenate([xyz[::10], rng.uniform(-42, 42, (1500, 3)).astype(np.float32)])
     pos4 = dev4(pts)
@@ -485,10 +414,10 @@ def test_slabs_merge_to_the_single_context_bytes(cuts):
         if step:
             one.step(1)
             slab.step_local(ranks)
-        frame(one)
+        open_frame(one)
         want = one.probe(pos4, outcome=True)
         assert want["served"] == inside.sum() and want["foreign"] == 0
-        slab_until_pairs(ranks)
+        slab.to_pairs(ranks)
         parts = [s.probe(pos4, outcome=True) for s in ranks]
         codes = np.stack([p["outcome"].cpu().numpy() for p in parts])
         assert ((codes == 0).sum(0) == inside).all(), "an in-box probe is served by exactly one rank, the others by none"
@@ -498,7 +427,8 @@ def test_slabs_merge_to_the_single_context_bytes(cuts):
         assert merged["served"] == want["served"] == sum(p["served"] for p in parts) and merged["nonfinite"] == want["nonfinite"]
         assert merged["outside"] == want["outside"] and merged["foreign"] == 0
         one.calc_forces()
-        slab_rest(ranks)
+        slab.apply_stage(ranks)
+        slab.finish_stage(ranks)
     one.close()
     for s in ranks:
         s.close()
@@ -506,18 +436,19 @@ def test_slabs_merge_to_the_single_context_bytes(cuts):
 
 def test_all_pairs_slabs_are_refused_and_the_step_goes_on():
     n = 8000
-    xyz, age, v = slab_inputs(n)
+    xyz, age, v = slab_inputs(n, 81)
     over = dict(flags=ps.FLAG_ALL_PAIRS, max_particles_num=1 << 18, **QUIET)
     one = ps.ParticleSystem(ps.default_config(**over))
     ranks = [ps.ParticleSystem(ps.default_config(rank=r, world=2, cuts=[0, 7, 16], **over)) for r in range(2)]
     for s in [one] + ranks:
         s.fill_particles(xyz, age=age, fert_age=np.float32(1e6), vxyz=v)
-    slab_until_pairs(ranks)
+    slab.to_pairs(ranks)
     for s in ranks:
         with pytest.raises(ps.PsamdError) as e:
             s.probe(dev4(xyz[:64]))
         assert e.value.status == ERR_UNSUPPORTED
-    slab_rest(ranks)
+    slab.apply_stage(ranks)
+    slab.finish_stage(ranks)
     one.step(1)
     def state(systems):
         ex = [s.export_live(ps.EXPORT_ALL) for s in systems]
@@ -547,7 +478,7 @@ def test_state_and_arguments(the_cloud):
         rc = g.lib.psamd_probe(g.h, C.byref(spec))
         assert rc == expect, (kw, rc)
     call(ERR_STATE)                                              # before build_grid
-    frame(g)
+    open_frame(g)
     for bad in (dict(fields=0), dict(fields=4), dict(fields=7), dict(reserved=1), dict(max_count=-1), dict(max_count=1 << 31),
                 dict(pos4=None), dict(out4=None), dict(pos4=pos4.data_ptr() + 4), dict(out4=out4.data_ptr() + 8),
                 dict(outcome_dev=aux.data_ptr() + 2), dict(count_dev=aux.data_ptr() + 4), dict(result_dev=aux.data_ptr() + 4)):
@@ -557,25 +488,22 @@ def test_state_and_arguments(the_cloud):
     call(0, max_count=0, pos4=None, out4=None)                   # nothing to read or write
     g.synchronize()
     # a capture that needs growth is refused; the same capture after the growth is not
-    hip = hip_runtime()
     big_in, big_out = torch.zeros((50000, 4), dtype=torch.float32, device=DEV), torch.zeros((50000, 4), dtype=torch.float32, device=DEV)
-    torch.cuda.synchronize()
-    stream, graph = C.c_void_p(g.stream()), C.c_void_p()
-    assert hip.hipStreamBeginCapture(stream, 2) == 0
     spec = ps.ProbeSpec(fields=3, max_count=50000, pos4=big_in.data_ptr(), out4=big_out.data_ptr())
-    rc = g.lib.psamd_probe(g.h, C.byref(spec))
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0 and rc == ERR_STATE
-    assert hip.hipGraphDestroy(graph) == 0
+    with captured(g) as cap:
+        rc = g.lib.psamd_probe(g.h, C.byref(spec))
+    assert rc == ERR_STATE
+    cap.close()
     call(0)                                                      # the context stays usable
     # a probe between two stage calls leaves the step's bytes unchanged
     h = system(xyz, age, w)
-    frame(h)
+    open_frame(h)
     g.calc_forces_pairs(); h.calc_forces_pairs()
     g.probe(pos4)
     g.calc_forces_apply(); h.calc_forces_apply()
     assert g.download_particles().tobytes() == h.download_particles().tobytes()
     call(ERR_STATE)                                              # after calc_forces
-    frame(g)
+    open_frame(g)
     call(0)
     g.inject(dev4(np.array([(1.0, 2.0, 3.0)], np.float32)))
     call(ERR_STATE)                                              # an inject ends the frame

@@ -14,13 +14,11 @@ import torch
 import particlesystem_amd as ps
 import remove_model as M
 from particlesystem_amd.slab import merge_owned, step_local
-from test_gpu_inject import batch, dev, hip_runtime, inject, many_records, same_state, start, state
+from service_harness import DEV, ERR_INVALID_ARG, ERR_STATE, OK, batch, captured, dev, inject, many_records, same_state, start, state
 from util import SLOT_TILE, assert_same_particles, cloud, ragged
 
 pytestmark = pytest.mark.gpu
 
-OK, INVALID, STATE = 0, 1, 8
-DEV = torch.device("cuda", 0)
 TILE = 4096          # inject's and remove's tile of entries
 
 
@@ -341,15 +339,15 @@ def test_arguments_capture_and_the_frame():
             setattr(s, k, v)
         return s
     lib = b.lib
-    assert lib.psamd_remove(None, C.byref(spec())) == INVALID
-    assert lib.psamd_remove(b.h, None) == INVALID
-    assert lib.psamd_remove_result_get(b.h, None) == INVALID
+    assert lib.psamd_remove(None, C.byref(spec())) == ERR_INVALID_ARG
+    assert lib.psamd_remove(b.h, None) == ERR_INVALID_ARG
+    assert lib.psamd_remove_result_get(b.h, None) == ERR_INVALID_ARG
     for bad in (spec(flags=4), spec(flags=ps.REMOVE_OUTSIDE), spec(reserved=1), spec(max_count=-1), spec(max_count=1 << 31),
                 spec(ids=None), spec(ids=ids.data_ptr() + 2), spec(outcome_dev=out.data_ptr() + 2),
                 spec(count_dev=cnt.data_ptr() + 4), spec(result_dev=res.data_ptr() + 4),
                 box(flags=ps.REMOVE_BOX | 8), box(reserved=1), box(ids=ids.data_ptr()), box(count_dev=cnt.data_ptr()),
                 box(outcome_dev=out.data_ptr()), box(max_count=1), box(result_dev=res.data_ptr() + 4)):
-        assert lib.psamd_remove(b.h, C.byref(bad)) == INVALID, [(n, getattr(bad, n)) for n, _ in bad._fields_[:6]]
+        assert lib.psamd_remove(b.h, C.byref(bad)) == ERR_INVALID_ARG, [(n, getattr(bad, n)) for n, _ in bad._fields_[:6]]
     same_state(a, b, "after the refused calls")
     # max_count == 0: a zero result, nothing else
     assert b.remove(ids=ids[:1000].contiguous())["done"] == 1000
@@ -361,18 +359,13 @@ def test_arguments_capture_and_the_frame():
     assert res[:6].cpu().tolist() == [0] * 6
     same_state(a, b, "max_count 0")
     # capture: refused, the graph stays empty, the state untouched
-    hip = hip_runtime()
-    stream = C.c_void_p(b.stream())
-    graph = C.c_void_p()
-    assert hip.hipStreamBeginCapture(stream, 2) == 0       # hipStreamCaptureModeRelaxed
-    rc = lib.psamd_remove(b.h, C.byref(spec(ids=ids.data_ptr() + 4)))
-    rc2 = lib.psamd_remove(b.h, C.byref(box()))
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0
-    assert rc == STATE and rc2 == STATE, (rc, rc2)
+    with captured(b) as cap:
+        rc = lib.psamd_remove(b.h, C.byref(spec(ids=ids.data_ptr() + 4)))
+        rc2 = lib.psamd_remove(b.h, C.byref(box()))
+    assert rc == ERR_STATE and rc2 == ERR_STATE, (rc, rc2)
     assert b"captured" in lib.psamd_last_error(b.h)
-    nodes = C.c_size_t(99)
-    assert hip.hipGraphGetNodes(graph, None, C.byref(nodes)) == 0 and nodes.value == 0
-    assert hip.hipGraphDestroy(graph) == 0
+    assert cap.nodes() == 0
+    cap.close()
     same_state(a, b, "after the refused capture")
     # a remove between build_grid and calc_forces ends the frame
     for g in (a, b):
@@ -380,7 +373,7 @@ def test_arguments_capture_and_the_frame():
         g.build_grid()
     assert b.remove(ids=ids[1:1001].contiguous())["done"] == 1000
     a.remove(ids=ids[1:1001].contiguous())
-    assert lib.psamd_calc_forces(b.h) == STATE and lib.psamd_calc_forces_pairs(b.h) == STATE
+    assert lib.psamd_calc_forces(b.h) == ERR_STATE and lib.psamd_calc_forces_pairs(b.h) == ERR_STATE
     for g in (a, b):
         g.init_iframe()
         g.build_grid()

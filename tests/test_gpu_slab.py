@@ -11,44 +11,10 @@ import pytest
 import oracle_py as O
 import particlesystem_amd as ps
 from particlesystem_amd.slab import merge_owned, step_local
+from service_harness import compare_world, make_world
 from util import assert_same_particles, cloud, explosion_rng, g2_cloud, oracle_cfg_from
 
 pytestmark = pytest.mark.gpu
-
-COUNTERS = ("deaths_age", "deaths_collision", "survives", "integrated", "relocations",
-            "relocations_lost", "births", "births_failed", "cell_overflow_kills")
-
-
-def make_world(world, xyz, age, fert, flags=0, cuts=None, **over):
-    ranks = []
-    for r in range(world):
-        kw = dict(rank=r, world=world, flags=flags, **over)
-        if cuts is not None:
-            kw["cuts"] = cuts
-        ranks.append(ps.ParticleSystem(ps.default_config(**kw)))
-    o = O.System(oracle_cfg_from(ranks[0].cfg))
-    ids_o = o.fill(xyz, age=age, fert_age=fert)
-    ids = np.stack([g.fill_particles(xyz, age=age, fert_age=fert) for g in ranks])
-    # every particle was placed by exactly one rank, in the slot the oracle gave it
-    assert ((ids >= 0).sum(0) == 1).all()
-    assert np.array_equal(ids.max(0), ids_o)
-    return ranks, o
-
-
-def compare_world(ranks, o, what):
-    plans = [g.slab_plan() for g in ranks]
-    p = merge_owned([g.download_particles() for g in ranks], plans)
-    assert_same_particles(p, o.particles, what)
-    qs = [g.download_queues() for g in ranks]
-    qi = merge_owned([q[0] for q in qs], plans, "records")
-    q = merge_owned([q[1] for q in qs], plans)
-    assert qi.tobytes() == o.queue_info.tobytes(), what + ": QUEUE_INFO differs"
-    assert np.array_equal(q, o.queue), what + ": queue array differs"
-    cs = [g.counters for g in ranks]
-    for k in COUNTERS:
-        assert sum(c[k] for c in cs) == o.counters[k], (what, k, [c[k] for c in cs], o.counters[k])
-    return cs
-
 
 def changed_owner(ranks):
     """particles that arrived from a neighbour so far = relocations + births whose slot the

@@ -13,12 +13,11 @@ import particlesystem_amd as ps
 from particlesystem_amd import slab
 from particlesystem_amd.slab import step_local
 from test_frame_stage_cpu import old_call
-from test_gpu_slab import compare_world, make_world
+from service_harness import ERR_STATE, compare_world, make_world
 from util import assert_same_particles, cloud, oracle_cfg_from
 
 pytestmark = pytest.mark.gpu
 
-ERR_STATE = 8
 GRID = {"chunk_factor": 2, "chunk_dim": 4, "max_particles_num": 4000}       # 8^3 cells
 N = 2000
 AGE, FERT = np.float32(3.0), np.float32(1e6)
@@ -88,20 +87,6 @@ def test_world_one_refuses_a_call_of_the_other_family(oracle_steps, before, offe
     g.close()
 
 
-def deliver(ranks, phase):
-    for r, s in enumerate(ranks):
-        for ph, out_slot, peer, in_slot in slab.routes(r, len(ranks)):
-            if ph == phase and s.msg_bytes(out_slot):
-                ranks[peer].msg_upload(in_slot, s.msg_download(out_slot))
-
-
-def gather(ranks, out_slot, in_slot):
-    if ranks[0].msg_bytes(out_slot):
-        every = np.concatenate([s.msg_download(out_slot) for s in ranks])
-        for s in ranks:
-            s.msg_upload(in_slot, every)
-
-
 def test_world_two_orders_and_the_field_window():
     import torch
     ranks, o = make_world(2, inputs(), AGE, FERT, cuts=[0, 3, 8], **GRID)
@@ -143,21 +128,21 @@ def test_world_two_orders_and_the_field_window():
     assert not call("slab_apply")                       # before slab_pairs
     assert not call("slab_finish")
     field(False)                                        # the halos are not in yet
-    gather(ranks, slab.STATUS_OUT, slab.STATUS_IN)
+    slab.gather(ranks, slab.STATUS_OUT, slab.STATUS_IN)
     assert call("slab_pairs_interior")
     stats = [s.graph_stats() for s in ranks]
     assert call("slab_pairs_interior")                  # a second one: accepted, and nothing runs
     assert [s.graph_stats() for s in ranks] == stats
-    deliver(ranks, "halo")
+    slab.deliver(ranks, "halo")
     assert call("slab_pairs")
     assert not call("slab_pairs_interior")              # after slab_pairs
     assert not call("slab_pairs") and not call("slab_finish")       # ... twice; before slab_apply
     field(True)
-    deliver(ranks, "force")
+    slab.deliver(ranks, "force")
     assert call("slab_apply")
     field(False)
     assert not call("slab_apply") and not call("slab_pairs")
-    deliver(ranks, "xfer")
+    slab.deliver(ranks, "xfer")
     assert call("slab_finish")
     assert not call("slab_finish")
     field(False)

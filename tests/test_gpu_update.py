@@ -14,13 +14,11 @@ import particlesystem_amd as ps
 import remove_model as R
 import update_model as U
 from particlesystem_amd.slab import merge_owned, step_local
-from test_gpu_inject import dev, start, state
-from util import SLOT_TILE, assert_same_particles, cloud, hip_runtime, ragged
+from service_harness import DEV, ERR_INVALID_ARG, ERR_STATE, OK, captured, dev, start, state
+from util import SLOT_TILE, assert_same_particles, cloud, ragged
 
 pytestmark = pytest.mark.gpu
 
-OK, INVALID, STATE = 0, 1, 8
-DEV = torch.device("cuda", 0)
 TILE = 4096          # the tile of entries (ENTRY_TILE)
 VEL, AGE, MASS, FERT, ADD, ORDER = U.VEL, U.AGE, U.MASS, U.FERT, U.ADD, U.EXPORT_ORDER
 FIELD_SETS = (VEL, VEL | ADD, MASS | AGE | FERT, VEL | AGE | MASS | FERT)
@@ -240,40 +238,33 @@ def test_the_frame_rules_and_capture():
         g.init_iframe(); g.build_grid()
         r = g.update(ids=None if fields & ORDER else ids, vel4=vel4, w=w, fields=fields)
         assert r["done"] == 2000 and r["updated"] > 1000, r
-        assert lib.psamd_calc_forces(g.h) == STATE and lib.psamd_calc_forces_pairs(g.h) == STATE, hex(fields)
+        assert lib.psamd_calc_forces(g.h) == ERR_STATE and lib.psamd_calc_forces_pairs(g.h) == ERR_STATE, hex(fields)
         g.init_iframe(); g.build_grid(); g.calc_forces()
     # a kick captured into a graph, by id and by export order (no scratch grows: 2000 entries were served above); every replay kicks once
-    hip = hip_runtime()
-    torch.cuda.synchronize()
     p0 = g.download_particles()
-    stream, graph, exe = C.c_void_p(g.stream()), C.c_void_p(), C.c_void_p()
-    assert hip.hipStreamBeginCapture(stream, 2) == 0       # hipStreamCaptureModeRelaxed
-    rc = raw(g, VEL | ADD, 2000, ids, vel4)
-    rc2 = raw(g, VEL | ADD | ORDER, 1500, None, vel4)
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0 and (rc, rc2) == (OK, OK), (rc, rc2)
+    with captured(g) as cap:
+        rc = raw(g, VEL | ADD, 2000, ids, vel4)
+        rc2 = raw(g, VEL | ADD | ORDER, 1500, None, vel4)
+    assert (rc, rc2) == (OK, OK), (rc, rc2)
     assert g.download_particles().tobytes() == p0.tobytes(), "a capture runs nothing"
-    assert hip.hipGraphInstantiate(C.byref(exe), graph, None, None, 0) == 0
     want = p0
     for k in range(3):
-        assert hip.hipGraphLaunch(exe, stream) == 0 and hip.hipStreamSynchronize(stream) == 0
+        cap.launch()
         want = U.apply(want, g.sizes.num_cells, VEL | ADD, ids_np, vel_np)[0]
         want = U.apply(want, g.sizes.num_cells, VEL | ADD, None, vel_np[:1500])[0]
         assert_same_particles(g.download_particles(), want, "replay %d of the captured kicks" % (k + 1))
         assert g.update_result() == dict(done=1500, updated=1500, not_live=0, foreign=0, invalid=0, duplicate=0)
-    assert hip.hipGraphExecDestroy(exe) == 0 and hip.hipGraphDestroy(graph) == 0
+    cap.close()
     # refused under capture: a new mass or age (by id and by export order), and a scratch that would have to grow
     big_ids = torch.zeros(50000, dtype=torch.int32, device=DEV)
     big_vel = torch.zeros((50000, 4), dtype=torch.float32, device=DEV)
-    torch.cuda.synchronize()
-    assert hip.hipStreamBeginCapture(stream, 2) == 0
-    rcs = [raw(g, MASS, 2000, ids, None, w), raw(g, AGE | ORDER, 2000, None, vel4), raw(g, VEL | MASS | ADD, 2000, ids, vel4, w),
-           raw(g, VEL, 50000, big_ids, big_vel)]
-    msg = lib.psamd_last_error(g.h)
-    assert hip.hipStreamEndCapture(stream, C.byref(graph)) == 0
-    assert rcs == [STATE] * 4 and b"captured" in msg and b"grow" in msg, (rcs, msg)
-    nodes = C.c_size_t(99)
-    assert hip.hipGraphGetNodes(graph, None, C.byref(nodes)) == 0 and nodes.value == 0
-    assert hip.hipGraphDestroy(graph) == 0
+    with captured(g) as cap:
+        rcs = [raw(g, MASS, 2000, ids, None, w), raw(g, AGE | ORDER, 2000, None, vel4), raw(g, VEL | MASS | ADD, 2000, ids, vel4, w),
+               raw(g, VEL, 50000, big_ids, big_vel)]
+        msg = lib.psamd_last_error(g.h)
+    assert rcs == [ERR_STATE] * 4 and b"captured" in msg and b"grow" in msg, (rcs, msg)
+    assert cap.nodes() == 0
+    cap.close()
     assert_same_particles(g.download_particles(), want, "after the refused captures")
     assert raw(g, VEL, 50000, big_ids, big_vel) == OK           # outside a capture the scratch grows
     g.step(2)
@@ -371,7 +362,7 @@ def test_slabs(world):
         for s in rs:
             rcs = [raw(s, VEL, len(ids), d_ids, d_vel), raw(s, VEL | ADD, len(ids), d_ids, d_vel), raw(s, FERT | ORDER, 100, None, None, None, d_w),
                    raw(s, MASS, len(ids), d_ids, None, d_w), raw(s, AGE | ORDER, 100, None, d_vel), raw(s, VEL, 0)]
-            assert rcs == [STATE] * 6 and b"slab_apply" in s.lib.psamd_last_error(s.h), rcs
+            assert rcs == [ERR_STATE] * 6 and b"slab_apply" in s.lib.psamd_last_error(s.h), rcs
     torch.cuda.synchronize()
     step_local(ranks, after_apply=refused)
     one.step(1)
@@ -401,9 +392,9 @@ def test_arguments():
         for k, v in over.items():
             setattr(s, k, v)
         return s
-    assert lib.psamd_update(None, C.byref(spec())) == INVALID
-    assert lib.psamd_update(b.h, None) == INVALID
-    assert lib.psamd_update_result_get(b.h, None) == INVALID
+    assert lib.psamd_update(None, C.byref(spec())) == ERR_INVALID_ARG
+    assert lib.psamd_update(b.h, None) == ERR_INVALID_ARG
+    assert lib.psamd_update_result_get(b.h, None) == ERR_INVALID_ARG
     for bad in (spec(fields=0), spec(fields=ADD), spec(fields=ORDER, ids=None), spec(fields=ADD | MASS), spec(fields=VEL | 0x10), spec(fields=VEL | 0x400),
                 spec(fields=VEL | 0x80000000), spec(reserved=1), spec(max_count=-1), spec(max_count=1 << 31),
                 spec(ids=None), spec(fields=VEL | ORDER), spec(vel4=None), spec(fields=AGE, vel4=None), spec(fields=MASS, w=None),
@@ -411,7 +402,7 @@ def test_arguments():
                 spec(ids=ids.data_ptr() + 2), spec(vel4=vel4.data_ptr() + 8), spec(fields=MASS, w=w.data_ptr() + 2),
                 spec(fields=FERT, fert_age=w.data_ptr() + 2), spec(outcome_dev=out.data_ptr() + 2),
                 spec(count_dev=cnt.data_ptr() + 4), spec(result_dev=res.data_ptr() + 4)):
-        assert lib.psamd_update(b.h, C.byref(bad)) == INVALID, [(n, getattr(bad, n)) for n, _ in bad._fields_]
+        assert lib.psamd_update(b.h, C.byref(bad)) == ERR_INVALID_ARG, [(n, getattr(bad, n)) for n, _ in bad._fields_]
     b.synchronize()
     assert state(a)[0].tobytes() == state(b)[0].tobytes(), "after the refused calls"
     # arrays the fields do not name are not looked at
@@ -457,12 +448,12 @@ def test_a_wedged_context_is_refused(monkeypatch):
     with torch.cuda.stream(ext):
         torch.cuda._sleep(int(200 * per_ms))
     lib = g.lib
-    assert lib.psamd_step(g.h, 1) == STATE and b"stopped answering" in lib.psamd_last_error(g.h)
+    assert lib.psamd_step(g.h, 1) == ERR_STATE and b"stopped answering" in lib.psamd_last_error(g.h)
     before = g.download_particles()                 # (waits until the stream has drained: the step itself ran)
     for fields, i in ((VEL, ids), (VEL | ADD, ids), (VEL | ORDER, None), (MASS | ORDER, None)):
-        assert raw(g, fields, 1000, i, vel4, ids) == STATE, hex(fields)        # (w: any aligned pointer, never read)
+        assert raw(g, fields, 1000, i, vel4, ids) == ERR_STATE, hex(fields)        # (w: any aligned pointer, never read)
         assert b"stopped answering" in lib.psamd_last_error(g.h)
-    assert raw(g, VEL, 0) == STATE
-    assert lib.psamd_update_result_get(g.h, C.byref(ps.UpdateResult())) == STATE
+    assert raw(g, VEL, 0) == ERR_STATE
+    assert lib.psamd_update_result_get(g.h, C.byref(ps.UpdateResult())) == ERR_STATE
     assert g.download_particles().tobytes() == before.tobytes()
     g.close()

@@ -14,7 +14,7 @@ import pytest
 import oracle_py as O
 import particlesystem_amd as ps
 from oracle_slab import OracleSlabRank
-from particlesystem_amd.slab import HostRing, merge_owned, routes, step_local
+from particlesystem_amd.slab import FORCE_OUT, HostRing, apply_stage, finish_stage, merge_owned, routes, step_local, to_pairs
 from util import cloud, g2_cloud
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -118,6 +118,35 @@ def test_stand_in_slabs_reproduce_the_serial_reference(world):
         ref.step(1)
         union_equals(ranks, ref, "world %d step %d" % (world, step + 1))
     assert sum(s.sent for s in ranks) > 0 and ref.counters["relocations"] > 0
+
+
+def test_the_three_stages_are_step_local():
+    """a world of three (both neighbours and the ring): step_local against to_pairs, apply_stage, finish_stage called one by one.
+    8^3 cells and a container of 18 000 slots (a rank's download is the whole container, 150 MB at the default sizes); the cut
+    at layer 4 lends a layer, so that force messages travel too"""
+    dt = 0.05
+    xyz = cloud(2000, 23, 20.0)
+    fert = (1e6 + np.arange(len(xyz))).astype(np.float32)
+
+    def world():           # (as make_ranks, without the serial reference: the two worlds are held against each other)
+        ranks = [OracleSlabRank(ps.default_config(rank=r, world=3, dt=dt, cuts=[0, 2, 4, 8], chunk_factor=2, chunk_dim=4, max_particles_num=4096))
+                 for r in range(3)]
+        for s in ranks:
+            s.fill_particles(xyz, np.float32(40 * dt), fert)
+        return ranks
+    whole, staged = world(), world()
+    for step in range(3):
+        step_local(whole)
+        to_pairs(staged)
+        apply_stage(staged)
+        finish_stage(staged)
+        for r, (a, b) in enumerate(zip(whole, staged)):
+            pa, pb = a.download_particles(), b.download_particles()
+            for f in pa.dtype.names:            # (field by field: a copy of a record array leaves its pad bytes undefined)
+                assert pa[f].tobytes() == pb[f].tobytes(), (step, r, f)
+            for qa, qb in zip(a.download_queues(), b.download_queues()):
+                assert qa.tobytes() == qb.tobytes(), (step, r)
+    assert sum(s.sent for s in staged) == sum(s.sent for s in whole) > 0 and any(s.msg_bytes(FORCE_OUT) for s in staged)
 
 
 def state_hash(p, qi, q):

@@ -1,5 +1,4 @@
 """Shared helpers for the parity tests (oracle side is test infrastructure)."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -99,21 +98,3 @@ def ragged(seed=31, **over):
 
 def capacities(live):
     return [c if k < 5 else live + c for k, c in enumerate(CAPACITIES)]
-
-
-# ---- stream capture from a test (the GPU tests that capture a call into a graph) ------------------------------------------------
-def hip_runtime():
-    """the HIP runtime torch loaded (the library is bound to the same copy)"""
-    for line in open("/proc/self/maps"):
-        if "libamdhip64.so" in line:
-            hip = C.CDLL(line.split()[-1])
-            break
-    else:
-        raise RuntimeError("no HIP runtime in this process")
-    vp = C.c_void_p
-    for name, args in (("hipStreamBeginCapture", [vp, C.c_int]), ("hipStreamEndCapture", [vp, C.POINTER(vp)]),
-                       ("hipGraphInstantiate", [C.POINTER(vp), vp, vp, vp, C.c_size_t]), ("hipGraphLaunch", [vp, vp]),
-                       ("hipStreamSynchronize", [vp]), ("hipGraphExecDestroy", [vp]), ("hipGraphDestroy", [vp])):
-        getattr(hip, name).restype = C.c_int
-        getattr(hip, name).argtypes = args
-    return hip

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/psamd.h"
+#include "context_params.hpp"
 #include "device_types.h"
 #include "frame_stage.hpp"
 #include "geometry.hpp"
@@ -23,16 +24,11 @@
 #include "step_ledger.hpp"
 
 namespace psamd {
-// A slab message (device), by the ABI's `which` numbering (psamd_slab_msg_download in include/psamd.h); in a pair,
-// + 0 = the rank below, + 1 = the rank above.  The *_IN of status, allg and far hold every rank's message, all-gathered.
-enum { MSG_HALO_OUT = 0, MSG_HALO_IN = 2, MSG_FORCE_OUT = 4, MSG_FORCE_IN, MSG_XFER_OUT = 6, MSG_XFER_IN = 8, MSG_STATUS_OUT = 10, MSG_STATUS_IN,
-       MSG_ALLG_OUT, MSG_ALLG_IN, MSG_XFER2_OUT = 14, MSG_XFER2_IN = 16, MSG_FAR_OUT = 18, MSG_FAR_IN, MSG_COUNT };
+// a slab message's buffer (device), by the MSG_* numbering of context_params.hpp
 struct SlabMsg {
     int *ptr = nullptr;
     size_t bytes = 0, alloc = 0;    // what travels now; the buffer's room (they differ for MSG_XFER_*: bytes grows with P.xfer_cap)
 };
-// bytes of a transfer message with room for `recs` records
-inline size_t xfer_msg_bytes(size_t recs) { return ((size_t)MSG_HEADER_WORDS + recs * (sizeof(XferRec) / sizeof(int))) * sizeof(int); }
 // the kinds of stage sequence that are captured as hipGraphs (step.hip: run_segment)
 enum { SEG_BUILD = 0, SEG_PAIRS, SEG_APPLY, SEG_FINISH, SEG_STEP, NSEG };
 }  // namespace psamd
@@ -109,12 +105,6 @@ struct psamd_ctx {
 namespace psamd {
 
 const char *status_text(int status);
-
-// what the far-field flags make of a context: far monopoles (flat or as a pyramid); one whose host has said that it
-// all-gathers the cell sums (PSAMD_FLAG_FAR_SLAB); the fp64 planes per cell
-inline bool far_context(uint32_t flags) { return (flags & (PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID)) != 0; }
-inline bool far_slab(uint32_t flags) { return (flags & PSAMD_FLAG_FAR_SLAB) && far_context(flags); }
-inline int far_planes(uint32_t flags) { return (flags & PSAMD_FLAG_FAR_QUADRUPOLE) ? 10 : 4; }
 
 // what the ledger's rules read of the context
 inline LedgerParams ledger_params(const psamd_ctx *c)

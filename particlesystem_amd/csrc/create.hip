@@ -54,176 +54,6 @@ int psamd_default_config(psamd_config *cfg)
     return PSAMD_OK;
 }
 
-static SlabPlan plan_for(const Geometry &g, const psamd_config &cfg)
-{
-    const bool given = cfg.world >= 1 && cfg.world <= PSAMD_MAX_RANKS && cfg.cuts[cfg.world] != 0;
-    return make_slab_plan(g.F, g.D, g.seg_base, g.seg_size_t, g.info_base, cfg.rank, cfg.world, given ? cfg.cuts : nullptr);
-}
-
-// DevParams fields that describe what this rank holds (partition.hpp -> device_types.h)
-static void fill_slab_params(const Geometry &g, const SlabPlan &pl, const psamd_config &cfg, DevParams &P)
-{
-    const int GG = g.G * g.G;
-    P.rank = pl.rank; P.world = pl.world; P.num_cells_global = g.num_cells;
-    const int first[4] = {pl.state_lo, pl.below_lo, pl.lentin_lo, pl.above_lo};
-    const int layers[4] = {pl.state_hi - pl.state_lo, pl.lentin_lo - pl.below_lo, pl.lentin_hi - pl.lentin_lo, pl.above_hi - pl.above_lo};
-    P.halo_cap_cell = (cfg.halo_cap_cell > 0 && cfg.halo_cap_cell < g.max_per_cell) ? cfg.halo_cap_cell : g.max_per_cell;
-    P.xfer_cap = pl.world > 1 ? (cfg.xfer_cap > 0 ? cfg.xfer_cap : std::max(4096, GG * g.max_per_cell / 4)) : 0;
-    // how far the transfer messages may grow (their buffers' room): by default a step's worst case -- everything two cell
-    // layers hold, and a child of each (a particle moves one layer a step, two when the rounded sum lands on the far face)
-    P.xfer_cap0 = P.xfer_cap;
-    P.xfer_cap_max = pl.world > 1 ? std::max(P.xfer_cap, cfg.xfer_cap_max > 0 ? cfg.xfer_cap_max
-                                                         : (int)std::min<int64_t>(4ll * GG * g.max_per_cell, INT32_MAX / 256)) : 0;
-    int64_t slots = 0;
-    for (int t = 0; t < 4; t++) { P.slot_lo[t] = pl.slot_lo[t]; P.slot_n[t] = pl.slot_hi[t] - pl.slot_lo[t]; slots += P.slot_n[t];
-                                  P.rec_lo[t] = pl.rec_lo[t]; P.rec_hi[t] = pl.rec_hi[t]; }
-    P.slots_total = (int)slots;
-    int base = 0;
-    int64_t sorted = 0;
-    for (int r = 0; r < 4; r++) {
-        P.reg_first[r] = first[r]; P.reg_layers[r] = layers[r]; P.reg_base[r] = base; P.reg_sorted[r] = (int)sorted;
-        base += layers[r] * GG + 1;                                     // + the gap cell
-        // the own block can hold every owned slot (overflow-killed entries keep their place in
-        // the sorted order for the frame); a remote block what its messages can carry
-        sorted += r == 0 ? slots : (int64_t)layers[r] * GG * P.halo_cap_cell;
-    }
-    P.n_local_cells = base; P.n_own_cells = layers[0] * GG;
-    P.sorted_cap = (int)sorted;
-    P.own_comp0 = (std::max(pl.cut_lo, pl.state_lo) - pl.state_lo) * GG;
-    P.own_comp1 = (std::min(pl.cut_hi, pl.state_hi) - pl.state_lo) * GG;
-    if (P.own_comp1 < P.own_comp0) P.own_comp1 = P.own_comp0;
-    // the whole pair stage in one pass: the lent cells, then the own ones
-    P.comp_lo[0] = P.reg_base[2]; P.comp_hi[0] = P.reg_base[2] + layers[2] * GG;
-    P.comp_lo[1] = P.own_comp0; P.comp_hi[1] = P.own_comp1;
-    P.comp_lo[2] = P.comp_hi[2] = 0;
-    P.lentout_c0 = (pl.lentout_lo - pl.state_lo) * GG; P.lentout_c1 = (pl.lentout_hi - pl.state_lo) * GG;
-}
-
-// the largest squared distance two in-box particles can have, with slack for one wrap of drift
-static double max_d2(const Geometry &g) { const double L = (double)g.G * g.cfg.cell_size; return 3.0 * (2.0 * L) * (2.0 * L); }
-
-// Everything the kernels' parameters (c->P, c->S) take from the configuration, the geometry and the ranks' plans:
-// host arithmetic only, no HIP call.
-static int derive_params(psamd_ctx *c, const psamd_config *cfg)
-{
-    const Geometry &g = c->geo; DevParams &P = c->P;
-    P.G = g.G; P.num_cells = g.num_cells; P.num_chunks = g.num_chunks; P.container = g.container;
-    P.max_per_cell = g.max_per_cell; P.max_per_chunk = g.max_per_chunk;
-    P.slices = (g.max_per_cell + 63) / 64;
-    P.flags = cfg->flags;
-    P.t = (float)cfg->dt;
-    P.kid_thr = float_ceil(g.kid_age);
-    P.life_thr = float_floor(g.particle_life);
-    // every pair whose fp32 squared distance is at or below this gets the exact
-    // collision test; the margin only has to cover the rounding of sqrtf
-    P.coll_d2_gate = (float)(cfg->collision_radius * cfg->collision_radius * 1.001 + 1e-30);
-    P.dmax = (float)cfg->cell_size;   // MAX_DX = CELL_SIZE, common.h:65
-    P.vmax = (float)cfg->max_v;
-    P.w_default = (float)cfg->particle_weight;
-    P.fert_lo = (float)g.min_fert; P.fert_hi = (float)g.max_fert;
-    P.cell_size = cfg->cell_size; P.eps2 = cfg->eps2; P.coll_radius = cfg->collision_radius;
-    P.kid_age = g.kid_age; P.life = g.particle_life; P.expl_speed = cfg->explosion_speed;
-    P.seed = cfg->seed;
-    P.drag = (float)cfg->drag;
-    P.force_sign = cfg->force_sign < 0 ? -1.0f : 1.0f;
-    if (cfg->drag < 0) return fail(c, PSAMD_ERR_INVALID_ARG, "drag must be >= 0");
-    if ((cfg->flags & PSAMD_FLAG_FAR_SLAB) && !(cfg->flags & (PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID)))
-        return fail(c, PSAMD_ERR_INVALID_ARG, "PSAMD_FLAG_FAR_SLAB is a modifier of PSAMD_FLAG_FAR_MONOPOLE and PSAMD_FLAG_FAR_PYRAMID: set one of them too");
-    fill_slab_params(g, c->plan, *cfg, P);
-    P.status_words = STATUS_CHUNK_OFF + 4 * g.num_chunks;
-    if (cfg->world > 1) {
-        // the ring neighbours' queue records; and whether any rank's whole state is ONE cell layer: a particle
-        // that crosses two layers in a step (from one ulp below a face, moved by exactly CELL_SIZE) can fly over
-        // such a rank, to the rank beyond it -- those records get outboxes of their own, sent straight to rank +-2.
-        // All-pairs: every rank's block of the all-gathered snapshot has the same size, room for the rank with the
-        // most cells / slots.  A far slab (PSAMD_FLAG_FAR_SLAB): its block of the all-gathered cell sums likewise, room for the
-        // rank with the most cells.
-        bool single = false;
-        int cells = 0;
-        int64_t slots = 0;
-        psamd_config rc = *cfg;
-        for (int r = 0; r < cfg->world; r++) {
-            rc.rank = r;
-            const SlabPlan pr = plan_for(g, rc);
-            if (!pr.valid) return fail(c, PSAMD_ERR_UNSUPPORTED, "no slab partition for this grid and world size");
-            single |= pr.state_hi - pr.state_lo < 2;
-            const int which = r == (cfg->rank + cfg->world - 1) % cfg->world ? 0 : -1, which2 = r == (cfg->rank + 1) % cfg->world ? 1 : -1;
-            for (int w : {which, which2})
-                if (w >= 0) for (int t = 0; t < 4; t++) { P.nbr_rec_lo[w][t] = pr.rec_lo[t]; P.nbr_rec_hi[w][t] = pr.rec_hi[t]; }
-            int64_t sl = 0;
-            for (int t = 0; t < 4; t++) sl += pr.slot_hi[t] - pr.slot_lo[t];
-            cells = std::max(cells, (pr.state_hi - pr.state_lo) * g.G * g.G);
-            slots = std::max(slots, sl);
-        }
-        P.xfer2_cap = (single && cfg->world >= 4) ? 1024 : 0;       // (a ring of two or three has no rank beyond the neighbours)
-        // A record for a rank further away: only a particle whose position stopped being a number travels that far (it is
-        // filed under one fixed cell wherever it was), and only births make such particles (a child with the direction
-        // (0, 0, 0)): with births on, a world of four or more all-gathers a small far outbox in the transfer phase.
-        P.far_cap = (cfg->world >= 4 && (cfg->flags & PSAMD_FLAG_EXPLOSIONS)) ? 16 : 0;
-        if (cfg->flags & PSAMD_FLAG_ALL_PAIRS) {
-            P.allg_cells = cells;
-            P.allg_cap = (int)((slots + 63) & ~(int64_t)63);
-            P.allg_block = MSG_HEADER_WORDS + P.allg_cells + 4 * P.allg_cap;
-        } else if (far_slab(cfg->flags)) {
-            // 16 header | 4 or 10 planes (S, Sx, Sy, Sz; Sxx, Syy, Szz, Sxy, Sxz, Syz) of allg_cells doubles
-            P.allg_cells = cells;
-            P.allg_block = (int)(far_slab_block_bytes(far_planes(cfg->flags), cells) / sizeof(int));
-        }
-    }
-    auto bits_for = [](int64_t n) { int b = 1; while (((int64_t)1 << b) < n) b++; return b; };
-    P.key_chunk_shift = 2 + bits_for(g.container);
-    P.key_rec_shift = P.key_chunk_shift + bits_for((int64_t)g.num_chunks + 1);
-    P.key_bits = P.key_rec_shift + bits_for(g.queue_infos);
-    {
-        // (r.r + eps2)^3 over every pair of in-box positions, with slack for one wrap of drift
-        const double lo = cfg->eps2 * cfg->eps2 * cfg->eps2, hi = std::pow(max_d2(g) + cfg->eps2, 3.0);
-        // (scripts/field_bits.py's "probe-cutoff-8-generic" relies on eps2 = 1e-8 lying below this range: move the range, move the case)
-        P.lean_math = (lo > std::ldexp(1.0, -60) && hi < std::ldexp(1.0, 60)) ? 1 : 0;
-        // Collision flags before forces (lean modes): a collision needs two bodies within
-        // COLLISION_RADIUS, so only bodies that close to a cell face concern the cell beyond it;
-        // 2.5 % + 1e-3 of slack covers every rounding between here and the exact test.  Needs
-        // the radius to be small against the cell (else the halo is the whole neighbour).
-        P.halo_reach = (float)(cfg->collision_radius * 1.025 + 1e-3);
-        {   // largest float t with (double)sqrtf(t) <= COLLISION_RADIUS (sqrtf: correctly rounded, monotone)
-            auto collides = [&](float t) { return !((double)std::sqrt(t) > cfg->collision_radius); };
-            uint32_t lo_b = 0u, hi_b = 0x7f7fffffu;                 // bit patterns of non-negative floats order like the floats
-            auto as_f = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
-            if (!collides(0.0f)) P.coll_d2_max = -1.0f;
-            else {
-                while (lo_b < hi_b) { const uint32_t mid = lo_b + (hi_b - lo_b + 1) / 2; if (collides(as_f(mid))) lo_b = mid; else hi_b = mid - 1; }
-                P.coll_d2_max = as_f(lo_b);
-            }
-        }
-        P.two_pass = (P.lean_math && P.halo_reach < 0.25 * cfg->cell_size && !std::getenv("PSAMD_ONE_PASS")) ? 1 : 0;
-    }
-    if (P.key_bits > 63) return fail(c, PSAMD_ERR_UNSUPPORTED, "queue-op key does not fit 64 bits for this configuration");
-    if ((cfg->flags & PSAMD_FLAG_ALL_PAIRS) && !P.lean_math) return fail(c, PSAMD_ERR_UNSUPPORTED, "all-pairs forces are built for the lean pair arithmetic only (EPS2 in its validated range)");
-    if ((cfg->flags & PSAMD_FLAG_ALL_PAIRS) && !P.two_pass) return fail(c, PSAMD_ERR_UNSUPPORTED, "all-pairs forces need the two-pass pair stage (collision radius small against the cell)");
-    if ((cfg->flags & PSAMD_FLAG_FAR_QUADRUPOLE) && !(cfg->flags & PSAMD_FLAG_FAR_PYRAMID))
-        return fail(c, PSAMD_ERR_INVALID_ARG, "quadrupoles (PSAMD_FLAG_FAR_QUADRUPOLE) belong to the pyramid of monopoles: set PSAMD_FLAG_FAR_PYRAMID too");
-    if (cfg->flags & (PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID)) {
-        // (both flags: what the flat method refuses comes first, then the choice between the two)
-        const bool mono = (cfg->flags & PSAMD_FLAG_FAR_MONOPOLE) != 0, pyr = (cfg->flags & PSAMD_FLAG_FAR_PYRAMID) != 0;
-        const std::string who = mono ? "far monopoles" : "the pyramid of monopoles", is = mono ? " are " : " is ";
-        const char *two = "far monopoles and all-pairs forces are two force models: choose one";
-        const char *three = "the pyramid of monopoles, far monopoles and all-pairs forces are three force models: choose one";
-        if (cfg->flags & PSAMD_FLAG_ALL_PAIRS) return fail(c, PSAMD_ERR_INVALID_ARG, mono ? two : three);
-        if (cfg->world > 1 && !(cfg->flags & PSAMD_FLAG_FAR_SLAB))
-            return fail(c, PSAMD_ERR_UNSUPPORTED, who + is + "served on one context only (world == 1)");
-        if (!P.lean_math) return fail(c, PSAMD_ERR_UNSUPPORTED, who + is + "built for the lean pair arithmetic only (EPS2 in its validated range)");
-        if (!P.two_pass) return fail(c, PSAMD_ERR_UNSUPPORTED, who + (mono ? " need" : " needs") + " the two-pass pair stage (collision radius small against the cell)");
-        if (mono && pyr) return fail(c, PSAMD_ERR_INVALID_ARG, three);
-    }
-    for (int k = 0; k < 5; k++) { c->S.seg_base[k] = g.seg_base[k]; c->S.info_base[k] = g.info_base[k]; }
-    for (int k = 0; k < 4; k++) c->S.seg_size_t[k] = g.seg_size_t[k];
-    P.eps2f = (float)cfg->eps2;
-    P.eps_f32_from = INFINITY;   // always add EPS2 in double, unless probe_eps_f32 finds a threshold
-    return PSAMD_OK;
-}
-
-// room of a neighbour transfer message, in records: the most a step can ask for (also sizes the op and move lists)
-static size_t xfer_room(const DevParams &P) { return (size_t)P.xfer_cap_max + (size_t)P.xfer2_cap + (size_t)P.far_cap * (size_t)std::max(1, P.world) / 2 + 1; }
-
 // What a far pass by (dense task, part) waves needs, the all-pairs one and the monopoles': the partial sums -- one float4 per
 // (part, particle that needs a force), dense, 64 to a task; every entry of the sorted order could be one -- and the dense order.
 static int alloc_dense_parts(psamd_ctx *c, size_t SC, size_t LC)
@@ -240,18 +70,13 @@ static int alloc_dense_parts(psamd_ctx *c, size_t SC, size_t LC)
 // The step's device arrays.  The SEQUENCE of the HIP calls here is load-bearing, the copies and fills between the
 // allocations included (the runtime allocates on their first use): with the three fills and the chunk_segs copy moved
 // behind the last allocation the all-pairs step measured 0.15-0.17 % slower, with the same kernels (see also ctask_start).
-static int alloc_step_arrays(psamd_ctx *c)
+static int alloc_step_arrays(psamd_ctx *c, const std::vector<int> &far_plan)
 {
     const Geometry &g = c->geo; const DevParams &P = c->P; DeviceState &d = c->d;
     const size_t C = (size_t)P.slots_total;          // owned slots
     const size_t SC = (size_t)P.sorted_cap + 64;     // sorted-order arrays (+ slack: scalar loads fetch whole groups)
     const size_t LC = (size_t)P.n_local_cells;
-    const size_t xf = xfer_room(P);
-    d.ops_cap = (int)std::min<size_t>(3 * C + 2 * xf + 64 + (P.world > 1 ? (size_t)P.world * STATUS_KILL_CAP : 0), (size_t)INT32_MAX / 2);
-    d.moves_cap = (int)std::min<size_t>(2 * C + 2 * xf + 64, (size_t)INT32_MAX / 2);
     int *frame = nullptr;
-    // cell counts, chunk counts, queue-op counts and cursors per record, halo counts, active-list lengths, hand-off flags of the force pass
-    const size_t frame_ints = LC + g.num_chunks + 2 * (size_t)g.queue_infos + LC + LC + 2 * LC * P.slices;   // (flags: one block per pass of the pair stage)
     PS_HIP(c, dev_alloc(c, &d.pos4, C));
     PS_HIP(c, dev_alloc(c, &d.vel4, C));
     PS_HIP(c, dev_alloc(c, &d.acc4, C));
@@ -260,13 +85,12 @@ static int alloc_step_arrays(psamd_ctx *c)
     PS_HIP(c, dev_alloc(c, &d.tdata, 6 * C));
     PS_HIP(c, dev_alloc(c, &d.qinfo, (size_t)g.queue_infos));
     PS_HIP(c, dev_alloc(c, &d.queue, C));
-    PS_HIP(c, dev_alloc(c, &frame, frame_ints));
+    PS_HIP(c, dev_alloc(c, &frame, c->frame_ints));
     d.cell_count = frame; d.chunk_count = frame + LC; d.rec_count = d.chunk_count + g.num_chunks;
     d.rec_cursor = d.rec_count + g.queue_infos;
     d.halo_count = d.rec_cursor + g.queue_infos;
     d.active_count = d.halo_count + LC;
     d.task_ready = d.active_count + LC;
-    c->frame_ints = frame_ints;
     PS_HIP(c, dev_alloc(c, &d.halo_f, (size_t)3 * LC * HALO_CAP + 64));   // + slack: scalar loads fetch whole groups
     PS_HIP(c, dev_alloc(c, &d.halo_id, LC * HALO_CAP + 64));
     PS_HIP(c, dev_alloc(c, &d.active_list, SC));
@@ -363,7 +187,6 @@ static int alloc_step_arrays(psamd_ctx *c)
         // the central second moments behind X, Y, Z, M and the raw ones behind S, Sx, Sy, Sz
         const bool pyramid = (P.flags & PSAMD_FLAG_FAR_PYRAMID) != 0;
         const size_t planes = (P.flags & PSAMD_FLAG_FAR_QUADRUPOLE) ? 10 : 4;
-        d.lev = pyramid ? far_levels_of(g.G) : far_one_level(g.G);
         static_assert(FAR_MAX_LEVELS <= ALLP_PARTS, "a level's sum goes into one of the partial-sum planes");
         PS_TRY(alloc_dense_parts(c, SC, LC));
         d.mom_cap = d.lev.off[d.lev.n];
@@ -377,12 +200,8 @@ static int alloc_step_arrays(psamd_ctx *c)
         if (sums) PS_HIP(c, hipMemsetAsync(d.lev_sum, 0, planes * (size_t)d.mom_cap * sizeof(double), c->stream));
         if (P.world > 1) {
             // what every rank's block of the gathered cell sums must say of itself: (first global cell, cells) by rank
-            const psamd_config &cf = g.cfg;
-            std::vector<int> first, cells, tab;
-            gather_block_cells(g.F, g.D, g.seg_base, g.seg_size_t, g.info_base, cf.world, cf.cuts[cf.world] != 0 ? cf.cuts : nullptr, &first, &cells);
-            for (int r = 0; r < cf.world; r++) { tab.push_back(first[(size_t)r]); tab.push_back(cells[(size_t)r]); }
-            PS_HIP(c, dev_alloc(c, &d.far_plan, tab.size()));
-            PS_HIP(c, hipMemcpy(d.far_plan, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+            PS_HIP(c, dev_alloc(c, &d.far_plan, far_plan.size()));
+            PS_HIP(c, hipMemcpy(d.far_plan, far_plan.data(), far_plan.size() * sizeof(int), hipMemcpyHostToDevice));
         }
     }
     // psamd_update's fixed scratch and result record (behind everything older, which stays where it was)
@@ -398,75 +217,29 @@ static int alloc_step_arrays(psamd_ctx *c)
     return PSAMD_OK;
 }
 
-// a slab message's buffer, zeroed: `bytes` travel, `alloc` is the buffer's room (0: the same)
-static hipError_t alloc_msg(psamd_ctx *c, int which, size_t bytes, size_t alloc = 0)
-{
-    SlabMsg &m = c->msg[which];
-    m.bytes = bytes; m.alloc = alloc ? alloc : bytes;
-    const hipError_t e = dev_alloc(c, &m.ptr, m.alloc / sizeof(int));
-    return e != hipSuccess ? e : hipMemsetAsync(m.ptr, 0, m.alloc, c->stream);
-}
-
-// slab messages: sizes fixed by the plan (see slab.hip "slab exchange")
+// The slab messages' buffers, zeroed, in the table's order (context_params.hpp sized them); beside them what indexes them.
 static int alloc_slab_msgs(psamd_ctx *c)
 {
-    const Geometry &g = c->geo; const DevParams &P = c->P; const SlabPlan &pl = c->plan; DeviceState &d = c->d;
-    if (P.world <= 1) return PSAMD_OK;
-    const int GG = g.G * g.G;
-    auto halo_bytes = [&](int cells) { return ((size_t)MSG_HEADER_WORDS + (size_t)cells + 6 * (size_t)cells * P.halo_cap_cell) * sizeof(int); };
-        // out: own layers for the rank below / above; in: what they hold for this rank
-        c->halo_out_cells[0] = (pl.send_down_hi - pl.send_down_lo) * GG; c->halo_out_c0[0] = (pl.send_down_lo - pl.state_lo) * GG;
-        c->halo_out_cells[1] = (pl.send_up_hi - pl.send_up_lo) * GG;     c->halo_out_c0[1] = (pl.send_up_lo - pl.state_lo) * GG;
-        c->halo_in_cells[0] = (pl.below_hi - pl.below_lo) * GG;
-        c->halo_in_cells[1] = (pl.above_hi - pl.above_lo) * GG;
-    for (int k = 0; k < 2; k++) {
-        if (c->halo_out_cells[k] > 0) {
-            PS_HIP(c, alloc_msg(c, MSG_HALO_OUT + k, halo_bytes(c->halo_out_cells[k])));
-            PS_HIP(c, dev_alloc(c, &c->pack_off[k], (size_t)c->halo_out_cells[k] + 1));
-        }
-        if (c->halo_in_cells[k] > 0) {
-            PS_HIP(c, alloc_msg(c, MSG_HALO_IN + k, halo_bytes(c->halo_in_cells[k])));
-            PS_HIP(c, dev_alloc(c, &c->unpack_off[k], (size_t)c->halo_in_cells[k] + 1));
-        }
-    }
-    auto force_bytes = [&](int cells) { return ((size_t)MSG_HEADER_WORDS + 4 * (size_t)cells * P.halo_cap_cell) * sizeof(int); };
-    if (P.reg_layers[2] > 0) PS_HIP(c, alloc_msg(c, MSG_FORCE_OUT, force_bytes(P.reg_layers[2] * GG)));
-    if (P.lentout_c1 > P.lentout_c0) PS_HIP(c, alloc_msg(c, MSG_FORCE_IN, force_bytes(P.lentout_c1 - P.lentout_c0)));
-    // to the neighbours (what travels follows P.xfer_cap, psamd_slab_build; room for a step's worst case), then two ranks away
-    for (int k = 0; k < 2; k++) {
-        PS_HIP(c, alloc_msg(c, MSG_XFER_OUT + k, xfer_msg_bytes((size_t)P.xfer_cap + 1), xfer_msg_bytes(xfer_room(P))));
-        PS_HIP(c, alloc_msg(c, MSG_XFER_IN + k, xfer_msg_bytes((size_t)P.xfer_cap + 1), xfer_msg_bytes(xfer_room(P))));
-    }
-    for (int k = 0; k < 2 && P.xfer2_cap > 0; k++) {
-        PS_HIP(c, alloc_msg(c, MSG_XFER2_OUT + k, xfer_msg_bytes((size_t)P.xfer2_cap)));
-        PS_HIP(c, alloc_msg(c, MSG_XFER2_IN + k, xfer_msg_bytes((size_t)P.xfer2_cap)));
-    }
-    if (P.far_cap > 0) {
-        PS_HIP(c, alloc_msg(c, MSG_FAR_OUT, xfer_msg_bytes((size_t)P.far_cap)));
-        PS_HIP(c, alloc_msg(c, MSG_FAR_IN, xfer_msg_bytes((size_t)P.far_cap) * (size_t)P.world));
-    }
-    const int outbox[5] = {MSG_XFER_OUT, MSG_XFER_OUT + 1, MSG_XFER2_OUT, MSG_XFER2_OUT + 1, MSG_FAR_OUT};
-    for (int k = 0; k < 5; k++)
-        if (c->msg[outbox[k]].ptr) d.xfer_out[k] = reinterpret_cast<XferRec *>(c->msg[outbox[k]].ptr + MSG_HEADER_WORDS);
-    if (P.flags & PSAMD_FLAG_ALL_PAIRS) {
-        const size_t block = (size_t)P.allg_block * sizeof(int);
-        PS_HIP(c, alloc_msg(c, MSG_ALLG_OUT, block));
-        PS_HIP(c, alloc_msg(c, MSG_ALLG_IN, block * P.world, block * P.world + 64 * sizeof(int)));      // + slack: scalar loads fetch whole groups
+    const Geometry &g = c->geo; const DevParams &P = c->P; DeviceState &d = c->d;
+    for (int which : MSG_ALLOC_ORDER) {
+        SlabMsg &m = c->msg[which];
+        if (!m.alloc) continue;
+        PS_HIP(c, dev_alloc(c, &m.ptr, m.alloc / sizeof(int)));
+        PS_HIP(c, hipMemsetAsync(m.ptr, 0, m.alloc, c->stream));
+        const int k = which & 1;
+        if (which - k == MSG_HALO_OUT) PS_HIP(c, dev_alloc(c, &c->pack_off[k], (size_t)c->halo_out_cells[k] + 1));
+        if (which - k == MSG_HALO_IN) PS_HIP(c, dev_alloc(c, &c->unpack_off[k], (size_t)c->halo_in_cells[k] + 1));
+        if (which == MSG_ALLG_IN && (P.flags & PSAMD_FLAG_ALL_PAIRS)) {
             PS_HIP(c, dev_alloc(c, &d.gstart, (size_t)g.num_cells + 1));
             PS_HIP(c, dev_alloc(c, &d.gn, (size_t)g.num_cells + 1));
             PS_HIP(c, hipMemsetAsync(d.gstart, 0, ((size_t)g.num_cells + 1) * sizeof(int), c->stream));
             PS_HIP(c, hipMemsetAsync(d.gn, 0, ((size_t)g.num_cells + 1) * sizeof(int), c->stream));
-        d.allg_in = c->msg[MSG_ALLG_IN].ptr;
+        }
     }
-    if (far_slab(P.flags)) {
-        // the cell sums of every rank's own cells (slab.hip, "far field on slabs"): the all-pairs slot, which a far context leaves free
-        const size_t block = (size_t)P.allg_block * sizeof(int);
-        PS_HIP(c, alloc_msg(c, MSG_ALLG_OUT, block));
-        PS_HIP(c, alloc_msg(c, MSG_ALLG_IN, block * P.world));
-        d.allg_in = c->msg[MSG_ALLG_IN].ptr;
-    }
-    PS_HIP(c, alloc_msg(c, MSG_STATUS_OUT, (size_t)P.status_words * sizeof(int)));
-    PS_HIP(c, alloc_msg(c, MSG_STATUS_IN, (size_t)P.status_words * sizeof(int) * P.world));
+    const int outbox[5] = {MSG_XFER_OUT, MSG_XFER_OUT + 1, MSG_XFER2_OUT, MSG_XFER2_OUT + 1, MSG_FAR_OUT};
+    for (int k = 0; k < 5; k++)
+        if (c->msg[outbox[k]].ptr) d.xfer_out[k] = reinterpret_cast<XferRec *>(c->msg[outbox[k]].ptr + MSG_HEADER_WORDS);
+    d.allg_in = c->msg[MSG_ALLG_IN].ptr;
     d.status_out = c->msg[MSG_STATUS_OUT].ptr;
     return PSAMD_OK;
 }
@@ -496,29 +269,6 @@ static int probe_eps_f32(psamd_ctx *c, const psamd_config *cfg)
     }
     P.slow_below = std::max(P.eps_f32_from, std::nextafterf(P.coll_d2_gate, INFINITY));
     return PSAMD_OK;
-}
-
-// Interior own cells: computed layers whose neighbour layers are both own state (or outside
-// the grid): their collision flags and forces need nothing from another rank, so that
-// pass can run while the halo messages travel (two-pass mode; slab_pairs_interior).
-static void split_interior(psamd_ctx *c)
-{
-    const Geometry &g = c->geo; const DevParams &P = c->P; const SlabPlan &pl = c->plan;
-    const int GG = g.G * g.G, lo = std::max(pl.cut_lo, pl.state_lo), hi = std::min(pl.cut_hi, pl.state_hi);
-    auto own = [&](int l) { return l < 0 || l >= g.G || (l >= pl.state_lo && l < pl.state_hi); };
-    int i0 = lo, i1 = lo;
-    for (int l = lo; l < hi; l++) if (own(l - 1) && own(l + 1)) { if (i1 == i0) i0 = l; i1 = l + 1; } else if (i1 > i0) break;
-    c->P_int = P; c->P_rest = P;
-    c->have_interior = P.world > 1 && P.two_pass && P.lean_math && i1 > i0 && (i1 - i0) < (hi - lo) + (pl.lentin_hi - pl.lentin_lo)
-                       && !(P.flags & (PSAMD_FLAG_ALL_PAIRS | PSAMD_FLAG_FAR_MONOPOLE | PSAMD_FLAG_FAR_PYRAMID));
-    // (an all-pairs pass needs the gathered snapshot, a far pass the gathered cell sums: nothing to do before they land)
-    if (c->have_interior) {
-        const int a = (i0 - pl.state_lo) * GG, b = (i1 - pl.state_lo) * GG;
-        c->P_int.comp_lo[0] = a; c->P_int.comp_hi[0] = b;
-        c->P_int.comp_lo[1] = c->P_int.comp_hi[1] = c->P_int.comp_lo[2] = c->P_int.comp_hi[2] = 0;
-        c->P_rest.comp_lo[1] = P.own_comp0; c->P_rest.comp_hi[1] = a;
-        c->P_rest.comp_lo[2] = b; c->P_rest.comp_hi[2] = P.own_comp1;
-    }
 }
 
 // The state a fresh context starts from, and the tables that never change.
@@ -569,11 +319,9 @@ int psamd_create(const psamd_config *cfg, psamd_ctx **out)
     if (!c) return PSAMD_ERR_OUT_OF_MEMORY;
     *out = c;  // returned even on failure so psamd_last_error can explain; caller destroys it
     if (!c->geo.init(*cfg)) return fail(c, PSAMD_ERR_INVALID_ARG, "bad configuration (chunk_dim >= 3, sizes > 0, container < 2^31)");
-    if (cfg->world < 1 || cfg->world > PSAMD_MAX_RANKS || cfg->rank < 0 || cfg->rank >= cfg->world) return fail(c, PSAMD_ERR_INVALID_ARG, "rank/world");
-    const Geometry &g = c->geo;
-    c->plan = plan_for(g, *cfg);
-    if (!c->plan.valid) return fail(c, PSAMD_ERR_UNSUPPORTED, "no slab partition for this grid and world size (every rank needs >= 2 cell layers "
-                                                                "and its neighbours must hold every layer it reads)");
+    // (derive_context_params' first two refusals, also ahead of the device's: a bad rank or plan is told apart from a missing GPU)
+    std::string why;
+    if (const int rc = rank_plan(*cfg, c->geo, c->plan, why)) return fail(c, rc, why);
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(c, PSAMD_ERR_NO_DEVICE, "hipGetDeviceCount found none");
@@ -585,12 +333,23 @@ int psamd_create(const psamd_config *cfg, psamd_ctx **out)
     PS_HIP(c, hipEventCreateWithFlags(&c->d.ev_fork, hipEventDisableTiming));
     PS_HIP(c, hipEventCreateWithFlags(&c->d.ev_join, hipEventDisableTiming));
 
-    int rc = derive_params(c, cfg);
-    if (rc == PSAMD_OK) rc = alloc_step_arrays(c);
+    ContextParams cp;
+    int rc = derive_context_params(*cfg, c->geo, std::getenv("PSAMD_ONE_PASS") != nullptr, cp, why);
+    if (rc != PSAMD_OK) return fail(c, rc, why);
+    c->P = cp.P; c->S = cp.S; c->have_interior = cp.have_interior;
+    c->frame_ints = cp.frame_ints; c->d.ops_cap = cp.ops_cap; c->d.moves_cap = cp.moves_cap; c->d.lev = cp.lev;
+    for (int k = 0; k < 2; k++) { c->halo_out_c0[k] = cp.halo_out_c0[k]; c->halo_out_cells[k] = cp.halo_out_cells[k]; c->halo_in_cells[k] = cp.halo_in_cells[k]; }
+    for (int w = 0; w < MSG_COUNT; w++) { c->msg[w].bytes = cp.msg[w].bytes; c->msg[w].alloc = cp.msg[w].alloc; }
+    rc = alloc_step_arrays(c, cp.far_plan);
     if (rc == PSAMD_OK) rc = alloc_slab_msgs(c);
     if (rc == PSAMD_OK) rc = probe_eps_f32(c, cfg);      // (on the device: after the allocations, as ever)
     if (rc != PSAMD_OK) return rc;
-    split_interior(c);
+    // the pair stage cut in two: the probed parameters, each pass's own ranges
+    c->P_int = c->P_rest = c->P;
+    for (int k = 0; k < 3; k++) {
+        c->P_int.comp_lo[k] = cp.int_lo[k]; c->P_int.comp_hi[k] = cp.int_hi[k];
+        c->P_rest.comp_lo[k] = cp.rest_lo[k]; c->P_rest.comp_hi[k] = cp.rest_hi[k];
+    }
     return init_state(c);
 }
 
@@ -668,9 +427,9 @@ int psamd_slab_plan_describe(const psamd_config *cfg, psamd_slab_plan *o)
     if (!cfg || !o) return PSAMD_ERR_INVALID_ARG;
     Geometry g;
     if (!g.init(*cfg)) return PSAMD_ERR_INVALID_ARG;
-    if (cfg->world < 1 || cfg->world > PSAMD_MAX_RANKS || cfg->rank < 0 || cfg->rank >= cfg->world) return PSAMD_ERR_INVALID_ARG;
-    const SlabPlan p = plan_for(g, *cfg);
-    if (!p.valid) return PSAMD_ERR_UNSUPPORTED;
+    SlabPlan p;
+    std::string why;
+    if (const int rc = rank_plan(*cfg, g, p, why)) return rc;
     std::memset(o, 0, sizeof *o);
     o->world = p.world; o->rank = p.rank; o->grid_dim = p.G;
     o->cut_lo = p.cut_lo; o->cut_hi = p.cut_hi; o->state_lo = p.state_lo; o->state_hi = p.state_hi;

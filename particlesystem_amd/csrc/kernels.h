@@ -155,12 +155,19 @@ struct DepositScratch {
     psamd_deposit_result *own;    // the context's own result record (psamd_deposit_result_get)
 };
 
-// Container layout by segment type (slots and QUEUE_INFO records), device copy.
-struct SegLayout {
-    int32_t seg_base[5];
-    int32_t info_base[5];
-    int32_t seg_size_t[4];
+// All-pairs force pass.  The cells beyond the stencil are found by GLOBAL cell in a snapshot buffer (the own
+// one, or the all-gathered one of all ranks): x at buf[start], y, z, w_eff at multiples of `plane` behind.
+// The stencil's chain comes from the ordinary (cutoff) force pass; the rest of a particle's sum is split into
+// ALLP_PARTS partial sums, each by a wave of its own (or a lone rank of eight would have half a wave per SIMD
+// walking the whole cloud): part p covers its share of the 64-cell blocks of the global cell order; partial sums
+// land in part_acc[p * part_plane + r], r = the particle's place among those that need a force, and
+// k_allpairs_combine adds them to the stencil's chain in part order (allpairs.hip, k_allp_far).
+struct FarCells {
+    unsigned long long plane = 0;
+    float4 *part_acc = nullptr;
+    unsigned long long part_plane = 0;
 };
+constexpr int ALLP_PARTS = 16;
 
 // Every device allocation of a context.  SoA by slot unless noted.
 struct DeviceState {

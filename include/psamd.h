@@ -369,6 +369,36 @@ typedef struct psamd_deposit_spec {
     psamd_deposit_result *result_dev;  /* optional out (device), 8-byte aligned; NULL: the context's own record only */
 } psamd_deposit_spec;         /* 32 bytes */
 
+/* psamd_sample_spec.flags (see "a lattice field at the particles" below) */
+#define PSAMD_SAMPLE_VEC4         0x1u  /* field is float4 per voxel, out is float4 per entry; without it float / float */
+#define PSAMD_SAMPLE_EXPORT_ORDER 0x2u  /* pos4 must be NULL: entry k is the k-th live owned particle in ascending global
+                                           slot id (psamd_export_live's pairing); its x, y, z come from the context */
+
+/* What psamd_sample did. */
+typedef struct psamd_sample_result {
+    int64_t done;             /* n: entries examined                                                          */
+    int64_t served;           /* outcome 0                                                                    */
+    int64_t outside;          /* outcome 1                                                                    */
+    int64_t nonfinite;        /* of served, entries with a word of out not finite                             */
+} psamd_sample_result;        /* 32 bytes */
+
+/* What psamd_sample reads and where it writes (device pointers; none of them inside the context's own arrays). */
+typedef struct psamd_sample_spec {
+    uint32_t flags;           /* PSAMD_SAMPLE_*                                                               */
+    int32_t  refine;          /* k: 1, 2 or 4 -- psamd_deposit's lattice                                      */
+    const void *field;        /* float[capacity] or float4[capacity], indexed as psamd_deposit's out; required */
+    int64_t  capacity;        /* >= (grid_dim * refine)^3 voxels                                              */
+    const void *pos4;         /* float4[max_count], x, y, z (w ignored); NULL with PSAMD_SAMPLE_EXPORT_ORDER  */
+    int64_t  max_count;       /* 0 <= max_count < 2^31; sizes the launches                                    */
+    const int64_t *count_dev; /* optional, 8-byte aligned: n = clamp(*count_dev, 0, max_count), read by the
+                                 kernels; NULL: n = max_count                                                 */
+    void    *out;             /* float[max_count] or float4[max_count]                                        */
+    float    scale;           /* every word of out is RN(scale * value); taken as given (0 gives zeros)       */
+    int32_t  reserved;        /* 0                                                                            */
+    int32_t *outcome_dev;     /* optional out, int32[max_count]: every entry's outcome code                   */
+    psamd_sample_result *result_dev;   /* optional out (device), 8-byte aligned; NULL: the context's own record only */
+} psamd_sample_spec;          /* 80 bytes */
+
 typedef struct psamd_ctx psamd_ctx;
 
 /* ---- lifetime ------------------------------------------------------------ */
@@ -1064,6 +1094,86 @@ int psamd_probe_result_get(psamd_ctx *ctx, psamd_probe_result *out);
 int psamd_deposit(psamd_ctx *ctx, const psamd_deposit_spec *spec);
 int psamd_deposit_result_get(psamd_ctx *ctx, psamd_deposit_result *out);
 int psamd_download_deposit(psamd_ctx *ctx, int32_t refine, float *out, int64_t capacity, psamd_deposit_result *result);
+
+/* ---- a lattice field at the particles ---------------------------------------------- */
+/* psamd_sample: a field the CALLER holds on psamd_deposit's lattice -- a potential or a force solved from the deposit with an
+ * FFT or a stencil, a hand-made external field -- read back at points of the caller's choosing or at the live particles
+ * themselves, cloud-in-cell.  It is the exact adjoint of psamd_deposit: the weight a body gives a voxel there is the weight
+ * that voxel's value has in the body's sample here, the same fp32 number.  Adjoint weights are what make a particle-mesh
+ * force free of self-force and momentum-conserving; with psamd_update (VEL | ADD | EXPORT_ORDER) behind it the loop
+ * deposit -> solve -> sample -> kick stays on the device.  psamd_probe serves the library's own pair field; this serves the
+ * caller's.  Not in the reference; the step's arithmetic is untouched and PSAMD_ABI_VERSION stays 8.
+ *
+ * Lattice and axes.  psamd_deposit's, word for word ("mass on a lattice" above): refine = k in {1, 2, 4}, M = G k voxels per
+ * axis, the axes (q1, q2, q3) = (-y, x, -z), voxel (n1, n2, n3) at index (n3 M + n1) M + n2, inv_h and off as there.  `field`
+ * holds one float per voxel, or with PSAMD_SAMPLE_VEC4 one float4 (say a force and a potential, solved together); `out` has
+ * the same layout per entry.
+ *
+ * Weights.  Per axis u = RN(RN(s inv_h) + off), u_c = min(max(u, 0), M - 1), n0 = (int)floor(u_c), f = u_c - n0 (exact); the
+ * weights are RN(1 - f) for voxel n0 and f for n0 + 1.  Every operation is rounded on its own, nothing is fused.
+ *
+ * Terms.  The eight voxels (n3 + d3, n1 + d1, n2 + d2) are visited in the order (d3, d1, d2), each 0 then 1 -- the deposit's
+ * loop order -- with W = RN(RN(W1 W2) W3).  A voxel with an axis weight of exactly 0 is NOT READ and adds no term: n0 + 1 == M
+ * is never touched, and a NaN in a voxel the point does not reach is harmless.  Otherwise the term is RN(W v) in fp32, per
+ * component.
+ *
+ * Sum.  One fp64 chain per component starts at +0 and takes the terms in that order; value = (float)sum and every word of
+ * out[k] is RN(scale value).  Consequences: with scale 1 a point on a voxel centre returns that voxel's value (-0 becomes
+ * +0); a point beyond the outermost centres returns the face voxel's value -- the deposit's fold, read backwards.
+ *
+ * Outcomes.  Every entry k < n:
+ *     0  served
+ *     1  outside the box by Geometry::locate (the fp64 floor test psamd_probe and psamd_inject use); coordinates that are not
+ *        numbers, and huge ones, count as outside
+ * An entry with outcome 1 gets the quiet NaN 0x7fc00000 in every word of out[k].  Entries at or past n are not touched.  There
+ * is no "foreign" outcome: the call reads the geometry, the caller's lattice and, with PSAMD_SAMPLE_EXPORT_ORDER, the context's
+ * pos4 and cell.  It reads no frame.
+ *
+ * Result.  done: the entries examined; served / outside: those with outcome 0 / 1; nonfinite: of the served, the entries
+ * with a word of out that is not finite (the lattice's, or scale's).
+ *
+ * Slabs.  A rank serves every in-box point it is given, whichever rank owns the cell, and the caller hands each rank the
+ * WHOLE lattice: psamd_deposit writes a rank's voxels only, so the ranks' lattices are summed first (psamd_download_deposit's
+ * arrays add up exactly across ranks, see above).  By PSAMD_SAMPLE_EXPORT_ORDER a rank's entries are its own export's.  The
+ * words are the single context's bytes.
+ *
+ * PSAMD_SAMPLE_EXPORT_ORDER.  pos4 is NULL; entry k is the k-th live owned particle in ascending slot id -- the pairing of
+ * psamd_export_live, of psamd_potential's phi[] and of psamd_update's order form, so out feeds psamd_update as it is -- and
+ * its x, y, z are read from the context.  Live particles past n are not served; entries at or past the live count are not
+ * touched; done = min(n, live count).  A live particle whose position is not a number gets outcome 1.  Valid wherever
+ * psamd_export_live is valid, except between psamd_slab_apply and psamd_slab_finish (the departing particles are staged:
+ * PSAMD_ERR_STATE, as psamd_update).
+ *
+ * Window.  The points form is valid at any stage of any context kind -- before the first psamd_build_grid, mid-frame, on
+ * far-field slabs.  The only refusal is a wedged context (PSAMD_ERR_STATE).  The call neither ends nor disturbs a frame and
+ * writes nothing of the context's but its own result record.
+ *
+ * Everything is enqueued on the context's stream (psamd_get_stream): nothing waits, nothing is read back, no host
+ * bookkeeping; PSAMD_OK says the work is enqueued, only the result record says what happened.  The scratch -- three integer
+ * counters, and by export order psamd_update's live count per tile of slots -- is allocated at psamd_create, so the call
+ * allocates nothing and may always be captured into a graph.  The counters meet by integer atomics, in any order the same
+ * record; no floating-point atomic appears anywhere.  *result_dev and the context's own record (psamd_sample_result_get) are
+ * written by the time the stream reaches the end of the call.
+ *
+ * Determinism.  An entry's words depend on its position, the lattice and scale alone: not on the other entries, max_count,
+ * graphs, the form (points or export order) or the rank.
+ *
+ * Cost on an MI355X at N = 2^20 on 16^3 cells, 321 670 live in 2 997 648 owned slots (scripts/sample_cost.py;
+ * profiles/sample_cost.txt), measured: by export order 0.069 ms (float) and 0.074 ms (float4) at refine 2 -- 0.068 to 0.075 ms over
+ * the three refines and both layouts -- and 0.090 to 0.092 ms for the points form at the export's positions, beside 0.58 ms (float)
+ * and 0.97 ms (float4) for psamd_export_live plus the same interpolation written in torch (index arithmetic, eight gathers, a
+ * weighted sum) in the same run: 8 and 13 times the order form.  The export of POS alone took 0.062 ms and psamd_probe ACC | PHI
+ * on the same positions 1.30 ms (host clock around the call plus psamd_synchronize, the stream idle before it).
+ *
+ * PSAMD_ERR_INVALID_ARG: a NULL context or spec, unknown flag bits, reserved != 0, refine not 1, 2 or 4, capacity < M^3,
+ * max_count outside [0, 2^31), field NULL, out NULL with max_count > 0, pos4 NULL without PSAMD_SAMPLE_EXPORT_ORDER (with
+ * max_count > 0) or not NULL with it, pos4 not 16-byte aligned, field or out not 16-byte aligned under PSAMD_SAMPLE_VEC4 or not
+ * 4-byte aligned without it, outcome_dev not 4-byte aligned, count_dev or result_dev not 8-byte aligned.  max_count == 0
+ * writes a zero result and launches nothing else.
+ *
+ * psamd_sample_result_get: the last sample's record, into host memory; waits for the context's stream. */
+int psamd_sample(psamd_ctx *ctx, const psamd_sample_spec *spec);
+int psamd_sample_result_get(psamd_ctx *ctx, psamd_sample_result *out);
 
 /* ---- long-range gravity (PSAMD_FLAG_FAR_MONOPOLE) ------------------------------ */
 /* The cutoff pass leaves most of a long-range force out; PSAMD_FLAG_ALL_PAIRS has all of it at O(N^2).  With this flag a

@@ -302,6 +302,29 @@ def merge_deposit(results):
     return out
 
 
+# psamd_sample: the flags, and the outcome codes of the entries
+SAMPLE_VEC4, SAMPLE_EXPORT_ORDER = 0x1, 0x2
+SAMPLE_SERVED, SAMPLE_OUTSIDE = 0, 1
+
+
+class SampleResult(_Record):
+    """psamd_sample_result: what psamd_sample did."""
+    _fields_ = [(n, C.c_int64) for n in ("done", "served", "outside", "nonfinite")]
+
+
+class SampleSpec(C.Structure):
+    """psamd_sample_spec: what psamd_sample reads and where it writes (device pointers)."""
+    _fields_ = [("flags", C.c_uint32), ("refine", C.c_int32), ("field", C.c_void_p), ("capacity", C.c_int64), ("pos4", C.c_void_p),
+                ("max_count", C.c_int64), ("count_dev", C.c_void_p), ("out", C.c_void_p), ("scale", C.c_float), ("reserved", C.c_int32),
+                ("outcome_dev", C.c_void_p), ("result_dev", C.c_void_p)]
+
+
+def merge_sample(results):
+    """The sample of a slab world from its ranks' records (dicts of sample(result=True) / sample_result()): every count adds
+    (by export order each rank serves its own particles; given the same points, `done` adds up to world * n)."""
+    return _merge_counts(results, SampleResult)
+
+
 def merge_live_stats(stats):
     """The statistics of a system from its ranks' (dicts of live_stats() / export_live()["stats"]): counts and sums
     add, in rank order; the box and the ages take the minima and maxima."""
@@ -414,6 +437,8 @@ ABI = [
     ("psamd_deposit", C.c_int, [_vp, C.POINTER(DepositSpec)]),
     ("psamd_deposit_result_get", C.c_int, [_vp, C.POINTER(DepositResult)]),
     ("psamd_download_deposit", C.c_int, [_vp, C.c_int32, _vp, _i64, C.POINTER(DepositResult)]),
+    ("psamd_sample", C.c_int, [_vp, C.POINTER(SampleSpec)]),
+    ("psamd_sample_result_get", C.c_int, [_vp, C.POINTER(SampleResult)]),
 ]
 
 _lib = None
@@ -1076,6 +1101,53 @@ class ParticleSystem:
         r = DepositResult()
         self._ck(self.lib.psamd_download_deposit(self.h, int(refine), _ptr(out), out.size, C.byref(r)))
         return out, r.to_dict()
+
+    # ---- a lattice field at the particles (include/psamd.h) ---------------------
+    def sample(self, field, pos4=None, count=None, scale=1.0, out=None, outcome=False, result=False):
+        """psamd_sample: a lattice field of the caller's read at points, cloud-in-cell with deposit()'s weights.  field: a
+        float32 torch device tensor [M, M, M] or [M, M, M, 4] on deposit()'s lattice (indexed [n3, n1, n2]; refine is
+        M / grid_dim).  pos4: float32 [m, 4] (x, y, z; w ignored), or None: export order -- entry k is the k-th live particle
+        of export_live(), as many entries as `out` has, or as the context owns slots.  count: None (all entries) or a
+        1-element int64 device tensor that work on torch's current stream may write just before.  out: a float32 tensor [m]
+        or [m, 4] to write into (entries that are not served stay as they are); None: a fresh one of zeros.  Every word is
+        scale times the interpolated value; a point outside the box gets quiet NaNs.  Returns out, or with outcome=True
+        and / or result=True the tuple (out, [outcome: int32 [m], SAMPLE_SERVED / SAMPLE_OUTSIDE, -1 where no entry was
+        examined], [the record as a dict]).  Waits for the context's stream.  torch must have been imported before the
+        library was loaded."""
+        import torch
+        dev = field.device
+        vec4 = field.dim() == 4
+        M = int(field.shape[0])
+        G = int(self.sizes.grid_dim)
+        assert M % G == 0, "sample: the field's edge is no multiple of grid_dim"
+        fp = _tensor_ptr("sample", field, torch.float32, (M, M, M, 4) if vec4 else (M, M, M), what="field tensor")
+        if pos4 is not None:
+            m = int(pos4.shape[0])
+        else:
+            m = int(out.shape[0]) if out is not None else self.owned_slots()
+        shape = (max(m, 1), 4) if vec4 else (max(m, 1),)
+        if out is None:
+            out = torch.zeros(shape, dtype=torch.float32, device=dev)
+            op = out.data_ptr()
+        else:
+            op = _tensor_ptr("sample", out, torch.float32, (m, 4) if vec4 else (m,), dev, "out tensor")
+        spec = SampleSpec(flags=(SAMPLE_VEC4 if vec4 else 0) | (SAMPLE_EXPORT_ORDER if pos4 is None else 0), refine=M // G, field=fp,
+                          capacity=M ** 3, max_count=m, scale=float(scale))
+        spec.pos4 = _tensor_ptr("sample", pos4, torch.float32, (m, 4), dev, "pos4 tensor") if m > 0 else None
+        spec.out = op if m > 0 else None
+        spec.count_dev = _count_ptr("sample", count, dev)
+        codes = _outcome(m, dev) if outcome else None
+        spec.outcome_dev = None if codes is None else codes.data_ptr()
+        rec = torch.zeros(C.sizeof(SampleResult), dtype=torch.uint8, device=dev) if result else None
+        spec.result_dev = None if rec is None else rec.data_ptr()
+        with self._on_stream(dev):
+            self._ck(self.lib.psamd_sample(self.h, C.byref(spec)))
+        ret = (out[:m],) + ((codes[:m],) if outcome else ()) + ((SampleResult.from_device(rec).to_dict(),) if result else ())
+        return ret if len(ret) > 1 else ret[0]
+
+    def sample_result(self):
+        """psamd_sample_result_get: the last sample's record as a dict"""
+        return self._own_record(SampleResult, self.lib.psamd_sample_result_get)
 
     def device_view(self):
         v = DeviceView()

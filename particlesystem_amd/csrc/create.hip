@@ -214,6 +214,10 @@ static int alloc_step_arrays(psamd_ctx *c, const std::vector<int> &far_plan)
     PS_HIP(c, dev_alloc(c, &c->dep.parts, ((size_t)comp_count(P) * 8 + DEPOSIT_WG_TASKS - 1) / DEPOSIT_WG_TASKS));
     PS_HIP(c, dev_alloc(c, &c->dep.own, 1));
     PS_HIP(c, hipMemsetAsync(c->dep.own, 0, sizeof(psamd_deposit_result), c->stream));
+    // psamd_sample's counters and result record
+    PS_HIP(c, dev_alloc(c, &c->smp.hdr, SAMPLE_HDR_WORDS));
+    PS_HIP(c, dev_alloc(c, &c->smp.own, 1));
+    PS_HIP(c, hipMemsetAsync(c->smp.own, 0, sizeof(psamd_sample_result), c->stream));
     return PSAMD_OK;
 }
 

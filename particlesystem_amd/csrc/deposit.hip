@@ -23,6 +23,7 @@
 //
 // VGPRs / waves per SIMD as the compiler reports them for gfx950, no instance with scratch, no LDS beyond the 96 bytes of
 // the partials:    K = 1: 29 / 8      K = 2: 52 / 8      K = 4: 52 / 8      k_deposit_finish: 28 / 8 (its LDS: tile_order_sums')
+#include "lattice.hpp"
 #include "slot_walk.hpp"
 
 namespace psamd {
@@ -30,22 +31,7 @@ namespace psamd {
 constexpr int DEP_THREADS = 64 * DEPOSIT_WG_TASKS;
 static_assert(DEP_THREADS == SLOT_THREADS, "k_deposit_finish is a workgroup of tile_order_sums");
 
-__device__ __forceinline__ bool dep_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// one axis of one body: u = RN(RN(s inv_h) + off) clamped to [0, M - 1]; n0 = floor, f = u - n0 (exact); the weights
-// RN(1 - f) for voxel n0 and f for n0 + 1
-struct DepAxis {
-    int n0;
-    float w0, w1;
-    __device__ __forceinline__ DepAxis(float s, const DepositArgs &a)
-    {
-        const float u = __fadd_rn(__fmul_rn(s, a.inv_h), a.off);
-        const float uc = fminf(fmaxf(u, 0.f), a.top), fl = floorf(uc);
-        n0 = (int)fl; w1 = __fsub_rn(uc, fl); w0 = __fsub_rn(1.f, w1);
-    }
-    // the weight the body gives voxel n of this axis (n0 + 1 == M is no voxel: never asked for)
-    __device__ __forceinline__ float at(int n) const { return n == n0 ? w0 : n == n0 + 1 ? w1 : 0.f; }
-};
+// (the weights of one axis of one body: DepAxis, lattice.hpp -- psamd_sample reads a lattice back with the same ones)
 
 template <int K>
 __global__ __launch_bounds__(DEP_THREADS) void k_deposit(DevParams P, const int *__restrict__ cell_start,

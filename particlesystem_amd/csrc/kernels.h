@@ -135,12 +135,14 @@ struct ProbeScratch {
 // 2 x 2 x 2 voxels of it): 1, 1 or 8 tasks a cell for refine 1, 2, 4; four tasks to a workgroup, whose partials are one entry
 constexpr int DEPOSIT_WG_TASKS = 4;
 inline int deposit_cell_tasks(int refine) { return refine == 4 ? 8 : 1; }
-struct DepositArgs {
+struct DepLattice {   // the lattice of refine k on a context's grid (the host: deposit_lattice, services.hip), psamd_sample's too
     int32_t refine;   // k: voxels per cell edge (1, 2 or 4)
     int32_t M;        // G * k voxels per axis
     float inv_h;      // (float)((double)k / cell_size)
     float off;        // (float)((G / 2) * k) - 0.5f
     float top;        // (float)(M - 1)
+};
+struct DepositArgs : DepLattice {
     float *out;       // [M^3] the lattice, voxel (n1, n2, n3) at (n3 * M + n1) * M + n2
     psamd_deposit_result *result;   // the caller's record (may be null)
 };
@@ -153,6 +155,26 @@ struct DepositPart {  // what a workgroup's (up to) four tasks saw, merged in ta
 struct DepositScratch {
     DepositPart *parts;     // [ceil(compute cells * 8 / 4)]: room for refine 4, sized at creation
     psamd_deposit_result *own;    // the context's own result record (psamd_deposit_result_get)
+};
+
+// psamd_sample (sample.hip): the caller's lattice on psamd_deposit's lattice, what else the caller gave, and the scratch.  By
+// export order the tiles' live counts are psamd_update's (UpdateScratch::tile_live: the two services are ordered by the
+// stream and each counts anew); all of it is sized at creation
+constexpr int SAMPLE_HDR_WORDS = 3;
+struct SampleArgs : DepLattice {
+    uint32_t flags;   // PSAMD_SAMPLE_*
+    float scale;
+    const void *field;          // float[M^3] or float4[M^3], indexed as DepositArgs::out
+    const float4 *pos4;         // null by export order
+    int64_t max_count;
+    const int64_t *count_dev;
+    void *out;                  // float[max_count] or float4[max_count]
+    int *outcome;
+    psamd_sample_result *result;    // the caller's record, or the context's own
+};
+struct SampleScratch {
+    int *hdr;         // [SAMPLE_HDR_WORDS] the entries served, outside, and of the served those with a word that is not finite
+    psamd_sample_result *own;     // the context's own result record (psamd_sample_result_get)
 };
 
 // All-pairs force pass.  The cells beyond the stencil are found by GLOBAL cell in a snapshot buffer (the own
@@ -381,5 +403,12 @@ hipError_t launch_remove_box(hipStream_t st, const DevParams &P, const SegLayout
 hipError_t launch_update_ids(hipStream_t st, const DevParams &P, const DeviceState &d, const UpdateArgs &a, const UpdateScratch &s,
                              int *claim);
 hipError_t launch_update_order(hipStream_t st, const DevParams &P, const DeviceState &d, const UpdateArgs &a, const UpdateScratch &s);
+// ... the first pass of the order form on its own: per tile of SLOT_TILE owned slots the live slots (psamd_sample's too)
+hipError_t launch_live_tiles(hipStream_t st, const DevParams &P, const DeviceState &d, int *tile_live);
+
+// psamd_sample (max_count > 0): the three counters zeroed, one pass over the entries (the points form) or the tiles' live
+// counts and one pass over the owned slots (by export order; tile_live: psamd_update's), the result record
+hipError_t launch_sample(hipStream_t st, const DevParams &P, const DeviceState &d, const SampleArgs &a, const SampleScratch &s,
+                         int *tile_live);
 
 }  // namespace psamd

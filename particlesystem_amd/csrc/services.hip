@@ -1,5 +1,5 @@
 // services.hip -- the host side of the on-stream services: psamd_export_live (export.hip), psamd_inject (inject.hip),
-// psamd_remove (remove.hip), psamd_update (update.hip), psamd_potential (potential.hip), psamd_probe (probe.hip), psamd_deposit (deposit.hip), their host-array forms and their result records.
+// psamd_remove (remove.hip), psamd_update (update.hip), psamd_potential (potential.hip), psamd_probe (probe.hip), psamd_deposit (deposit.hip), psamd_sample (sample.hip), their host-array forms and their result records.
 // A service enqueues its launches on the context's stream and returns; nothing here enqueues a stage of the step.
 #include "context.hpp"
 
@@ -416,7 +416,7 @@ int psamd_probe_result_get(psamd_ctx *c, psamd_probe_result *out) { return read_
 
 // ---- mass on a lattice (deposit.hip) ----
 // the lattice of refine k on this context's grid, or nothing (refine not 1, 2 or 4)
-static bool deposit_lattice(const psamd_ctx *c, int32_t refine, DepositArgs &a, int64_t &voxels)
+static bool deposit_lattice(const psamd_ctx *c, int32_t refine, DepLattice &a, int64_t &voxels)
 {
     if (refine != 1 && refine != 2 && refine != 4) return false;
     const int G = c->P.G;
@@ -465,5 +465,37 @@ int psamd_download_deposit(psamd_ctx *c, int32_t refine, float *out, int64_t cap
     PS_HIP(c, hipStreamSynchronize(c->stream));
     return PSAMD_OK;
 }
+
+// ---- a lattice field at the particles (sample.hip) ----
+int psamd_sample(psamd_ctx *c, const psamd_sample_spec *spec)
+{
+    PS_TRY(service_args(c, spec));
+    SampleArgs a{};
+    int64_t voxels = 0;
+    const bool vec4 = (spec->flags & PSAMD_SAMPLE_VEC4) != 0, order = (spec->flags & PSAMD_SAMPLE_EXPORT_ORDER) != 0, some = spec->max_count > 0;
+    if ((spec->flags & ~(PSAMD_SAMPLE_VEC4 | PSAMD_SAMPLE_EXPORT_ORDER)) || spec->reserved != 0)
+        return fail(c, PSAMD_ERR_INVALID_ARG, "sample: unknown flag bits, or reserved not 0");
+    if (!deposit_lattice(c, spec->refine, a, voxels)) return fail(c, PSAMD_ERR_INVALID_ARG, "sample: refine is not 1, 2 or 4");
+    if (spec->capacity < voxels) return fail(c, PSAMD_ERR_INVALID_ARG, "sample: capacity is less than (grid_dim * refine)^3");
+    if (spec->max_count < 0 || spec->max_count > INT32_MAX) return fail(c, PSAMD_ERR_INVALID_ARG, "sample: max_count outside [0, 2^31)");
+    if (!spec->field || (some && !spec->out)) return fail(c, PSAMD_ERR_INVALID_ARG, "sample: field missing, or out missing");
+    if (order ? spec->pos4 != nullptr : some && !spec->pos4)
+        return fail(c, PSAMD_ERR_INVALID_ARG, "sample: pos4 missing, or given with PSAMD_SAMPLE_EXPORT_ORDER");
+    const size_t word = vec4 ? 16 : 4;
+    if (!aligned(spec->pos4, 16) || !aligned(spec->field, word) || !aligned(spec->out, word) || !aligned(spec->outcome_dev, 4) ||
+        !aligned(spec->count_dev, 8) || !aligned(spec->result_dev, 8))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "sample: an array misaligned");
+    if (order && !update_window(c->stage))
+        return fail(c, PSAMD_ERR_STATE, "sample: between slab_apply and slab_finish the departing particles are staged (by export order "
+                                        "their entries would pair with no export)");
+    psamd_sample_result *res = spec->result_dev ? spec->result_dev : c->smp.own;
+    if (!some) return zero_result(c, c->smp.own, res, sizeof *res);
+    a.flags = spec->flags; a.scale = spec->scale; a.field = spec->field; a.pos4 = (const float4 *)spec->pos4;
+    a.max_count = spec->max_count; a.count_dev = spec->count_dev; a.out = spec->out; a.outcome = spec->outcome_dev; a.result = res;
+    PS_HIP(c, launch_sample(c->stream, c->P, c->d, a, c->smp, c->upd.tile_live));
+    return PSAMD_OK;
+}
+
+int psamd_sample_result_get(psamd_ctx *c, psamd_sample_result *out) { return read_own(c, out, c ? c->smp.own : nullptr, sizeof *out); }
 
 }  // extern "C"

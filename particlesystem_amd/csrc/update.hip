@@ -212,13 +212,20 @@ hipError_t launch_update_ids(hipStream_t st, const DevParams &P, const DeviceSta
     return hipSuccess;
 }
 
-hipError_t launch_update_order(hipStream_t st, const DevParams &P, const DeviceState &d, const UpdateArgs &a, const UpdateScratch &s)
+hipError_t launch_live_tiles(hipStream_t st, const DevParams &P, const DeviceState &d, int *tile_live)
 {
     const int ntiles = slot_tiles(P.slots_total);
     if (ntiles > 0) {
-        k_update_count<<<ntiles, SLOT_THREADS, 0, st>>>(P, d.cell, s.tile_live);
+        k_update_count<<<ntiles, SLOT_THREADS, 0, st>>>(P, d.cell, tile_live);
         PS_LAUNCH_CHECK();
     }
+    return hipSuccess;
+}
+
+hipError_t launch_update_order(hipStream_t st, const DevParams &P, const DeviceState &d, const UpdateArgs &a, const UpdateScratch &s)
+{
+    const int ntiles = slot_tiles(P.slots_total);
+    {   const hipError_t e = launch_live_tiles(st, P, d, s.tile_live); if (e != hipSuccess) return e; }
     k_update_order<<<ntiles + 1, SLOT_THREADS, 0, st>>>(P, a.fields, ntiles, a.max_count, a.count_dev, d.cell, s.tile_live, a.vel4, a.w,
                                                         a.fert_age, a.outcome, s.own, a.result, d.pos4, d.vel4, d.acc4);
     PS_LAUNCH_CHECK();

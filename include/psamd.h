@@ -399,6 +399,33 @@ typedef struct psamd_sample_spec {
     psamd_sample_result *result_dev;   /* optional out (device), 8-byte aligned; NULL: the context's own record only */
 } psamd_sample_spec;          /* 80 bytes */
 
+/* psamd_neighbours_spec.flags (see "neighbours within a radius" below) */
+#define PSAMD_NEIGHBOURS_INDEX 0x1u     /* a neighbour is named by its export index, not by its global slot id (world == 1) */
+
+/* What psamd_neighbours found. */
+typedef struct psamd_neighbours_result {
+    int64_t listed;           /* the queries: the particles of the own cells' lists                           */
+    int64_t pairs;            /* the sum of all queries' counts, the whole context's: directed pairs          */
+    int64_t wanted;           /* offsets[m]: the list entries the first m = min(live, capacity) particles have */
+    int32_t max_count;        /* the largest count                                                            */
+    int32_t reserved;         /* 0                                                                            */
+    double  d2_min;           /* the smallest d2 over all neighbours; +inf if there is none                   */
+} psamd_neighbours_result;    /* 40 bytes */
+
+/* What psamd_neighbours writes and where (device pointers; none of them inside the context's own arrays). */
+typedef struct psamd_neighbours_spec {
+    uint32_t flags;           /* PSAMD_NEIGHBOURS_*                                                           */
+    float    radius;          /* finite, > 0, (double)radius <= cell_size                                     */
+    int32_t *count;           /* optional out, int32[capacity], 4-byte aligned: neighbours; -1: in no list    */
+    int32_t *nearest;         /* optional out, int32[capacity]: the neighbour with the smallest d2, or -1     */
+    float   *nearest_d2;      /* optional out, float[capacity]: that d2, or +inf                              */
+    int64_t *offsets;         /* optional out, int64[capacity + 1], 8-byte aligned: exclusive prefix of max(count, 0) */
+    int64_t  capacity;        /* >= 0: entries of the export order that are written                           */
+    int32_t *list;            /* optional out, int32[list_capacity]; needs offsets                            */
+    int64_t  list_capacity;   /* >= 0: position p of the lists is written iff p < list_capacity               */
+    psamd_neighbours_result *result_dev;   /* optional out (device), 8-byte aligned; NULL: the context's own record only */
+} psamd_neighbours_spec;      /* 72 bytes */
+
 typedef struct psamd_ctx psamd_ctx;
 
 /* ---- lifetime ------------------------------------------------------------ */
@@ -1174,6 +1201,80 @@ int psamd_download_deposit(psamd_ctx *ctx, int32_t refine, float *out, int64_t c
  * psamd_sample_result_get: the last sample's record, into host memory; waits for the context's stream. */
 int psamd_sample(psamd_ctx *ctx, const psamd_sample_spec *spec);
 int psamd_sample_result_get(psamd_ctx *ctx, psamd_sample_result *out);
+
+/* ---- neighbours within a radius ---------------------------------------------------- */
+/* psamd_neighbours: every pair within a radius, in CSR form, in a fixed order, lined up with psamd_export_live.  With the
+ * export, torch gathers over the lists and psamd_update (VEL | ADD | EXPORT_ORDER) a caller builds a short-range force of its
+ * own -- an SPH density, springs, flocking, a soft contact -- without a download and without a second grid.  Not in the
+ * reference; the step's arithmetic is untouched and PSAMD_ABI_VERSION stays 8.
+ *
+ * Queries.  A query is a listed particle of the context's own cells: entry gi of the sorted order with
+ * gi - cell_start[c] < min(count_c, MAX_PARTICLES_PER_CELL) -- exactly the set psamd_potential forms phi for.  Its position is
+ * the snapshot's; a kid's snapshot position is the origin, so a kid is queried at its true position, from its slot.
+ *
+ * Candidates.  The bodies the force pass walks for the query's cell, in its order: the 27-cell non-periodic stencil in the
+ * reference's order, the own cell first; of each cell the first min(count, MAX_PARTICLES_PER_CELL) entries in list order (ids
+ * ascending).  Left out are the query's own entry -- by sorted index: two particles at one point are each other's neighbours
+ * -- and every kid (its snapshot entry is not where it is, and a halo carries nothing better): a kid has neighbours and is
+ * nobody's neighbour.  Over-age particles are candidates like any other.
+ *
+ * Test.  fp32, nothing fused: rx = xj - xi (ry, rz alike), d2 = RN(RN(RN(rx rx) + RN(ry ry)) + RN(rz rz)), r2 = RN(radius
+ * radius); j is a neighbour iff d2 <= r2, and a NaN on either side is no neighbour.  d2 is symmetric bit for bit: two adults
+ * inside their lists' capacities list each other or neither.
+ *
+ * Radius.  Finite, > 0 and (double)radius <= cell_size, else PSAMD_ERR_INVALID_ARG.  The definition is OVER THE STENCIL: with
+ * radius == cell_size a pair that lies a rounding inside the radius across two cell walls is not in the stencil and is not
+ * listed.  The stencil is not periodic, as the force is not: a pair across the box's wrap is not listed.
+ *
+ * Outputs.  All optional, in export order: entry k is the k-th live owned particle in ascending global slot id, for the first
+ * m = min(live, capacity) of them -- psamd_export_live's and phi[]'s pairing.
+ *     count[k]       the number of neighbours; it depends on no list capacity.  -1: a live particle that is in no list of the
+ *                    frame (psamd_potential gives it a NaN)
+ *     nearest[k], nearest_d2[k]   the neighbour with the smallest d2, ties to the lower global slot id; none: -1 and +inf
+ *     offsets[0..m]  the exclusive prefix of max(count, 0) over the export order; offsets[m] is the entries these m have
+ *     list[p]        the neighbours of entry k at offsets[k] <= p < offsets[k + 1], in walk order (stencil order, list order
+ *                    inside a cell).  Position p is written iff p < list_capacity: a buffer too small cuts the tail and
+ *                    nothing else.  list needs offsets (PSAMD_ERR_INVALID_ARG without)
+ * A neighbour is named by its global slot id (a halo's particle by the id the halo carried).  With PSAMD_NEIGHBOURS_INDEX it is
+ * named by its export index, so that pos[list] is a plain gather; a neighbour whose export index is >= capacity keeps its true
+ * index.  The index form is served for world == 1 only (PSAMD_ERR_UNSUPPORTED otherwise).
+ *
+ * Record.  listed: the queries; pairs: the sum of all queries' counts, the whole context's (directed pairs); wanted:
+ * offsets[m] -- written = min(wanted, list_capacity) is the caller's to form; max_count; d2_min over all neighbours, +inf if
+ * there is none.  A slab world's records combine: the counts add, max_count and d2_min take the maximum and the minimum.
+ *
+ * Window and refusals: psamd_potential's.  world == 1: from psamd_build_grid until the frame ends; world > 1: between
+ * psamd_slab_pairs and psamd_slab_apply, and only on a plan that lends nothing (a lending plan: PSAMD_ERR_UNSUPPORTED, the
+ * context stays usable); elsewhere and on a wedged context PSAMD_ERR_STATE.  The query does not depend on the force model: it
+ * is served on cutoff, all-pairs and all far-field contexts with world == 1, on cutoff and PSAMD_FLAG_FAR_SLAB contexts with
+ * world > 1; an all-pairs context with world > 1 returns PSAMD_ERR_UNSUPPORTED.  The call changes nothing in the frame, the
+ * force records or the step.
+ *
+ * Stream.  Everything is enqueued on the context's stream; nothing waits, nothing is read back.  The scratch (the count and the
+ * nearest pair per sorted entry and per slot, the slot -> export index table, the slots' starts) is the context's: the first
+ * call allocates it -- that call may wait for the device and returns PSAMD_ERR_STATE under a capture -- and it never grows, its
+ * size depends on the container alone; every later call may be captured into a graph.  Contexts that never call pay nothing.
+ *
+ * Determinism.  Every output word is an integer or one fp32 value with a fixed operand order: the same bytes from run to run,
+ * with graphs or without.  By id, the union of a slab world's outputs is the single context's byte for byte (offsets compared
+ * as counts).
+ *
+ * Cost on an MI355X at N = 2^20 on 16^3 cells, 321 502 live in 2 997 648 owned slots (scripts/neighbours_cost.py;
+ * profiles/neighbours_cost.txt), measured: count and offsets 0.82 ms at radius 0.4 (wanted 5 356), 0.83 ms at 1.0 (78 260) and
+ * 0.83 ms at cell_size (8 712 345); with the lists 1.36, 1.35 and 1.39 ms; psamd_potential beside them 0.62 ms (a host clock
+ * around the call plus psamd_synchronize, the stream idle before it).  The call does not get cheaper with the radius: it walks
+ * the whole stencil whatever the radius is.
+ *
+ * PSAMD_ERR_INVALID_ARG: a NULL context or spec, unknown flag bits, a bad radius, capacity < 0 or list_capacity < 0, count,
+ * nearest, nearest_d2 or list not 4-byte aligned, offsets or result_dev not 8-byte aligned, list without offsets.
+ *
+ * psamd_neighbours_result_get: the last call's record, into host memory; waits for the context's stream.
+ * psamd_download_neighbours: the host form -- the same passes staged on the device, then what was asked for copied into host
+ * arrays (any may be NULL) of capacity (offsets: capacity + 1) and list_capacity entries; waits for the stream. */
+int psamd_neighbours(psamd_ctx *ctx, const psamd_neighbours_spec *spec);
+int psamd_neighbours_result_get(psamd_ctx *ctx, psamd_neighbours_result *out);
+int psamd_download_neighbours(psamd_ctx *ctx, uint32_t flags, float radius, int32_t *count, int32_t *nearest, float *nearest_d2,
+                              int64_t *offsets, int64_t capacity, int32_t *list, int64_t list_capacity, psamd_neighbours_result *result);
 
 /* ---- long-range gravity (PSAMD_FLAG_FAR_MONOPOLE) ------------------------------ */
 /* The cutoff pass leaves most of a long-range force out; PSAMD_FLAG_ALL_PAIRS has all of it at O(N^2).  With this flag a

@@ -325,6 +325,32 @@ def merge_sample(results):
     return _merge_counts(results, SampleResult)
 
 
+NEIGHBOURS_INDEX = 0x1  # psamd_neighbours_spec.flags: a neighbour is named by its export index, not by its global slot id
+
+
+class NeighboursResult(_Record):
+    """psamd_neighbours_result: the queries, the directed pairs, the list entries wanted, the largest count, the smallest d2."""
+    _fields_ = [("listed", C.c_int64), ("pairs", C.c_int64), ("wanted", C.c_int64), ("max_count", C.c_int32),
+                ("reserved", C.c_int32), ("d2_min", C.c_double)]
+
+
+class NeighboursSpec(C.Structure):
+    """psamd_neighbours_spec: what psamd_neighbours writes and where (device pointers)."""
+    _fields_ = [("flags", C.c_uint32), ("radius", C.c_float), ("count", C.c_void_p), ("nearest", C.c_void_p),
+                ("nearest_d2", C.c_void_p), ("offsets", C.c_void_p), ("capacity", C.c_int64), ("list", C.c_void_p),
+                ("list_capacity", C.c_int64), ("result_dev", C.c_void_p)]
+
+
+def merge_neighbours(results):
+    """The record of a slab world from its ranks' (dicts of neighbours() / neighbours_result()): the counts add, max_count
+    and d2_min take the maximum and the minimum.  (The arrays pair with the ranks' own exports.)"""
+    results = list(results)
+    out = {n: sum(int(r[n]) for r in results) for n in ("listed", "pairs", "wanted")}
+    out["max_count"] = max(int(r["max_count"]) for r in results)
+    out["d2_min"] = float(min(float(r["d2_min"]) for r in results))
+    return out
+
+
 def merge_live_stats(stats):
     """The statistics of a system from its ranks' (dicts of live_stats() / export_live()["stats"]): counts and sums
     add, in rank order; the box and the ages take the minima and maxima."""
@@ -439,6 +465,9 @@ ABI = [
     ("psamd_download_deposit", C.c_int, [_vp, C.c_int32, _vp, _i64, C.POINTER(DepositResult)]),
     ("psamd_sample", C.c_int, [_vp, C.POINTER(SampleSpec)]),
     ("psamd_sample_result_get", C.c_int, [_vp, C.POINTER(SampleResult)]),
+    ("psamd_neighbours", C.c_int, [_vp, C.POINTER(NeighboursSpec)]),
+    ("psamd_neighbours_result_get", C.c_int, [_vp, C.POINTER(NeighboursResult)]),
+    ("psamd_download_neighbours", C.c_int, [_vp, C.c_uint32, C.c_float, _vp, _vp, _vp, _vp, _i64, _vp, _i64, C.POINTER(NeighboursResult)]),
 ]
 
 _lib = None
@@ -1148,6 +1177,86 @@ class ParticleSystem:
     def sample_result(self):
         """psamd_sample_result_get: the last sample's record as a dict"""
         return self._own_record(SampleResult, self.lib.psamd_sample_result_get)
+
+    # ---- neighbours within a radius (include/psamd.h) -----------------------------
+    def neighbours(self, radius, lists=True, nearest=False, index=False, capacity=None, list_capacity=None):
+        """psamd_neighbours on the frame that is built (psamd_potential's window): every pair within `radius` (<= cell_size)
+        over the 27-cell stencil, in export order -- entry k belongs to the k-th live particle of export_live() at the same
+        point of the stream.  Returns the record (listed, pairs, wanted, max_count, d2_min) as a dict with torch tensors on
+        the context's device beside it: "count" int32 [m] (-1: in no list of the frame), m = min(live count, capacity); with
+        lists=True "offsets" int64 [m + 1] and "list" int32 [min(wanted, list_capacity)] -- the neighbours of entry k are
+        list[offsets[k]:offsets[k + 1]], in walk order, named by global slot id or, with index=True, by export index
+        (pos[list] is then a plain gather; world == 1 only); with nearest=True "nearest" int32 [m] and "nearest_d2" float32 [m].
+        With lists=True and no list_capacity this is the two-call pattern: a count call first, whose `wanted` is read back
+        and sizes the list -- it waits for the context's stream once more than the one call a given list_capacity takes.
+        Waits for the context's stream.  torch must have been imported before the library was loaded."""
+        import torch
+        dev = torch.device("cuda", int(self.cfg.device))
+        capacity = self.owned_slots() if capacity is None else int(capacity)
+        flags = NEIGHBOURS_INDEX if index else 0
+
+        def call(want_list, room):
+            spec = NeighboursSpec(flags=flags, radius=float(radius), capacity=capacity)
+            out = {"count": torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)}
+            spec.count = out["count"].data_ptr()
+            if lists:
+                out["offsets"] = torch.zeros(capacity + 1, dtype=torch.int64, device=dev)
+                spec.offsets = out["offsets"].data_ptr()
+            if nearest:
+                out["nearest"] = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
+                out["nearest_d2"] = torch.empty(max(capacity, 1), dtype=torch.float32, device=dev)
+                spec.nearest, spec.nearest_d2 = out["nearest"].data_ptr(), out["nearest_d2"].data_ptr()
+            if want_list:
+                out["list"] = torch.empty(max(room, 1), dtype=torch.int32, device=dev)
+                spec.list, spec.list_capacity = out["list"].data_ptr(), room
+            result = torch.zeros(C.sizeof(NeighboursResult), dtype=torch.uint8, device=dev)
+            live = torch.zeros(1, dtype=torch.int64, device=dev)
+            spec.result_dev = result.data_ptr()
+            with self._on_stream(dev):
+                self._ck(self.lib.psamd_neighbours(self.h, C.byref(spec)))
+                # how many entries were written: the live count at this point of the stream
+                self._ck(self.lib.psamd_export_live(self.h, C.byref(Export(fields=0, capacity=0, count_dev=live.data_ptr()))))
+            return out, NeighboursResult.from_device(result).to_dict(), min(int(live.item()), capacity)
+        if lists and list_capacity is None:
+            _, rec, _ = call(False, 0)
+            list_capacity = rec["wanted"]
+        out, rec, m = call(lists, int(list_capacity or 0))
+        res = dict(rec)
+        for k, t in out.items():
+            res[k] = t[:m + 1] if k == "offsets" else t[:min(rec["wanted"], int(list_capacity))] if k == "list" else t[:m]
+        return res
+
+    def neighbours_result(self):
+        """psamd_neighbours_result_get: the last neighbours call's record"""
+        return self._own_record(NeighboursResult, self.lib.psamd_neighbours_result_get)
+
+    def download_neighbours(self, radius, lists=True, nearest=False, index=False, capacity=None, list_capacity=None):
+        """psamd_download_neighbours, the numpy form of neighbours(): the same keys, numpy arrays"""
+        capacity = self.owned_slots() if capacity is None else int(capacity)
+        flags = NEIGHBOURS_INDEX if index else 0
+        r = NeighboursResult()
+        if lists and list_capacity is None:
+            offs = np.zeros(capacity + 1, np.int64)       # the count call: `wanted` is offsets[m]
+            self._ck(self.lib.psamd_download_neighbours(self.h, flags, float(radius), None, None, None, _ptr(offs), capacity, None, 0, C.byref(r)))
+            list_capacity = int(r.wanted)
+        list_capacity = int(list_capacity or 0)
+        out = {"count": np.full(max(capacity, 1), -7, np.int32)}
+        if lists:
+            out["offsets"] = np.zeros(capacity + 1, np.int64)
+            out["list"] = np.full(max(list_capacity, 1), -7, np.int32)
+        if nearest:
+            out["nearest"] = np.full(max(capacity, 1), -7, np.int32)
+            out["nearest_d2"] = np.zeros(max(capacity, 1), np.float32)
+        self._ck(self.lib.psamd_download_neighbours(self.h, flags, float(radius), _ptr(out["count"]), _ptr(out.get("nearest")),
+                                                    _ptr(out.get("nearest_d2")), _ptr(out.get("offsets")), capacity,
+                                                    _ptr(out.get("list")), list_capacity if lists else 0, C.byref(r)))
+        n = C.c_int64()        # how many entries were written: the export's count at this point (no fields, nothing copied)
+        self._ck(self.lib.psamd_download_live(self.h, 0, None, None, None, None, None, 0, C.byref(n)))
+        m = min(n.value, capacity)
+        res = r.to_dict()
+        for k, a in out.items():
+            res[k] = a[:m + 1] if k == "offsets" else a[:min(res["wanted"], list_capacity)] if k == "list" else a[:m]
+        return res
 
     def device_view(self):
         v = DeviceView()

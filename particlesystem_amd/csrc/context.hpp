@@ -74,6 +74,7 @@ struct psamd_ctx {
     UpdateScratch upd{};              // psamd_update's scratch: code grows with max_count, the rest is fixed (by id it borrows rem.claim)
     DepositScratch dep{};             // psamd_deposit's scratch: fixed (the geometry and the plan size it)
     SampleScratch smp{};              // psamd_sample's scratch: fixed (three counters; by export order it borrows upd.tile_live)
+    NbrScratch nbr{};                 // psamd_neighbours' scratch: one block the first call allocates, sized by the container alone
     // timing
     int timing = 0;                    // 0 off, 1 pair pass / apply / life cycle, 2 every stage
     int timing_period = 1;             // events are recorded on every timing_period-th step since set_timing

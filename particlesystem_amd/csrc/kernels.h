@@ -131,6 +131,46 @@ struct ProbeScratch {
     psamd_probe_result *own;    // the context's own result record (psamd_probe_result_get)
 };
 
+// psamd_neighbours (neighbours.hip): what the caller gave, and the scratch.  All of the scratch is ONE allocation whose size
+// depends on the container alone; the first call makes it (the host: neighbours_scratch, services.hip), contexts that never
+// call the service hold none of it
+struct NbrArgs {
+    uint32_t flags;   // PSAMD_NEIGHBOURS_*
+    float r2;         // RN(radius * radius)
+    int *count, *nearest;       // [capacity] by export order (any may be null)
+    float *nearest_d2;
+    int64_t *offsets;           // [capacity + 1]
+    int64_t capacity;
+    int *list;                  // [list_capacity]
+    int64_t list_capacity;
+    psamd_neighbours_result *result;    // the caller's record (may be null)
+};
+struct __align__(16) NbrTile {  // what a tile of the sorted order saw of the queries
+    long long pairs;  // the sum of their counts
+    float d2_min;     // +inf: no neighbour
+    int listed, max_count;
+    int pad;
+};
+struct NbrOut {       // the context's own result record (psamd_neighbours_result_get), and the live count the host form copies by
+    psamd_neighbours_result result;
+    int64_t live;
+};
+struct NbrScratch {
+    void *block;      // the one allocation; null: no call yet
+    int *cnt_sorted, *who_sorted;   // [sorted_cap] per query, by sorted index: its count, its nearest neighbour's global slot id
+    float *d2_sorted;               // ... and that pair's d2
+    int *cnt_slot, *who_slot;       // [slots] the same by storage index; cnt -1: in no list of the frame
+    float *d2_slot;
+    int *index;       // [slots] storage index -> export index (-1: not live)
+    long long *start; // [slots] storage index -> offsets[] of its entry (-1: past the capacity, or not live)
+    NbrTile *tiles;   // [tiles of slots]
+    int *tile_live;   // [tiles of slots] the tile's live slots
+    long long *tile_sum;    // [tiles of slots] the counts of the tile's entries below the capacity
+    NbrOut *own;
+};
+size_t neighbours_scratch_bytes(const DevParams &P);
+void neighbours_scratch_carve(const DevParams &P, void *block, NbrScratch &s);
+
 // psamd_deposit (deposit.hip): the lattice, what the caller gave, and the scratch.  A task is (compute cell, block of at most
 // 2 x 2 x 2 voxels of it): 1, 1 or 8 tasks a cell for refine 1, 2, 4; four tasks to a workgroup, whose partials are one entry
 constexpr int DEPOSIT_WG_TASKS = 4;
@@ -380,6 +420,11 @@ hipError_t launch_potential(hipStream_t st, const DevParams &P, const DeviceStat
 // psamd_probe (max_count > 0): locate + count, the cells' prefix, the cell-major order, the pair pass (one probe to a lane), the
 // result record
 hipError_t launch_probe(hipStream_t st, const DevParams &P, const DeviceState &d, const ProbeArgs &a, const ProbeScratch &s);
+
+// psamd_neighbours: the count walk over the own cells' (cell, slice) tasks, the three launches on the slot walk (to slot
+// order and the tiles' partials; the slot -> export index table and the tiles' sums; the record, the export-order arrays and
+// offsets), then -- a.list given -- the same walk again, storing the names
+hipError_t launch_neighbours(hipStream_t st, const DevParams &P, const DeviceState &d, const NbrArgs &a, const NbrScratch &s);
 
 // psamd_deposit: the gather over the compute cells' tasks, then the result record (mass, vmax and the counts over the
 // workgroups' partials in task order)

@@ -32,6 +32,7 @@
 //   remove.hip     psamd_remove, particles out of their slots and the slots back into the queues
 //   potential.hip  psamd_potential, every listed particle's potential and the potential energy
 //   probe.hip      psamd_probe, the acceleration and the potential at points of the caller's choosing
+//   neighbours.hip psamd_neighbours, every listed particle's neighbours within a radius in CSR form (nbr_walk.hpp: its walk)
 //
 // Reference arithmetic is reproduced operation for operation: every file is built with
 // -ffp-contract=off; where the reference evaluates in double (EPS2 add, 0.5*a*t*t) so

@@ -1,7 +1,9 @@
 // services.hip -- the host side of the on-stream services: psamd_export_live (export.hip), psamd_inject (inject.hip),
-// psamd_remove (remove.hip), psamd_update (update.hip), psamd_potential (potential.hip), psamd_probe (probe.hip), psamd_deposit (deposit.hip), psamd_sample (sample.hip), their host-array forms and their result records.
+// psamd_remove (remove.hip), psamd_update (update.hip), psamd_potential (potential.hip), psamd_probe (probe.hip), psamd_deposit (deposit.hip), psamd_sample (sample.hip), psamd_neighbours (neighbours.hip), their host-array forms and their result records.
 // A service enqueues its launches on the context's stream and returns; nothing here enqueues a stage of the step.
 #include "context.hpp"
+
+#include <cmath>
 
 // ---- what the services share ----
 static bool aligned(const void *p, size_t a) { return (uintptr_t)p % a == 0; }
@@ -288,16 +290,21 @@ static int refuse_far_slab(psamd_ctx *c, const char *who)
     return PSAMD_OK;
 }
 
-// ... and nothing of the plan is lent
+// ... and nothing of the plan is lent (potential and neighbours)
+static int window_nothing_lent(psamd_ctx *c, const char *who)
+{
+    PS_TRY(frame_ready(c, who));
+    const SlabPlan &pl = c->plan;
+    if (c->P.world > 1 && (pl.lentin_lo < pl.lentin_hi || pl.lentout_lo < pl.lentout_hi))
+        return fail(c, PSAMD_ERR_UNSUPPORTED, std::string(who) + ": this rank's plan lends cell layers (lentin / lentout not empty); only plans "
+                                              "with group-aligned cuts are served");
+    return PSAMD_OK;
+}
+
 static int potential_ready(psamd_ctx *c, uint32_t flags)
 {
     PS_TRY(refuse_far_monopole(c, "potential", (flags & PSAMD_POTENTIAL_FAR) != 0, (flags & PSAMD_POTENTIAL_QUADRUPOLE) != 0));
-    PS_TRY(frame_ready(c, "potential"));
-    const SlabPlan &pl = c->plan;
-    if (c->P.world > 1 && (pl.lentin_lo < pl.lentin_hi || pl.lentout_lo < pl.lentout_hi))
-        return fail(c, PSAMD_ERR_UNSUPPORTED, "potential: this rank's plan lends cell layers (lentin / lentout not empty); only plans "
-                                              "with group-aligned cuts are served");
-    return PSAMD_OK;
+    return window_nothing_lent(c, "potential");
 }
 
 // the spec's flags, of psamd_potential and of its host forms: no bit this context kind does not know, no modifier alone
@@ -497,5 +504,91 @@ int psamd_sample(psamd_ctx *c, const psamd_sample_spec *spec)
 }
 
 int psamd_sample_result_get(psamd_ctx *c, psamd_sample_result *out) { return read_own(c, out, c ? c->smp.own : nullptr, sizeof *out); }
+
+// ---- neighbours within a radius (neighbours.hip) ----
+// the arguments of psamd_neighbours and of its host form (device: the kernels store to the arrays), in the services' order:
+// flags, the radius, pointers and alignment, the context kind
+static int neighbours_args(psamd_ctx *c, uint32_t flags, float radius, const void *count, const void *nearest, const void *nearest_d2,
+                           const void *offsets, int64_t capacity, const void *list, int64_t list_capacity, const void *result, bool device)
+{
+    if (flags & ~PSAMD_NEIGHBOURS_INDEX) return fail(c, PSAMD_ERR_INVALID_ARG, "neighbours: unknown flag bits");
+    if (!std::isfinite(radius) || !(radius > 0.f) || !((double)radius <= c->P.cell_size))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "neighbours: radius is not finite, not > 0 or exceeds cell_size (the walk is over the 27-cell stencil)");
+    if (capacity < 0 || list_capacity < 0) return fail(c, PSAMD_ERR_INVALID_ARG, "neighbours: capacity < 0 or list_capacity < 0");
+    if (device && (!aligned(count, 4) || !aligned(nearest, 4) || !aligned(nearest_d2, 4) || !aligned(list, 4) || !aligned(offsets, 8) ||
+                   !aligned(result, 8)))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "neighbours: an array misaligned");
+    if (list && !offsets) return fail(c, PSAMD_ERR_INVALID_ARG, "neighbours: list needs offsets");
+    if ((flags & PSAMD_NEIGHBOURS_INDEX) && c->P.world > 1)
+        return fail(c, PSAMD_ERR_UNSUPPORTED, "neighbours: PSAMD_NEIGHBOURS_INDEX is served on one context only (world == 1): a halo's particle "
+                                              "has no export index here");
+    if ((c->P.flags & PSAMD_FLAG_ALL_PAIRS) && c->P.world > 1)
+        return fail(c, PSAMD_ERR_UNSUPPORTED, "neighbours: all-pairs contexts are served on one context only (world == 1)");
+    return PSAMD_OK;
+}
+
+// the scratch: one block, made by the first call (hipMalloc may wait for the device and cannot be recorded) and kept
+static int neighbours_scratch(psamd_ctx *c)
+{
+    if (c->nbr.block) return PSAMD_OK;
+    PS_TRY(refuse_capture(c, "neighbours", "the first call allocates the scratch"));
+    void *block = nullptr;
+    PS_HIP(c, hipMalloc(&block, neighbours_scratch_bytes(c->P)));
+    neighbours_scratch_carve(c->P, block, c->nbr);
+    PS_HIP(c, hipMemsetAsync(c->nbr.own, 0, sizeof(NbrOut), c->stream));
+    return PSAMD_OK;
+}
+
+int psamd_neighbours(psamd_ctx *c, const psamd_neighbours_spec *spec)
+{
+    PS_TRY(service_args(c, spec));
+    PS_TRY(neighbours_args(c, spec->flags, spec->radius, spec->count, spec->nearest, spec->nearest_d2, spec->offsets, spec->capacity,
+                           spec->list, spec->list_capacity, spec->result_dev, true));
+    PS_TRY(window_nothing_lent(c, "neighbours"));
+    PS_TRY(neighbours_scratch(c));
+    const NbrArgs a{spec->flags, spec->radius * spec->radius, spec->count, spec->nearest, spec->nearest_d2, spec->offsets, spec->capacity,
+                    spec->list, spec->list_capacity, spec->result_dev};
+    PS_HIP(c, launch_neighbours(c->stream, c->P, c->d, a, c->nbr));
+    return PSAMD_OK;
+}
+
+int psamd_neighbours_result_get(psamd_ctx *c, psamd_neighbours_result *out)
+{
+    PS_TRY(service_args(c, out));
+    if (!c->nbr.block) { *out = psamd_neighbours_result{}; out->d2_min = HUGE_VAL; return PSAMD_OK; }     // no call yet
+    return read_own(c, out, &c->nbr.own->result, sizeof *out);
+}
+
+// the same passes into the staging buffer: what was asked for of the first min(live, capacity) particles, then -- the lists --
+// the first min(wanted, list_capacity) names
+int psamd_download_neighbours(psamd_ctx *c, uint32_t flags, float radius, int32_t *count, int32_t *nearest, float *nearest_d2, int64_t *offsets,
+                              int64_t capacity, int32_t *list, int64_t list_capacity, psamd_neighbours_result *result)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    PS_TRY(neighbours_args(c, flags, radius, count, nearest, nearest_d2, offsets, capacity, list, list_capacity, result, false));
+    PS_TRY(window_nothing_lent(c, "download_neighbours"));
+    PS_TRY(neighbours_scratch(c));
+    const int64_t n = std::min<int64_t>(capacity, c->P.slots_total);
+    void *const host[5] = {offsets, count, nearest, nearest_d2, list};
+    const size_t words[5] = {(size_t)n + 1, (size_t)n, (size_t)n, (size_t)n, (size_t)list_capacity}, width[5] = {8, 4, 4, 4, 4};
+    size_t off[5], bytes = 0;
+    for (int k = 0; k < 5; k++) { off[k] = bytes; if (host[k]) bytes += (words[k] * width[k] + 255) / 256 * 256; }
+    PS_TRY(ensure_staging(c, std::max<size_t>(bytes, 256)));
+    void *dev[5];
+    for (int k = 0; k < 5; k++) dev[k] = host[k] ? (char *)c->staging + off[k] : nullptr;
+    const NbrArgs a{flags, radius * radius, (int *)dev[1], (int *)dev[2], (float *)dev[3], (int64_t *)dev[0], n, (int *)dev[4], list_capacity, nullptr};
+    PS_HIP(c, launch_neighbours(c->stream, c->P, c->d, a, c->nbr));
+    NbrOut got{};
+    PS_HIP(c, hipMemcpyAsync(&got, c->nbr.own, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t m = (size_t)std::min<int64_t>(got.live, n);
+    const size_t take[5] = {m + 1, m, m, m, (size_t)std::min<int64_t>(got.result.wanted, list_capacity)};
+    for (int k = 0; k < 5; k++)
+        if (host[k] && take[k] > 0) PS_HIP(c, hipMemcpyAsync(host[k], dev[k], take[k] * width[k], hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    if (result) *result = got.result;
+    return PSAMD_OK;
+}
 
 }  // extern "C"

@@ -426,6 +426,31 @@ typedef struct psamd_neighbours_spec {
     psamd_neighbours_result *result_dev;   /* optional out (device), 8-byte aligned; NULL: the context's own record only */
 } psamd_neighbours_spec;      /* 72 bytes */
 
+/* psamd_groups_spec.flags (see "groups within a radius" below) */
+#define PSAMD_GROUPS_INDEX 0x1u   /* group_first names a particle by its export index, not its global slot id */
+
+/* What psamd_groups found. */
+typedef struct psamd_groups_result {
+    int64_t members;     /* particles that belong to a group (see Members) */
+    int64_t groups;      /* the number of groups, singles included */
+    int64_t links;       /* undirected member pairs with d2 <= r2 over the stencil */
+    int64_t singles;     /* groups of one */
+    int32_t largest;     /* the largest group's size; 0 if there is no member */
+    int32_t unfinished;  /* unions that hit the step cap (see Bounded loops): 0, always, on correct code */
+} psamd_groups_result;   /* 40 bytes */
+
+/* What psamd_groups writes and where (device pointers; none of them inside the context's own arrays). */
+typedef struct psamd_groups_spec {
+    uint32_t flags;          /* PSAMD_GROUPS_* */
+    float    radius;         /* psamd_neighbours' rule: finite, > 0, (double)radius <= cell_size */
+    int32_t *group;          /* optional out, int32[capacity], export order: the dense group number g, -1: no member */
+    int64_t  capacity;       /* >= 0 */
+    int32_t *group_first;    /* optional out, int32[group_capacity]: group g's smallest member */
+    int32_t *group_size;     /* optional out, int32[group_capacity]: group g's members */
+    int64_t  group_capacity; /* >= 0: entry g of the two tables is written iff g < group_capacity */
+    psamd_groups_result *result_dev;  /* optional out (device), 8-byte aligned */
+} psamd_groups_spec;     /* 56 bytes */
+
 typedef struct psamd_ctx psamd_ctx;
 
 /* ---- lifetime ------------------------------------------------------------ */
@@ -1275,6 +1300,75 @@ int psamd_neighbours(psamd_ctx *ctx, const psamd_neighbours_spec *spec);
 int psamd_neighbours_result_get(psamd_ctx *ctx, psamd_neighbours_result *out);
 int psamd_download_neighbours(psamd_ctx *ctx, uint32_t flags, float radius, int32_t *count, int32_t *nearest, float *nearest_d2,
                               int64_t *offsets, int64_t capacity, int32_t *list, int64_t list_capacity, psamd_neighbours_result *result);
+
+/* ---- groups within a radius --------------------------------------------------------- */
+/* psamd_groups: the friends-of-friends groups -- the connected components of psamd_neighbours' "within a radius" relation --
+ * on the device, without a pair list: which particles hang together, how many groups there are and how big each one is.
+ * With the export and torch.index_add_ over group[] a caller has group masses and centres, a clump finder or a halo
+ * catalogue, without a download.  Not in the reference; the step's arithmetic is untouched and PSAMD_ABI_VERSION stays 8.
+ *
+ * Members.  The listed particles of the context's own cells that are not kids: psamd_neighbours' candidates seen as queries.
+ * A kid is nobody's neighbour there, so a relation that took kids in would not be symmetric: a kid is no member.  A kid and a
+ * live particle that is in no list of the frame have group[k] = -1.  Over-age particles are members like any other.  A member
+ * with a non-finite coordinate links to nobody and is a group of one.
+ *
+ * Links.  psamd_neighbours' test, word for word: the same fp32 d2 with the same operand order, d2 <= r2 with r2 = RN(radius
+ * radius), over the 27-cell non-periodic stencil, the own entry left out by sorted index -- two particles at one point are
+ * linked.  d2 is symmetric bit for bit and so is the stencil: the relation is symmetric, and the walk takes each pair from
+ * the side of its higher slot only.  As there, the definition is OVER THE STENCIL and the stencil is not periodic.
+ *
+ * Groups.  The connected components of the links over the members, numbered g = 0 .. groups - 1 in ascending order of their
+ * smallest member's global slot id -- the export order is ascending slot id, so also of their smallest export index.
+ *     group[k]        entry k of the export order (psamd_export_live's pairing, the first m = min(live, capacity)): its
+ *                     group's number, always the true g, also when g >= group_capacity; -1: no member
+ *     group_first[g]  the group's smallest member, by global slot id or, with PSAMD_GROUPS_INDEX, by export index (an index at
+ *                     or past capacity is kept true)
+ *     group_size[g]   its member count
+ * Entry g of the two tables is written iff g < group_capacity: tables too small cut the tail and nothing else.
+ *
+ * Record.  members; groups, singles included; links: the undirected member pairs with d2 <= r2 over the stencil (on a frame
+ * without kids twice this is psamd_neighbours' pairs); singles: the groups of one; largest: the largest group's size, 0 if
+ * there is no member; unfinished: see Bounded loops.
+ *
+ * Window and refusals.  world == 1 only: a group can span ranks, and merging the ranks' groups across the slab cuts is a
+ * later change; world > 1 returns PSAMD_ERR_UNSUPPORTED and leaves the context usable.  With world == 1 the window is
+ * psamd_potential's: from psamd_build_grid until the frame ends; elsewhere and on a wedged context PSAMD_ERR_STATE.  The
+ * result does not depend on the force model: the call is served on cutoff, fast-math, all-pairs and all far-field contexts
+ * alike.  It writes nothing of the frame, the force records or the step.
+ *
+ * Stream.  psamd_neighbours' rules: everything is enqueued on the context's stream, nothing waits, nothing is read back.  The
+ * scratch (six words per owned slot: the union-find, the members, the roots, the sizes, the numbers, the slot -> export index
+ * table) is the context's: the first call allocates it -- that call may wait for the device and returns PSAMD_ERR_STATE under
+ * a capture -- and it never grows, its size depends on the container alone; every later call may be captured into a graph.
+ * Contexts that never call pay nothing.
+ *
+ * Bounded loops.  The groups are found by a union-find over the owned slots whose every write is an atomicMin: a word never
+ * rises, every step of a find or a union moves to a strictly smaller slot, and a loop therefore ends by itself whatever the
+ * other waves do -- there is no lock, no wait on another thread's word and no grid barrier (groups.hip states the argument).
+ * On top of that a union stops after slots_total steps and counts itself in `unfinished`.  Correct code cannot get there:
+ * unfinished != 0 says the library is broken, and then the groups are not to be trusted.
+ *
+ * Determinism.  Every output word is an integer that depends on the frame and the radius alone; the order in which the waves
+ * hook the pairs does not enter.  The same bytes from run to run, with graphs or without.
+ *
+ * Cost on an MI355X at N = 2^20 on 16^3 cells, 321 502 live in 2 997 648 owned slots, 23 632 of them members -- the others
+ * are kids on that frame (scripts/groups_cost.py; profiles/groups_cost.txt), measured: 0.66 ms at radius 0.4 (22 981 groups,
+ * 673 links), 0.66 ms at 1.0 (17 072 groups, 8 259 links) and 0.88 ms at cell_size (one group, 405 285 links) for the record
+ * alone, 0.01 ms more with group[] and both tables; psamd_neighbours' count-and-offsets call beside it 0.81, 0.82 and 0.83 ms
+ * (a host clock around the call plus psamd_synchronize, the stream idle before it).  The walk costs the same at every radius;
+ * what grows with the radius is the hooking of many links into few roots.
+ *
+ * PSAMD_ERR_INVALID_ARG: a NULL context or spec, unknown flag bits, a bad radius, capacity < 0 or group_capacity < 0, group,
+ * group_first or group_size not 4-byte aligned, result_dev not 8-byte aligned.
+ *
+ * psamd_groups_result_get: the last call's record, into host memory; waits for the context's stream.
+ * psamd_download_groups: the host form -- the same passes staged on the device, then what was asked for copied into host
+ * arrays (any may be NULL) of capacity and group_capacity entries: the first min(live, capacity) entries of group, the first
+ * min(groups, group_capacity) of the tables; waits for the stream. */
+int psamd_groups(psamd_ctx *ctx, const psamd_groups_spec *spec);
+int psamd_groups_result_get(psamd_ctx *ctx, psamd_groups_result *out);
+int psamd_download_groups(psamd_ctx *ctx, uint32_t flags, float radius, int32_t *group, int64_t capacity,
+                          int32_t *group_first, int32_t *group_size, int64_t group_capacity, psamd_groups_result *result);
 
 /* ---- long-range gravity (PSAMD_FLAG_FAR_MONOPOLE) ------------------------------ */
 /* The cutoff pass leaves most of a long-range force out; PSAMD_FLAG_ALL_PAIRS has all of it at O(N^2).  With this flag a

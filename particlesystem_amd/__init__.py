@@ -351,6 +351,22 @@ def merge_neighbours(results):
     return out
 
 
+GROUPS_INDEX = 0x1  # psamd_groups_spec.flags: group_first names a particle by its export index, not by its global slot id
+
+
+class GroupsResult(_Record):
+    """psamd_groups_result: the members, the groups, the undirected links, the groups of one, the largest group, the unions
+    that hit the step cap (0 on correct code)."""
+    _fields_ = [("members", C.c_int64), ("groups", C.c_int64), ("links", C.c_int64), ("singles", C.c_int64),
+                ("largest", C.c_int32), ("unfinished", C.c_int32)]
+
+
+class GroupsSpec(C.Structure):
+    """psamd_groups_spec: what psamd_groups writes and where (device pointers)."""
+    _fields_ = [("flags", C.c_uint32), ("radius", C.c_float), ("group", C.c_void_p), ("capacity", C.c_int64),
+                ("group_first", C.c_void_p), ("group_size", C.c_void_p), ("group_capacity", C.c_int64), ("result_dev", C.c_void_p)]
+
+
 def merge_live_stats(stats):
     """The statistics of a system from its ranks' (dicts of live_stats() / export_live()["stats"]): counts and sums
     add, in rank order; the box and the ages take the minima and maxima."""
@@ -468,6 +484,9 @@ ABI = [
     ("psamd_neighbours", C.c_int, [_vp, C.POINTER(NeighboursSpec)]),
     ("psamd_neighbours_result_get", C.c_int, [_vp, C.POINTER(NeighboursResult)]),
     ("psamd_download_neighbours", C.c_int, [_vp, C.c_uint32, C.c_float, _vp, _vp, _vp, _vp, _i64, _vp, _i64, C.POINTER(NeighboursResult)]),
+    ("psamd_groups", C.c_int, [_vp, C.POINTER(GroupsSpec)]),
+    ("psamd_groups_result_get", C.c_int, [_vp, C.POINTER(GroupsResult)]),
+    ("psamd_download_groups", C.c_int, [_vp, C.c_uint32, C.c_float, _vp, _i64, _vp, _vp, _i64, C.POINTER(GroupsResult)]),
 ]
 
 _lib = None
@@ -1256,6 +1275,75 @@ class ParticleSystem:
         res = r.to_dict()
         for k, a in out.items():
             res[k] = a[:m + 1] if k == "offsets" else a[:min(res["wanted"], list_capacity)] if k == "list" else a[:m]
+        return res
+
+    # ---- groups within a radius (include/psamd.h) -----------------------------------
+    def groups(self, radius, index=False, capacity=None, group_capacity=None):
+        """psamd_groups on the frame that is built (psamd_potential's window, world == 1): the friends-of-friends groups --
+        the connected components of neighbours()' relation at `radius` (<= cell_size) over the members, the listed particles
+        that are no kids.  Returns the record (members, groups, links, singles, largest, unfinished) as a dict with torch
+        tensors on the context's device beside it: "group" int32 [m], m = min(live count, capacity), in export order -- the
+        dense group number of the k-th live particle of export_live() at the same point of the stream, -1: no member;
+        "group_first" and "group_size" int32 [min(groups, group_capacity)] -- group g's smallest member (by global slot id
+        or, with index=True, by export index) and its member count.  Groups are numbered in ascending order of their smallest
+        member.  With no group_capacity this is the two-call pattern: a record-only call first, whose `groups` is read back
+        and sizes the tables -- it waits for the context's stream once more than the one call a given group_capacity takes.
+        Waits for the context's stream.  torch must have been imported before the library was loaded."""
+        import torch
+        dev = torch.device("cuda", int(self.cfg.device))
+        capacity = self.owned_slots() if capacity is None else int(capacity)
+        flags = GROUPS_INDEX if index else 0
+
+        def call(arrays, room):
+            spec = GroupsSpec(flags=flags, radius=float(radius))
+            out = {}
+            if arrays:
+                out = {"group": torch.empty(max(capacity, 1), dtype=torch.int32, device=dev),
+                       "group_first": torch.empty(max(room, 1), dtype=torch.int32, device=dev),
+                       "group_size": torch.empty(max(room, 1), dtype=torch.int32, device=dev)}
+                spec.group, spec.capacity = out["group"].data_ptr(), capacity
+                spec.group_first, spec.group_size, spec.group_capacity = out["group_first"].data_ptr(), out["group_size"].data_ptr(), room
+            result = torch.zeros(C.sizeof(GroupsResult), dtype=torch.uint8, device=dev)
+            live = torch.zeros(1, dtype=torch.int64, device=dev)
+            spec.result_dev = result.data_ptr()
+            with self._on_stream(dev):
+                self._ck(self.lib.psamd_groups(self.h, C.byref(spec)))
+                # how many entries were written: the live count at this point of the stream
+                self._ck(self.lib.psamd_export_live(self.h, C.byref(Export(fields=0, capacity=0, count_dev=live.data_ptr()))))
+            return out, GroupsResult.from_device(result).to_dict(), min(int(live.item()), capacity)
+        if group_capacity is None:
+            _, rec, _ = call(False, 0)
+            group_capacity = rec["groups"]
+        group_capacity = int(group_capacity)
+        out, rec, m = call(True, group_capacity)
+        res = dict(rec)
+        for k, t in out.items():
+            res[k] = t[:m] if k == "group" else t[:min(rec["groups"], group_capacity)]
+        return res
+
+    def groups_result(self):
+        """psamd_groups_result_get: the last groups call's record"""
+        return self._own_record(GroupsResult, self.lib.psamd_groups_result_get)
+
+    def download_groups(self, radius, index=False, capacity=None, group_capacity=None):
+        """psamd_download_groups, the numpy form of groups(): the same keys, numpy arrays"""
+        capacity = self.owned_slots() if capacity is None else int(capacity)
+        flags = GROUPS_INDEX if index else 0
+        r = GroupsResult()
+        if group_capacity is None:
+            self._ck(self.lib.psamd_download_groups(self.h, flags, float(radius), None, 0, None, None, 0, C.byref(r)))
+            group_capacity = int(r.groups)
+        group_capacity = int(group_capacity)
+        out = {"group": np.full(max(capacity, 1), -7, np.int32), "group_first": np.full(max(group_capacity, 1), -7, np.int32),
+               "group_size": np.full(max(group_capacity, 1), -7, np.int32)}
+        self._ck(self.lib.psamd_download_groups(self.h, flags, float(radius), _ptr(out["group"]), capacity, _ptr(out["group_first"]),
+                                                _ptr(out["group_size"]), group_capacity, C.byref(r)))
+        n = C.c_int64()        # how many entries were written: the export's count at this point (no fields, nothing copied)
+        self._ck(self.lib.psamd_download_live(self.h, 0, None, None, None, None, None, 0, C.byref(n)))
+        m = min(n.value, capacity)
+        res = r.to_dict()
+        for k, a in out.items():
+            res[k] = a[:m] if k == "group" else a[:min(res["groups"], group_capacity)]
         return res
 
     def device_view(self):

@@ -75,8 +75,9 @@ struct psamd_ctx {
     DepositScratch dep{};             // psamd_deposit's scratch: fixed (the geometry and the plan size it)
     SampleScratch smp{};              // psamd_sample's scratch: fixed (three counters; by export order it borrows upd.tile_live)
     NbrScratch nbr{};                 // psamd_neighbours' scratch: one block the first call allocates, sized by the container alone
+    GrpScratch grp{};                 // psamd_groups' scratch: one block the first call allocates, sized by the container alone
     // timing
-    int timing = 0;                    // 0 off, 1 pair pass / apply / life cycle, 2 every stage
+    int timing = 0;                   // 0 off, 1 pair pass / apply / life cycle, 2 every stage
     int timing_period = 1;             // events are recorded on every timing_period-th step since set_timing
     int64_t timing_steps = 0;          // steps since set_timing
     int timing_now = 0;                // the level in force for the step being run (0 on the steps in between)

@@ -171,6 +171,42 @@ struct NbrScratch {
 size_t neighbours_scratch_bytes(const DevParams &P);
 void neighbours_scratch_carve(const DevParams &P, void *block, NbrScratch &s);
 
+// psamd_groups (groups.hip): what the caller gave, and the scratch -- ONE allocation sized by the container alone, made by the
+// first call (the host: groups_scratch, services.hip), like psamd_neighbours'
+struct GrpArgs {
+    uint32_t flags;   // PSAMD_GROUPS_*
+    float r2;         // RN(radius * radius)
+    int *group;       // [capacity] by export order (may be null)
+    int64_t capacity;
+    int *group_first, *group_size;      // [group_capacity] by group number (any may be null)
+    int64_t group_capacity;
+    psamd_groups_result *result;        // the caller's record (may be null)
+};
+struct __align__(16) GrpTile {  // what a tile of the owned slots holds
+    int live, members, roots, singles;  // live slots; members; members that are their set's root; roots of a set of one
+    int largest;      // the largest set rooted in the tile
+    int pad[3];
+};
+struct GrpOut {       // the context's own result record (psamd_groups_result_get), and the live count the host form copies by
+    psamd_groups_result result;
+    int64_t live;
+};
+struct GrpScratch {
+    void *block;      // the one allocation; null: no call yet
+    int *parent;      // [slots] the union-find over storage indices: a word only ever falls (atomicMin), a root names itself
+    int *member;      // [slots] 1: a listed particle of the own cells that is no kid
+    int *root;        // [slots] the set's smallest storage index, once the hooking is over
+    int *size;        // [slots] at a root: its set's members
+    int *number;      // [slots] at a root: the dense group number
+    int *index;       // [slots] storage index -> export index (-1: not live)
+    GrpTile *tiles;   // [tiles of slots]
+    unsigned long long *links;  // undirected links, each counted by its higher slot
+    int *unfinished;  // unions that hit the step cap
+    GrpOut *own;
+};
+size_t groups_scratch_bytes(const DevParams &P);
+void groups_scratch_carve(const DevParams &P, void *block, GrpScratch &s);
+
 // psamd_deposit (deposit.hip): the lattice, what the caller gave, and the scratch.  A task is (compute cell, block of at most
 // 2 x 2 x 2 voxels of it): 1, 1 or 8 tasks a cell for refine 1, 2, 4; four tasks to a workgroup, whose partials are one entry
 constexpr int DEPOSIT_WG_TASKS = 4;
@@ -425,6 +461,10 @@ hipError_t launch_probe(hipStream_t st, const DevParams &P, const DeviceState &d
 // order and the tiles' partials; the slot -> export index table and the tiles' sums; the record, the export-order arrays and
 // offsets), then -- a.list given -- the same walk again, storing the names
 hipError_t launch_neighbours(hipStream_t st, const DevParams &P, const DeviceState &d, const NbrArgs &a, const NbrScratch &s);
+
+// psamd_groups: the sets' start, the hooking walk over psamd_neighbours' tasks, then three launches on the slot walk (the roots
+// and the sizes; the group numbers, the slot -> export index table and the two tables; the record and group[])
+hipError_t launch_groups(hipStream_t st, const DevParams &P, const DeviceState &d, const GrpArgs &a, const GrpScratch &s);
 
 // psamd_deposit: the gather over the compute cells' tasks, then the result record (mass, vmax and the counts over the
 // workgroups' partials in task order)

@@ -1,5 +1,5 @@
 // services.hip -- the host side of the on-stream services: psamd_export_live (export.hip), psamd_inject (inject.hip),
-// psamd_remove (remove.hip), psamd_update (update.hip), psamd_potential (potential.hip), psamd_probe (probe.hip), psamd_deposit (deposit.hip), psamd_sample (sample.hip), psamd_neighbours (neighbours.hip), their host-array forms and their result records.
+// psamd_remove (remove.hip), psamd_update (update.hip), psamd_potential (potential.hip), psamd_probe (probe.hip), psamd_deposit (deposit.hip), psamd_sample (sample.hip), psamd_neighbours (neighbours.hip), psamd_groups (groups.hip), their host-array forms and their result records.
 // A service enqueues its launches on the context's stream and returns; nothing here enqueues a stage of the step.
 #include "context.hpp"
 
@@ -586,6 +586,87 @@ int psamd_download_neighbours(psamd_ctx *c, uint32_t flags, float radius, int32_
     const size_t take[5] = {m + 1, m, m, m, (size_t)std::min<int64_t>(got.result.wanted, list_capacity)};
     for (int k = 0; k < 5; k++)
         if (host[k] && take[k] > 0) PS_HIP(c, hipMemcpyAsync(host[k], dev[k], take[k] * width[k], hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    if (result) *result = got.result;
+    return PSAMD_OK;
+}
+
+// ---- groups within a radius (groups.hip) ----
+// the arguments of psamd_groups and of its host form, in psamd_neighbours' order; then the context kind: one context only
+static int groups_args(psamd_ctx *c, uint32_t flags, float radius, const void *group, int64_t capacity, const void *group_first,
+                       const void *group_size, int64_t group_capacity, const void *result, bool device)
+{
+    if (flags & ~PSAMD_GROUPS_INDEX) return fail(c, PSAMD_ERR_INVALID_ARG, "groups: unknown flag bits");
+    if (!std::isfinite(radius) || !(radius > 0.f) || !((double)radius <= c->P.cell_size))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "groups: radius is not finite, not > 0 or exceeds cell_size (the walk is over the 27-cell stencil)");
+    if (capacity < 0 || group_capacity < 0) return fail(c, PSAMD_ERR_INVALID_ARG, "groups: capacity < 0 or group_capacity < 0");
+    if (device && (!aligned(group, 4) || !aligned(group_first, 4) || !aligned(group_size, 4) || !aligned(result, 8)))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "groups: an array misaligned");
+    if (c->P.world > 1)
+        return fail(c, PSAMD_ERR_UNSUPPORTED, "groups: served on one context only (world == 1): a group can span ranks, and the ranks' groups "
+                                              "are not merged");
+    return PSAMD_OK;
+}
+
+// the scratch: one block, made by the first call and kept (neighbours_scratch's rules)
+static int groups_scratch(psamd_ctx *c)
+{
+    if (c->grp.block) return PSAMD_OK;
+    PS_TRY(refuse_capture(c, "groups", "the first call allocates the scratch"));
+    void *block = nullptr;
+    PS_HIP(c, hipMalloc(&block, groups_scratch_bytes(c->P)));
+    groups_scratch_carve(c->P, block, c->grp);
+    PS_HIP(c, hipMemsetAsync(c->grp.own, 0, sizeof(GrpOut), c->stream));
+    return PSAMD_OK;
+}
+
+int psamd_groups(psamd_ctx *c, const psamd_groups_spec *spec)
+{
+    PS_TRY(service_args(c, spec));
+    PS_TRY(groups_args(c, spec->flags, spec->radius, spec->group, spec->capacity, spec->group_first, spec->group_size, spec->group_capacity,
+                       spec->result_dev, true));
+    PS_TRY(frame_ready(c, "groups"));
+    PS_TRY(groups_scratch(c));
+    const GrpArgs a{spec->flags, spec->radius * spec->radius, spec->group, spec->capacity, spec->group_first, spec->group_size,
+                    spec->group_capacity, spec->result_dev};
+    PS_HIP(c, launch_groups(c->stream, c->P, c->d, a, c->grp));
+    return PSAMD_OK;
+}
+
+int psamd_groups_result_get(psamd_ctx *c, psamd_groups_result *out)
+{
+    PS_TRY(service_args(c, out));
+    if (!c->grp.block) { *out = psamd_groups_result{}; return PSAMD_OK; }     // no call yet
+    return read_own(c, out, &c->grp.own->result, sizeof *out);
+}
+
+// the same passes into the staging buffer: group[] of the first min(live, capacity) particles, the tables' first
+// min(groups, group_capacity) entries (there are no more groups than owned slots)
+int psamd_download_groups(psamd_ctx *c, uint32_t flags, float radius, int32_t *group, int64_t capacity, int32_t *group_first,
+                          int32_t *group_size, int64_t group_capacity, psamd_groups_result *result)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    PS_TRY(groups_args(c, flags, radius, group, capacity, group_first, group_size, group_capacity, result, false));
+    PS_TRY(frame_ready(c, "download_groups"));
+    PS_TRY(groups_scratch(c));
+    const int64_t n = std::min<int64_t>(capacity, c->P.slots_total), ng = std::min<int64_t>(group_capacity, c->P.slots_total);
+    void *const host[3] = {group, group_first, group_size};
+    const size_t words[3] = {(size_t)n, (size_t)ng, (size_t)ng};
+    size_t off[3], bytes = 0;
+    for (int k = 0; k < 3; k++) { off[k] = bytes; if (host[k]) bytes += (words[k] * 4 + 255) / 256 * 256; }
+    PS_TRY(ensure_staging(c, std::max<size_t>(bytes, 256)));
+    void *dev[3];
+    for (int k = 0; k < 3; k++) dev[k] = host[k] ? (char *)c->staging + off[k] : nullptr;
+    const GrpArgs a{flags, radius * radius, (int *)dev[0], n, (int *)dev[1], (int *)dev[2], ng, nullptr};
+    PS_HIP(c, launch_groups(c->stream, c->P, c->d, a, c->grp));
+    GrpOut got{};
+    PS_HIP(c, hipMemcpyAsync(&got, c->grp.own, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t m = (size_t)std::min<int64_t>(got.live, n), mg = (size_t)std::min<int64_t>(got.result.groups, ng);
+    const size_t take[3] = {m, mg, mg};
+    for (int k = 0; k < 3; k++)
+        if (host[k] && take[k] > 0) PS_HIP(c, hipMemcpyAsync(host[k], dev[k], take[k] * 4, hipMemcpyDeviceToHost, c->stream));
     PS_HIP(c, hipStreamSynchronize(c->stream));
     if (result) *result = got.result;
     return PSAMD_OK;

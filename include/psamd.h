@@ -451,6 +451,32 @@ typedef struct psamd_groups_spec {
     psamd_groups_result *result_dev;  /* optional out (device), 8-byte aligned */
 } psamd_groups_spec;     /* 56 bytes */
 
+/* psamd_knn_spec.flags (see "the k nearest within a radius" below) */
+#define PSAMD_KNN_INDEX 0x1u      /* a neighbour is named by its export index, not its global slot id (world == 1) */
+#define PSAMD_KNN_MAX_K 32
+
+/* What psamd_knn found. */
+typedef struct psamd_knn_result {
+    int64_t listed;     /* the queries: psamd_neighbours' */
+    int64_t found;      /* the sum over the queries of min(count, k) */
+    int64_t full;       /* queries with count >= k */
+    int32_t k, reserved;
+    double  dk2_min, dk2_max;   /* smallest / largest d2 of a k-th neighbour over the full queries; +inf / -inf if none */
+} psamd_knn_result;     /* 48 bytes */
+
+/* What psamd_knn writes and where (device pointers; none of them inside the context's own arrays). */
+typedef struct psamd_knn_spec {
+    uint32_t flags;     /* PSAMD_KNN_* */
+    float    radius;    /* psamd_neighbours' rule: finite, > 0, (double)radius <= cell_size */
+    int32_t  k;         /* 1 .. PSAMD_KNN_MAX_K */
+    int32_t  reserved;  /* 0 */
+    int32_t *found;     /* optional out, int32[capacity]: min(count, k); -1: in no list of the frame */
+    int32_t *who;       /* optional out, int32[capacity * k], row-major: entry o's j-th nearest at who[o * k + j] */
+    float   *d2;        /* optional out, float[capacity * k]: that pair's d2 */
+    int64_t  capacity;  /* >= 0: entries of the export order that are written */
+    psamd_knn_result *result_dev;   /* optional out (device), 8-byte aligned */
+} psamd_knn_spec;       /* 56 bytes */
+
 typedef struct psamd_ctx psamd_ctx;
 
 /* ---- lifetime ------------------------------------------------------------ */
@@ -1369,6 +1395,81 @@ int psamd_groups(psamd_ctx *ctx, const psamd_groups_spec *spec);
 int psamd_groups_result_get(psamd_ctx *ctx, psamd_groups_result *out);
 int psamd_download_groups(psamd_ctx *ctx, uint32_t flags, float radius, int32_t *group, int64_t capacity,
                           int32_t *group_first, int32_t *group_size, int64_t group_capacity, psamd_groups_result *result);
+
+/* ---- the k nearest within a radius -------------------------------------------------- */
+/* psamd_knn: every listed particle's k nearest neighbours within a radius, ordered by distance, on the device, lined up with
+ * psamd_export_live: an adaptive SPH smoothing length (the distance to the 32nd neighbour), a k-th-neighbour density estimate
+ * k / (4/3 pi r_k^3), topological flocking (the seven nearest whatever their distance), nearest-neighbour statistics --
+ * without the lists of psamd_neighbours and a ragged sort behind them.  Not in the reference; the step's arithmetic is untouched
+ * and PSAMD_ABI_VERSION stays 8.
+ *
+ * Queries, candidates and d2.  psamd_neighbours' rules, word for word: the queries are the listed particles of the context's
+ * own cells, a kid queried from its slot's position; the candidates are the 27-cell non-periodic stencil in the reference's
+ * order with the list capacities honoured; kids are nobody's neighbour; the own entry is left out by sorted index, so two
+ * particles at one point are each other's nearest, at d2 == 0; a hit is d2 <= r2 = RN(radius radius), with the same fp32 d2,
+ * never fused.  count below is psamd_neighbours' count: the number of hits.
+ *
+ * Order.  A row holds the min(count, k) hits that are smallest under the key (d2 as an fp32 value, global slot id), in
+ * ascending order of that key: nearest's rule -- "ties to the lower global slot id" -- extended.  An id stands once in the
+ * stencil, so the key is a total order on a query's hits: the row does not depend on the walk order, on the launch shape or on
+ * k, and row(k) is the first k words of row(k').  With k = 1, who and d2 are psamd_neighbours' nearest and nearest_d2, byte
+ * for byte.
+ *
+ * Outputs.  All optional, in export order: entry o is the o-th live owned particle in ascending global slot id, for the first
+ * m = min(live, capacity) of them.
+ *     found[o]          min(count, k); -1: a live particle that is in no list of the frame
+ *     who[o * k + j]    the j-th nearest neighbour, j < found; the words j >= found of a row are -1
+ *     d2[o * k + j]     that pair's d2; the words j >= found are +inf
+ * A live particle in no list has found = -1 and a row of -1 / +inf.  A neighbour is named by its global slot id (a halo's
+ * particle by the id the halo carried).  With PSAMD_KNN_INDEX it is named by its export index, so that pos[who] is a plain
+ * gather once the -1 are masked; an index at or past capacity is kept true.  The order is still by global slot id -- the
+ * export order is ascending slot id, so this is the same order.  The index form is served for world == 1 only
+ * (PSAMD_ERR_UNSUPPORTED otherwise).
+ *
+ * What `full` means.  Every particle outside a query's stencil is a cell edge or more away from it.  So with radius ==
+ * cell_size, the row of a query that counts in `full` holds its k nearest candidates of the whole non-periodic box -- with
+ * psamd_neighbours' caveat at exactly cell_size: a pair a rounding inside the radius across two cell walls is not in the
+ * stencil.  A query that does not count in `full` says the cap -- the radius -- was hit, not that nobody else is near.
+ *
+ * Record.  listed: the queries, psamd_neighbours'; found: the sum over the queries of min(count, k), the whole context's
+ * whatever the capacity; full: the queries with count >= k; k; dk2_min and dk2_max: the smallest and the largest d2 of a k-th
+ * neighbour over the full queries, +inf and -inf if there is none.  found and full are integer sums, dk2_min and dk2_max a
+ * minimum and a maximum of fp32 values: any reduction tree gives the same words.  A slab world's records combine: the counts
+ * add, dk2_min takes the minimum, dk2_max the maximum.
+ *
+ * Window, refusals, stream and determinism: psamd_neighbours'.  world == 1: from psamd_build_grid until the frame ends;
+ * world > 1: between psamd_slab_pairs and psamd_slab_apply, on a plan that lends nothing; a lending plan and an all-pairs world
+ * return PSAMD_ERR_UNSUPPORTED and leave the context usable; elsewhere and on a wedged context PSAMD_ERR_STATE.  The call is
+ * served on every force model and writes nothing of the frame, the force records or the step.  Everything is enqueued on the
+ * context's stream; nothing waits, nothing is read back.  The scratch (the slot -> export index table and a few words per
+ * walk task) is the context's: the first call allocates it -- that call may wait for the device and returns PSAMD_ERR_STATE
+ * under a capture -- and it never grows: its size depends on the container alone and never on k, the rows go straight to the
+ * caller's arrays; every later call may be captured into a graph.  Contexts that never call pay nothing.  Every output word
+ * is an integer or one fp32 value with a fixed operand order: the same bytes from run to run, with graphs or without; by id,
+ * the union of a slab world's rows is the single context's byte for byte.
+ *
+ * Cost on an MI355X at N = 2^20 on 16^3 cells, 321 502 live in 2 997 648 owned slots (scripts/knn_cost.py;
+ * profiles/knn_cost.txt), measured: psamd_knn with found and the rows 0.86 ms at k = 1, 0.91 ms at k = 8 and
+ * 1.60 ms at k = 32 at radius 1.0 (found 55 915, 78 242 and 78 260), 0.88, 1.00 and 2.26 ms at cell_size (found 316 611, 2 413 297
+ * and 7 684 457; 109 241 of the 321 502 queries full at k = 32); the record alone 0.12 ms less at k = 32 and within 0.03 ms at
+ * k <= 8.  Beside them in the same run psamd_neighbours' count-and-offsets call 0.81 and 0.84 ms -- the same walk, which k = 1
+ * stays within 0.05 ms of -- and its with-lists call 1.37 and 1.39 ms, today's route before its ragged sort and the figure to
+ * beat: k = 1 and k = 8 beat it, k = 32 does not.  On this frame a row of 32 almost never fills, so the reject in front of
+ * the insertion never closes and every hit of any lane sends its whole wave through the 32-position sweep; that kernel also
+ * runs at 5 waves per SIMD instead of 8 (a host clock around the call plus psamd_synchronize, the stream idle before it).
+ *
+ * PSAMD_ERR_INVALID_ARG: a NULL context or spec, unknown flag bits, reserved != 0, a bad radius, k outside 1 ..
+ * PSAMD_KNN_MAX_K, capacity < 0 or capacity * k not below 2^62, found, who or d2 not 4-byte aligned, result_dev not 8-byte
+ * aligned.
+ *
+ * psamd_knn_result_get: the last call's record, into host memory; waits for the context's stream.
+ * psamd_download_knn: the host form -- the same passes staged on the device (the staging holds min(capacity, owned slots)
+ * rows: give a capacity near the live count), then what was asked for copied into host arrays (any may be NULL) of capacity
+ * and capacity * k entries; waits for the stream. */
+int psamd_knn(psamd_ctx *ctx, const psamd_knn_spec *spec);
+int psamd_knn_result_get(psamd_ctx *ctx, psamd_knn_result *out);
+int psamd_download_knn(psamd_ctx *ctx, uint32_t flags, float radius, int32_t k, int32_t *found, int32_t *who, float *d2,
+                       int64_t capacity, psamd_knn_result *result);
 
 /* ---- long-range gravity (PSAMD_FLAG_FAR_MONOPOLE) ------------------------------ */
 /* The cutoff pass leaves most of a long-range force out; PSAMD_FLAG_ALL_PAIRS has all of it at O(N^2).  With this flag a

@@ -367,6 +367,34 @@ class GroupsSpec(C.Structure):
                 ("group_first", C.c_void_p), ("group_size", C.c_void_p), ("group_capacity", C.c_int64), ("result_dev", C.c_void_p)]
 
 
+KNN_INDEX = 0x1  # psamd_knn_spec.flags: a neighbour is named by its export index, not by its global slot id
+KNN_MAX_K = 32   # the largest k psamd_knn serves
+
+
+class KnnResult(_Record):
+    """psamd_knn_result: the queries, the sum of min(count, k), the queries with count >= k, k, the smallest and the largest
+    d2 of a k-th neighbour over the full queries (+inf / -inf: none)."""
+    _fields_ = [("listed", C.c_int64), ("found", C.c_int64), ("full", C.c_int64), ("k", C.c_int32), ("reserved", C.c_int32),
+                ("dk2_min", C.c_double), ("dk2_max", C.c_double)]
+
+
+class KnnSpec(C.Structure):
+    """psamd_knn_spec: what psamd_knn writes and where (device pointers)."""
+    _fields_ = [("flags", C.c_uint32), ("radius", C.c_float), ("k", C.c_int32), ("reserved", C.c_int32), ("found", C.c_void_p),
+                ("who", C.c_void_p), ("d2", C.c_void_p), ("capacity", C.c_int64), ("result_dev", C.c_void_p)]
+
+
+def merge_knn(results):
+    """The record of a slab world from its ranks' (dicts of knn() / knn_result()): the counts add, dk2_min and dk2_max take
+    the minimum and the maximum.  (The rows pair with the ranks' own exports.)"""
+    results = list(results)
+    out = {n: sum(int(r[n]) for r in results) for n in ("listed", "found", "full")}
+    out["k"] = int(results[0]["k"])
+    out["dk2_min"] = float(min(float(r["dk2_min"]) for r in results))
+    out["dk2_max"] = float(max(float(r["dk2_max"]) for r in results))
+    return out
+
+
 def merge_live_stats(stats):
     """The statistics of a system from its ranks' (dicts of live_stats() / export_live()["stats"]): counts and sums
     add, in rank order; the box and the ages take the minima and maxima."""
@@ -487,7 +515,20 @@ ABI = [
     ("psamd_groups", C.c_int, [_vp, C.POINTER(GroupsSpec)]),
     ("psamd_groups_result_get", C.c_int, [_vp, C.POINTER(GroupsResult)]),
     ("psamd_download_groups", C.c_int, [_vp, C.c_uint32, C.c_float, _vp, _i64, _vp, _vp, _i64, C.POINTER(GroupsResult)]),
+    ("psamd_knn", C.c_int, [_vp, C.POINTER(KnnSpec)]),
+    ("psamd_knn_result_get", C.c_int, [_vp, C.POINTER(KnnResult)]),
+    ("psamd_download_knn", C.c_int, [_vp, C.c_uint32, C.c_float, C.c_int32, _vp, _vp, _vp, _i64, C.POINTER(KnnResult)]),
 ]
+
+def _knn_dict(rec, out, m, k):
+    """knn()'s and download_knn()'s result: the record (its `found`, a sum, under "found_sum": the array has the name), the
+    arrays cut to m entries, the rows as [m, k]"""
+    res = dict(rec)
+    res["found_sum"] = res.pop("found")
+    for name, a in out.items():
+        res[name] = a[:m] if name == "found" else a[:m * k].reshape(m, k)
+    return res
+
 
 _lib = None
 
@@ -1345,6 +1386,57 @@ class ParticleSystem:
         for k, a in out.items():
             res[k] = a[:m] if k == "group" else a[:min(res["groups"], group_capacity)]
         return res
+
+    # ---- the k nearest within a radius (include/psamd.h) ------------------------------
+    def knn(self, radius, k, index=False, capacity=None, found=True):
+        """psamd_knn on the frame that is built (psamd_neighbours' window): every listed particle's k nearest neighbours within
+        `radius` (<= cell_size) over the 27-cell stencil, ordered by (d2, global slot id), in export order -- entry o belongs
+        to the o-th live particle of export_live() at the same point of the stream.  Returns the record (listed, found, full,
+        k, dk2_min, dk2_max) as a dict with torch tensors on the context's device beside it: "who" int32 [m, k] and "d2"
+        float32 [m, k], m = min(live count, capacity) -- the words past a row's min(count, k) are -1 and +inf -- and, with
+        found=True, "found" int32 [m]: min(count, k), -1: in no list of the frame.  The record's own `found`, the sum, stands
+        under "found_sum" (knn_result() has it under the record's name).  A neighbour is named by its global slot id or, with index=True, by its export index (world == 1 only).
+        With no capacity the live count is read first and sizes the rows.  Waits for the context's stream.  torch must have
+        been imported before the library was loaded."""
+        import torch
+        dev = torch.device("cuda", int(self.cfg.device))
+        k = int(k)
+        capacity = self.live_count() if capacity is None else int(capacity)
+        spec = KnnSpec(flags=KNN_INDEX if index else 0, radius=float(radius), k=k, capacity=capacity)
+        rows = max(capacity, 1) * max(min(k, KNN_MAX_K), 1)
+        out = {"who": torch.empty(rows, dtype=torch.int32, device=dev), "d2": torch.empty(rows, dtype=torch.float32, device=dev)}
+        spec.who, spec.d2 = out["who"].data_ptr(), out["d2"].data_ptr()
+        if found:
+            out["found"] = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev)
+            spec.found = out["found"].data_ptr()
+        result = torch.zeros(C.sizeof(KnnResult), dtype=torch.uint8, device=dev)
+        live = torch.zeros(1, dtype=torch.int64, device=dev)
+        spec.result_dev = result.data_ptr()
+        with self._on_stream(dev):
+            self._ck(self.lib.psamd_knn(self.h, C.byref(spec)))
+            # how many entries were written: the live count at this point of the stream
+            self._ck(self.lib.psamd_export_live(self.h, C.byref(Export(fields=0, capacity=0, count_dev=live.data_ptr()))))
+        m = min(int(live.item()), capacity)
+        return _knn_dict(KnnResult.from_device(result).to_dict(), out, m, k)
+
+    def knn_result(self):
+        """psamd_knn_result_get: the last knn call's record"""
+        return self._own_record(KnnResult, self.lib.psamd_knn_result_get)
+
+    def download_knn(self, radius, k, index=False, capacity=None, found=True):
+        """psamd_download_knn, the numpy form of knn(): the same keys, numpy arrays"""
+        k = int(k)
+        capacity = self.live_count() if capacity is None else int(capacity)
+        rows = max(capacity, 1) * max(min(k, KNN_MAX_K), 1)
+        out = {"who": np.full(rows, -7, np.int32), "d2": np.zeros(rows, np.float32)}
+        if found:
+            out["found"] = np.full(max(capacity, 1), -7, np.int32)
+        r = KnnResult()
+        self._ck(self.lib.psamd_download_knn(self.h, KNN_INDEX if index else 0, float(radius), k, _ptr(out.get("found")), _ptr(out["who"]),
+                                             _ptr(out["d2"]), capacity, C.byref(r)))
+        n = C.c_int64()        # how many entries were written: the export's count at this point (no fields, nothing copied)
+        self._ck(self.lib.psamd_download_live(self.h, 0, None, None, None, None, None, 0, C.byref(n)))
+        return _knn_dict(r.to_dict(), out, min(n.value, capacity), k)
 
     def device_view(self):
         v = DeviceView()

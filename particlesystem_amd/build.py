@@ -6,9 +6,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpsamd.so")
-# the step's kernels by stage (kernels_common.hpp holds the map), the live-particle export, the injection, the removal, the update in place, the potential, the probes, the mass on a lattice, a lattice field at the particles, the neighbours within a radius, the groups within a radius; the host side of the
+# the step's kernels by stage (kernels_common.hpp holds the map), the live-particle export, the injection, the removal, the update in place, the potential, the probes, the mass on a lattice, a lattice field at the particles, the neighbours within a radius, the groups within a radius, the k nearest within a radius; the host side of the
 # C ABI by concern (context.hpp holds the context they share): making a context, stepping it, state in and out, the on-stream services
-SOURCES = ["grid.hip", "collide.hip", "plan.hip", "force.hip", "allpairs.hip", "farfield.hip", "selftest.hip", "apply.hip", "lifecycle.hip", "slab.hip", "export.hip", "inject.hip", "remove.hip", "update.hip", "potential.hip", "probe.hip", "deposit.hip", "sample.hip", "neighbours.hip", "groups.hip", "create.hip", "step.hip", "io.hip", "services.hip"]
+SOURCES = ["grid.hip", "collide.hip", "plan.hip", "force.hip", "allpairs.hip", "farfield.hip", "selftest.hip", "apply.hip", "lifecycle.hip", "slab.hip", "export.hip", "inject.hip", "remove.hip", "update.hip", "potential.hip", "probe.hip", "deposit.hip", "sample.hip", "neighbours.hip", "groups.hip", "knn.hip", "create.hip", "step.hip", "io.hip", "services.hip"]
 DEPS = SOURCES + ["context.hpp", "context_params.hpp", "frame_stage.hpp", "kernels_common.hpp", "pair_math.hpp", "balanced.hpp", "pack_fit.hpp", "tile_walk.hpp", "slot_walk.hpp", "multisplit.hpp", "pot_walk.hpp", "far_walk.hpp", "nbr_walk.hpp", "lattice.hpp", "kernels.h", "device_types.h", "frame_scalars.h", "step_ledger.hpp", "geometry.hpp", "partition.hpp", os.path.join("..", "..", "include", "psamd.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 

@@ -76,6 +76,7 @@ struct psamd_ctx {
     SampleScratch smp{};              // psamd_sample's scratch: fixed (three counters; by export order it borrows upd.tile_live)
     NbrScratch nbr{};                 // psamd_neighbours' scratch: one block the first call allocates, sized by the container alone
     GrpScratch grp{};                 // psamd_groups' scratch: one block the first call allocates, sized by the container alone
+    KnnScratch knn{};                 // psamd_knn's scratch: one block the first call allocates, sized by the container alone (not by k)
     // timing
     int timing = 0;                   // 0 off, 1 pair pass / apply / life cycle, 2 every stage
     int timing_period = 1;             // events are recorded on every timing_period-th step since set_timing

@@ -366,7 +366,7 @@ int psamd_destroy(psamd_ctx *c)
     if (c->staging) (void)hipFree(c->staging);
     for (const EntryScratch &e : {c->inj.e, c->rem.e})
         for (void *p : {(void *)e.ent, (void *)e.tcount, (void *)e.tile_out}) if (p) (void)hipFree(p);
-    for (void *p : {(void *)c->prb.code, (void *)c->prb.order, (void *)c->upd.code, c->nbr.block, c->grp.block}) if (p) (void)hipFree(p);
+    for (void *p : {(void *)c->prb.code, (void *)c->prb.order, (void *)c->upd.code, c->nbr.block, c->grp.block, c->knn.block}) if (p) (void)hipFree(p);
     if (c->h_fs) (void)hipHostFree(c->h_fs);
     if (c->ev_made) for (auto &set : c->ev) for (auto &e : set) (void)hipEventDestroy(e);
     if (c->d.ev_fork) (void)hipEventDestroy(c->d.ev_fork);

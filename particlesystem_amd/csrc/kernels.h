@@ -207,6 +207,37 @@ struct GrpScratch {
 size_t groups_scratch_bytes(const DevParams &P);
 void groups_scratch_carve(const DevParams &P, void *block, GrpScratch &s);
 
+// psamd_knn (knn.hip): what the caller gave, and the scratch -- ONE allocation sized by the container alone (never by k: the
+// rows go straight to the caller's arrays), made by the first call (the host: knn_scratch, services.hip)
+struct KnnArgs {
+    uint32_t flags;   // PSAMD_KNN_*
+    float r2;         // RN(radius * radius)
+    int k;            // 1 .. PSAMD_KNN_MAX_K
+    int *found;       // [capacity] by export order (may be null)
+    int *who;         // [capacity * k] row-major (may be null)
+    float *d2;        // [capacity * k] (may be null)
+    int64_t capacity;
+    psamd_knn_result *result;           // the caller's record (may be null)
+};
+struct __align__(16) KnnPart {  // what a task's wave saw of its queries
+    int found, full, listed, pad;       // the sum of min(count, k); queries with count >= k; queries
+    float dk_min, dk_max;               // the smallest / largest d2 of a k-th neighbour (+inf / -inf: no full query)
+    float pad2[2];
+};
+struct KnnOut {       // the context's own result record (psamd_knn_result_get), and the live count the host form copies by
+    psamd_knn_result result;
+    int64_t live;
+};
+struct KnnScratch {
+    void *block;      // the one allocation; null: no call yet
+    int *index;       // [slots] storage index -> export index (-1: not live)
+    int *tile_live;   // [tiles of slots] the tile's live slots
+    KnnPart *parts;   // [own cells * slices] by task
+    KnnOut *own;
+};
+size_t knn_scratch_bytes(const DevParams &P);
+void knn_scratch_carve(const DevParams &P, void *block, KnnScratch &s);
+
 // psamd_deposit (deposit.hip): the lattice, what the caller gave, and the scratch.  A task is (compute cell, block of at most
 // 2 x 2 x 2 voxels of it): 1, 1 or 8 tasks a cell for refine 1, 2, 4; four tasks to a workgroup, whose partials are one entry
 constexpr int DEPOSIT_WG_TASKS = 4;
@@ -465,6 +496,10 @@ hipError_t launch_neighbours(hipStream_t st, const DevParams &P, const DeviceSta
 // psamd_groups: the sets' start, the hooking walk over psamd_neighbours' tasks, then three launches on the slot walk (the roots
 // and the sizes; the group numbers, the slot -> export index table and the two tables; the record and group[])
 hipError_t launch_groups(hipStream_t st, const DevParams &P, const DeviceState &d, const GrpArgs &a, const GrpScratch &s);
+
+// psamd_knn: two launches on the slot walk (the tiles' live counts; the slot -> export index table and the default rows), the
+// walk over psamd_neighbours' tasks that keeps each query's best k and stores its row, then the record over the tasks' partials
+hipError_t launch_knn(hipStream_t st, const DevParams &P, const DeviceState &d, const KnnArgs &a, const KnnScratch &s);
 
 // psamd_deposit: the gather over the compute cells' tasks, then the result record (mass, vmax and the counts over the
 // workgroups' partials in task order)

@@ -34,6 +34,7 @@
 //   probe.hip      psamd_probe, the acceleration and the potential at points of the caller's choosing
 //   neighbours.hip psamd_neighbours, every listed particle's neighbours within a radius in CSR form (nbr_walk.hpp: its walk)
 //   groups.hip     psamd_groups, the friends-of-friends groups of that relation: a union-find hooked on the same walk
+//   knn.hip        psamd_knn, every listed particle's k nearest by (d2, id) on the same walk: the best k in registers
 //
 // Reference arithmetic is reproduced operation for operation: every file is built with
 // -ffp-contract=off; where the reference evaluates in double (EPS2 add, 0.5*a*t*t) so

@@ -1,5 +1,5 @@
 // services.hip -- the host side of the on-stream services: psamd_export_live (export.hip), psamd_inject (inject.hip),
-// psamd_remove (remove.hip), psamd_update (update.hip), psamd_potential (potential.hip), psamd_probe (probe.hip), psamd_deposit (deposit.hip), psamd_sample (sample.hip), psamd_neighbours (neighbours.hip), psamd_groups (groups.hip), their host-array forms and their result records.
+// psamd_remove (remove.hip), psamd_update (update.hip), psamd_potential (potential.hip), psamd_probe (probe.hip), psamd_deposit (deposit.hip), psamd_sample (sample.hip), psamd_neighbours (neighbours.hip), psamd_groups (groups.hip), psamd_knn (knn.hip), their host-array forms and their result records.
 // A service enqueues its launches on the context's stream and returns; nothing here enqueues a stage of the step.
 #include "context.hpp"
 
@@ -667,6 +667,88 @@ int psamd_download_groups(psamd_ctx *c, uint32_t flags, float radius, int32_t *g
     const size_t take[3] = {m, mg, mg};
     for (int k = 0; k < 3; k++)
         if (host[k] && take[k] > 0) PS_HIP(c, hipMemcpyAsync(host[k], dev[k], take[k] * 4, hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    if (result) *result = got.result;
+    return PSAMD_OK;
+}
+
+// ---- the k nearest within a radius (knn.hip) ----
+// the arguments of psamd_knn and of its host form, in psamd_neighbours' order; then the context kind
+static int knn_args(psamd_ctx *c, uint32_t flags, float radius, int32_t k, int32_t reserved, const void *found, const void *who,
+                    const void *d2, int64_t capacity, const void *result, bool device)
+{
+    if (flags & ~PSAMD_KNN_INDEX) return fail(c, PSAMD_ERR_INVALID_ARG, "knn: unknown flag bits");
+    if (reserved != 0) return fail(c, PSAMD_ERR_INVALID_ARG, "knn: reserved must be 0");
+    if (!std::isfinite(radius) || !(radius > 0.f) || !((double)radius <= c->P.cell_size))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "knn: radius is not finite, not > 0 or exceeds cell_size (the walk is over the 27-cell stencil)");
+    if (k < 1 || k > PSAMD_KNN_MAX_K) return fail(c, PSAMD_ERR_INVALID_ARG, "knn: k outside 1 .. PSAMD_KNN_MAX_K");
+    if (capacity < 0 || capacity >= ((int64_t)1 << 62) / k) return fail(c, PSAMD_ERR_INVALID_ARG, "knn: capacity < 0, or capacity * k not below 2^62");
+    if (device && (!aligned(found, 4) || !aligned(who, 4) || !aligned(d2, 4) || !aligned(result, 8)))
+        return fail(c, PSAMD_ERR_INVALID_ARG, "knn: an array misaligned");
+    if ((flags & PSAMD_KNN_INDEX) && c->P.world > 1)
+        return fail(c, PSAMD_ERR_UNSUPPORTED, "knn: PSAMD_KNN_INDEX is served on one context only (world == 1): a halo's particle has no "
+                                              "export index here");
+    if ((c->P.flags & PSAMD_FLAG_ALL_PAIRS) && c->P.world > 1)
+        return fail(c, PSAMD_ERR_UNSUPPORTED, "knn: all-pairs contexts are served on one context only (world == 1)");
+    return PSAMD_OK;
+}
+
+// the scratch: one block, made by the first call and kept (neighbours_scratch's rules)
+static int knn_scratch(psamd_ctx *c)
+{
+    if (c->knn.block) return PSAMD_OK;
+    PS_TRY(refuse_capture(c, "knn", "the first call allocates the scratch"));
+    void *block = nullptr;
+    PS_HIP(c, hipMalloc(&block, knn_scratch_bytes(c->P)));
+    knn_scratch_carve(c->P, block, c->knn);
+    PS_HIP(c, hipMemsetAsync(c->knn.own, 0, sizeof(KnnOut), c->stream));
+    return PSAMD_OK;
+}
+
+int psamd_knn(psamd_ctx *c, const psamd_knn_spec *spec)
+{
+    PS_TRY(service_args(c, spec));
+    PS_TRY(knn_args(c, spec->flags, spec->radius, spec->k, spec->reserved, spec->found, spec->who, spec->d2, spec->capacity, spec->result_dev, true));
+    PS_TRY(window_nothing_lent(c, "knn"));
+    PS_TRY(knn_scratch(c));
+    const KnnArgs a{spec->flags, spec->radius * spec->radius, spec->k, spec->found, spec->who, spec->d2, spec->capacity, spec->result_dev};
+    PS_HIP(c, launch_knn(c->stream, c->P, c->d, a, c->knn));
+    return PSAMD_OK;
+}
+
+int psamd_knn_result_get(psamd_ctx *c, psamd_knn_result *out)
+{
+    PS_TRY(service_args(c, out));
+    if (!c->knn.block) { *out = psamd_knn_result{}; out->dk2_min = HUGE_VAL; out->dk2_max = -HUGE_VAL; return PSAMD_OK; }     // no call yet
+    return read_own(c, out, &c->knn.own->result, sizeof *out);
+}
+
+// the same passes into the staging buffer: found and the rows of the first min(live, capacity) particles
+int psamd_download_knn(psamd_ctx *c, uint32_t flags, float radius, int32_t k, int32_t *found, int32_t *who, float *d2, int64_t capacity,
+                       psamd_knn_result *result)
+{
+    if (!c) return PSAMD_ERR_INVALID_ARG;
+    if (c->wedged) return refuse_wedged(c);
+    PS_TRY(knn_args(c, flags, radius, k, 0, found, who, d2, capacity, result, false));
+    PS_TRY(window_nothing_lent(c, "download_knn"));
+    PS_TRY(knn_scratch(c));
+    const int64_t n = std::min<int64_t>(capacity, c->P.slots_total);
+    void *const host[3] = {found, who, d2};
+    const size_t words[3] = {(size_t)n, (size_t)n * (size_t)k, (size_t)n * (size_t)k};
+    size_t off[3], bytes = 0;
+    for (int i = 0; i < 3; i++) { off[i] = bytes; if (host[i]) bytes += (words[i] * 4 + 255) / 256 * 256; }
+    PS_TRY(ensure_staging(c, std::max<size_t>(bytes, 256)));
+    void *dev[3];
+    for (int i = 0; i < 3; i++) dev[i] = host[i] ? (char *)c->staging + off[i] : nullptr;
+    const KnnArgs a{flags, radius * radius, k, (int *)dev[0], (int *)dev[1], (float *)dev[2], n, nullptr};
+    PS_HIP(c, launch_knn(c->stream, c->P, c->d, a, c->knn));
+    KnnOut got{};
+    PS_HIP(c, hipMemcpyAsync(&got, c->knn.own, sizeof got, hipMemcpyDeviceToHost, c->stream));
+    PS_HIP(c, hipStreamSynchronize(c->stream));
+    const size_t m = (size_t)std::min<int64_t>(got.live, n);
+    const size_t take[3] = {m, m * (size_t)k, m * (size_t)k};
+    for (int i = 0; i < 3; i++)
+        if (host[i] && take[i] > 0) PS_HIP(c, hipMemcpyAsync(host[i], dev[i], take[i] * 4, hipMemcpyDeviceToHost, c->stream));
     PS_HIP(c, hipStreamSynchronize(c->stream));
     if (result) *result = got.result;
     return PSAMD_OK;
